@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- forward-dynamics evals/sec on batched random states, MIT Humanoid cluster model.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,15 +9,21 @@ A "step" is one pass of the hot path (batched cluster ABA, ClusterTreeModel::for
 over one batch of B synthetic states per GPU, inputs and outputs resident in HBM.  Scaling: weak by
 default (every rank owns its own B-state shard); `--scaling strong` splits the workload's batch over the
 ranks (BASELINE config 4: 1 048 576 Tello states over 8 GPUs).  States are independent and the model plan is
-replicated, so there is no data-path collective inside a step; `value` times the K steps alone.  The one
-exchange the path has -- results to rank 0 over RCCL -- is measured separately: `gather_ms` for one
-blocking gather, and `end_to_end` for K steps that each gather their results, the gather of step i running
-beside the kernel of step i + 1 (two result buffers).  After the timed region a strided sample of the results is
-checked against the CPU oracle (`verified`: max error of the sample under the tolerance).
+replicated, so there is no data-path collective inside a step; `value` times the K steps alone.
+A plain run sets up, runs W warm-up steps, times EXACTLY K steps once (`--replays`, default 1) and prints its line.
+`--dump-outputs DIR` writes what the last timed step computed (DIR/ydd.npy for forward dynamics, DIR/tau.npy for
+inverse dynamics, in the run's precision; rank 0's shard; a fixed, seeded sample of its rows above 64 MB).  The inputs
+come from a counter-based RNG with a fixed seed per workload, so two runs with the same arguments see the same states.
+`--full` adds everything else the benchmark measures, after the timed region: the K steps timed `--replays` times
+(default 7, `value` the MEDIAN repetition, `spread` min / max); the kernel's own duration and the roofline figures;
+a strided sample of the results against the CPU oracle (`verified`: max error of the sample under the tolerance);
+the other BASELINE configs (`configs`) and the CPU baseline (`cpu_baseline`) on one GPU; on several ranks the one
+exchange the path has -- results to rank 0 over RCCL: `gather_ms` for one blocking gather, and
+`end_to_end` for K steps that each gather their results, the gather of step i running beside the kernel of step
+i + 1 (two result buffers) -- and the strong split of config 4 (`strong`).
 `python bench.py --gpus N` without a torchrun environment starts the N ranks itself (torch.distributed.run as a child
 process, before this process touches a GPU) and relays rank 0's line and the children's exit code.
-The K steps are timed `--replays` times (default 7), every repetition bracketed by barrier + synchronize; `value` is
-the MEDIAN repetition, `spread` carries min / max.
+Every repetition of the K steps is bracketed by barrier + synchronize.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -153,6 +159,23 @@ def verify_sample(blob, q, qd, x, out, algo, dtype_name, n=1024):
     tol = 1e-3 if dtype_name == "f32" else 1e-9
     return {"verified": bool(err.max() < tol and np.isfinite(got).all()), "verify_states": int(idx.size),
             "verify_max_rel_err": float(err.max()), "verify_states_over_tol": int((err >= tol).sum()), "verify_tol": tol}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, name, out):
+    """--dump-outputs: the results of the last timed step as <path>/<name>.npy, in the dtype they were computed in.  Above
+    DUMP_MAX_BYTES a fixed, seeded sample of the rows (sorted) stands for the whole batch: the same rows on every run."""
+    import numpy as np
+
+    a = out.detach().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES // (a.itemsize * int(np.prod(a.shape[1:]))))
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+    return {"file": f"{name}.npy", "rows": int(a.shape[0]), "of_rows": int(out.shape[0]), "dtype": str(a.dtype)}
 
 
 def load_plan(G, workload):
@@ -467,14 +490,20 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="states per GPU (default: the workload's)")
     ap.add_argument("--dtype", default="", choices=["", "f32", "f64"])
     ap.add_argument("--algo", default="aba", choices=["aba", "rnea"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the repetitions, kernel time, roofline, oracle check, other configs, CPU baseline and gathers")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's results to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="time a plain loop of K launches instead of one hipGraph replay")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the workload's batch per GPU; strong: the workload's batch split over the GPUs")
-    ap.add_argument("--replays", type=int, default=7, help="repetitions of the K timed steps (median reported)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` sub-records (the other BASELINE configs)")
-    ap.add_argument("--configs", default="", help="comma-separated workloads to keep in `configs` (default: all)")
+    ap.add_argument("--replays", type=int, default=None,
+                    help="repetitions of the K timed steps, median reported (default: 1, with --full 7)")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip the `configs` sub-records (the other BASELINE configs)")
+    ap.add_argument("--configs", default="", help="(--full) comma-separated workloads to keep in `configs` (default: all)")
     args = ap.parse_args()
+    if args.replays is None:
+        args.replays = 7 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus, sys.argv[1:])  # does not return
@@ -621,13 +650,18 @@ def main():
         reps.append(el)
     elapsed = sorted(reps)[len(reps) // 2]
 
+    # what the last timed step computed, before anything below launches into `out` again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, "ydd" if args.algo == "aba" else "tau", out)
+
     # kernel-only duration: hipEvents on the launch stream (torch's current stream here)
-    kernel_ms = plan.time_kernel(args.algo, tq, tqd, tx, out, iters=max(5, min(args.steps, 50)))
+    kernel_ms = plan.time_kernel(args.algo, tq, tqd, tx, out, iters=max(5, min(args.steps, 50))) if args.full else None
 
     # the path's one exchange step: results to rank 0 over RCCL.  (a) one blocking gather; (b) K steps that each gather
     # their results, the gather of step i overlapping the kernel of step i + 1 (two result buffers)
     gather_ms, e2e_elapsed = None, None
-    if dist is not None:
+    if dist is not None and args.full:
         bufs = [torch.empty_like(out) for _ in range(world)] if rank == 0 else None
         barrier()
         g0 = time.perf_counter()
@@ -656,7 +690,7 @@ def main():
 
     # N > 1 (weak, the default workload): the strong split of BASELINE config 4 beside the weak value
     strong = None
-    if dist is not None and args.scaling == "weak" and args.workload == "mit_humanoid" and args.algo == "aba" and \
+    if args.full and dist is not None and args.scaling == "weak" and args.workload == "mit_humanoid" and args.algo == "aba" and \
             os.environ.get("BENCH_NO_STRONG") != "1":
         strong = strong_split_record(G, dist, rank, world, dev, args.steps, args.replays, args.warmup)
 
@@ -665,22 +699,11 @@ def main():
             dist.destroy_process_group()
         return
 
-    elem = 4 if dtype_name == "f32" else 8
-    bytes_per_eval = (plan.nq + 3 * plan.nv) * elem  # q, qd, tau in + ydd out (SURVEY 8d)
     total_states = B_global if args.scaling == "strong" else world * B
     evals_per_s = total_states * args.steps / elapsed
-    kernel_evals_per_s = B / (kernel_ms * 1e-3)
-    achieved_gbs = kernel_evals_per_s * bytes_per_eval / 1e9
-    flops = info.flops_aba if args.algo == "aba" else info.flops_rnea
-    # measured HBM-side traffic of the same launch configuration, if a PMC run is committed (profiles/)
-    # (only counters taken on THESE kernel sources: a file records the sha of the sources it was measured on)
-    sha = kernel_sources_sha()
-    traffic, traffic_src, flops_pmc, flops_pmc_src = committed_counters(sha, args.workload, args.algo, dtype_name, B)
     from generalized_rbda_amd.states import parse_clusters
 
     general = any(c[9] >= 2 for c in parse_clusters(blob)["clusters"])
-    # the kernel this batch ran on, from the library's own selection (grbda_kernel_name)
-    kernel_name = plan.kernel_name(args.algo, dtype_name, B, dev.index or 0)
     line = {
         "metric": "forward-dynamics evals/sec (batched random states), MIT Humanoid cluster model"
         if args.workload == "mit_humanoid" and args.algo == "aba"
@@ -700,33 +723,52 @@ def main():
         "config": {"workload": f"{urdf} cluster-{'ABA' if args.algo == 'aba' else 'RNEA'}, {B} random states per GPU",
                    "batch_per_gpu": B, "batch_global": total_states, "nq": plan.nq, "nv": plan.nv, "n_bodies": plan.n_bodies,
                    "n_clusters": plan.n_clusters, "parallelism": f"batch-sharded x{world}, plan replicated"},
-        # `bound` names the resource `achieved` / `peak` / `frac` are figures OF: the HBM roofline of the ALGORITHMIC bytes, as the
-        # contract asks.  `binding_measured` names the resource the measurements say binds the kernel (per-wavefront latency: dependent
-        # VALU issue and scalar / LDS / slab waits at two wavefronts per SIMD -- profiles/r5_chain_phase_profile.txt); its figures are
-        # under `valu`
-        "roofline": {"bound": "hbm", "binding_measured": "valu_issue", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": bytes_per_eval * B,
-                     "frac_traffic": None if traffic is None else traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "kernel": kernel_name,
-                     "kernel_ms": kernel_ms, "bytes_per_eval": bytes_per_eval,
-                     "note": "`achieved`/`frac` price the ALGORITHMIC bytes as the contract asks; `frac_traffic` prices the "
-                             "HBM-side bytes rocprofv3 counted; what binds is instruction issue -- two wavefronts per SIMD run at ~85 % of the rate this instruction mix (dependent VALU chains, scalar / LDS / slab waits) issues at, profiles/r5_chain_phase_profile.txt -- not bytes and not flops (see valu; DESIGN.md 4)",
-                     "valu": {"flops_model": flops, "flops_pmc": flops_pmc, "flops_pmc_source": flops_pmc_src,
-                              "flops_per_eval": flops_pmc if flops_pmc is not None else flops,
-                              "achieved_tflops": kernel_evals_per_s * (flops_pmc if flops_pmc is not None else flops) / 1e12,
-                              "peak_tflops": VALU_PEAK_TFLOPS[dtype_name],
-                              "frac": kernel_evals_per_s * (flops_pmc if flops_pmc is not None else flops) / 1e12
-                              / VALU_PEAK_TFLOPS[dtype_name],
-                              "attainable_tflops": VALU_ATTAINABLE_TFLOPS.get(dtype_name),
-                              "note": "flops_model = the plan compiler's operation count; flops_pmc = executed, from the "
-                                      "committed SQ_INSTS_VALU_* counters; achieved_tflops / frac use flops_pmc when present"}},
         "spread": {"replays": len(reps), "ms_per_step_min": min(reps) / max(args.steps, 1) * 1e3,
                    "ms_per_step_median": elapsed / max(args.steps, 1) * 1e3, "ms_per_step_max": max(reps) / max(args.steps, 1) * 1e3,
                    "value_min": total_states * args.steps / max(reps), "value_max": total_states * args.steps / min(reps)},
         "inputs": {"distinct_states": n_distinct, "gate": "implicit clusters: max |Kd^-1 Ki| < 150, cond(Kd) < 3000 and |q_span| < 32 rad "
                                                           "(generalized_rbda_amd/states.py; profiles/r4_gate_f32_oracle.txt)" if general else None},
     }
+    if dumped is not None:
+        line["outputs"] = dumped
+    if not args.full:
+        print(json.dumps(line))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    elem = 4 if dtype_name == "f32" else 8
+    bytes_per_eval = (plan.nq + 3 * plan.nv) * elem  # q, qd, tau in + ydd out (SURVEY 8d)
+    kernel_evals_per_s = B / (kernel_ms * 1e-3)
+    achieved_gbs = kernel_evals_per_s * bytes_per_eval / 1e9
+    flops = info.flops_aba if args.algo == "aba" else info.flops_rnea
+    # measured HBM-side traffic of the same launch configuration, if a PMC run is committed (profiles/)
+    # (only counters taken on THESE kernel sources: a file records the sha of the sources it was measured on)
+    sha = kernel_sources_sha()
+    traffic, traffic_src, flops_pmc, flops_pmc_src = committed_counters(sha, args.workload, args.algo, dtype_name, B)
+    # the kernel this batch ran on, from the library's own selection (grbda_kernel_name)
+    kernel_name = plan.kernel_name(args.algo, dtype_name, B, dev.index or 0)
+    # `bound` names the resource `achieved` / `peak` / `frac` are figures OF: the HBM roofline of the ALGORITHMIC bytes, as the
+    # contract asks.  `binding_measured` names the resource the measurements say binds the kernel (per-wavefront latency: dependent
+    # VALU issue and scalar / LDS / slab waits at two wavefronts per SIMD -- profiles/r5_chain_phase_profile.txt); its figures are
+    # under `valu`
+    line["roofline"] = {"bound": "hbm", "binding_measured": "valu_issue", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                        "algorithmic_bytes_per_launch": bytes_per_eval * B,
+                        "frac_traffic": None if traffic is None else traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "kernel": kernel_name,
+                        "kernel_ms": kernel_ms, "bytes_per_eval": bytes_per_eval,
+                        "note": "`achieved`/`frac` price the ALGORITHMIC bytes as the contract asks; `frac_traffic` prices the "
+                                "HBM-side bytes rocprofv3 counted; what binds is instruction issue -- two wavefronts per SIMD run at ~85 % of the rate this instruction mix (dependent VALU chains, scalar / LDS / slab waits) issues at, profiles/r5_chain_phase_profile.txt -- not bytes and not flops (see valu; DESIGN.md 4)",
+                        "valu": {"flops_model": flops, "flops_pmc": flops_pmc, "flops_pmc_source": flops_pmc_src,
+                                 "flops_per_eval": flops_pmc if flops_pmc is not None else flops,
+                                 "achieved_tflops": kernel_evals_per_s * (flops_pmc if flops_pmc is not None else flops) / 1e12,
+                                 "peak_tflops": VALU_PEAK_TFLOPS[dtype_name],
+                                 "frac": kernel_evals_per_s * (flops_pmc if flops_pmc is not None else flops) / 1e12
+                                 / VALU_PEAK_TFLOPS[dtype_name],
+                                 "attainable_tflops": VALU_ATTAINABLE_TFLOPS.get(dtype_name),
+                                 "note": "flops_model = the plan compiler's operation count; flops_pmc = executed, from the "
+                                         "committed SQ_INSTS_VALU_* counters; achieved_tflops / frac use flops_pmc when present"}}
     line.update(verify_sample(blob, q, qd, x, out, args.algo, dtype_name))
     if gather_ms is not None:
         line["gather_ms"] = gather_ms

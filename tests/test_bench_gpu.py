@@ -24,7 +24,7 @@ def _run(extra_env, *args):
 
 
 def test_bench_line_is_verified_and_carries_roofline_and_cpu_baseline(gpu):
-    line = _run({}, "--steps", "10", "--warmup", "2")
+    line = _run({}, "--full", "--steps", "10", "--warmup", "2")
     assert line["verified"] is True and line["verify_states"] >= 1000
     assert line["n_gpus"] == 1 and line["scaling"] == "weak" and line["dtype"] == "f32"
     r = line["roofline"]
@@ -62,7 +62,7 @@ def test_bench_multi_rank_path_on_one_rank(gpu):
         port = sk.getsockname()[1]
     env = {"BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": "0", "WORLD_SIZE": "1",
            "LOCAL_RANK": "0"}
-    line = _run(env, "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--workload", "tello", "--scaling", "strong",
+    line = _run(env, "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--workload", "tello", "--scaling", "strong",
                 "--batch", "131072")
     assert line["verified"] is True
     assert line["gather_ms"] > 0 and line["end_to_end"]["value"] > 0
@@ -81,8 +81,32 @@ def test_bench_weak_run_carries_the_strong_split_of_config_4(gpu):
         port = sk.getsockname()[1]
     env = {"BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": "0", "WORLD_SIZE": "1",
            "LOCAL_RANK": "0"}
-    line = _run(env, "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--replays", "3")
+    line = _run(env, "--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--replays", "3")
     assert line["verified"] is True and line["scaling"] == "weak"
     st = line["strong"]
     assert st["scaling"] == "strong" and st["batch_global"] == 1048576 and st["batch_per_gpu"] == 1048576 and st["n_gpus"] == 1
     assert st["verified"] is True and st["value"] > 0 and st["ms_per_step"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(gpu, tmp_path):
+    """A plain run times exactly K steps once and prints the headline alone; --dump-outputs writes the results of the last
+    timed step, which are the forward dynamics of the seeded inputs (checked here against the oracle on a few rows)."""
+    import numpy as np
+
+    import generalized_rbda_amd as G
+    import oracle_py as O
+    from generalized_rbda_amd.states import random_states
+
+    line = _run({}, "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 7 and line["spread"]["replays"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert abs(line["value"] - line["config"]["batch_global"] / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    for key in ("configs", "cpu_baseline", "roofline", "verified"):
+        assert key not in line, key
+    ydd = np.load(tmp_path / "ydd.npy")
+    plan = G.Plan.from_urdf(os.path.join(ROOT, "tests", "golden", "robot-models", "mit_humanoid.urdf"))
+    assert ydd.dtype == np.float32 and ydd.shape == (262144, plan.nv) and np.isfinite(ydd).all()
+    q, qd, tau = (a[:64].astype(np.float32).astype(np.float64) for a in random_states(plan.blob, 262144, 2))
+    ref = O.forward_dynamics(plan.blob, q, qd, tau)
+    assert (np.abs(ydd[:64] - ref).max(axis=1) / (1.0 + np.abs(ref).max(axis=1))).max() < 1e-3

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/${1:-prof}
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 30 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_derivs -- python3 $ROOT/tools/time_derivs.py jvrc1_humanoid 131072 > $OUT/derivs_under_rocprof.txt 2> $OUT/stats_derivs.log
 : > $OUT/traffic.txt
 for spec in "aba 32 mit_humanoid 262144" "rnea 32 mit_humanoid 262144" "aba 32 tello 1048576" "rnea 32 tello 1048576" \
