@@ -121,6 +121,14 @@ asan:
 	    -x c oracle/grbda_oracle.c -x none -lm -lpthread -o build/asan/asan_driver
 .PHONY: asan
 
+# host-side checker of the chain programs' LDS / slab schedules against the kernels' accesses (tests/test_lds_schedule_cpu.py)
+#   make lds-check && build/lds_check/lds_schedule_check --self-test tests/golden/robot-models/*.urdf
+lds-check:
+	@mkdir -p build/lds_check
+	g++ -std=c++17 -O1 -g -Wall -I include -I generalized_rbda_amd/include tests/cpp/lds_schedule_check.cpp $(CSRC)/plan.cpp \
+	    $(CSRC)/urdf.cpp -o build/lds_check/lds_schedule_check
+.PHONY: lds-check
+
 # experiment builds of the manifold kernels: make expm NAME=foo DEFS="-D..." -> build/exp/libgrbda_foo.so
 expm: $(OBJ)/minv_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/crba_kernels.o $(OBJ)/kernels.o
 	@mkdir -p build/exp

@@ -1626,6 +1626,10 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                         f.lds_va = f.lds_f = f.lds_f2 = f.lds_f3 = f.lds_f4 = -1;
                         int last = rt_free_fwd[c];
                         for (int id : free_chains[c]) last = std::max(last, rt_fwd[id]);
+                        // (latency mode: the limbs of the other wavefronts read [v | a] when THEIR forward runs start, which the program
+                        // order does not tell -- the block lives until the barrier that closes the concurrent phase, so that no kid chain of
+                        // a limb later in the program, on another wavefront, can take its rows; tests/cpp/lds_schedule_check.cpp)
+                        if (rlm) last = rt_free_bwd[c];
                         if (!free_chains[c].empty()) robjs.push_back({&f.lds_va, 12, 0, rt_free_fwd[c], last, -1, 1});
                         robjs.push_back({&f.lds_f, 6, 0, rt_free_fwd[c], rt_free_bwd[c], -1, 1});
                         if (rlm) {  // one force row block per wavefront: no two wavefronts read-modify-write the same rows
@@ -1864,6 +1868,10 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                         objs.push_back({acc_of[o], 27, acc_lds ? 10 : 1, acc_lds ? B0(t_free_fwd[c]) : B0(fb) + 1, B0(t_free_bwd[c]), -1, acc_lds ? 0 : 2});
                     }
                 }
+                // (latency mode: the limbs of the other wavefronts read [v | a] when THEIR acceleration runs start, which the program order
+                // does not tell -- the block lives to the end of the acceleration phase, the last segment of the program, so that no kid chain
+                // of a limb later in the program, on another wavefront, can take its rows; tests/cpp/lds_schedule_check.cpp)
+                if (lm) last_acc = static_cast<int>(CP.segs.size()) - 1;
                 objs.push_back({&f.lds_va, 12, 0, B0(t_free_acc[c]), D1(last_acc), -1, 1});
                 if (k_lds) objs.push_back({&f.glb_y0, 6, 11, B0(t_free_bwd[c]), D1(t_free_acc[c]), -1, 0});
             }

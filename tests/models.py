@@ -201,6 +201,57 @@ def chain_test_tree(seed, n_limbs=4, ori_repr="quaternion", rotors=True, deep_pa
     return m
 
 
+def tello_with_arms_arms_first():
+    """TelloWithArms with the two arms appended BEFORE the two legs (the package builder appends the legs first).  Cluster order
+    decides the order of the limbs below the torso in the chain programs and how latency mode deals them to wavefronts: with the
+    arms first, the last limb in program order is a leg whose hip differential and knee-ankle differential are kid chains, and
+    each wavefront of a two-wavefront tile owns an arm and a leg.  The builder's calls are recorded and replayed in that order,
+    so the model's parameters are the package's."""
+    import generalized_rbda_amd.robots as R
+
+    calls = []
+
+    class Recorder:
+        def __init__(self, *a, **k):
+            calls.append(("__init__", a, k))
+
+        def __getattr__(self, name):
+            return lambda *a, **k: calls.append((name, a, k))
+
+    real = R.ClusterTreeModel
+    R.ClusterTreeModel = Recorder
+    try:
+        R.tello_with_arms()
+    finally:
+        R.ClusterTreeModel = real
+    groups, cur = [], []
+    for c in calls[1:]:
+        cur.append(c)
+        if c[0].startswith("append"):  # appendBody / appendRegisteredBodiesAsCluster / appendTrigPolyCluster close a cluster
+            groups.append(cur)
+            cur = []
+    assert not cur
+    is_arm = lambda g: any(s in g[-1][1][0] for s in ("shoulder", "elbow"))
+    base, rest = groups[0], groups[1:]
+    m = real(*calls[0][1], **calls[0][2])
+    for g in [base] + [g for g in rest if is_arm(g)] + [g for g in rest if not is_arm(g)]:
+        for name, a, k in g:
+            getattr(m, name)(*a, **k)
+    return m
+
+
+# The generated family of tests/test_lds_schedule_cpu.py: chain_test_tree over these seeds, 2 - 6 limbs, deep pairs on and off
+def lds_family():
+    """name -> ClusterTreeModel"""
+    fam = {}
+    for n_limbs in range(2, 7):
+        for deep in (False, True):
+            for seed in range(12):
+                fam[f"chain_tree_l{n_limbs}_{'deep' if deep else 'flat'}_s{seed}"] = chain_test_tree(
+                    1000 + 100 * n_limbs + seed, n_limbs, deep_pairs=deep)
+    return fam
+
+
 ROBOT_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "robot-models")
 
 
