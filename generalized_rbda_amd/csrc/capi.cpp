@@ -121,6 +121,12 @@ struct grbda_plan {
     mutable std::map<std::pair<int, void *>, Scratch> work;  // expanded batches of the derived quantities
     mutable std::map<std::pair<int, void *>, Scratch> work_cvt;  // fp64 copies of fp32 inputs (grbda_fd_dq_f32)
     mutable std::map<std::pair<int, void *>, Scratch> work_proj; // projection_run (called from inside the users of `work`)
+    // the chunk decision of the last eager analytic_derivs call per (device, stream): a capture of the same call replays it
+    struct DerivChunk {
+        size_t B = 0, per_state_bytes = 0, chunk = 0;
+        bool need_d = false, ydd_all = false;
+    };
+    mutable std::map<std::pair<int, void *>, DerivChunk> deriv_chunk;
     // launch shape per kernel, index = (rnea ? 2 : 0) + (f64 ? 1 : 0): LDS budget per wavefront for the
     // slot store, and wavefronts launched per CU (the grid is persistent)
     // (defaults from sweeps on MI355X over the MIT humanoid, Mini Cheetah and JVRC-1 at 4096 tiles: the f32
@@ -1383,20 +1389,14 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
     const size_t n_rows = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);
     void *scratch = nullptr;
     if (int rc = ensure_scratch(p, device, stream, grid * n_rows * kWave * sizeof(T) + 256, &scratch)) return rc;
-    // a block of zeros stands in for the velocities and torques of every tile
-    Scratch &zs = p->work[{device, stream}];
+    // a block of zeros stands in for the velocities and torques of every tile (grown under ensure_work's capture rule)
     const size_t zneed = B * static_cast<size_t>(h.nv) * sizeof(T) + 256;
-    hipError_t e;
-    if (zs.bytes < zneed) {
-        if (zs.ptr && (e = hipFree(zs.ptr)) != hipSuccess) return hip_err(e, "hipFree");
-        zs.ptr = nullptr;
-        zs.bytes = 0;
-        if ((e = hipMalloc(&zs.ptr, zneed)) != hipSuccess) return hip_err(e, "hipMalloc(work)");
-        zs.bytes = zneed;
-    }
+    void *zeros = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, zneed, &zeros)) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    if ((e = hipMemsetAsync(zs.ptr, 0, zneed, hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    e = launch_osim_chain<T>(d, A, q, static_cast<const T *>(zs.ptr), Linv, J, B, static_cast<T *>(scratch), static_cast<int>(grid),
+    hipError_t e;
+    if ((e = hipMemsetAsync(zeros, 0, zneed, hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    e = launch_osim_chain<T>(d, A, q, static_cast<const T *>(zeros), Linv, J, B, static_cast<T *>(scratch), static_cast<int>(grid),
                              lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "osim chain launch");
 }
@@ -1934,25 +1934,49 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     const bool h_in_place = !minv && dtau && (il == 1 || (B % kDerivGroup) == 0);
     const size_t per_state = minv ? static_cast<size_t>(mv.n_entries) + (need_d ? 2 * nn + nv : 0)
                                   : (h_in_place ? 0 : nn) + (need_d ? 2 * nn + nv : 0);
-    size_t budget = work_budget(p, p->work, device, stream, (4096ull << 20) + (need_d ? B * nv * sizeof(T) : 0));
-    if (need_d && budget > 2 * B * nv * sizeof(T)) budget -= B * nv * sizeof(T);  // (room for the whole batch's ydd, below)
-    size_t chunk = budget / (per_state ? per_state * sizeof(T) : 1);
-    chunk &= ~static_cast<size_t>(kWave - 1);  // whole tiles, whole groups of the interleaved workspace
-    if (chunk < static_cast<size_t>(kWave)) chunk = kWave;
+    // Chunk size.  The slab holds chunk * per_state scalars, plus B nv of them when the forward dynamics of the WHOLE batch runs in one
+    // launch up front (160 MB for a million JVRC-1 states in fp32) instead of one launch per chunk -- a quarter-million-state launch runs at
+    // 0.35 ms, a quarter of the million-state launch at 0.29.  Every branch keeps the slab within the budget, or at one tile of states when
+    // the budget is smaller than that.  A stream that captures replays the decision of the eager call it captures after (same B, same
+    // layout): the held slab may have grown since, and a chunk derived from it again would record another launch sequence.
+    const size_t ps_bytes = per_state * sizeof(T), ydd_bytes = need_d ? B * nv * sizeof(T) : 0;
+    const size_t B_groups = (B + kDerivGroup - 1) / kDerivGroup * kDerivGroup;  // (the last group of the workspace is allocated whole)
+    size_t chunk = 0;
+    bool ydd_all = false;
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    const bool capturing = stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cst) == hipSuccess && cst != hipStreamCaptureStatusNone;
     {
-        // whole ROUNDS of the one-state-per-lane kernels: a chunk of 2.4 rounds of wavefront slots takes as long as 3 (measured: 159 488-state
-        // chunks of JVRC-1, 2 492 tiles on 1 024 slots of the recursion and 2 048 of the factor kernel / the ABA: 19 % and 40 % of the
-        // slots idle in the last round).  n_cu * 8 wavefronts = one round at two per SIMD, two rounds of the recursion's four per CU.
-        const size_t round = static_cast<size_t>(t->n_cu) * 8 * kWave;
-        if (chunk >= round) chunk = chunk / round * round;
+        const auto it = p->deriv_chunk.find({device, stream});
+        if (capturing && it != p->deriv_chunk.end() && it->second.B == B && it->second.per_state_bytes == ps_bytes && it->second.need_d == need_d) {
+            chunk = it->second.chunk;
+            ydd_all = it->second.ydd_all;
+        }
     }
-    if (chunk > B) chunk = (B + kDerivGroup - 1) / kDerivGroup * kDerivGroup;  // (the last group of the workspace is allocated whole)
+    if (!chunk) {
+        const size_t budget = work_budget(p, p->work, device, stream, (4096ull << 20) + ydd_bytes);
+        const size_t tile = static_cast<size_t>(kWave) * ps_bytes;
+        if (B_groups * ps_bytes <= budget) {
+            chunk = B_groups;  // one chunk: no whole-batch ydd
+        } else {
+            // (room for the whole batch's ydd and a tile of states besides; otherwise the forward dynamics runs per chunk)
+            ydd_all = need_d && budget >= ydd_bytes + tile;
+            chunk = (budget - (ydd_all ? ydd_bytes : 0)) / (ps_bytes ? ps_bytes : 1);
+            chunk &= ~static_cast<size_t>(kWave - 1);  // whole tiles, whole groups of the interleaved workspace
+            if (chunk < static_cast<size_t>(kWave)) chunk = kWave;
+            // whole ROUNDS of the one-state-per-lane kernels: a chunk of 2.4 rounds of wavefront slots takes as long as 3 (measured: 159 488-state
+            // chunks of JVRC-1, 2 492 tiles on 1 024 slots of the recursion and 2 048 of the factor kernel / the ABA: 19 % and 40 % of the
+            // slots idle in the last round).  n_cu * 8 wavefronts = one round at two per SIMD, two rounds of the recursion's four per CU.
+            const size_t round = static_cast<size_t>(t->n_cu) * 8 * kWave;
+            if (chunk >= round) chunk = chunk / round * round;
+            if (chunk >= B) {  // (only when the budget is below one tile: a single chunk, then without the whole-batch ydd)
+                chunk = B_groups;
+                ydd_all = false;
+            }
+        }
+        if (!capturing) p->deriv_chunk[{device, stream}] = {B, ps_bytes, chunk, need_d, ydd_all};
+    }
     // f32 with the matrix-core solve: the recursion writes H, dID/dq, dID/dqd interleaved by groups of kDerivGroup states
     // (deriv_kernels.hip); every other combination keeps the state-major layout (il, above)
-    // several chunks: the forward dynamics of the WHOLE batch in one launch up front (B nv scalars more of workspace: 160 MB for a million
-    // JVRC-1 states in fp32) instead of one launch per chunk -- a quarter-million-state launch runs at 0.35 ms, a quarter of the
-    // million-state launch at 0.29
-    const bool ydd_all = need_d && B > chunk;
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, (chunk * per_state + (ydd_all ? B * nv : 0)) * sizeof(T) + 256, &wptr)) return rc;
     T *wnext = static_cast<T *>(wptr);
@@ -2449,20 +2473,32 @@ void grbda_plan_free(grbda_plan *p)
     delete p;
 }
 
+// A stream that is capturing must not lose a buffer its graph refers to, and hipFree would wait for the capture: every slab of the plan
+// (and of its spanning-tree plan) is checked first, so that a refused release frees nothing.
+static bool holds_capturing_slab(const grbda_plan *p)
+{
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj})
+        for (auto &kv : *m) {
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (kv.second.ptr && kv.first.second && hipStreamIsCapturing(static_cast<hipStream_t>(kv.first.second), &cs) == hipSuccess &&
+                cs != hipStreamCaptureStatusNone)
+                return true;
+        }
+    return p->span && holds_capturing_slab(p->span);
+}
+
 int grbda_plan_release_work(grbda_plan *p, unsigned long long *bytes_released)
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
+    if (holds_capturing_slab(p))
+        return set_err(GRBDA_EINVAL, "a stream of this plan is capturing: its work buffers cannot be released now");
     unsigned long long total = 0;
     for (auto *m : {&p->work, &p->work_cvt, &p->work_proj})
         for (auto &kv : *m) {
             if (!kv.second.ptr) continue;
             hipError_t e = hipSetDevice(kv.first.first);
             if (e != hipSuccess) return hip_err(e, "hipSetDevice");
-            // a stream that is capturing must not lose a buffer its graph refers to, and hipFree would wait for the capture
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (kv.first.second && hipStreamIsCapturing(static_cast<hipStream_t>(kv.first.second), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-                return set_err(GRBDA_EINVAL, "a stream of this plan is capturing: its work buffer cannot be released now");
             if ((e = hipFree(kv.second.ptr)) != hipSuccess) return hip_err(e, "hipFree");  // (waits for the work enqueued on it)
             total += kv.second.bytes;
             kv.second.ptr = nullptr;

@@ -302,21 +302,36 @@ def test_mass_matrix_bias_and_fd_derivatives_match_oracle(name, blob, gpu):
     assert rel_err(C32, C_ref) < TOL32
 
 
-def test_derived_quantities_chunked_large_batch(gpu):
-    """The expanded batch is processed in chunks below 256 MiB: a batch that needs several chunks gives the
-    same matrices as a small one."""
+def test_derived_quantities_chunked_large_batch(gpu, monkeypatch):
+    """The mass matrix of a large batch equals the matrices of a small batch of the same states (the CRBA kernel, one launch); and the
+    route that does chunk -- the difference batches of derived() (GRBDA_NO_CRBA=1), nv + 1 inverse dynamics per state in chunks of
+    256 MiB of expanded rows -- runs three chunks and a ragged tail (kernel nodes of its captured call against a 64-state batch) and gives,
+    at its seams, the CRBA's matrices to rounding."""
     import torch
+    from graph_capture import capture
 
     blob = zoo()["urdf_mini_cheetah"]
     plan = G.Plan(blob)
-    B = 40000  # (nv + 1) * B rows of fp64 exceed one chunk
+    nq, nv = plan.nq, plan.nv
+    chunk = (256 << 20) // ((nq + 3 * nv) * 8 * (nv + 1))
+    B = 3 * chunk + 45
     q, qd, tau = random_states(blob, B, 5)
     tq = torch.as_tensor(q, dtype=torch.float64, device=gpu)
     H = plan.mass_matrix(tq)
-    idx = torch.tensor([0, 17, B // 2, B - 1], device=gpu)
+    idx = torch.tensor([0, 17, B // 2, B - 1] + [c * chunk + d for c in (1, 2, 3) for d in (-1, 0, 1)], device=gpu)
     H_small = plan.mass_matrix(tq[idx].contiguous())
     torch.cuda.synchronize()
     assert torch.equal(H[idx], H_small)
+    monkeypatch.setenv("GRBDA_NO_CRBA", "1")
+    diff = G.Plan(blob)
+    cap = capture(lambda: (diff.mass_matrix(tq),))
+    n_B, H_diff = cap.nodes["kernel"], cap.replay()[0][idx].clone()
+    cap.drop()
+    cap = capture(lambda: (diff.mass_matrix(tq[:64]),))
+    n_64 = cap.nodes["kernel"]
+    cap.drop()
+    assert n_B >= 3 * n_64
+    assert ((H_diff - H_small).abs().max() / (1.0 + H_small.abs().max())).item() < TOL64
 
 
 def test_derivative_entry_points_edge_cases(gpu):
@@ -349,10 +364,11 @@ def test_derivative_entry_points_edge_cases(gpu):
     assert np.abs(db["dqd"][:, :, k].cpu().numpy() - col).max() / (1 + np.abs(col).max()) < 1e-8
 
 
-def test_analytic_derivatives_chunked_large_batch(gpu):
-    """The analytic derivative pipeline works through the batch in chunks of its 512 MiB work space (H, dID/dq, dID/dqd,
-    ydd per state): a batch that needs several chunks gives, at the chunk seams and the ragged end, the matrices of a small
-    batch of the same states."""
+def test_analytic_derivatives_chunked_large_batch(gpu, monkeypatch):
+    """The analytic derivative pipeline works through a batch in chunks of its work budget (here cut to 64 MiB with GRBDA_WORK_MAX_MB; the
+    minv route keeps the factor records, dID/dq, dID/dqd and ydd per state): the slab stays within the cap -- under a third of the
+    one-chunk slab, so at least three chunks -- and the chunked call gives the one-chunk call's matrices bit for bit and, at the tile
+    boundaries the seams fall on and the ragged end, the matrices of a small batch of the same states."""
     import torch
 
     blob = zoo()["urdf_mini_cheetah"]
@@ -365,8 +381,18 @@ def test_analytic_derivatives_chunked_large_batch(gpu):
     q, qd, tau = random_states(blob, B, 6)
     t = lambda a: torch.as_tensor(a, dtype=torch.float32, device=gpu)
     tq, tqd, tt = t(q), t(qd), t(tau)
+    whole = plan.fd_derivatives(tq, tqd, tt, want=("dq", "dtau"))
+    torch.cuda.synchronize()
+    one_chunk = plan.release_work()
+    monkeypatch.setenv("GRBDA_WORK_MAX_MB", "64")
     d = plan.fd_derivatives(tq, tqd, tt, want=("dq", "dtau"))
-    idx = torch.tensor([0, 63, chunk - 1, chunk, chunk + 1, 2 * chunk - 1, 2 * chunk, B - 1], device=gpu)
+    torch.cuda.synchronize()
+    held = plan.release_work()
+    assert held <= (64 << 20) + 256 and 3 * held < one_chunk, (held, one_chunk)
+    for k in ("dq", "dtau"):
+        assert torch.equal(d[k], whole[k]), k
+    seams = [s + o for s in range(64, B, 64) for o in (-1, 0, 1)]  # (chunks are whole tiles)
+    idx = torch.tensor(sorted(set([0, 63, chunk - 1, chunk, chunk + 1, 2 * chunk - 1, 2 * chunk, B - 1] + seams)), device=gpu)
     small = plan.fd_derivatives(tq[idx].contiguous(), tqd[idx].contiguous(), tt[idx].contiguous(), want=("dq", "dtau"))
     torch.cuda.synchronize()
     # (equal up to rounding, not bit for bit: the small batch's forward dynamics run in latency mode, which sums the limbs'
