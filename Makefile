@@ -31,7 +31,7 @@ $(OBJ)/chain_kernels_u1.o: $(CSRC)/chain_kernels.hip $(CSRC)/gen_segments.h $(CS
 # third unit: the kernels of chain programs with generic clusters (gen_segments.h)
 $(OBJ)/chain_kernels_u2.o: $(CSRC)/chain_kernels.hip $(CSRC)/gen_segments.h $(CSRC)/gen_rnea_segments.h $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(CHAINFLAGS) -DGRBDA_CHAIN_UNIT=2 $(U2FLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(CHAINFLAGS) -DGRBDA_CHAIN_UNIT=2 -c $< -o $@
 # fourth unit: the latency-mode kernel with four wavefronts per tile (its [K | y0] blocks are LDS objects: GRBDA_KLDS)
 $(OBJ)/chain_kernels_u3.o: $(CSRC)/chain_kernels.hip $(CSRC)/gen_segments.h $(CSRC)/gen_rnea_segments.h $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h
 	@mkdir -p $(OBJ)
@@ -58,21 +58,6 @@ $(OBJ)/urdf.o: $(CSRC)/urdf.cpp include/grbda_hip.h include/grbda_model_desc.h g
 	@mkdir -p $(OBJ)
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 
-# a build variant of the chain kernels for A/B runs (both units): make variant VARIANT=x VFLAGS="-D..." [U1FLAGS="..."]
-# -> build/variants/libgrbda_hip_x.so (GRBDA_HIP_LIB selects it)
-VARIANT ?= v
-VFLAGS ?=
-U1FLAGS ?=
-U2FLAGS ?=
-# (VFLAGS=-DGRBDA_EXP also compiles the ablation switches GRBDA_CHAIN_DEBUG / GRBDA_DEBUG_SWEEPS into the variant: the product
-# library ignores them)
-variant: $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/kernels.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/plan.o $(OBJ)/urdf.o
-	@mkdir -p build/variants
-	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -x hip -c $(CSRC)/capi.cpp -o build/variants/capi_$(VARIANT).o
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(CHAINFLAGS) $(VFLAGS) -c $(CSRC)/chain_kernels.hip -o build/variants/chain_kernels_$(VARIANT).o
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(CHAINFLAGS) $(VFLAGS) -DGRBDA_CHAIN_UNIT=1 $(U1FLAGS) -c $(CSRC)/chain_kernels.hip -o build/variants/chain_kernels_u1_$(VARIANT).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/libgrbda_hip_$(VARIANT).so build/variants/chain_kernels_$(VARIANT).o build/variants/chain_kernels_u1_$(VARIANT).o build/variants/capi_$(VARIANT).o $^
-
 $(LIB): $(OBJ)/kernels.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
@@ -86,30 +71,6 @@ clean:
 	rm -rf build $(LIB) oracle/_build oracle/_ref
 
 .PHONY: all oracle ref clean
-
-# profiling variant with in-kernel cycle accounting (tools/prof_run.py); not part of `all`
-prof: $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o
-	@mkdir -p build/prof
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -DGRBDA_PROFILE -c $(CSRC)/kernels.hip -o build/prof/kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/prof/libgrbda_hip_prof.so build/prof/kernels.o $^
-
-# experiment builds: make exp NAME=foo DEFS="-DGRBDA_EXP_FOO" -> build/exp/libgrbda_foo.so
-exp: $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o
-	@mkdir -p build/exp
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(DEFS) -c $(CSRC)/kernels.hip -o build/exp/kernels_$(NAME).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libgrbda_$(NAME).so build/exp/kernels_$(NAME).o $^
-
-# experiment builds of the derivative kernels: make expd NAME=foo DEFS="-D..." -> build/exp/libgrbda_foo.so
-expd: $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/crba_kernels.o $(OBJ)/kernels.o
-	@mkdir -p build/exp
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(DEFS) -c $(CSRC)/deriv_kernels.hip -o build/exp/deriv_$(NAME).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libgrbda_$(NAME).so build/exp/deriv_$(NAME).o $^
-
-# experiment builds of the chain kernels: make expc NAME=foo DEFS="-D..." -> build/exp/libgrbda_foo.so
-expc: $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/deriv_kernels.o $(OBJ)/crba_kernels.o $(OBJ)/kernels.o
-	@mkdir -p build/exp
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(CHAINFLAGS) $(DEFS) -c $(CSRC)/chain_kernels.hip -o build/exp/chain_$(NAME).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libgrbda_$(NAME).so build/exp/chain_$(NAME).o $^
 
 # AddressSanitizer + UBSan build of the HOST-side code (CPU only: GPU sanitizers are not available on this pool): the plan
 # compiler, the URDF+ reader and the oracle, driven by tools/asan_driver.cpp over every robot URDF and a serialised model.
@@ -128,15 +89,3 @@ lds-check:
 	g++ -std=c++17 -O1 -g -Wall -I include -I generalized_rbda_amd/include tests/cpp/lds_schedule_check.cpp $(CSRC)/plan.cpp \
 	    $(CSRC)/urdf.cpp -o build/lds_check/lds_schedule_check
 .PHONY: lds-check
-
-# experiment builds of the manifold kernels: make expm NAME=foo DEFS="-D..." -> build/exp/libgrbda_foo.so
-expm: $(OBJ)/minv_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/crba_kernels.o $(OBJ)/kernels.o
-	@mkdir -p build/exp
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(DEFS) -c $(CSRC)/manifold_kernels.hip -o build/exp/manifold_$(NAME).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libgrbda_$(NAME).so build/exp/manifold_$(NAME).o $^
-
-# experiment builds of the minv kernels: make expv NAME=foo DEFS="-D..." -> build/exp/libgrbda_foo.so
-expv: $(OBJ)/deriv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/crba_kernels.o $(OBJ)/kernels.o
-	@mkdir -p build/exp
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(DEFS) -c $(CSRC)/minv_kernels.hip -o build/exp/minv_$(NAME).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libgrbda_$(NAME).so build/exp/minv_$(NAME).o $^

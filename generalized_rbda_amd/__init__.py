@@ -14,7 +14,7 @@ from typing import Optional
 from . import modeldesc  # noqa: F401  (model-description builder)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# GRBDA_HIP_LIB: another build of the same library (kernel build variants, `make variant`); development A/B runs only
+# GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
 LIB_PATH = os.environ.get("GRBDA_HIP_LIB") or os.path.join(_HERE, "libgrbda_hip.so")
 
 # every entry point include/grbda_hip.h declares
@@ -27,7 +27,7 @@ C_ABI_SYMBOLS = [
     "grbda_fd_dtau_f64", "grbda_fd_dtau_f32", "grbda_fd_dqd_f64", "grbda_fd_dqd_f32",
     "grbda_aba_sharded_f32", "grbda_aba_sharded_f64", "grbda_rnea_sharded_f32", "grbda_rnea_sharded_f64",
     "grbda_aba_sharded_dev_f32", "grbda_aba_sharded_dev_f64", "grbda_rnea_sharded_dev_f32", "grbda_rnea_sharded_dev_f64",
-    "grbda_debug_dump_plan", "grbda_body_poses_host_f64", "grbda_apply_test_force_host_f64",
+    "grbda_body_poses_host_f64", "grbda_apply_test_force_host_f64",
     "grbda_inv_osim_host_f64", "grbda_fd_dq_f64", "grbda_fd_dq_f32", "grbda_body_poses_f64", "grbda_body_poses_f32",
     "grbda_apply_test_force_f64", "grbda_apply_test_force_f32", "grbda_inv_osim_f64", "grbda_inv_osim_f32",
     "grbda_project_positions_f64", "grbda_project_positions_f32", "grbda_plan_span_dims",

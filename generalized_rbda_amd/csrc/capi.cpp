@@ -127,35 +127,7 @@ struct grbda_plan {
         bool need_d = false, ydd_all = false;
     };
     mutable std::map<std::pair<int, void *>, DerivChunk> deriv_chunk;
-    // launch shape per kernel, index = (rnea ? 2 : 0) + (f64 ? 1 : 0): LDS budget per wavefront for the
-    // slot store, and wavefronts launched per CU (the grid is persistent)
-    // (defaults from sweeps on MI355X over the MIT humanoid, Mini Cheetah and JVRC-1 at 4096 tiles: the f32
-    // RNEA kernel needs ~100 VGPRs and gains from 16 wavefronts per CU with 10 KiB each; the f64 RNEA kernel is
-    // register-bound to 8 per CU and prefers 6 with more LDS)
-    int lds_bytes_per_wave[4] = {20480, 20480, 10240, 26624};
-    int waves_per_cu[4] = {8, 8, 16, 6};
-    // fp64 forward dynamics OFF the plain chain kernels -- the cluster interpreter, and chain programs with generic segments (one wavefront
-    // per SIMD, 428 registers, chain_kernels.hip) -- runs best at one wavefront per SIMD (measured on the zoo, 131 072 states: interpreter
-    // 0.71-0.94 -> 0.46-0.66 ms; generic chain kernel even); GRBDA_WAVES_PER_CU / _ABA64 set it like the others
-    int waves_per_cu_f64_wide_regs = 4;
-    bool no_split = false;
-    bool no_chain = false;  // GRBDA_NO_CHAIN=1: keep the general interpreter (A/B runs, tests of the general kernels)
-    int chain_debug = 0;
-    bool no_crba = false;
-    bool rnea_narrow = false;  // GRBDA_RNEA_NARROW=1: the inverse-dynamics chain kernel stays at two wavefronts per SIMD
-    bool no_analytic = false;  // GRBDA_NO_ANALYTIC=1: derivatives by the unit-vector / central-difference batches only
-    bool solve_f64 = false;    // GRBDA_SOLVE_F64=1: the SPD solve of the f32 derivative entry points computes in f64
-    int gen1_tiles_per_wave = 0;   // GRBDA_GEN1_TILES_PER_WAVE > 0: grid = tiles / this (the dispatcher balances the workgroups)
-    int gen1_waves_cap = 0;        // GRBDA_GEN1_WAVES_PER_CU > 0: wavefronts per CU of the single-cluster kernels (experiments)
-    bool no_latency_mode = false;  // GRBDA_NO_LATENCY_MODE=1: small batches keep the one-wavefront-per-tile kernel
-    int lm_waves = 0;              // GRBDA_LM_WAVES=2: latency mode never takes four wavefronts per tile (A/B runs)
-    int crba_waves = 16;       // GRBDA_CRBA_WAVES_PER_CU: grid of the composite-rigid-body kernel (fp32: 99 registers, four wavefronts per SIMD:
-                               // JVRC-1 mass matrix 1.95 -> 1.81 ms per 262 144 states against eight per CU; fp64 is capped at eight)
-    int deriv_waves = 0;       // GRBDA_DERIV_WAVES_PER_CU: grid of the inverse-dynamics derivative kernel (0: 3)
-    bool no_minv = false;      // GRBDA_NO_MINV=1: the derivative pipeline keeps the dense factorisation of H (A/B runs)
-    int minv_wpc = 0;          // GRBDA_MINV_WPC: upper limit of the workgroups per CU of minv_mfma_kernel (0: what registers and LDS hold)
-    bool no_efpa = false;  // GRBDA_NO_EFPA=1: inverse OSIM through unit wrenches and the ABA / RNEA kernels  // GRBDA_NO_CRBA=1: mass matrix through nv + 1 inverse-dynamics evaluations (the path of loop models)
-    bool chain_wide = false;  // GRBDA_CHAIN_WIDE=1: chain kernel at four wavefronts per SIMD for batches that fill them
+    PlanOptions opt;  // read once, when the plan is made (plan_options_from_env)
     // Models with implicit clusters: the spanning-tree model as a plan of its own (plan.cpp, make_spanning_blob) -- the analytic
     // derivatives and the mass matrix are taken on it and projected with the per-state G (manifold_kernels.hip).  span_q / span_v:
     // spanning position / velocity index of every body; crow: first row of every implicit cluster in the coupling slab.
@@ -165,7 +137,6 @@ struct grbda_plan {
     int n_cpl_rows = 0;
     bool has_trig = false;     // some implicit cluster is a trig-polynomial constraint (its sine / cosine cache takes dynamic LDS of the manifold constraint kernel)
     int constraint_shape = 0;  // manifold_kernels.hip, launch_manifold_constraint: 0 structured, 1 beyond the limits, 2 at most 4 bodies / 2 coordinates
-    bool no_manifold = false;  // GRBDA_NO_MANIFOLD=1: implicit models keep the difference batches (A/B runs)
 };
 
 namespace {
@@ -333,8 +304,7 @@ int ensure_scratch(const grbda_plan *p, int device, void *stream, size_t bytes, 
 // (device, stream) and never shrink by themselves; grbda_plan_release_work() hands them back.
 static size_t work_budget(const grbda_plan *p, const std::map<std::pair<int, void *>, Scratch> &pool, int device, void *stream, size_t want)
 {
-    const int want_mb = env_int("GRBDA_WORK_WANT_MB", 0);  // (experiments: another chunk size)
-    size_t cap = want_mb > 0 ? static_cast<size_t>(want_mb) << 20 : want;
+    size_t cap = want;
     size_t held = 0;
     {
         std::lock_guard<std::recursive_mutex> lk(p->mu);
@@ -385,8 +355,8 @@ DevPlan<T> make_dev_plan(const grbda_plan *p, const DeviceTables &t, bool rnea, 
     d.steps = rnea ? t.rnea_steps : t.aba_steps;
     d.n_steps = static_cast<int>(rnea ? h.rnea_steps.size() : h.aba_steps.size());
     int w = (sizeof(T) == 4 ? 0 : 1) + (fext ? 2 : 0);
-    // f32 fast path: the split layout when it exists for this kernel (GRBDA_NO_SPLIT=1 keeps the mixed one, for A/B runs)
-    const bool split = w == 0 && (rnea ? h.lay32s.split_rnea : h.lay32s.split_aba) && !p->no_split;
+    // f32 fast path: the split layout when it exists for this kernel
+    const bool split = w == 0 && (rnea ? h.lay32s.split_rnea : h.lay32s.split_aba);
     if (split) w = 4;
     const Layout &L = layout_of(h, w);
     d.clusters = rnea ? t.rnea_clusters[w] : t.clusters[w];
@@ -410,14 +380,14 @@ DevPlan<T> make_dev_plan(const grbda_plan *p, const DeviceTables &t, bool rnea, 
 template <class T>
 bool chain_covers(const grbda_plan *p)
 {
-    if (p->no_chain) return false;
+    if (p->opt.no_chain) return false;
     if (sizeof(T) == 8) return p->host.chain64.ok;
-    return p->host.chain32.ok || (p->host.chain32w.ok && p->host.chain32w.diffs.empty() && p->host.chain32w.gens.empty() && p->chain_wide);
+    return p->host.chain32.ok;
 }
 
 // which forward-dynamics kernel a batch of B states runs on a device with n_cu compute units: ONE definition, used by the launch
 // path below and by grbda_kernel_name (bench.py prints the name next to the roofline figures)
-enum AbaPath { ABA_GEN1, ABA_LM, ABA_LM4, ABA_CHAIN_WIDE, ABA_CHAIN, ABA_INTERPRETER };
+enum AbaPath { ABA_GEN1, ABA_LM, ABA_LM4, ABA_CHAIN, ABA_INTERPRETER };
 template <class T>
 size_t lm_lds_bytes(const grbda_plan *p, int n_waves = 2)
 {
@@ -447,20 +417,18 @@ AbaPath choose_aba(const grbda_plan *p, int n_cu, size_t B, bool f_ext)
     if (f_ext || !chain_covers<T>(p)) return ABA_INTERPRETER;
     const size_t n_tiles = (B + kWave - 1) / kWave;
     const ChainProgram &sp = sizeof(T) == 8 ? h.chain64 : h.chain32;
-    if (sp.ok && sp.single_gen && !p->chain_debug && gen1_lds_bytes<T>(p) <= 65536 && gen1_positions_fit(h.nq, sp.gens[0])) return ABA_GEN1;
+    if (sp.ok && sp.single_gen && gen1_lds_bytes<T>(p) <= 65536 && gen1_positions_fit(h.nq, sp.gens[0])) return ABA_GEN1;
     const ChainProgram &lp = sizeof(T) == 8 ? h.chain64p : h.chain32p;
     // four wavefronts per tile while that still leaves at most two wavefronts per SIMD (two tiles per CU); GRBDA_LM_WAVES=2 keeps two
     // (only the fp32 latency-mode kernels carry the differential segments: plan.cpp builds no fp64 program with them)
     const ChainProgram &lq = sizeof(T) == 8 ? h.chain64q : h.chain32q;
-    if (lq.ok && (sizeof(T) == 4 || lq.diffs.empty()) && !p->no_latency_mode && !p->chain_debug && p->lm_waves != 2 && n_tiles > 0 &&
+    if (lq.ok && (sizeof(T) == 4 || lq.diffs.empty()) && !p->opt.no_latency_mode && p->opt.lm_waves != 2 && n_tiles > 0 &&
         n_tiles <= static_cast<size_t>(n_cu) * 2 && lm_lds_bytes<T>(p, 4) <= 81920)
         return ABA_LM4;
-    if (lp.ok && (sizeof(T) == 4 || lp.diffs.empty()) && !p->no_latency_mode && !p->chain_debug && n_tiles <= static_cast<size_t>(n_cu) * 4 && n_tiles > 0 &&
+    if (lp.ok && (sizeof(T) == 4 || lp.diffs.empty()) && !p->opt.no_latency_mode && n_tiles <= static_cast<size_t>(n_cu) * 4 && n_tiles > 0 &&
         lm_lds_bytes<T>(p) <= 40960)
         return ABA_LM;
-    const bool wide = sizeof(T) == 4 && h.chain32w.ok && h.chain32w.diffs.empty() && h.chain32w.gens.empty() && p->chain_wide &&
-                      (!h.chain32.ok || n_tiles > static_cast<size_t>(n_cu) * 8);
-    return wide ? ABA_CHAIN_WIDE : ABA_CHAIN;
+    return ABA_CHAIN;
 }
 
 template <class T>
@@ -493,9 +461,9 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *q
             size_t per_cu = static_cast<size_t>(gen1_waves_per_simd<T>(sp.gens[0].n)) * 4;
             const size_t fit = lds_workgroups_per_cu(lds_total);
             if (fit < per_cu) per_cu = fit;
-            if (p->gen1_waves_cap > 0 && static_cast<size_t>(p->gen1_waves_cap) < per_cu) per_cu = static_cast<size_t>(p->gen1_waves_cap);
+            if (p->opt.gen1_waves_cap > 0 && static_cast<size_t>(p->opt.gen1_waves_cap) < per_cu) per_cu = static_cast<size_t>(p->opt.gen1_waves_cap);
             size_t grid = static_cast<size_t>(t.n_cu) * per_cu;
-            if (p->gen1_tiles_per_wave > 0) grid = (n_tiles0 + p->gen1_tiles_per_wave - 1) / p->gen1_tiles_per_wave;
+            if (p->opt.gen1_tiles_per_wave > 0) grid = (n_tiles0 + p->opt.gen1_tiles_per_wave - 1) / p->opt.gen1_tiles_per_wave;
             if (grid > n_tiles0) grid = n_tiles0;
             hipError_t e = launch_aba_gen1<T>(d, sp.gens[0].n, sp.gens[0].kind != 0, q, qd, tau, ydd, B, static_cast<int>(grid), lds_total,
                                               static_cast<hipStream_t>(stream));
@@ -544,14 +512,11 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *q
             return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba chain launch (latency mode)");
         }
     }
-    // f32: four wavefronts per SIMD (16 per CU, half the LDS each) once the batch fills them, when that layout exists
-    const bool wide = path == ABA_CHAIN_WIDE;
-    const int w = sizeof(T) == 8 ? 2 : (wide ? 1 : 0);
+    const int w = sizeof(T) == 8 ? 2 : 0;
     const int kid = sizeof(T) == 8 ? 1 : 0;
-    const ChainProgram &cp = w == 2 ? h.chain64 : (wide ? h.chain32w : h.chain32);
-    const size_t waves_per_cu = wide ? static_cast<size_t>(4 * kChainWideWps)
-                                     : static_cast<size_t>((sizeof(T) == 8 && !cp.gens.empty()) ? p->waves_per_cu_f64_wide_regs : p->waves_per_cu[kid]);
-    const size_t lds_budget = wide ? static_cast<size_t>(kChainWideLdsBytes) : static_cast<size_t>(p->lds_bytes_per_wave[kid]);
+    const ChainProgram &cp = w == 2 ? h.chain64 : h.chain32;
+    const size_t waves_per_cu = static_cast<size_t>((sizeof(T) == 8 && !cp.gens.empty()) ? p->opt.waves_per_cu_f64_wide_regs : p->opt.waves_per_cu[kid]);
+    const size_t lds_budget = static_cast<size_t>(p->opt.lds_bytes_per_wave[kid]);
     ChainDev<T> d;
     d.bad_count = t.bad_count;
     d.segs = t.chain_segs[w];
@@ -570,7 +535,7 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *q
     d.nv = h.nv;
     d.n_glb_slots = cp.n_glb;
     d.ori_repr = h.ori_repr;
-    d.debug = p->chain_debug;
+    d.debug = 0;
     d.sv_global = cp.sv_global ? 1 : 0;
     d.out_lds = cp.out_lds;
     d.fuse = d.stage_lds_v = d.stage_v_index = 0;
@@ -586,7 +551,6 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *q
         if (n_free_bwd == 1 && at_bwd + 1 < static_cast<int>(cp.segs.size()) && cp.segs[at_bwd + 1].op == SEG_FREE_ACC &&
             cp.segs[at_bwd + 1].first == cp.segs[at_bwd].first)
             d.fuse |= 2;
-        if (env_int("GRBDA_NO_FREE_FUSE", 0)) d.fuse = 0;
     }
     for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
     const size_t n_tiles = (B + kWave - 1) / kWave;
@@ -609,7 +573,7 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *q
     void *scratch = nullptr;
     if (int rc = ensure_scratch(p, device, stream, grid * n_rows * kWave * sizeof(T) + 256, &scratch)) return rc;
     hipError_t e = launch_aba_chain<T>(d, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_bytes,
-                                           static_cast<hipStream_t>(stream), wide);
+                                           static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba chain launch");
 }
 
@@ -624,7 +588,7 @@ template <class T>
 bool rnea_gen1_usable(const grbda_plan *p)
 {
     const RneaChainProgram &rp = sizeof(T) == 8 ? p->host.rchain64 : p->host.rchain32;
-    return rp.ok && rp.single_gen && !p->chain_debug && rnea_gen1_lds_bytes<T>(p) <= 65536 && gen1_positions_fit(p->host.nq, rp.gens[0]);
+    return rp.ok && rp.single_gen && rnea_gen1_lds_bytes<T>(p) <= 65536 && gen1_positions_fit(p->host.nq, rp.gens[0]);
 }
 
 // latency mode of the inverse dynamics: wavefronts per tile for a batch of B states (0: the one-wavefront kernels); ONE definition, used by the launch path
@@ -634,11 +598,11 @@ int choose_rnea_lm(const grbda_plan *p, int n_cu, size_t B)
 {
     const HostPlan &h = p->host;
     const size_t n_tiles = (B + kWave - 1) / kWave;
-    if (p->no_latency_mode || p->no_chain || n_tiles == 0) return 0;
+    if (p->opt.no_latency_mode || p->opt.no_chain || n_tiles == 0) return 0;
     const bool kid = sizeof(T) == 8;
     const RneaChainProgram &r4 = kid ? h.rchain64q : h.rchain32q, &r2 = kid ? h.rchain64p : h.rchain32p;
     const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(h.nq + 2 * h.nv) * sizeof(T);
-    if (r4.ok && r4.n_waves == 4 && (!kid || r4.diffs.empty()) && p->lm_waves != 2 && n_tiles <= static_cast<size_t>(n_cu) * 2 &&
+    if (r4.ok && r4.n_waves == 4 && (!kid || r4.diffs.empty()) && p->opt.lm_waves != 2 && n_tiles <= static_cast<size_t>(n_cu) * 2 &&
         std::max(static_cast<size_t>(r4.n_lds) * kWave * sizeof(T), stage_all) <= 81920)
         return 4;
     if (r2.ok && r2.n_waves == 2 && (!kid || r2.diffs.empty()) && n_tiles <= static_cast<size_t>(n_cu) * 4 && std::max(static_cast<size_t>(r2.n_lds) * kWave * sizeof(T), stage_all) <= 40960)
@@ -657,7 +621,7 @@ int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const
     // LDS of the two-per-SIMD shape (no global-slab fallback) run the program laid out for half the LDS per wavefront
     // once the batch fills 16 wavefronts per CU (MIT humanoid 0.105 -> 0.095 ms, Mini Cheetah 0.079 -> 0.070 ms; JVRC-1,
     // whose blocks spill already, loses)
-    const bool wide = sizeof(T) == 4 && !p->rnea_narrow && h.rchain32w.ok && h.rchain32.ok && h.rchain32.n_glb == 0 && h.rchain32.gens.empty() &&
+    const bool wide = sizeof(T) == 4 && h.rchain32w.ok && h.rchain32.ok && h.rchain32.n_glb == 0 && h.rchain32.gens.empty() &&
                       n_tiles > static_cast<size_t>(t.n_cu) * 8;
     const int w = wide ? 2 : kid;
     const RneaChainProgram &rp = wide ? h.rchain32w : (kid ? h.rchain64 : h.rchain32);
@@ -713,9 +677,9 @@ int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const
         size_t per_cu = static_cast<size_t>(rnea_gen1_waves_per_simd<T>(rp.gens[0].n)) * 4;
         const size_t fit = lds_workgroups_per_cu(lds_total);
         if (fit < per_cu) per_cu = fit;
-        if (p->gen1_waves_cap > 0 && static_cast<size_t>(p->gen1_waves_cap) < per_cu) per_cu = static_cast<size_t>(p->gen1_waves_cap);
+        if (p->opt.gen1_waves_cap > 0 && static_cast<size_t>(p->opt.gen1_waves_cap) < per_cu) per_cu = static_cast<size_t>(p->opt.gen1_waves_cap);
         size_t grid = static_cast<size_t>(t.n_cu) * per_cu;
-        if (p->gen1_tiles_per_wave > 0) grid = (n_tiles + p->gen1_tiles_per_wave - 1) / p->gen1_tiles_per_wave;
+        if (p->opt.gen1_tiles_per_wave > 0) grid = (n_tiles + p->opt.gen1_tiles_per_wave - 1) / p->opt.gen1_tiles_per_wave;
         if (grid > n_tiles) grid = n_tiles;
         hipError_t e = launch_rnea_gen1<T>(d, rp.gens[0].n, rp.gens[0].kind != 0, q, qd, ydd, tau, B, static_cast<int>(grid), lds_total,
                                            static_cast<hipStream_t>(stream));
@@ -739,8 +703,9 @@ int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const
     d.n_glb_slots = rp.n_glb;
     d.ori_repr = h.ori_repr;
     for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
-    const size_t waves_per_cu = wide ? static_cast<size_t>(4 * kChainWideWps) : static_cast<size_t>(p->waves_per_cu[kid]);  // the ABA launch shape: 8 wavefronts per CU
-    const size_t lds_budget = wide ? static_cast<size_t>(kChainWideLdsBytes) : static_cast<size_t>(p->lds_bytes_per_wave[kid]);
+    // (wide: four wavefronts per SIMD; otherwise the ABA launch shape, 8 wavefronts per CU)
+    const size_t waves_per_cu = wide ? static_cast<size_t>(16) : static_cast<size_t>(p->opt.waves_per_cu[kid]);
+    const size_t lds_budget = static_cast<size_t>(wide ? p->opt.chain32w_lds_bytes : p->opt.lds_bytes_per_wave[kid]);
     size_t grid = static_cast<size_t>(t.n_cu) * waves_per_cu;
     if (grid > n_tiles) grid = n_tiles;
     size_t lds_bytes = static_cast<size_t>(rp.n_lds) * kWave * sizeof(T);
@@ -788,13 +753,13 @@ int run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, con
     if (int rc = ensure_device(p, device, &t)) return rc;
     // chain-structured fast path (chain_kernels.hip): forward dynamics of models the chain program covers
     if (!rnea && !f_ext && chain_covers<T>(p)) return run_chain<T>(p, *t, q, qd, x, out, B, device, stream);
-    if (rnea && !f_ext && !p->no_chain && (sizeof(T) == 8 ? p->host.rchain64.ok : p->host.rchain32.ok))
+    if (rnea && !f_ext && !p->opt.no_chain && (sizeof(T) == 8 ? p->host.rchain64.ok : p->host.rchain32.ok))
         return run_rnea_chain<T>(p, *t, q, qd, x, out, B, device, stream);
     DevPlan<T> d = make_dev_plan<T>(p, *t, rnea, f_ext != nullptr);
     d.fext = f_ext;
     const size_t n_tiles = (B + kWave - 1) / kWave;
     const int kid = (rnea ? 2 : 0) + (sizeof(T) == 8 ? 1 : 0);
-    const size_t waves_per_cu = static_cast<size_t>(kid == 1 ? p->waves_per_cu_f64_wide_regs : p->waves_per_cu[kid]);
+    const size_t waves_per_cu = static_cast<size_t>(kid == 1 ? p->opt.waves_per_cu_f64_wide_regs : p->opt.waves_per_cu[kid]);
     size_t grid = static_cast<size_t>(t->n_cu) * waves_per_cu;
     if (grid > n_tiles) grid = n_tiles;
     const size_t n_glb = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);  // + staged inputs
@@ -806,7 +771,7 @@ int run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, con
     const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
     const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
     if (lds_bytes < stage_one) lds_bytes = stage_one;
-    if (lds_bytes < stage_all && stage_all <= static_cast<size_t>(p->lds_bytes_per_wave[kid])) lds_bytes = stage_all;
+    if (lds_bytes < stage_all && stage_all <= static_cast<size_t>(p->opt.lds_bytes_per_wave[kid])) lds_bytes = stage_all;
     d.lds_bytes = static_cast<int>(lds_bytes);
     // a CU holds 160 KiB of LDS: never launch more persistent wavefronts than can be resident at once
     const size_t fit = lds_workgroups_per_cu(lds_bytes);
@@ -896,7 +861,7 @@ int aux_setup(const grbda_plan *p, size_t B, int device, void *stream, DevPlan<T
     const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
     const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
     if (lb < stage_one) lb = stage_one;
-    if (lb < stage_all && stage_all <= static_cast<size_t>(p->lds_bytes_per_wave[kid])) lb = stage_all;
+    if (lb < stage_all && stage_all <= static_cast<size_t>(p->opt.lds_bytes_per_wave[kid])) lb = stage_all;
     d.lds_bytes = static_cast<int>(lb);
     *scratch = static_cast<T *>(sp);
     *grid = static_cast<int>(g);
@@ -1242,7 +1207,7 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
     const HostPlan &h = p->host;
     const ChainProgram &cp = sizeof(T) == 8 ? h.chain64 : h.chain32;
     // (programs with generic clusters -- plan.h, ChainGen -- have no walk steps in the force-propagation kernel: unit-wrench path)
-    if (p->no_chain || p->no_efpa || !cp.ok || !cp.gens.empty() || n_contacts > kOsimMaxContacts) return 1;
+    if (p->opt.no_chain || p->opt.no_efpa || !cp.ok || !cp.gens.empty() || n_contacts > kOsimMaxContacts) return 1;
     const Layout &L = h.lay64;
     OsimArgs<T> A;
     std::memset(&A, 0, sizeof A);
@@ -1384,7 +1349,7 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
     const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
     const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
     if (lds_bytes < stage_one) lds_bytes = stage_one;
-    if (lds_bytes < stage_all && stage_all <= static_cast<size_t>(p->lds_bytes_per_wave[kid])) lds_bytes = stage_all;
+    if (lds_bytes < stage_all && stage_all <= static_cast<size_t>(p->opt.lds_bytes_per_wave[kid])) lds_bytes = stage_all;
     d.lds_bytes = static_cast<int>(lds_bytes);
     const size_t n_rows = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);
     void *scratch = nullptr;
@@ -1569,11 +1534,11 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const int nq = p->host.nq, nv = p->host.nv;
-    if (mode == DM_MASS && p->host.crba.ok && !p->no_crba) {
+    if (mode == DM_MASS && p->host.crba.ok && !p->opt.no_crba) {
         // composite-rigid-body kernel (crba_kernels.hip): one launch instead of nv + 1 inverse-dynamics evaluations
         DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
         const size_t n_tiles = (B + kWave - 1) / kWave;
-        const size_t crba_waves = static_cast<size_t>(sizeof(T) == 4 ? p->crba_waves : std::min(p->crba_waves, 8));  // (fp64: 256 registers, two per SIMD)
+        const size_t crba_waves = static_cast<size_t>(sizeof(T) == 4 ? p->opt.crba_waves : std::min(p->opt.crba_waves, 8));  // (fp64: 256 registers, two per SIMD)
         size_t grid = static_cast<size_t>(t->n_cu) * crba_waves;
         if (grid > n_tiles) grid = n_tiles;
         void *scratch = nullptr;
@@ -1586,7 +1551,7 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
             // (JVRC-1, 131 072 states, f32: 1.10 against 1.65 ms for the plain layout; f64 about even)
             // whole groups of kDerivGroup states interleaved (crba_kernels.hip: a quarter of the open cache lines per store), the tail
             // of the batch state-major
-            const int il = unpack_symmetric_lds_bytes(nv, sizeof(T), kDerivGroup) <= 60 * 1024 && !env_int("GRBDA_CRBA_STATE_MAJOR", 0) ? kDerivGroup : 1;
+            const int il = unpack_symmetric_lds_bytes(nv, sizeof(T), kDerivGroup) <= 60 * 1024 ? kDerivGroup : 1;
             const size_t Bg = il > 1 ? B / il * il : 0;
             for (int part = 0; part < 2; part++) {
                 const size_t b0 = part == 0 ? 0 : Bg, nbp = part == 0 ? Bg : B - Bg;
@@ -1661,7 +1626,7 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
 template <class T>
 bool analytic_covers(const grbda_plan *p)
 {
-    return p->host.deriv.ok && p->host.crba.ok && !p->no_analytic && !p->no_crba && p->host.nv <= kWave;
+    return p->host.deriv.ok && p->host.crba.ok && !p->opt.no_analytic && !p->opt.no_crba && p->host.nv <= kWave;
 }
 // Forward / inverse dynamics through the spanning tree (HostPlan::projection_only; the reference's Projection-method cross-check,
 // RigidBodyTreeDynamics.cpp:86-97):  tau = G^T ID_s(q_s, G yd, G ydd + g);  ydd = (G^T H_s G)^-1 (tau - G^T ID_s(q_s, G yd, g)).
@@ -1792,7 +1757,7 @@ int projection_run_f32_through_f64(const grbda_plan *p, bool rnea, const float *
 template <class T>
 bool manifold_covers(const grbda_plan *p)
 {
-    return p->span && !p->no_manifold && !p->no_analytic && p->host.nv <= kWave && p->span->host.nv <= kWave &&
+    return p->span && !p->opt.no_manifold && !p->opt.no_analytic && p->host.nv <= kWave && p->span->host.nv <= kWave &&
            p->host.deriv.related.size() == static_cast<size_t>(p->host.nv);
 }
 template <class T>
@@ -1919,7 +1884,7 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     const bool need_d = dq || dqd;
     // H is built in the caller's d/dtau array when that is wanted (the factor is out of it before H^-1 goes in); dID/dq and
     // dID/dqd in rnea_deriv_kernel's packed layout, the H nobody asked for, and ydd take workspace
-    const bool wide0 = sizeof(T) == 4 && p->solve_f64;
+    const bool wide0 = sizeof(T) == 4 && p->opt.solve_f64;
     const int n_rhs = (dq ? 1 : 0) + (dqd ? 1 : 0);
     // (d / d tau alone: the CRBA kernel writes the same interleaved H and the matrix-core solve inverts it)
     // (fp64 stays state-major: its interleaved workspace was built and measured in round 4 -- MIT Humanoid 8 % faster, JVRC-1 36 % slower, the
@@ -1927,7 +1892,7 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     // H^-1 = W^T W from the articulated-body quantities (minv_kernels.hip): no H, no dense factorisation; f32 and f64 alike on the
     // matrix cores, both workspaces interleaved by groups of kDerivGroup states.  GRBDA_NO_MINV=1 keeps the factorisation route (A/B runs)
     const MinvProgram &mv = p->host.deriv.minv;
-    const bool minv = mv.ok && t->minv_bodies && t->minv_coltab && !wide0 && !p->no_minv &&
+    const bool minv = mv.ok && t->minv_bodies && t->minv_coltab && !wide0 && !p->opt.no_minv &&
                       minv_solve_lds_bytes(static_cast<int>(nv), n_rhs, mv.n_entries, sizeof(T)) <= 160u * 1024u;
     const int il = minv ? kDerivGroup : ((!wide0 && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs)) ? kDerivGroup : 1);
     // (only an INTERLEAVED H block can reach past the caller's array: the state-major layouts always build H in place)
@@ -2010,7 +1975,7 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
         if (grid > n_tiles) grid = n_tiles;
         const size_t rows = std::max(p->host.crba.n_rows, (need_d || minv) ? p->host.deriv.n_rows : 0);  // (the factor kernel of the minv route uses the recursion's rows)
         // (state-major results: three wavefronts per CU -- a fourth only adds open cache lines; interleaved: one per SIMD)
-        const size_t deriv_waves = p->deriv_waves ? static_cast<size_t>(p->deriv_waves) : (il > 1 ? 4 : 3);
+        const size_t deriv_waves = p->opt.deriv_waves ? static_cast<size_t>(p->opt.deriv_waves) : (il > 1 ? 4 : 3);
         const size_t slabs = std::max(grid, static_cast<size_t>(t->n_cu) * deriv_waves);  // (the factor kernel of the minv route runs n_cu * 8 wavefronts, as `grid`)
         void *scratch = nullptr;
         if (int rc = ensure_scratch(p, device, stream, slabs * rows * kWave * sizeof(T) + 256, &scratch)) return rc;
@@ -2036,7 +2001,7 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
                                      t->bad_count);
             if (e != hipSuccess) return hip_err(e, "articulated-inertia factor launch");
             size_t per_cu = static_cast<size_t>(minv_workgroups_per_cu<T>(static_cast<int>(nv), p->host.deriv.n_max, n_rhs, mv.n_entries));
-            if (p->minv_wpc > 0 && per_cu > static_cast<size_t>(p->minv_wpc)) per_cu = static_cast<size_t>(p->minv_wpc);
+            if (p->opt.minv_wpc > 0 && per_cu > static_cast<size_t>(p->opt.minv_wpc)) per_cu = static_cast<size_t>(p->opt.minv_wpc);
             size_t g3 = static_cast<size_t>(t->n_cu) * per_cu;
             const size_t units = (nb + kDerivGroup - 1) / kDerivGroup;
             if (g3 > units) g3 = units;
@@ -2046,7 +2011,7 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
             continue;
         }
         // one wavefront per state; as many as the LDS of a CU holds
-        const bool wide = sizeof(T) == 4 && p->solve_f64;
+        const bool wide = sizeof(T) == 4 && p->opt.solve_f64;
         const size_t lds = spd_solve_lds_bytes(static_cast<int>(nv), wide ? 8 : sizeof(T), (dq ? 1 : 0) + (dqd ? 1 : 0));
         size_t per_cu = lds ? lds_workgroups_per_cu(lds) : 16;
         const bool mfma = !wide && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs);
@@ -2073,7 +2038,7 @@ template <class T>
 int manifold_mass(const grbda_plan *p, const T *q, T *H, size_t B, int device, void *stream)
 {
     // models with implicit clusters: H = G^T H_s G through the spanning tree (manifold_kernels.hip) instead of nv + 1 inverse dynamics
-    if (!p || !q || !H || p->no_crba) return 1;
+    if (!p || !q || !H || p->opt.no_crba) return 1;
     GRBDA_CALL_SCOPE(p);
     if (!manifold_covers<T>(p)) return 1;
     return manifold_derivs<T>(p, q, nullptr, nullptr, nullptr, nullptr, nullptr, H, B, device, stream);
@@ -2100,7 +2065,6 @@ static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_
             case ABA_LM4:
                 std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_lm_kernel<%s, 4%s>", tn, (sizeof(T) == 8 ? h.chain64q : h.chain32q).diffs.empty() ? "" : ", true");
                 return buf;
-            case ABA_CHAIN_WIDE: std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_kernel<%s, %d, 0>", tn, kChainWideWps); return buf;
             case ABA_CHAIN:
                 std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_kernel<%s, %d, %d>", tn, (sizeof(T) == 8 && !cp.gens.empty()) ? 1 : 2,
                               !cp.gens.empty() ? 2 : (!cp.diffs.empty() ? 1 : 0));
@@ -2112,7 +2076,7 @@ static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_
         std::snprintf(buf, sizeof buf, "grbda_hip::aba_kernel<%s, %s>", tn, loop ? "true" : "false");
         return buf;
     }
-    const bool chain = !p->no_chain && (sizeof(T) == 8 ? h.rchain64.ok : h.rchain32.ok);
+    const bool chain = !p->opt.no_chain && (sizeof(T) == 8 ? h.rchain64.ok : h.rchain32.ok);
     if (chain) {
         const RneaChainProgram &rp = sizeof(T) == 8 ? h.rchain64 : h.rchain32;
         if (rnea_gen1_usable<T>(p)) {
@@ -2316,71 +2280,60 @@ static void build_related_table(HostPlan &h)
                 }
 }
 
-int grbda_plan_from_blob(const void *blob, size_t bytes, grbda_plan **out)
+}  // extern "C"
+
+namespace {
+
+// the GRBDA_* variables of INTEGRATION.md section 3 (PlanOptions): read once, when a plan is made
+PlanOptions plan_options_from_env()
+{
+    PlanOptions o;
+    auto flag = [](const char *name) { return env_int(name, 0) != 0; };
+    auto clamp = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
+    // launch shapes: GRBDA_LDS_BYTES_PER_WAVE / GRBDA_WAVES_PER_CU set all four kernels, the suffixed forms one of them
+    static const char *const suffix[4] = {"_ABA32", "_ABA64", "_RNEA32", "_RNEA64"};
+    for (int k = 0; k < 4; k++) {
+        int v = env_int("GRBDA_LDS_BYTES_PER_WAVE", o.lds_bytes_per_wave[k]);
+        v = env_int((std::string("GRBDA_LDS_BYTES_PER_WAVE") + suffix[k]).c_str(), v);
+        o.lds_bytes_per_wave[k] = clamp(v, 0, 160 * 1024);
+        int w = env_int("GRBDA_WAVES_PER_CU", o.waves_per_cu[k]);
+        w = env_int((std::string("GRBDA_WAVES_PER_CU") + suffix[k]).c_str(), w);
+        o.waves_per_cu[k] = clamp(w, 1, 32);
+    }
+    o.waves_per_cu_f64_wide_regs = clamp(env_int("GRBDA_WAVES_PER_CU_ABA64", env_int("GRBDA_WAVES_PER_CU", o.waves_per_cu_f64_wide_regs)), 1, 32);
+    o.gen1_waves_cap = env_int("GRBDA_GEN1_WAVES_PER_CU", o.gen1_waves_cap);
+    o.gen1_tiles_per_wave = env_int("GRBDA_GEN1_TILES_PER_WAVE", o.gen1_tiles_per_wave);
+    o.lm_waves = env_int("GRBDA_LM_WAVES", o.lm_waves);
+    o.minv_wpc = env_int("GRBDA_MINV_WPC", o.minv_wpc);
+    o.deriv_waves = std::max(0, env_int("GRBDA_DERIV_WAVES_PER_CU", o.deriv_waves));
+    o.crba_waves = env_int("GRBDA_CRBA_WAVES_PER_CU", o.crba_waves);
+    if (o.crba_waves < 1 || o.crba_waves > 16) o.crba_waves = 16;
+    // routes
+    o.no_chain = flag("GRBDA_NO_CHAIN");
+    o.no_latency_mode = flag("GRBDA_NO_LATENCY_MODE");
+    o.no_gen1 = std::getenv("GRBDA_NO_GEN1") != nullptr;
+    o.no_crba = flag("GRBDA_NO_CRBA");
+    o.no_minv = flag("GRBDA_NO_MINV");
+    o.solve_f64 = flag("GRBDA_SOLVE_F64");
+    o.no_analytic = flag("GRBDA_NO_ANALYTIC");
+    o.no_manifold = flag("GRBDA_NO_MANIFOLD");
+    o.no_small_constraint = flag("GRBDA_NO_SMALL_CONSTRAINT");
+    o.no_efpa = flag("GRBDA_NO_EFPA");
+    o.no_projection = std::getenv("GRBDA_NO_PROJECTION") != nullptr;
+    return o;
+}
+
+int plan_from_blob(const void *blob, size_t bytes, const PlanOptions &opt, grbda_plan **out)
 {
     if (!out) return set_err(GRBDA_EINVAL, "null out pointer");
     *out = nullptr;
     std::unique_ptr<grbda_plan> p(new (std::nothrow) grbda_plan());
     if (!p) return set_err(GRBDA_ENOMEM, "allocation failed");
     char msg[256] = {0};
-    // tuning knobs: GRBDA_LDS_BYTES_PER_WAVE / GRBDA_WAVES_PER_CU set all four kernels, the suffixed
-    // forms (_ABA32, _ABA64, _RNEA32, _RNEA64) one of them
-    static const char *const suffix[4] = {"_ABA32", "_ABA64", "_RNEA32", "_RNEA64"};
-    for (int k = 0; k < 4; k++) {
-        int v = env_int("GRBDA_LDS_BYTES_PER_WAVE", p->lds_bytes_per_wave[k]);
-        v = env_int((std::string("GRBDA_LDS_BYTES_PER_WAVE") + suffix[k]).c_str(), v);
-        p->lds_bytes_per_wave[k] = v < 0 ? 0 : (v > 160 * 1024 ? 160 * 1024 : v);
-        int w = env_int("GRBDA_WAVES_PER_CU", p->waves_per_cu[k]);
-        w = env_int((std::string("GRBDA_WAVES_PER_CU") + suffix[k]).c_str(), w);
-        p->waves_per_cu[k] = w < 1 ? 1 : (w > 32 ? 32 : w);
-    }
-    {
-        int w = env_int("GRBDA_WAVES_PER_CU", p->waves_per_cu_f64_wide_regs);
-        w = env_int("GRBDA_WAVES_PER_CU_ABA64", w);
-        p->waves_per_cu_f64_wide_regs = w < 1 ? 1 : (w > 32 ? 32 : w);
-    }
-    p->no_split = env_int("GRBDA_NO_SPLIT", 0) != 0;
-    p->no_minv = env_int("GRBDA_NO_MINV", 0) != 0;
-    p->minv_wpc = env_int("GRBDA_MINV_WPC", 0);
-    p->no_chain = env_int("GRBDA_NO_CHAIN", 0) != 0;
-    p->no_latency_mode = env_int("GRBDA_NO_LATENCY_MODE", 0) != 0;
-    p->lm_waves = env_int("GRBDA_LM_WAVES", 0);
-    p->gen1_waves_cap = env_int("GRBDA_GEN1_WAVES_PER_CU", 0);
-    p->gen1_tiles_per_wave = env_int("GRBDA_GEN1_TILES_PER_WAVE", 0);
-    p->chain_wide = env_int("GRBDA_CHAIN_WIDE", 0) != 0;
-#ifdef GRBDA_EXP
-    // ablation switches of tools/chain_ablate.py: results are WRONG when set, so the product library does not read them -- only
-    // the experiment builds do (make variant VFLAGS=-DGRBDA_EXP)
-    p->chain_debug = env_int("GRBDA_CHAIN_DEBUG", 0);
-#else
-    p->chain_debug = 0;
-#endif
-    p->no_crba = env_int("GRBDA_NO_CRBA", 0) != 0;
-    p->rnea_narrow = env_int("GRBDA_RNEA_NARROW", 0) != 0;
-    p->no_analytic = env_int("GRBDA_NO_ANALYTIC", 0) != 0;
-    p->solve_f64 = env_int("GRBDA_SOLVE_F64", 0) != 0;
-    p->crba_waves = env_int("GRBDA_CRBA_WAVES_PER_CU", 16);
-    if (p->crba_waves < 1 || p->crba_waves > 16) p->crba_waves = 16;
-    p->deriv_waves = env_int("GRBDA_DERIV_WAVES_PER_CU", 0);
-    if (p->deriv_waves < 0) p->deriv_waves = 0;
-    p->no_efpa = env_int("GRBDA_NO_EFPA", 0) != 0;
-    LdsBudget lds;
-    lds.aba32 = p->lds_bytes_per_wave[0] / (4 * kWave);
-    lds.aba64 = p->lds_bytes_per_wave[1] / (8 * kWave);
-    lds.rnea32 = p->lds_bytes_per_wave[2] / (4 * kWave);
-    lds.rnea64 = p->lds_bytes_per_wave[3] / (8 * kWave);
-    lds.chain32w = kChainWideLdsBytes / (4 * kWave);
-    // profiling aid (results are wrong when set): GRBDA_DEBUG_SWEEPS is a bit mask of the ABA sweeps to
-    // keep -- 1 forward, 2 backward, 4 acceleration -- so that the cost of each sweep can be ablated
-#ifdef GRBDA_EXP
-    const int sweeps = env_int("GRBDA_DEBUG_SWEEPS", 7);
-#else
-    const int sweeps = 7;
-#endif
-    int rc = compile_plan(blob, bytes, lds, sweeps, p->host, msg, sizeof msg);
+    p->opt = opt;
+    int rc = compile_plan(blob, bytes, p->opt, p->host, msg, sizeof msg);
     if (rc) return set_err(rc, msg);
     p->blob.assign(static_cast<const unsigned char *>(blob), static_cast<const unsigned char *>(blob) + bytes);
-    p->no_manifold = env_int("GRBDA_NO_MANIFOLD", 0) != 0;
     bool implicit = false;
     for (const ClusterRec &cr : p->host.lay64.clusters) implicit = implicit || cr.kind == CK_LOOP;
     // (plans with big clusters: up to 128 velocities -- tables instead of the one-word masks, build_related_table)
@@ -2390,7 +2343,7 @@ int grbda_plan_from_blob(const void *blob, size_t bytes, grbda_plan **out)
         std::vector<unsigned char> sb;
         if (make_spanning_blob(blob, bytes, sb, p->span_q, p->span_v, msg, sizeof msg) == 0) {
             grbda_plan *sp = nullptr;
-            if (grbda_plan_from_blob(sb.data(), sb.size(), &sp) == GRBDA_OK) {
+            if (plan_from_blob(sb.data(), sb.size(), p->opt, &sp) == GRBDA_OK) {
                 if (sp->host.nv <= (p->host.big_clusters ? 2 * kWave : kWave) && sp->host.deriv.ok) {
                     p->span = sp;
                     if (p->host.nv > kWave || sp->host.nv > kWave) {
@@ -2414,7 +2367,7 @@ int grbda_plan_from_blob(const void *blob, size_t bytes, grbda_plan **out)
                         if (cr.kind == CK_LOOP && (cr.k > 4 || cr.n > 2)) small = false;
                         if (cr.kind == CK_LOOP && cr.cons_type != 0) p->has_trig = true;
                     }
-                    p->constraint_shape = p->host.big_clusters ? 1 : (small && !env_int("GRBDA_NO_SMALL_CONSTRAINT", 0) ? 2 : 0);
+                    p->constraint_shape = p->host.big_clusters ? 1 : (small && !p->opt.no_small_constraint ? 2 : 0);
                 } else {
                     grbda_plan_free(sp);
                 }
@@ -2423,6 +2376,15 @@ int grbda_plan_from_blob(const void *blob, size_t bytes, grbda_plan **out)
     }
     *out = p.release();
     return GRBDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grbda_plan_from_blob(const void *blob, size_t bytes, grbda_plan **out)
+{
+    return plan_from_blob(blob, bytes, plan_options_from_env(), out);
 }
 
 int grbda_urdf_to_blob(const char *const *paths, int n_paths, int ori_repr, void *buf, size_t cap, size_t *needed)
@@ -2564,20 +2526,20 @@ int grbda_plan_info(const grbda_plan *p, grbda_plan_info_t *info)
     info->bytes_aba_f64 = (p->host.nq + 3.0 * p->host.nv) * 8;
     for (const BodyRec &b : p->host.lay32.bodies) info->n_axisym_bodies += b.axisym;
     for (const ClusterRec &c : p->host.lay32.clusters) info->n_carry_clusters += c.carry_out;
-    info->split_aba_f32 = p->host.lay32s.split_aba && !p->no_split;
-    info->split_rnea_f32 = p->host.lay32s.split_rnea && !p->no_split;
+    info->split_aba_f32 = p->host.lay32s.split_aba;
+    info->split_rnea_f32 = p->host.lay32s.split_rnea;
     info->n_lds_slots_split_f32 = p->host.lay32s.n_lds_aba;
-    info->chain_aba_f32 = p->host.chain32.ok && !p->no_chain;
+    info->chain_aba_f32 = p->host.chain32.ok && !p->opt.no_chain;
     info->n_lds_slots_chain_f32 = p->host.chain32.n_lds;
     info->n_chain_segments = static_cast<int>(p->host.chain32.segs.size());
-    info->chain_aba_f64 = p->host.chain64.ok && !p->no_chain;
-    info->chain_rnea_f32 = p->host.rchain32.ok && !p->no_chain;
-    info->chain_rnea_f64 = p->host.rchain64.ok && !p->no_chain;
+    info->chain_aba_f64 = p->host.chain64.ok && !p->opt.no_chain;
+    info->chain_rnea_f32 = p->host.rchain32.ok && !p->opt.no_chain;
+    info->chain_rnea_f64 = p->host.rchain64.ok && !p->opt.no_chain;
     info->analytic_derivatives = (analytic_covers<double>(p) || manifold_covers<double>(p)) ? 1 : 0;
-    info->n_chain_differentials = p->no_chain ? 0 : static_cast<int>(p->host.chain32.diffs.size());
-    info->latency_mode_f32 = p->host.chain32p.ok && !p->no_chain && !p->no_latency_mode;
-    info->latency_mode_f64 = p->host.chain64p.ok && !p->no_chain && !p->no_latency_mode;
-    info->n_chain_generic = p->no_chain ? 0 : static_cast<int>(p->host.chain32.gens.size());
+    info->n_chain_differentials = p->opt.no_chain ? 0 : static_cast<int>(p->host.chain32.diffs.size());
+    info->latency_mode_f32 = p->host.chain32p.ok && !p->opt.no_chain && !p->opt.no_latency_mode;
+    info->latency_mode_f64 = p->host.chain64p.ok && !p->opt.no_chain && !p->opt.no_latency_mode;
+    info->n_chain_generic = p->opt.no_chain ? 0 : static_cast<int>(p->host.chain32.gens.size());
     info->spanning_tree_route = p->host.projection_only ? 1 : 0;
     return GRBDA_OK;
 }
@@ -3067,50 +3029,6 @@ int grbda_time_kernel(const grbda_plan *p, int kind, int precision, const void *
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return rc;
-}
-
-// Experiment support (tools/spec_experiment.py): the f32 fast-path tables of a plan as C initialisers.
-int grbda_debug_dump_plan(const grbda_plan *p, const char *path)
-{
-    if (!p || !path) return set_err(GRBDA_EINVAL, "null argument");
-    FILE *f = std::fopen(path, "w");
-    if (!f) return set_err(GRBDA_EINVAL, "cannot open the dump file");
-    const HostPlan &h = p->host;
-    const Layout &L = h.lay32;
-    auto ints = [&](const char *type, const char *name, const void *data, size_t count, size_t per) {
-        const int32_t *v = static_cast<const int32_t *>(data);
-        std::fprintf(f, "__constant__ const %s %s[] = {\n", type, name);
-        for (size_t i = 0; i < count; i++) {
-            std::fprintf(f, "  {");
-            for (size_t j = 0; j < per; j++) std::fprintf(f, "%d,", v[i * per + j]);
-            std::fprintf(f, "},\n");
-        }
-        std::fprintf(f, "};\n");
-    };
-    std::fprintf(f, "constexpr int kSpecNq = %d, kSpecNv = %d, kSpecSteps = %d, kSpecLds = %d, kSpecGlb = %d, kSpecOri = %d;\n",
-                 h.nq, h.nv, (int)h.aba_steps.size(), L.n_lds_aba, L.n_glb_aba, h.ori_repr);
-    std::fprintf(f, "constexpr float kSpecARoot[6] = {");
-    for (int i = 0; i < 6; i++) std::fprintf(f, "%.9ef,", (float)-h.gravity[i]);
-    std::fprintf(f, "};\n");
-    // records as flat int initialisers (the structs are all-int32 PODs; nested arrays written as scalars)
-    std::fprintf(f, "__constant__ const int32_t kSpecStepsRaw[] = {");
-    for (const Step &st : h.aba_steps) std::fprintf(f, "%d,%d,0,0,", st.op, st.cluster);
-    std::fprintf(f, "};\n");
-    auto raw = [&](const char *name, const void *data, size_t n_ints) {
-        const int32_t *v = static_cast<const int32_t *>(data);
-        std::fprintf(f, "__constant__ const int32_t %s[] = {", name);
-        for (size_t i = 0; i < n_ints; i++) std::fprintf(f, "%d,", v[i]);
-        std::fprintf(f, "};\n");
-    };
-    raw("kSpecClustersRaw", L.clusters.data(), L.clusters.size() * sizeof(ClusterRec) / 4);
-    raw("kSpecBodiesRaw", L.bodies.data(), L.bodies.size() * sizeof(BodyRec) / 4);
-    raw("kSpecAccK", L.acc_k.data(), L.acc_k.size());
-    std::fprintf(f, "__constant__ const float kSpecConsts[] = {");
-    for (double c : h.consts) std::fprintf(f, "%.9ef,", (float)c);
-    std::fprintf(f, "};\n");
-    (void)ints;
-    std::fclose(f);
-    return GRBDA_OK;
 }
 
 int grbda_device_count(void)

@@ -24,9 +24,9 @@
 // generic clusters (gen_segments.h: aba_chain_kernel<T, 2, 2>), GRBDA_CHAIN_UNIT == 1 carries the two fp64 kernels with the deepest
 // register pressure -- aba_chain_lm_kernel<double, 2> and aba_chain_kernel<double, 2, true> (the program with differentials); unit 0
 // is everything else.  Both fp64 kernels spill, and how much depends on what else the compiler sees in the unit: measured in
-// one run against the single-unit build (tools/ab3.sh), Mini Cheetah fp64 at 65 536 states 0.0727 -> 0.0664 ms and TelloWithArms
-// fp64 3.60 -> 2.61 ms, every other kernel unchanged.  (Scheduler strategies were tried on top -- make variant
-// U1FLAGS="-mllvm -amdgpu-sched-strategy=max-ilp": same figures for these two, fp32 kernels as fast or faster with the default.)
+// one run against the single-unit build, Mini Cheetah fp64 at 65 536 states 0.0727 -> 0.0664 ms and TelloWithArms
+// fp64 3.60 -> 2.61 ms, every other kernel unchanged.  (Scheduler strategies were tried on top -- unit 1 with
+// -mllvm -amdgpu-sched-strategy=max-ilp: same figures for these two, fp32 kernels as fast or faster with the default.)
 #include <hip/hip_runtime.h>
 
 #include "devplan.h"
@@ -38,98 +38,10 @@
 // objects (ChainMem::glb_ld / glb_st below): a unit of its own, so that the slot test exists in no other kernel's text (as a member flag
 // that every other kernel sets to false it still moved TelloWithArms' kernel to 68 bytes of scratch).
 #define GRBDA_KLDS (GRBDA_CHAIN_UNIT == 3)
-// Which code paths use the permutation-structured transforms of devmath.h (rzp_*).  The defaults are what the same-run A/B
-// (tools/ab3.sh, library variants of `make variant VFLAGS=-DGRBDA_PERM_...`) kept: links, general rotors and pairs of the fp32
-// forward dynamics (JVRC-1 1.234 -> 1.178 ms per 2^20 states, TelloWithArms 0.801 -> 0.789, MIT Humanoid unchanged at 0.1495 --
-// its limbs are short and the time is not in the transforms); NOT the acceleration run, the inverse dynamics (JVRC-1 fp32
-// 0.665 -> 0.715 ms with them: the switch costs more than the products save) and the fp64 kernels (they spill; Tello fp64
-// 2.6 -> 3.7 ms with them).
-#ifndef GRBDA_PERM_LINK
-#define GRBDA_PERM_LINK 1
-#endif
-#ifndef GRBDA_PERM_ACC
-#define GRBDA_PERM_ACC 0
-#endif
-#ifndef GRBDA_PERM_ROTOR
-#define GRBDA_PERM_ROTOR 1
-#endif
-#ifndef GRBDA_PERM_PAIR
-#define GRBDA_PERM_PAIR 1
-#endif
-#ifndef GRBDA_PERM_RNEA
-#define GRBDA_PERM_RNEA 0
-#endif
-#ifndef GRBDA_PERM_F64
-#define GRBDA_PERM_F64 0
-#endif
 
 namespace grbda_hip {
 
 #include "devmath.h"
-
-// optional in-kernel cycle accounting of the chain kernel (make expc NAME=cprof DEFS=-DGRBDA_CHAIN_PROFILE, tools/chain_prof.py;
-// never in the shipped library): s_memtime deltas per tile phase and segment type, summed over wavefronts
-#ifdef GRBDA_CHAIN_PROFILE
-__device__ unsigned long long grbda_chain_prof[128];
-#define CPROF_T0() unsigned long long cprof_t = __builtin_amdgcn_s_memtime(), cprof_acc = 0, cprof_cnt = 0
-// lane i keeps bucket i (no memory traffic inside the tile loop); CPROF_END adds the lanes' buckets to the global table
-#define CPROF_ADD(i, n)                                                                   \
-    do {                                                                                  \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                     \
-        if (lane == (i)) {                                                                \
-            cprof_acc += now_ - cprof_t;                                                  \
-            cprof_cnt += (unsigned long long)(n);                                         \
-        }                                                                                 \
-        cprof_t = now_;                                                                   \
-    } while (0)
-#define CPROF_END()                                                                       \
-    do {                                                                                  \
-        if (lane < 32) {                                                                  \
-            atomicAdd(&grbda_chain_prof[lane], cprof_acc);                                \
-            atomicAdd(&grbda_chain_prof[32 + lane], cprof_cnt);                           \
-        }                                                                                 \
-        atomicAdd(&grbda_chain_prof[64 + lane], M.pacc);                                  \
-    } while (0)
-// marks inside a run's link loop: issue-time stamps (ordered behind the value `dep`), summed per interval into lane buckets 32.. of
-// a second per-lane accumulator that lives in ChainMem (M.pacc)
-#define CMARK(k, dep)                                                                     \
-    do {                                                                                  \
-        asm volatile("" ::"v"(dep) : "memory");                                           \
-        cm_[k] = __builtin_amdgcn_s_memtime();                                            \
-    } while (0)
-#define CMARK_DECL(n) unsigned long long cm_[n]
-#define CMARK_SUM(base, n)                                                                \
-    do {                                                                                  \
-        _Pragma("unroll") for (int k_ = 0; k_ + 1 < (n); k_++)                            \
-            if (M.lane == (base) + k_) M.pacc += cm_[k_ + 1] - cm_[k_];                   \
-    } while (0)
-#else
-#define CPROF_T0()
-#define CPROF_ADD(i, n)
-#define CPROF_END()
-#define CMARK(k, dep)
-#define CMARK_DECL(n)
-#define CMARK_SUM(base, n)
-#endif
-
-// Every load the wavefront has in flight has landed (vmcnt(0) of the gfx9 s_waitcnt encoding, the other counters untouched).  Placed in
-// the PREHEADER of the run loops: the first link's inputs are fetched there, and without it the compiler's wait-count pass must
-// assume at the top of EVERY iteration that those loads are still in flight with nothing issued behind them -- it then waits
-// vmcnt(0) at the loop top, which drains the [K | y0] stores of the link before (backward run) or the block just requested for the
-// next link (acceleration run: the prefetch bought nothing).  With the loads of the preheader retired the waits inside the loops
-// count exactly (vmcnt(7) behind seven stores).
-// which runs use the restructured link loops (A/B switch): 1 forward run in chunks, 2 branch-free backward run, 4 acceleration run in chunks,
-// 8 the chunked runs in two phases (parent-independent work of four links first, the recursion on register operands after)
-#ifndef GRBDA_CHUNK_MASK
-#define GRBDA_CHUNK_MASK 15
-#endif
-#ifndef GRBDA_DRAIN_MASK
-#define GRBDA_DRAIN_MASK 0
-#endif
-#define PREHEADER_DRAIN(bit)                                                \
-    do {                                                                    \
-        if constexpr ((GRBDA_DRAIN_MASK) & (bit)) __builtin_amdgcn_s_waitcnt(0x0F70); \
-    } while (0)
 
 template <class T>
 struct ChainTables {
@@ -147,12 +59,8 @@ struct ChainTables {
 };
 
 // LDS slots [slot][lane]; global slab rows [slot][lane]; the tile's inputs as coordinate-major slab rows
-// Slab rows through a buffer descriptor instead of pointers: an experiment switch (make variant VFLAGS=-DGRBDA_SLAB_BUFFER=1), OFF in
-// the product.  Measured in one run on one box (profiles/r6_slab_buffer_ab.txt): MIT Humanoid fp32 ABA 0.1427 -> 0.1449 ms, inverse
-// dynamics 0.0809 -> 0.0815, JVRC-1 even, TelloWithArms 0.848 -> 0.824 (-3 %), Mini Cheetah fp64 in latency mode 0.0657 -> 0.0778 (+18 %).
-#ifndef GRBDA_SLAB_BUFFER
-#define GRBDA_SLAB_BUFFER 0
-#endif
+// (Slab rows through one buffer descriptor instead of pointers were tried and dropped.  Measured in one run on one box (profiles/r6_slab_buffer_ab.txt): MIT Humanoid fp32 ABA 0.1427 -> 0.1449 ms, inverse
+// dynamics 0.0809 -> 0.0815, JVRC-1 even, TelloWithArms 0.848 -> 0.824 (-3 %), Mini Cheetah fp64 in latency mode 0.0657 -> 0.0778 (+18 %).)
 template <class T>
 struct ChainMem {
     T *glb_u;           // wave's global slots (after the input rows): wave-uniform base
@@ -165,11 +73,7 @@ struct ChainMem {
     // state is COUNTED (grbda_spd_bad_pivots, the counter of the derivative solves).  A wave-uniform mask on the scalar unit: one
     // v_cmp that writes an SGPR pair and one s_or per pivot.
     mutable unsigned long long bad;
-#ifdef GRBDA_EXP_NO_PIVOT  // (A/B builds: make variant VFLAGS=-DGRBDA_EXP_NO_PIVOT)
-    __device__ __forceinline__ void pivot(T) const {}
-#else
     __device__ __forceinline__ void pivot(T d) const { bad |= __builtin_amdgcn_ballot_w64(!(d > T(0))); }
-#endif
     // (end of a tile: `valid` = ballot of the lanes that hold a state of the batch)
     __device__ __forceinline__ void flush_bad(unsigned long long *counter, int rows_valid) const
     {
@@ -178,8 +82,10 @@ struct ChainMem {
         if (b && counter && lane == 0) atomicAdd(counter, (unsigned long long)__builtin_popcountll(b));
         bad = 0;
     }
-    int gmul;  // 1; 0 under GRBDA_CHAIN_DEBUG bit 3: every global slot aliases row 0 (same instructions, no slab traffic)
-    int amask; // ~0; kSlotGlobal under GRBDA_CHAIN_DEBUG bit 4: the slots that overflowed the LDS alias row 0, the [K | y0] blocks stay
+    // Always 1 and ~0 (they were the slab-traffic ablations of profiling builds).  Kept as members: without them the compiler
+    // orders the address arithmetic of the latency-mode kernels differently.
+    int gmul;  // multiplies every global slot number
+    int amask; // masks the slot number of an accumulator that overflowed the LDS
 
     template <int N>
     __device__ __forceinline__ void lds_ld(int s, T (&x)[N]) const
@@ -195,43 +101,6 @@ struct ChainMem {
 #pragma unroll
         for (int i = 0; i < N; i++) p[i * kWave] = x[i];
     }
-    // The wave's slab [input rows | global slots] through ONE buffer descriptor (GRBDA_SLAB_BUFFER=1): a row access is buffer_load /
-    // buffer_store with the lane's byte offset in the VGPR that every access of the kernel shares, the row's byte offset in an SGPR
-    // (one 32-bit shift) and the element's row inside the block as the instruction's immediate -- 32-bit address arithmetic only,
-    // where the pointer form makes the compiler form 64-bit row addresses (s_mov + s_lshl_b64 and, where the row number is a loop
-    // variable, a v_lshl_add_u64 per access: 554 -> 363 of them in the headline kernel's text).  It did not pay (see the switch).
-    __amdgpu_buffer_rsrc_t rs;
-    unsigned glb_b, q_b, qd_b, x_b, out_b;  // byte offsets of the regions inside the slab
-    static constexpr unsigned kRowBytes = kWave * (unsigned)sizeof(T);
-    __device__ __forceinline__ void set_slab(T *slab, int n_rows_total, int nq, int nv)
-    {
-        rs = __builtin_amdgcn_make_buffer_rsrc(slab, /*stride*/ 0, (int)((unsigned)n_rows_total * kRowBytes), 0x00020000);
-        q_b = 0;
-        qd_b = (unsigned)nq * kRowBytes;
-        x_b = (unsigned)(nq + nv) * kRowBytes;
-        out_b = x_b;
-        glb_b = (unsigned)(nq + 2 * nv) * kRowBytes;
-    }
-    // element at row byte offset `so` (wave-uniform) + `imm` (a constant: folds into the instruction) of this lane
-    __device__ __forceinline__ T bld(unsigned so, int imm) const
-    {
-        if constexpr (sizeof(T) == 4) {
-            return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)lane_b + imm, (int)so, 0));
-        } else {
-            typedef unsigned u2 __attribute__((ext_vector_type(2)));
-            const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)lane_b + imm, (int)so, 0);
-            return __builtin_bit_cast(T, v);
-        }
-    }
-    __device__ __forceinline__ void bst(unsigned so, int imm, T v) const
-    {
-        if constexpr (sizeof(T) == 4) {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, (int)lane_b + imm, (int)so, 0);
-        } else {
-            typedef unsigned u2 __attribute__((ext_vector_type(2)));
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), rs, (int)lane_b + imm, (int)so, 0);
-        }
-    }
     // GRBDA_KLDS (unit 3, aba_chain_lm_kernel<float, NW>): the program's "slab" blocks [K | y0] are LDS objects unless their slot number
     // carries kSlotGlobal (plan.cpp, build_chain's k_lds)
     template <int N>
@@ -243,15 +112,9 @@ struct ChainMem {
             return;
         }
 #endif
-#if GRBDA_SLAB_BUFFER
-        const unsigned so = glb_b + (unsigned)((s & ~kSlotGlobal) * gmul) * kRowBytes;
-#pragma unroll
-        for (int i = 0; i < N; i++) x[i] = bld(so, i * (int)kRowBytes);
-#else
         const char *p = reinterpret_cast<const char *>(glb_u + (size_t)(unsigned)((s & ~kSlotGlobal) * gmul * kWave));
 #pragma unroll
         for (int i = 0; i < N; i++) x[i] = *reinterpret_cast<const T *>(p + i * (kWave * (int)sizeof(T)) + (size_t)lane_b);
-#endif
     }
     template <int N>
     __device__ __forceinline__ void glb_st(int s, const T (&x)[N]) const
@@ -262,15 +125,9 @@ struct ChainMem {
             return;
         }
 #endif
-#if GRBDA_SLAB_BUFFER
-        const unsigned so = glb_b + (unsigned)((s & ~kSlotGlobal) * gmul) * kRowBytes;
-#pragma unroll
-        for (int i = 0; i < N; i++) bst(so, i * (int)kRowBytes, x[i]);
-#else
         char *p = reinterpret_cast<char *>(glb_u + (size_t)(unsigned)((s & ~kSlotGlobal) * gmul * kWave));
 #pragma unroll
         for (int i = 0; i < N; i++) *reinterpret_cast<T *>(p + i * (kWave * (int)sizeof(T)) + (size_t)lane_b) = x[i];
-#endif
     }
     // accumulators of branching bodies: LDS, or the global slab when the plan could not fit them (rare accesses)
     template <int N>
@@ -289,27 +146,14 @@ struct ChainMem {
     {
         return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base_u + (size_t)(unsigned)(j * kWave)) + (size_t)lane_b);
     }
-#if GRBDA_SLAB_BUFFER
-    __device__ __forceinline__ T q(int j) const { return bld(q_b + (unsigned)j * kRowBytes, 0); }
-    __device__ __forceinline__ T qd(int j) const { return bld(qd_b + (unsigned)j * kRowBytes, 0); }
-    __device__ __forceinline__ T x(int j) const { return bld(x_b + (unsigned)j * kRowBytes, 0); }
-#else
     __device__ __forceinline__ T q(int j) const { return row_ld(in_q_u, j); }
     __device__ __forceinline__ T qd(int j) const { return row_ld(in_qd_u, j); }
     __device__ __forceinline__ T x(int j) const { return row_ld(in_x_u, j); }
-#endif
-#ifdef GRBDA_CHAIN_PROFILE
-    mutable unsigned long long pacc;
-#endif
     int out_row;  // >= 0: the result rows [coordinate][lane] live in LDS from this row on (ChainProgram::out_lds); -1: in the slab
     // a result row read back (the differential's forward segment leaves a partial torque its backward segment completes)
     __device__ __forceinline__ T got(int j) const
     {
-#if GRBDA_SLAB_BUFFER
-        return bld(out_b + (unsigned)j * kRowBytes, 0);
-#else
         return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(out_u + (size_t)(unsigned)(j * kWave)) + (size_t)lane_b);
-#endif
     }
     // (forward dynamics: rows in LDS or in the slab)
     // (forward dynamics: rows in LDS or in the slab; a wave-uniform branch, so that the store is a DS or a GLOBAL instruction: a
@@ -333,11 +177,7 @@ struct ChainMem {
     }
     __device__ __forceinline__ void put(int j, T v) const
     {
-#if GRBDA_SLAB_BUFFER
-        bst(out_b + (unsigned)j * kRowBytes, 0, v);
-#else
         *reinterpret_cast<T *>(reinterpret_cast<char *>(out_u + (size_t)(unsigned)(j * kWave)) + (size_t)lane_b) = v;
-#endif
     }
 };
 
@@ -397,10 +237,16 @@ __device__ __forceinline__ void link_up_p(T s, T c, const R3 &r, const T (&h)[6]
     xforce_inv_p<T, K>(s, c, r, t, psic);
     congruence_p<T, K>(s, c, r, IA, IAc);
 }
+// Which code paths use the permutation-structured transforms of devmath.h (rzp_*).  What a same-run A/B of library builds kept:
+// links, general rotors and pairs of the fp32 forward dynamics (JVRC-1 1.234 -> 1.178 ms per 2^20 states, TelloWithArms 0.801 -> 0.789, MIT Humanoid unchanged at 0.1495 --
+// its limbs are short and the time is not in the transforms); NOT the acceleration run, the inverse dynamics (JVRC-1 fp32
+// 0.665 -> 0.715 ms with them: the switch costs more than the products save) and the fp64 kernels (they spill; Tello fp64
+// 2.6 -> 3.7 ms with them).
+constexpr bool kPermLink = true, kPermAcc = false, kPermRotor = true, kPermPair = true, kPermRnea = false, kPermF64 = false;
 template <class T>
 __device__ __forceinline__ int perm_if(bool on, int perm)
 {
-    return on && (GRBDA_PERM_F64 || sizeof(T) == 4) ? perm : -1;
+    return on && (kPermF64 || sizeof(T) == 4) ? perm : -1;
 }
 template <class T, class A21>
 __device__ __forceinline__ void link_up(int perm, T s, T c, cptr<T> C, const T (&h)[6], const T (&t)[6], const A21 &IA,
@@ -494,10 +340,7 @@ __device__ __forceinline__ void run_fwd(const ChainTables<T> &P, const ChainMem<
     // the inputs of the next link travel (global slab rows, L2 latency) while the current link is computed
     ChainLink l = load_rec(P.links + sg.first);
     T qi = M.q(l.q_index), qdi_in = M.qd(l.v_index);
-    PREHEADER_DRAIN(1);
     for (int i = 0; i < sg.count; i++) {
-        CMARK_DECL(6);
-        CMARK(0, vp[0]);
         const bool more = i + 1 < sg.count;
         const ChainLink ln = load_rec(P.links + (sg.first + (more ? i + 1 : i)));
         T qn = 0, qdn = 0;
@@ -509,12 +352,9 @@ __device__ __forceinline__ void run_fwd(const ChainTables<T> &P, const ChainMem<
         const T g0 = C[kBodyConstFixed];
         T blk[8], v[6];
         const T ang = g0 * qi;
-        CMARK(1, ang);
         sincos_t(ang, &blk[0], &blk[1]);
-        CMARK(2, blk[0]);
-        link_down(perm_if<T>(GRBDA_PERM_LINK, l.perm), blk[0], blk[1], C, vp, v);
+        link_down(perm_if<T>(kPermLink, l.perm), blk[0], blk[1], C, vp, v);
         v[2] += g0 * qdi_in;
-        CMARK(3, v[2]);
 #pragma unroll
         for (int j = 0; j < 6; j++) {
             blk[2 + j] = v[j];
@@ -522,12 +362,9 @@ __device__ __forceinline__ void run_fwd(const ChainTables<T> &P, const ChainMem<
         }
         if constexpr (SVG) M.acc_st(l.lds_sv, blk);
         else M.lds_st(l.lds_sv, blk);
-        CMARK(4, v[0]);
         l = ln;
         qi = qn;
         qdi_in = qdn;
-        CMARK(5, qi);
-        CMARK_SUM(0, 6);
     }
 }
 
@@ -539,11 +376,10 @@ constexpr int kChunk = 4;
 template <class T>
 __device__ __forceinline__ void run_fwd_c(const ChainTables<T> &P, const ChainMem<T> &M, const ChainSeg &sg)
 {
-    // Two phases per chunk (GRBDA_CHUNK_MASK bit 3): A -- everything of a link that does not depend on its parent (constants, sin / cos,
+    // Two phases per chunk: A -- everything of a link that does not depend on its parent (constants, sin / cos,
     // E = Rz(q) Et, the offset r, the joint rate), four links side by side: the scalar loads of all four are in flight together and the
     // arithmetic of one link fills the waits of another; B -- the recursion proper, v_i = X_i v_(i-1) + z qd_i, on REGISTER operands only
     // (no constant fetched on the critical path: the phase profile showed ~780 of a link's ~1 500 cycles in serialized scalar waits).
-    constexpr bool TWO_PHASE = ((GRBDA_CHUNK_MASK) & 8) != 0;
     T vp[6];
     for (int base = 0; base < sg.count; base += kChunk) {
         const int n = sg.count - base;
@@ -566,53 +402,33 @@ __device__ __forceinline__ void run_fwd_c(const ChainTables<T> &P, const ChainMe
                 for (int j = 0; j < 6; j++) vp[j] = 0;
             }
         }
-        if constexpr (TWO_PHASE) {
-            T E[kChunk][9], r[kChunk][3], sc[kChunk][2], gq[kChunk];
+        T E[kChunk][9], r[kChunk][3], sc[kChunk][2], gq[kChunk];
 #pragma unroll
-            for (int u = 0; u < kChunk; u++) {
-                if (u < n) {
-                    cptr<T> C = P.consts + L[u].cofs;
-                    const T g0 = C[kBodyConstFixed];
-                    sincos_t(g0 * qv[u], &sc[u][0], &sc[u][1]);
-                    rotate_z(sc[u][0], sc[u][1], C, E[u]);
+        for (int u = 0; u < kChunk; u++) {
+            if (u < n) {
+                cptr<T> C = P.consts + L[u].cofs;
+                const T g0 = C[kBodyConstFixed];
+                sincos_t(g0 * qv[u], &sc[u][0], &sc[u][1]);
+                rotate_z(sc[u][0], sc[u][1], C, E[u]);
 #pragma unroll
-                    for (int j = 0; j < 3; j++) r[u][j] = C[9 + j];
-                    gq[u] = g0 * qdv[u];
-                }
+                for (int j = 0; j < 3; j++) r[u][j] = C[9 + j];
+                gq[u] = g0 * qdv[u];
             }
+        }
 #pragma unroll
-            for (int u = 0; u < kChunk; u++) {
-                if (u < n) {
-                    T blk[8], v[6];
-                    xmotion(E[u], r[u], vp, v);
-                    v[2] += gq[u];
-                    blk[0] = sc[u][0];
-                    blk[1] = sc[u][1];
+        for (int u = 0; u < kChunk; u++) {
+            if (u < n) {
+                T blk[8], v[6];
+                xmotion(E[u], r[u], vp, v);
+                v[2] += gq[u];
+                blk[0] = sc[u][0];
+                blk[1] = sc[u][1];
 #pragma unroll
-                    for (int j = 0; j < 6; j++) {
-                        blk[2 + j] = v[j];
-                        vp[j] = v[j];
-                    }
-                    M.lds_st(L[u].lds_sv, blk);
+                for (int j = 0; j < 6; j++) {
+                    blk[2 + j] = v[j];
+                    vp[j] = v[j];
                 }
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < kChunk; u++) {
-                if (u < n) {
-                    cptr<T> C = P.consts + L[u].cofs;
-                    const T g0 = C[kBodyConstFixed];
-                    T blk[8], v[6];
-                    sincos_t(g0 * qv[u], &blk[0], &blk[1]);
-                    link_down(perm_if<T>(GRBDA_PERM_LINK, L[u].perm), blk[0], blk[1], C, vp, v);
-                    v[2] += g0 * qdv[u];
-#pragma unroll
-                    for (int j = 0; j < 6; j++) {
-                        blk[2 + j] = v[j];
-                        vp[j] = v[j];
-                    }
-                    M.lds_st(L[u].lds_sv, blk);
-                }
+                M.lds_st(L[u].lds_sv, blk);
             }
         }
     }
@@ -780,7 +596,7 @@ __device__ __forceinline__ void pair_bwd(const ChainTables<T> &P, const ChainMem
                                          T (&psi)[6])
 {
     // (the knee-ankle pairs of the MIT Humanoid: both tree rotations the identity)
-    if (perm_if<T>(GRBDA_PERM_PAIR, pr.perm[0]) == 0 && pr.perm[1] == 0) pair_bwd_k<T, OSIM, 0, 0>(P, M, pr, IA, psi);
+    if (perm_if<T>(kPermPair, pr.perm[0]) == 0 && pr.perm[1] == 0) pair_bwd_k<T, OSIM, 0, 0>(P, M, pr, IA, psi);
     else pair_bwd_k<T, OSIM, -1, -1>(P, M, pr, IA, psi);
 }
 
@@ -830,13 +646,7 @@ __device__ __forceinline__ void diff_constraint(const TB &P, const ChainMem<T> &
         const int as = ip[4 + 3 * i], ac = ip[5 + 3 * i], al = ip[6 + 3 * i];
         if (as >= 0 || ac >= 0) {
             T sn, cs;
-#ifdef GRBDA_EXP_DIFF_PRECISE
-            sincos_precise(a, &sn, &cs);
-#elif defined(GRBDA_EXP_DIFF_HW_SINCOS)
-            sincos_t(a, &sn, &cs);
-#else
             sincos_cw(a, &sn, &cs);  // (devmath.h: the hardware sine / cosine cost the fp32 differentials a decimal digit)
-#endif
             if (as >= 0) {
                 const T v[2] = {sn, cs};
                 M.lds_st(lds_w + as, v);
@@ -893,15 +703,7 @@ __device__ __forceinline__ void diff_constraint(const TB &P, const ChainMem<T> &
         K[r][0] = k0; K[r][1] = k1; K[r][2] = k2; K[r][3] = k3;
     }
     // Kd = K[:, links], Ki = K[:, rotors]
-#ifdef GRBDA_EXP_DIFF_DIV
-    const T idet = T(1) / (K[0][2] * K[1][3] - K[0][3] * K[1][2]);
-#elif defined(GRBDA_EXP_DIFF_F64DET)
-    const T idet = T(1.0 / ((double)K[0][2] * (double)K[1][3] - (double)K[0][3] * (double)K[1][2]));
-#elif defined(GRBDA_EXP_DIFF_DIVDET)
-    const T idet = T(1) / __builtin_fmaf(K[0][2], K[1][3], -(K[0][3] * K[1][2]));
-#else
     const T idet = rcp_t(K[0][2] * K[1][3] - K[0][3] * K[1][2]);
-#endif
     const T i00 = K[1][3] * idet, i01 = -K[0][3] * idet, i10 = -K[1][2] * idet, i11 = K[0][2] * idet;
     X[0] = -(i00 * K[0][0] + i01 * K[1][0]);
     X[1] = -(i00 * K[0][1] + i01 * K[1][1]);
@@ -1139,19 +941,6 @@ __device__ __forceinline__ void diff_bwd(const ChainTables<T> &P, const ChainMem
             psi[j] += tp[j];
         }
     }
-#if defined(GRBDA_EXP_DIFF_F64D)
-    const double idet_d = 1.0 / ((double)D00 * (double)D11 - (double)D01 * (double)D01);
-    const double j00 = (double)D11 * idet_d, j01 = -(double)D01 * idet_d, j11 = (double)D00 * idet_d;
-    const T i00 = (T)j00, i01 = (T)j01, i11 = (T)j11;
-    T blk[14];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        blk[j] = (T)(j00 * (double)F0[j] + j01 * (double)F1[j]);
-        blk[6 + j] = (T)(j01 * (double)F0[j] + j11 * (double)F1[j]);
-    }
-    blk[12] = (T)(j00 * (double)u0 + j01 * (double)u1);
-    blk[13] = (T)(j01 * (double)u0 + j11 * (double)u1);
-#elif !defined(GRBDA_EXP_DIFF_DET)
     // L L^T = D: l00 = sqrt(D00), l10 = D01 / l00, l11 = sqrt(D11 - l10^2) and triangular solves.  The closed-form inverse
     // (adjugate / determinant, round 2) lost a decimal digit on the differentials: D = G^T Hc G is nearly rank one when the
     // transmission X is large, the determinant cancels, and every entry of D^-1 F^T inherits its error; measured against the oracle
@@ -1170,18 +959,6 @@ __device__ __forceinline__ void diff_bwd(const ChainTables<T> &P, const ChainMem
 #pragma unroll
     for (int j = 0; j < 6; j++) solve2(F0[j], F1[j], blk[j], blk[6 + j]);
     solve2(u0, u1, blk[12], blk[13]);
-#else
-    const T idet = rcp_t(D00 * D11 - D01 * D01);
-    const T i00 = D11 * idet, i01 = -D01 * idet, i11 = D00 * idet;
-    T blk[14];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        blk[j] = i00 * F0[j] + i01 * F1[j];
-        blk[6 + j] = i01 * F0[j] + i11 * F1[j];
-    }
-    blk[12] = i00 * u0 + i01 * u1;
-    blk[13] = i01 * u0 + i11 * u1;
-#endif
     M.glb_st(d.glb_k, blk);
     if constexpr (OSIM) {  // D^-1 for the force-propagator walk of the contact frames (osim_chain_kernel)
         const T ex[3] = {i00, i01, i11};
@@ -1295,10 +1072,7 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
     T yd = M.qd(l.v_index), tau_in = M.x(l.v_index), y_in = M.q(l.q_index);
     T blk[8];  // [sin, cos, v 6] of the current link; SVG: in the global slab, fetched one link ahead
     if constexpr (SVG) M.acc_ld(l.lds_sv, blk);
-    PREHEADER_DRAIN(2);
     for (int i = 0; i < sg.count; i++) {
-        CMARK_DECL(8);
-        CMARK(0, IAc[0]);
         const bool more = i + 1 < sg.count;
         const ChainLink ln = load_rec(P.links + (sg.first + (more ? i + 1 : i)));
         T ydn = 0, taun = 0, yn = 0;
@@ -1323,7 +1097,6 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
         for (int j = 0; j < 6; j++) v[j] = blk[2 + j];
         T chat[6];
         vxz(v, qdi, chat);
-        CMARK(1, chat[0]);
 
         T IA[21], psi[6];
         bias_force(Ic, v, psi);
@@ -1337,18 +1110,16 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
         const T bj = psi[2] + h[0] * chat[0] + h[1] * chat[1] + h[3] * chat[3] + h[4] * chat[4];
         T u = tau_in - g0 * bj;
         T D = h[2] * g0 * g0;
-        CMARK(2, u);
         T F[6];
         {
             T t[6];
             symv_z(IA, chat, t);
 #pragma unroll
             for (int j = 0; j < 6; j++) t[j] += psi[j];
-            link_up(perm_if<T>(GRBDA_PERM_LINK, l.perm), blk[0], blk[1], C, h, t, IA, F, psic, IAc);
+            link_up(perm_if<T>(kPermLink, l.perm), blk[0], blk[1], C, h, t, IA, F, psic, IAc);
         }
 #pragma unroll
         for (int r = 0; r < 6; r++) F[r] *= g0;
-        CMARK(3, F[0]);
         if (ROT == 0 && l.rofs >= 0 && l.rpre < 0) {
             cptr<T> Cr = P.consts + l.rofs;
             cptr<T> Ir = Cr + 12;
@@ -1364,7 +1135,7 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
             }
             T sr, cr_, vr[6], crv[6], prr[6], hr[6];
             sincos_t(gr * y_in, &sr, &cr_);
-            link_down(perm_if<T>(GRBDA_PERM_ROTOR, l.rperm), sr, cr_, Cr, vp, vr);
+            link_down(perm_if<T>(kPermRotor, l.rperm), sr, cr_, Cr, vp, vr);
             vr[2] += qdr;
             vxz(vr, qdr, crv);
             bias_force(Ir, vr, prr);
@@ -1377,7 +1148,7 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
             symv_z(Ir, crv, t);
 #pragma unroll
             for (int j = 0; j < 6; j++) t[j] += prr[j];
-            link_up(perm_if<T>(GRBDA_PERM_ROTOR, l.rperm), sr, cr_, Cr, hr, t, Ir, fr, tp, Br);
+            link_up(perm_if<T>(kPermRotor, l.rperm), sr, cr_, Cr, hr, t, Ir, fr, tp, Br);
 #pragma unroll
             for (int r = 0; r < 6; r++) F[r] += fr[r] * gr;
 #pragma unroll
@@ -1411,7 +1182,6 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
 #pragma unroll
             for (int j = 0; j < 6; j++) psic[j] += tp[j];
         }
-        CMARK(4, psic[0]);
         const T Dinv = rcp_t(D);
         M.pivot(D);
         T kb[7];  // [K 6][y0]: what the acceleration run needs (it recomputes sin / cos from q: two slab rows less per link)
@@ -1423,14 +1193,12 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
             const T ex[3] = {blk[0], blk[1], Dinv};
             M.glb_st(l.glb_k + 7, ex);
         }
-        CMARK(5, kb[6]);
 #pragma unroll
         for (int r = 0; r < 6; r++) {
             psic[r] += F[r] * kb[6];
 #pragma unroll
             for (int cc = r; cc < 6; cc++) IAc[sidx(r, cc)] -= F[r] * kb[cc];
         }
-        CMARK(6, IAc[0]);
         l = ln;
         yd = ydn;
         tau_in = taun;
@@ -1441,8 +1209,6 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
                 for (int j = 0; j < 8; j++) blk[j] = blkn[j];
             }
         }
-        CMARK(7, yd);
-        CMARK_SUM(8, 8);
     }
     // hand the chain's projected inertia / bias to the body it hangs off
     if (sg.lds_acc_out != -1) {
@@ -1489,12 +1255,9 @@ __device__ __forceinline__ void run_acc(const ChainTables<T> &P, const ChainMem<
     T kb[7];
     M.glb_ld(l.glb_k, kb);
     T yd = M.qd(l.v_index), yq = l.has_child ? M.q(l.q_index) : T(0);
-    PREHEADER_DRAIN(4);
     for (int i = 0; i < sg.count; i++) {
         // the next link's record, [K | y0] block and inputs travel while this link is computed (the joint angle only for
         // links with children: the others need no transform here)
-        CMARK_DECL(5);
-        CMARK(0, ap[0]);
         const bool more = i + 1 < sg.count;
         const ChainLink ln = load_rec(P.links + (sg.first + (more ? i + 1 : i)));
         T kn[7], ydn = 0, yqn = 0;
@@ -1506,16 +1269,14 @@ __device__ __forceinline__ void run_acc(const ChainTables<T> &P, const ChainMem<
         T ydd = kb[6];
 #pragma unroll
         for (int r = 0; r < 6; r++) ydd -= kb[r] * ap[r];
-        CMARK(1, ydd);
         M.put_f(l.v_index, ydd);
-        CMARK(2, ydd);
         if (l.has_child) {
             cptr<T> C = P.consts + l.cofs;
             const T g0 = C[kBodyConstFixed];
             const T qdi = g0 * yd;
             T v[6], a[6], chat[6], sn, cs;
             sincos_t(g0 * yq, &sn, &cs);
-            link_down2(perm_if<T>(GRBDA_PERM_ACC, l.perm), sn, cs, C, vp, ap, v, a);
+            link_down2(perm_if<T>(kPermAcc, l.perm), sn, cs, C, vp, ap, v, a);
             v[2] += qdi;
             vxz(v, qdi, chat);
 #pragma unroll
@@ -1536,7 +1297,6 @@ __device__ __forceinline__ void run_acc(const ChainTables<T> &P, const ChainMem<
                 ap[j] = a[j];
             }
         }
-        CMARK(3, ap[0]);
         if (more) {
             l = ln;
             yd = ydn;
@@ -1544,8 +1304,6 @@ __device__ __forceinline__ void run_acc(const ChainTables<T> &P, const ChainMem<
 #pragma unroll
             for (int j = 0; j < 7; j++) kb[j] = kn[j];
         }
-        CMARK(4, kb[0]);
-        CMARK_SUM(20, 5);
     }
 }
 
@@ -1558,12 +1316,9 @@ __device__ __forceinline__ void run_acc_c(const ChainTables<T> &P, const ChainMe
 {
     // (two phases per chunk as in run_fwd_c: the recursion a_i = X_i a_(i-1) + c_i + z g0 ydd_i with ydd_i = y0_i - K_i a_(i-1) runs on
     // register operands prepared for all four links beforehand)
-    constexpr bool TWO_PHASE = ((GRBDA_CHUNK_MASK) & 8) != 0;
     T vp[6], ap[6];
     for (int base = 0; base < sg.count; base += kChunk) {
         const int n = sg.count - base;
-        CMARK_DECL(5);
-        CMARK(0, ap[0]);
         // (one basic block, see run_fwd_c; the input rows are requested BEFORE the [K | y0] blocks, so that phase A -- which needs only
         // them -- runs while the blocks are still on their way from the Infinity Cache)
         ChainLink L[kChunk];
@@ -1594,26 +1349,21 @@ __device__ __forceinline__ void run_acc_c(const ChainTables<T> &P, const ChainMe
                 }
             }
         }
-        CMARK(1, ap[0]);
-        CMARK(2, ap[0]);
         T E[kChunk][9], r[kChunk][3], g0v[kChunk], qdi[kChunk];
-        if constexpr (TWO_PHASE) {
 #pragma unroll
-            for (int u = 0; u < kChunk; u++) {
-                if (u < n && L[u].has_child) {
-                    cptr<T> C = P.consts + L[u].cofs;
-                    const T g0 = C[kBodyConstFixed];
-                    T sn, cs;
-                    sincos_t(g0 * yq[u], &sn, &cs);
-                    rotate_z(sn, cs, C, E[u]);
+        for (int u = 0; u < kChunk; u++) {
+            if (u < n && L[u].has_child) {
+                cptr<T> C = P.consts + L[u].cofs;
+                const T g0 = C[kBodyConstFixed];
+                T sn, cs;
+                sincos_t(g0 * yq[u], &sn, &cs);
+                rotate_z(sn, cs, C, E[u]);
 #pragma unroll
-                    for (int j = 0; j < 3; j++) r[u][j] = C[9 + j];
-                    g0v[u] = g0;
-                    qdi[u] = g0 * yd[u];
-                }
+                for (int j = 0; j < 3; j++) r[u][j] = C[9 + j];
+                g0v[u] = g0;
+                qdi[u] = g0 * yd[u];
             }
         }
-        CMARK(3, ap[1]);
 #pragma unroll
         for (int u = 0; u < kChunk; u++) {
             if (u < n) {
@@ -1624,27 +1374,13 @@ __device__ __forceinline__ void run_acc_c(const ChainTables<T> &P, const ChainMe
                 M.put_f(l.v_index, ydd);
                 if (l.has_child) {
                     T v[6], a[6], chat[6];
-                    if constexpr (TWO_PHASE) {
-                        xmotion(E[u], r[u], vp, v);
-                        xmotion(E[u], r[u], ap, a);
-                        v[2] += qdi[u];
-                        vxz(v, qdi[u], chat);
+                    xmotion(E[u], r[u], vp, v);
+                    xmotion(E[u], r[u], ap, a);
+                    v[2] += qdi[u];
+                    vxz(v, qdi[u], chat);
 #pragma unroll
-                        for (int j = 0; j < 6; j++) a[j] += chat[j];
-                        a[2] += g0v[u] * ydd;
-                    } else {
-                        cptr<T> C = P.consts + l.cofs;
-                        const T g0 = C[kBodyConstFixed];
-                        const T qd1 = g0 * yd[u];
-                        T sn, cs;
-                        sincos_t(g0 * yq[u], &sn, &cs);
-                        link_down2(perm_if<T>(GRBDA_PERM_ACC, l.perm), sn, cs, C, vp, ap, v, a);
-                        v[2] += qd1;
-                        vxz(v, qd1, chat);
-#pragma unroll
-                        for (int j = 0; j < 6; j++) a[j] += chat[j];
-                        a[2] += g0 * ydd;
-                    }
+                    for (int j = 0; j < 6; j++) a[j] += chat[j];
+                    a[2] += g0v[u] * ydd;
                     if (l.lds_va >= 0) {
                         T va[12];
 #pragma unroll
@@ -1662,8 +1398,6 @@ __device__ __forceinline__ void run_acc_c(const ChainTables<T> &P, const ChainMe
                 }
             }
         }
-        CMARK(4, ap[0]);
-        CMARK_SUM(20, 5);
     }
 }
 
@@ -1841,7 +1575,6 @@ __device__ __forceinline__ void gen1_tiles(int work_bytes, int nq, const T *__re
     M.glb_u = nullptr;
     M.in_q_u = M.in_qd_u = M.in_x_u = nullptr;
     M.out_u = nullptr;
-    M.set_slab(nullptr, 0, 0, 0);  // (the single-cluster kernels touch no slab)
     M.out_row = -1;
     M.out_f = nullptr;
     // LDS: [work area][q rows | qd rows | tau / ydd rows]   (nv = N: the cluster is the whole model)
@@ -1981,40 +1714,21 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
     ChainMem<T> M;
     M.lane = lane;
     M.lane_b = (unsigned)lane * (unsigned)sizeof(T);
-#ifdef GRBDA_EXP  // ablation builds only (make variant VFLAGS=-DGRBDA_EXP): the product kernels carry no wrong-result switches
-    const int dbg = DP.debug;
-#else
-    constexpr int dbg = 0;
-#endif
-    M.gmul = (dbg & 8) ? 0 : 1;
-    M.amask = (dbg & 16) ? kSlotGlobal : ~0;
+    M.gmul = 1;
+    M.amask = ~0;
     M.glb_u = slab + (size_t)(P.nq + 2 * P.nv) * kWave;
     M.in_q_u = slab;
     M.in_qd_u = slab + (size_t)P.nq * kWave;
     M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
     M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
-    M.set_slab(slab, DP.n_glb_slots + P.nq + 2 * P.nv, P.nq, P.nv);
     M.set_out(DP.out_lds);
     M.bad = 0;
-#ifdef GRBDA_CHAIN_PROFILE
-    M.pacc = 0;
-#endif
 
     const size_t n_tiles = (B + kWave - 1) / kWave;
-    CPROF_T0();
-#ifdef GRBDA_EXP
-    // experiment: the wavefronts in the odd slots of their SIMD start late by (debug >> 8) x 127 x 64 clocks, so that the two wavefronts of a
-    // SIMD do not stage their inputs (an HBM burst of the whole grid) and run their latency-bound phases at the same moment
-    if ((dbg >> 8) && (__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) & 1)) {  // HW_REG_HW_ID (4), offset 0, size 4: WAVE_ID
-        for (int i = 0; i < (dbg >> 8); i++) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t left = B - tile * kWave;
         const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
-        // (DP.debug: profiling aid of tools/chain_ablate.py -- bit 0 skips the prologue, bit 1 the segments, bit 2 the
-        // epilogue; results are then meaningless)
-        if (!(dbg & 1)) stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
+        stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
         if (DP.fuse & 1) {  // the floating base's velocity: from the lane's row of the staged block (still there) to its LDS slot
             const T *mine = reinterpret_cast<const T *>(grbda_smem) + (kWave * P.nq + lane * P.nv + DP.stage_v_index);
             T v[6];
@@ -2023,28 +1737,21 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
             wave_lds_fence();
             M.lds_st(DP.stage_lds_v, v);
         }
-        CPROF_ADD(0, 1);
-        for (int s = 0; s < ((dbg & 2) ? 0 : P.n_segs); s++) {
+        for (int s = 0; s < P.n_segs; s++) {
             const ChainSeg sg = load_rec(P.segs + s);
-            // (ablation builds: bits 5 / 6 / 7 skip the forward / backward / acceleration segments of every kind)
-            if ((dbg & 32) && (sg.op == SEG_RUN_FWD || sg.op == SEG_FREE_FWD)) continue;
-            if ((dbg & 64) && (sg.op == SEG_RUN_BWD || sg.op == SEG_FREE_BWD)) continue;
-            if ((dbg & 128) && (sg.op == SEG_RUN_ACC || sg.op == SEG_FREE_ACC || sg.op == SEG_PAIR_ACC)) continue;
             switch (sg.op) {
                 case SEG_RUN_FWD:
                     if (DP.sv_global) run_fwd<T, true>(P, M, sg);
-                    else if constexpr ((GRBDA_CHUNK_MASK) & 1) run_fwd_c(P, M, sg);
-                    else run_fwd<T, false>(P, M, sg);
+                    else run_fwd_c(P, M, sg);
                     break;
                 case SEG_RUN_BWD: {
                     if (DP.sv_global) run_bwd<T, false, true>(P, M, sg);
-                    else if (((GRBDA_CHUNK_MASK) & 2) && sg.rot_kind == 1) run_bwd<T, false, false, 1>(P, M, sg);
+                    else if (sg.rot_kind == 1) run_bwd<T, false, false, 1>(P, M, sg);
                     else run_bwd<T, false, false>(P, M, sg);
                     break;
                 }
                 case SEG_RUN_ACC:
-                    if constexpr ((GRBDA_CHUNK_MASK) & 4) run_acc_c(P, M, sg);
-                    else run_acc(P, M, sg);
+                    run_acc_c(P, M, sg);
                     break;
                 case SEG_PAIR_ACC: pair_acc(P, M, load_rec(P.pairs + sg.first)); break;
                 case SEG_FREE_FWD:
@@ -2073,17 +1780,11 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
                     if (!(DP.fuse & 2)) free_acc(P, M, load_rec(P.frees + sg.first));
                     break;
             }
-            CPROF_ADD((sg.op == SEG_RUN_BWD && sg.head == HEAD_PAIR) ? 20 : 2 + sg.op,
-                      sg.op == SEG_RUN_FWD || sg.op == SEG_RUN_BWD || sg.op == SEG_RUN_ACC ? sg.count : 1);
         }
-        if (!(dbg & 4)) {
-            if (M.out_row >= 0) write_outputs_lds<T>(M.out_row, ydd, tile, rows_valid, P.nv, lane);
-            else write_outputs(slab + (size_t)(P.nq + P.nv) * kWave, ydd, tile, rows_valid, P.nv, lane);
-        }
+        if (M.out_row >= 0) write_outputs_lds<T>(M.out_row, ydd, tile, rows_valid, P.nv, lane);
+        else write_outputs(slab + (size_t)(P.nq + P.nv) * kWave, ydd, tile, rows_valid, P.nv, lane);
         M.flush_bad(DP.bad_count, rows_valid);
-        CPROF_ADD(1, 1);
     }
-    CPROF_END();
 }
 
 
@@ -2139,7 +1840,6 @@ void aba_chain_lm_kernel(ChainDev<T> DP, const T *__restrict__ q, const T *__res
     M.in_qd_u = slab + (size_t)P.nq * kWave;
     M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
     M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
-    M.set_slab(slab, DP.n_glb_slots + P.nq + 2 * P.nv, P.nq, P.nv);
     M.set_out(DP.out_lds);
     const unsigned bq = (unsigned)(kWave * P.nq) * (unsigned)sizeof(T), bv = (unsigned)(kWave * P.nv) * (unsigned)sizeof(T);
 
@@ -2329,7 +2029,6 @@ __global__ __launch_bounds__(kWave, 1) void osim_chain_kernel(ChainDev<T> DP, Os
     M.in_qd_u = slab + (size_t)P.nq * kWave;
     M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
     M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
-    M.set_slab(slab, DP.n_glb_slots + P.nq + 2 * P.nv, P.nq, P.nv);
     M.set_out(-1);
     const int m = A.n_contacts, nv = P.nv;
     const size_t n_tiles = (B + kWave - 1) / kWave;
@@ -2688,24 +2387,14 @@ hipError_t launch_aba_chain_gen(const ChainDev<T> &P, const T *q, const T *qd, c
                                 size_t lds_bytes, hipStream_t stream);
 template <class T>
 hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch, int grid,
-                            size_t lds_bytes, hipStream_t stream, bool four_waves_per_simd)
+                            size_t lds_bytes, hipStream_t stream)
 {
-    if (P.n_gens > 0) {
-        if (four_waves_per_simd) return hipErrorInvalidValue;
-        return launch_aba_chain_gen<T>(P, q, qd, tau, ydd, B, scratch, grid, lds_bytes, stream);  // (unit 2)
-    }
+    if (P.n_gens > 0) return launch_aba_chain_gen<T>(P, q, qd, tau, ydd, B, scratch, grid, lds_bytes, stream);  // (unit 2)
     if (P.n_diffs > 0) {
-        if (four_waves_per_simd) return hipErrorInvalidValue;  // (capi.cpp keeps such programs at two wavefronts per SIMD)
         if constexpr (sizeof(T) == 8) {
             return launch_aba_chain_diff_f64(P, q, qd, tau, ydd, B, scratch, grid, lds_bytes, stream);  // (unit 1, below)
         } else {
             hipLaunchKernelGGL((aba_chain_kernel<T, 2, 1>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (sizeof(T) == 4) {
-        if (four_waves_per_simd) {
-            hipLaunchKernelGGL((aba_chain_kernel<T, kChainWideWps, 0>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
             return hipGetLastError();
         }
     }
@@ -2714,9 +2403,9 @@ hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const
 }
 #if GRBDA_CHAIN_UNIT == 0
 template hipError_t launch_aba_chain<float>(const ChainDev<float> &, const float *, const float *, const float *, float *, size_t,
-                                            float *, int, size_t, hipStream_t, bool);
+                                            float *, int, size_t, hipStream_t);
 template hipError_t launch_aba_chain<double>(const ChainDev<double> &, const double *, const double *, const double *, double *,
-                                             size_t, double *, int, size_t, hipStream_t, bool);
+                                             size_t, double *, int, size_t, hipStream_t);
 #elif GRBDA_CHAIN_UNIT == 1
 hipError_t launch_aba_chain_diff_f64(const ChainDev<double> &P, const double *q, const double *qd, const double *tau, double *ydd, size_t B,
                                      double *scratch, int grid, size_t lds_bytes, hipStream_t stream)
@@ -2731,12 +2420,8 @@ hipError_t launch_aba_chain_gen(const ChainDev<T> &P, const T *q, const T *qd, c
 {
     // fp64: ONE wavefront per SIMD.  At two the kernel spills 1 377 registers (768 B of scratch per lane); with 512 registers it needs 428 and
     // none -- teleop_arm 0.526 -> 0.247 ms, planar leg linkage 0.199 -> 0.108, a tree of triple clusters 0.703 -> 0.307 per 262 144 states
-    // (tools/ab_gen64.py; -DGRBDA_EXP_GEN64_WPS=2 rebuilds the old shape)
-#ifndef GRBDA_EXP_GEN64_WPS
-#define GRBDA_EXP_GEN64_WPS 1
-#endif
     if constexpr (sizeof(T) == 8)
-        hipLaunchKernelGGL((aba_chain_kernel<T, GRBDA_EXP_GEN64_WPS, 2>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
+        hipLaunchKernelGGL((aba_chain_kernel<T, 1, 2>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
     else
         hipLaunchKernelGGL((aba_chain_kernel<T, 2, 2>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
     return hipGetLastError();
@@ -2860,7 +2545,7 @@ __device__ __forceinline__ void rnea_run_fwd(const RneaTables<T> &P, const Chain
         const T qdi = g0 * ydi;
         T blk[9], v[6], a[6], f[6];
         sincos_t(g0 * qi, &blk[6], &blk[7]);
-        link_down2(perm_if<T>(GRBDA_PERM_RNEA, l.perm), blk[6], blk[7], C, vp, ap, v, a);
+        link_down2(perm_if<T>(kPermRnea, l.perm), blk[6], blk[7], C, vp, ap, v, a);
         v[2] += qdi;
         a[0] += v[1] * qdi;
         a[1] -= v[0] * qdi;
@@ -2883,7 +2568,7 @@ __device__ __forceinline__ void rnea_run_fwd(const RneaTables<T> &P, const Chain
             const T qdr = gr * ydi;
             T sr, cr_, vr[6], ar[6], fr[6], fpr[6];
             sincos_t(gr * qi, &sr, &cr_);
-            link_down2(perm_if<T>(GRBDA_PERM_RNEA, l.rperm), sr, cr_, Cr, vp, ap, vr, ar);
+            link_down2(perm_if<T>(kPermRnea, l.rperm), sr, cr_, Cr, vp, ap, vr, ar);
             vr[2] += qdr;
             ar[0] += vr[1] * qdr;
             ar[1] -= vr[0] * qdr;
@@ -2892,7 +2577,7 @@ __device__ __forceinline__ void rnea_run_fwd(const RneaTables<T> &P, const Chain
             ar[2] += gr * yddi;
             body_force_c(Cr + 12, vr, ar, fr);
             blk[8] = gr * fr[2];
-            link_force_up(perm_if<T>(GRBDA_PERM_RNEA, l.rperm), sr, cr_, Cr, fr, fpr);
+            link_force_up(perm_if<T>(kPermRnea, l.rperm), sr, cr_, Cr, fr, fpr);
             if (l.lds_pf >= 0) add6<T, GLB>(M, l.lds_pf, fpr);
         }
 #pragma unroll
@@ -2933,7 +2618,7 @@ __device__ __forceinline__ void rnea_run_bwd(const RneaTables<T> &P, const Chain
 #pragma unroll
         for (int j = 0; j < 6; j++) ft[j] = blk[j] + fc[j];
         M.put(l.v_index, C[kBodyConstFixed] * ft[2] + blk[8]);
-        link_force_up(perm_if<T>(GRBDA_PERM_RNEA, l.perm), blk[6], blk[7], C, ft, fc);
+        link_force_up(perm_if<T>(kPermRnea, l.perm), blk[6], blk[7], C, ft, fc);
     }
     if (sg.lds_pf >= 0) add6<T, GLB>(M, sg.lds_pf, fc);
 }
@@ -3179,18 +2864,13 @@ __global__ __launch_bounds__(kWave, 2) void rnea_chain_kernel(RneaChainDev<T> DP
     M.in_qd_u = slab + (size_t)P.nq * kWave;
     M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
     M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
-    M.set_slab(slab, DP.n_glb_slots + P.nq + 2 * P.nv, P.nq, P.nv);
     M.set_out(-1);
     const size_t n_tiles = (B + kWave - 1) / kWave;
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t left = B - tile * kWave;
         const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
         stage_inputs(q, qd, ydd, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
-#ifdef GRBDA_EXP_RNEA_NO_SEGS  // (ablation build, results wrong: the tile's staging and epilogue alone -- profiles/r6_rnea_occupancy.txt)
-        for (int s = 0; s < 0; s++) {
-#else
         for (int s = 0; s < P.n_segs; s++) {
-#endif
             const RneaSeg sg = load_rec(P.segs + s);
             switch (sg.op) {
                 case RSEG_RUN_FWD: rnea_run_fwd<T, GLB>(P, M, sg); break;
@@ -3258,7 +2938,6 @@ void rnea_chain_lm_kernel(RneaChainDev<T> DP, const T *__restrict__ q, const T *
     M.in_qd_u = slab + (size_t)P.nq * kWave;
     M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
     M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
-    M.set_slab(slab, P.nq + 2 * P.nv, P.nq, P.nv);
     M.set_out(-1);
     const unsigned bq = (unsigned)(kWave * P.nq) * (unsigned)sizeof(T), bv = (unsigned)(kWave * P.nv) * (unsigned)sizeof(T);
     const size_t n_tiles = (B + kWave - 1) / kWave;
@@ -3471,17 +3150,6 @@ template hipError_t launch_rnea_chain<double>(const RneaChainDev<double> &, cons
                                               size_t, double *, int, size_t, hipStream_t);
 #endif
 
-#if defined(GRBDA_CHAIN_PROFILE) && GRBDA_CHAIN_UNIT == 0
-extern "C" int grbda_debug_chain_profile(unsigned long long *out, int reset)
-{
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(grbda_chain_prof), sizeof(unsigned long long) * 128) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[128] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(grbda_chain_prof), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
 
 static hipError_t set_max_dynamic_lds(const void *const *kernels, int n)
 {
@@ -3499,7 +3167,6 @@ hipError_t set_max_dynamic_lds_chain()
 {
     const void *const kernels[] = {
         reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 0>), reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 1>),
-        reinterpret_cast<const void *>(&aba_chain_kernel<float, 4, 0>),
         reinterpret_cast<const void *>(&aba_chain_kernel<double, 2, 0>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<float, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<float, 1, false>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<double, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<double, 1, false>),

@@ -34,42 +34,6 @@ namespace grbda_hip {
 
 #include "devmath.h"
 
-// optional in-kernel cycle accounting of the derivative recursion (make expd NAME=dprof DEFS=-DGRBDA_DERIV_PROFILE, tools/deriv_prof.py;
-// never in the shipped library): s_memtime deltas per phase, lane i keeps bucket i, summed over wavefronts at the end
-#ifdef GRBDA_DERIV_PROFILE
-__device__ unsigned long long grbda_deriv_prof[64];
-#define DPROF_T0() unsigned long long dprof_t = __builtin_amdgcn_s_memtime(), dprof_acc = 0, dprof_cnt = 0
-#define DPROF_ADD(i)                                                                      \
-    do {                                                                                  \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                     \
-        if (lane == (i)) {                                                                \
-            dprof_acc += now_ - dprof_t;                                                  \
-            dprof_cnt += 1;                                                               \
-        }                                                                                 \
-        dprof_t = now_;                                                                   \
-    } while (0)
-#define DPROF_END()                                                                       \
-    do {                                                                                  \
-        if (lane < 32) {                                                                  \
-            atomicAdd(&grbda_deriv_prof[lane], dprof_acc);                                \
-            atomicAdd(&grbda_deriv_prof[32 + lane], dprof_cnt);                           \
-        }                                                                                 \
-    } while (0)
-extern "C" int grbda_debug_deriv_profile(unsigned long long *out, int reset)
-{
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(grbda_deriv_prof), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[64] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(grbda_deriv_prof), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#else
-#define DPROF_T0()
-#define DPROF_ADD(i)
-#define DPROF_END()
-#endif
-
 // ---------------------------------------------------------------------------------------------------------------
 // spatial helpers in the common frame
 // ---------------------------------------------------------------------------------------------------------------
@@ -228,35 +192,18 @@ struct PartStore {
 // was bound by that (round 3, calibrated FETCH_SIZE / WRITE_SIZE).  Interleaving four states makes every store a run of
 // 16-byte pieces, a quarter of the open lines (measured 2.2 -> 1.45 ms per 131 072 states at four wavefronts per CU;
 // factors 8, 16 and 64 add 2-4 % more and cost the solve its cooperative 4-wavefront copy).
-// (experiment builds: -DGRBDA_EXP_DERIV_WPS=2 asks for two wavefronts per SIMD, -DGRBDA_EXP_PART_LDS keeps the carried composites in LDS
-// for fp32 too)
-#ifndef GRBDA_EXP_DERIV_WPS
-#define GRBDA_EXP_DERIV_WPS 1
-#endif
-// (experiment builds: -DGRBDA_EXP_ANC_LEVELS=n keeps n levels of the ancestor-row cache in LDS instead of kDerivAncLevels -- the cache is 4.6 KB per
-// level and wavefront, 36.9 KB at eight levels: FOUR wavefronts per CU whatever the register count)
-// Round 5: the cache is OFF by default (0 levels) -- with it or without it the kernel takes the same time (28.0 against 28.7 ms per million
+// One wavefront per SIMD.  The ancestor-row cache in LDS is 4.6 KB per level and wavefront, 36.9 KB at eight levels: FOUR wavefronts
+// per CU whatever the register count.  Round 5: the cache is OFF (0 levels) -- with it or without it the kernel takes the same time (28.0 against 28.7 ms per million
 // JVRC-1 states, profiles/r5_deriv_recursion_experiments.txt) -- and its LDS holds the tile's staged inputs instead (kStageInputsF32).
-#ifndef GRBDA_EXP_ANC_LEVELS
-#define GRBDA_EXP_ANC_LEVELS 0
-#endif
 // fp32: the tile's q / qd / ydd blocks are copied to LDS once (coalesced LDS-DMA, as the chain kernels stage theirs) and every body reads its
 // coordinates from the lane's own row there.  Read straight from the caller's arrays they are 4-byte accesses 150 bytes apart: 64 cache
 // lines per load instruction, three loads per body in pass 1 and again per leaf body in pass 2 -- the counters showed 27 KB fetched per state
 // for a kernel whose slab rows account for 12 (profiles/r5_rocprofv3_pmc_derivatives.txt; the kernel moves 4.5 TB/s at the fabric).
-#ifndef GRBDA_EXP_NO_STAGE
 constexpr bool kStageInputsF32 = true;
-#else
-constexpr bool kStageInputsF32 = false;
-#endif
-constexpr int kAncLevelsLds = GRBDA_EXP_ANC_LEVELS;
-#ifdef GRBDA_EXP_PART_LDS
-constexpr bool kPartLdsF32 = true;
-#else
+constexpr int kAncLevelsLds = 0;
 constexpr bool kPartLdsF32 = false;
-#endif
 template <class T, int NMAX, int IL>
-__global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(DevPlan<T> DP, const DerivBody *__restrict__ db_, int n_clusters, int n_rows,
+__global__ __launch_bounds__(kWave, 1) void rnea_deriv_kernel(DevPlan<T> DP, const DerivBody *__restrict__ db_, int n_clusters, int n_rows,
                                                               const T *__restrict__ q, const T *__restrict__ qd,
                                                               const T *__restrict__ ydd, T *__restrict__ Dq, T *__restrict__ Dqd,
                                                               T *__restrict__ H, size_t B, T *__restrict__ scratch)
@@ -269,15 +216,10 @@ __global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(
     Rows<T> R;
     R.p = scratch + (size_t)blockIdx.x * (size_t)n_rows * kWave + lane;
     const size_t n_tiles = (B + kWave - 1) / kWave;
-    DPROF_T0();
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t r = tile * kWave + lane;
         const size_t st = r < B ? r : B - 1;  // lanes past the end redo the last state and do not store
-#ifdef GRBDA_EXP_NO_STORE
-        const bool live = r < B && DP.nq < 0;
-#else
         const bool live = r < B;
-#endif
         const T *qs = q + st * (size_t)nq, *qds = qd + st * (size_t)nv, *ydds = ydd + st * (size_t)nv;
         if constexpr (sizeof(T) == 4 && kStageInputsF32) {
             // (lanes past the end of the batch read the last valid row, as they redo the last state)
@@ -436,7 +378,6 @@ __global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(
                 for (int j = 0; j < 24; j++) last_kin[j] = kin[j];
             }
         }
-        DPROF_ADD(0);   // pass 1
         // ---- pass 2, leaf side first ----
         PartStore<T, sizeof(T) == 8 || kPartLdsF32> part;  // what the in-cluster roots of a cluster hand to the parent body: one read-modify-write per cluster, or
                      // no memory traffic at all along chains (DerivBody::carry_out: it stays here for the next cluster)
@@ -498,7 +439,6 @@ __global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(
                         }
                     }
                 }
-                DPROF_ADD(4);   // base cluster
                 continue;
             }
             const int n = cr.n;
@@ -613,7 +553,6 @@ __global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(
 #pragma unroll
                     for (int j = 0; j < 6; j++) Fc[j] += acc[57 + j];
                 }
-                DPROF_ADD(1);   // body: records, kinematics (loads or recomputed), composites
                 // descendant-side vectors of this joint (Pd = Sd for a revolute joint)
                 T t1[6], t2[6], t3[6], t4[6];
                 mtv6(Bc, S, t1);
@@ -708,7 +647,6 @@ __global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(
                     for (int j = 0; j < 6; j++) part.set(57 + j, part.get(57 + j) + Fc[j]);
                 }
             }
-            DPROF_ADD(2);   // body: joint terms, in-cluster ancestors, hand-over
             if (cr.parent_body >= 0 && !xf.carry_out) {
                 const DerivBody xp = load_rec(db + cr.parent_body);
                 T out[63];
@@ -733,13 +671,8 @@ __global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(
                             put_h(cr.v_index + a2, cr.v_index + b2, Ch[a2][b2]);
                         }
             }
-            DPROF_ADD(3);   // accumulator row of the parent body, the cluster's own entries stored
             // ---- up the ancestors outside the cluster, block by block ----
-#ifdef GRBDA_EXP_NO_WALK
-            int j = -1;
-#else
             int j = cr.parent_body;
-#endif
             while (j >= 0) {
                 const DerivBody xj = load_rec(db + j);
                 const ClusterRec cd = load_rec(clusters + xj.cluster);
@@ -836,15 +769,11 @@ __global__ __launch_bounds__(kWave, GRBDA_EXP_DERIV_WPS) void rnea_deriv_kernel(
                             }
                 }
                 j = next;
-                DPROF_ADD(5);   // one ancestor cluster of the walk (rows, dot products, stores)
             }
-            DPROF_ADD(6);   // walk: the base's columns, loop exit
         }
-        DPROF_ADD(7);
         // entries between clusters on different branches are structural zeros: never written, and never read by the solve
         // (DerivProgram::related)
     }
-    DPROF_END();
 }
 
 template <class T, int IL>
@@ -903,7 +832,7 @@ template hipError_t launch_rnea_deriv<double>(const DevPlan<double> &, const Der
 // whatever the arrays hold.  Global traffic: every matrix read / written once.  TIO: array element type; TC: arithmetic.
 // ---------------------------------------------------------------------------------------------------------------
 // f32 solves run on the matrix cores (spd_mfma_kernel) when a workgroup's tiles and right-hand sides fit the LDS of a CU (nv <= 48
-// with two right-hand sides) and GRBDA_SOLVE_VALU=1 does not keep the triangular solves (A/B runs)
+// with two right-hand sides)
 static size_t spd_mfma_lds_bytes(int nv, int n_rhs)
 {
     const int nvb = nv <= 16 ? 16 : (nv <= 24 ? 24 : (nv <= 32 ? 32 : (nv <= 40 ? 40 : (nv <= 48 ? 48 : 64))));
@@ -914,15 +843,11 @@ static size_t spd_mfma_lds_bytes(int nv, int n_rhs)
 // wavefronts per SIMD (= workgroups per CU) of the matrix-core solve for nv <= 24: the kernel is bound by the issue of mostly dependent
 // instruction chains, which a third wavefront fills in -- MIT Humanoid all three matrices 3.03 -> 2.75 ms per 262 144 states, Mini Cheetah
 // 0.675 -> 0.614 per 65 536; a fourth costs spills (3.03); nv > 24 needs the registers (246 .. 256) and the LDS of two
-// (experiment builds: -DGRBDA_EXP_MF_WAVES24=2|4)
-#ifndef GRBDA_EXP_MF_WAVES24
-#define GRBDA_EXP_MF_WAVES24 3
-#endif
-int spd_mfma_workgroups_per_cu(int nv) { return nv <= 24 ? GRBDA_EXP_MF_WAVES24 : 2; }  // (= wavefronts per SIMD: workgroups of four)
+constexpr int kMfmaWaves24 = 3;
+int spd_mfma_workgroups_per_cu(int nv) { return nv <= 24 ? kMfmaWaves24 : 2; }  // (= wavefronts per SIMD: workgroups of four)
 bool spd_solve_on_mfma(size_t elem, int nv, int n_rhs)
 {
-    static const bool valu = [] { const char *e = std::getenv("GRBDA_SOLVE_VALU"); return e && std::atoi(e) != 0; }();
-    return elem == 4 && !valu && nv <= kWave && spd_mfma_lds_bytes(nv, n_rhs) <= 160u * 1024u;
+    return elem == 4 && nv <= kWave && spd_mfma_lds_bytes(nv, n_rhs) <= 160u * 1024u;
 }
 size_t spd_solve_lds_bytes(int nv, size_t elem, int n_rhs);
 
@@ -1151,16 +1076,10 @@ void spd_solve_kernel(const TIO *H, int h_packed, const TIO *P1, const TIO *P2, 
 // 30.7 + 46.2 KB, two workgroups per CU).
 // ---------------------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifdef GRBDA_EXP_MF_PROF
-__device__ unsigned long long mf_prof[8];
-#define MF_STAMP(i) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); prof_acc[i] += now_ - prof_t; prof_t = now_; }
-#else
-#define MF_STAMP(i)
-#endif
 
 template <int NVV>
 __global__ __launch_bounds__(kWave * kDerivGroup)
-    __attribute__((amdgpu_waves_per_eu(NVV > 48 ? 1 : (NVV <= 24 ? GRBDA_EXP_MF_WAVES24 : 2), NVV <= 24 ? GRBDA_EXP_MF_WAVES24 : 2)))
+    __attribute__((amdgpu_waves_per_eu(NVV > 48 ? 1 : (NVV <= 24 ? kMfmaWaves24 : 2), NVV <= 24 ? kMfmaWaves24 : 2)))
 void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, const float *P2, int p_il, float *Hinv, float *X1, float *X2,
                      const uint64_t *__restrict__ related, int nv, size_t B)
 {
@@ -1221,9 +1140,6 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
     }
     const uint64_t rel_mine = related ? related[lane < nv ? lane : 0] : ~uint64_t(0);
     const size_t n_groups = (B + G - 1) / G;
-#ifdef GRBDA_EXP_MF_PROF
-    unsigned long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_t = __builtin_amdgcn_s_memtime();
-#endif
     for (size_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
         const size_t s = grp * G + wave;
         const bool live = s < B;  // (a wavefront past the end of the batch works on whatever LDS holds and stores nothing)
@@ -1234,7 +1150,6 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
         group_copy(H + grp * (size_t)G * nn, Pg, (h_il == G ? G : n_valid) * nn);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        MF_STAMP(0)
         float Lr[NVV];  // row `lane` of H, then of L; the diagonal entry holds 1 / L[k][k]
         {
             const int lrow = lane < nv ? lane : 0;
@@ -1247,7 +1162,6 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
         }
         __syncthreads();  // every wavefront has its H: the right-hand sides may land over the block
         for (int m = 0; m < n_mat; m++) group_copy(src[m] + grp * (size_t)G * nn, Pg + (size_t)m * G * nn, (p_il == G ? G : n_valid) * nn);
-        MF_STAMP(1)
         // ---- 1. Cholesky ----
         bool bad = false;
 #pragma unroll
@@ -1263,7 +1177,6 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
         }
         if (bad && lane == 0 && live) atomicAdd(&grbda_spd_bad_count, 1ull);
         wave_lds_fence();
-        MF_STAMP(2)
         // ---- 2. W = L^-1: column `lane`, forward substitution by columns of L (rows of the stored L^T) ----
         {
             float x[NVV], l[NVV];
@@ -1289,7 +1202,6 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
             }
         }
         wave_lds_fence();
-        MF_STAMP(3)
         // ---- 3. H^-1 = W^T W (rows and columns NVV .. 16 NT - 1 of the tile are padding: never stored, read as zero) ----
         f32x4 hi[NT][NT];
 #pragma unroll
@@ -1340,7 +1252,6 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
                     }
                 }
         }
-        MF_STAMP(4)
         if (n_mat == 0) continue;
         __syncthreads();  // every wavefront's part of the copy has landed (and this wavefront's H^-1 is in LDS)
         // ---- 4. X = -H^-1 [P1 | P2] ----
@@ -1375,7 +1286,6 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
                     for (int a = 0; a < NT; a++) acc[a][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[t], av[a], acc[a][t], 0, 0, 0);
                 }
         }
-        MF_STAMP(5)
         // The product was taken transposed, (P^T H^-1)^T: with the right-hand-side fragment as the A operand a lane's four
         // accumulator values of tile (a, t) are X[16 a + c16][16 t + 4 g + 0..3] -- four consecutive entries of a row of the
         // result: one 16-byte store (two 8-byte ones at the odd alignment of an odd row when nv = 2 mod 4) instead of four.
@@ -1407,24 +1317,8 @@ void spd_mfma_kernel(const float *H, int h_packed, int h_il, const float *P1, co
                     }
                 }
         }
-        MF_STAMP(6)
     }
-#ifdef GRBDA_EXP_MF_PROF
-    if (lane == 0)
-        for (int i = 0; i < 8; i++) atomicAdd(&mf_prof[i], prof_acc[i]);
-#endif
 }
-#ifdef GRBDA_EXP_MF_PROF
-extern "C" int grbda_debug_mf_prof(unsigned long long *out, int reset)
-{
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(mf_prof), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[8] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(mf_prof), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
 
 template <int NVV>
 static hipError_t launch_spd_mfma_n(const float *H, int h_packed, int h_il, const float *P1, const float *P2, int p_il, float *Hinv, float *X1,
@@ -1465,9 +1359,8 @@ static hipError_t launch_spd_solve_n(const TIO *H, int h_packed, const TIO *P1, 
 {
     // two columns per lane: f32 arithmetic and more than one pass of 64 columns (register budget: 4 NV values per lane)
     const int ncols = (P1 ? nv : 0) + (P2 ? nv : 0) + (Hinv ? nv : 0);
-    static const int kc_env = [] { const char *e = std::getenv("GRBDA_SOLVE_KC"); return e ? std::atoi(e) : 0; }();
     if constexpr (sizeof(TC) == 4 && NV == 40) {  // (measured: it pays for JVRC-1's 114 columns only)
-        if (kc_env != 1 && (ncols > kWave || kc_env == 2)) {
+        if (ncols > kWave) {
             hipLaunchKernelGGL((spd_solve_kernel<TIO, TC, NV, 2>), dim3(grid), dim3(kWave), 0, stream, H, h_packed, P1, P2, Hinv, X1, X2,
                                related, nv, B);
             return hipGetLastError();

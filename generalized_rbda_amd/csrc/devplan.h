@@ -7,11 +7,6 @@
 
 namespace grbda_hip {
 
-// wavefronts per SIMD of the "wide" fp32 chain kernel (GRBDA_CHAIN_WIDE=1; experiment builds: -DGRBDA_EXP_WIDE_WPS=3)
-#ifndef GRBDA_EXP_WIDE_WPS
-#define GRBDA_EXP_WIDE_WPS 4
-#endif
-constexpr int kChainWideWps = GRBDA_EXP_WIDE_WPS;
 // wavefronts (one-wavefront workgroups) whose dynamic LDS fits a CU: gfx950 hands out its 160 KiB in granules of 1 280 bytes, so a
 // kernel asking for 13 312 bytes holds 11 workgroups per CU, not 12 -- and a persistent grid sized for 12 leaves every twelfth
 // workgroup waiting for a slot until another has finished ALL its tiles (measured: four_bar forward dynamics 0.103 ms at 12 per CU,
@@ -19,14 +14,9 @@ constexpr int kChainWideWps = GRBDA_EXP_WIDE_WPS;
 inline size_t lds_workgroups_per_cu(size_t lds_bytes)
 {
     if (lds_bytes == 0) return 32;
-    static const size_t granule = [] {  // (GRBDA_LDS_GRANULE=1: the naive quotient, for A/B runs)
-        const char *e = std::getenv("GRBDA_LDS_GRANULE");
-        const long v = e ? std::atol(e) : 0;
-        return static_cast<size_t>(v > 0 ? v : 1280);
-    }();
+    constexpr size_t granule = 1280;
     return (160u * 1024u) / ((lds_bytes + granule - 1) / granule * granule);
 }
-constexpr int kChainWideLdsBytes = (160 * 1024 / (4 * kChainWideWps)) / 256 * 256;  // per wavefront, whole rows of 64 floats
 
 
 template <class T>
@@ -98,7 +88,7 @@ struct ChainDev {
     int n_glb_slots;
     int lds_bytes;
     int ori_repr;
-    int debug;   // GRBDA_CHAIN_DEBUG: phase ablation for profiling (chain_kernels.hip)
+    int debug;   // unused (kept so that the argument layout does not move); the host writes 0
     int sv_global;  // ChainProgram::sv_global
     int out_lds;    // ChainProgram::out_lds
     // aba_chain_kernel only (capi.cpp, run_chain): bit 0 -- the program starts with the floating base's forward segment, whose whole work is
@@ -112,7 +102,7 @@ struct ChainDev {
 };
 template <class T>
 hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch, int grid,
-                            size_t lds_bytes, hipStream_t stream, bool four_waves_per_simd);
+                            size_t lds_bytes, hipStream_t stream);
 // latency mode: a tile per workgroup of n_waves = 2 (or, fp32, 4) wavefronts (chain_kernels.hip, aba_chain_lm_kernel)
 template <class T>
 hipError_t launch_aba_chain_lm(const ChainDev<T> &P, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch, int grid,

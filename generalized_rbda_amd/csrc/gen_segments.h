@@ -77,13 +77,7 @@ __device__ __forceinline__ void gen_st1(const MM &M, int s, T v)
 // sin / cos of the joint angles of an implicit cluster: K and the body transforms use the SAME values (devmath.h, sincos_cw)
 __device__ __forceinline__ void gen_sincos(float x, float *s, float *c)
 {
-#ifdef GRBDA_GEN_PRECISE
-    sincos_precise(x, s, c);
-#elif defined(GRBDA_GEN_HW_SINCOS)
-    sincos_t(x, s, c);
-#else
     sincos_cw(x, s, c);
-#endif
 }
 __device__ __forceinline__ void gen_sincos(double x, double *s, double *c) { sincos(x, s, c); }
 

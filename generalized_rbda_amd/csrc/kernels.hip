@@ -31,35 +31,10 @@
 
 namespace grbda_hip {
 
-// optional in-kernel cycle accounting (build with -DGRBDA_PROFILE, see tools/prof_run.py; never in
-// the shipped library): s_memtime deltas per phase, summed over waves into grbda_prof[]
 // wavefronts per SIMD the f32 ABA kernel is register-allocated for
-#ifndef GRBDA_ABA32_WAVES
-#define GRBDA_ABA32_WAVES 2
-#endif
+constexpr int kAba32Waves = 2;
 
 
-#ifdef GRBDA_PROFILE
-__device__ unsigned long long grbda_prof[32];
-#define PROF_T0() unsigned long long prof_t = __builtin_amdgcn_s_memtime()
-#define PROF_ARGS , unsigned long long (&prof_acc)[24], unsigned long long &prof_t
-#define PROF_PASS , prof_acc, prof_t
-#define PROF_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define PROF_SYNCV() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
-#define PROF_ADD(i)                                                    \
-    do {                                                               \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();  \
-        prof_acc[i] += now_ - prof_t;                                  \
-        prof_t = now_;                                                 \
-    } while (0)
-#else
-#define PROF_T0()
-#define PROF_ADD(i)
-#define PROF_ARGS
-#define PROF_PASS
-#define PROF_SYNC()
-#define PROF_SYNCV()
-#endif
 
 #include "devmath.h"
 
@@ -607,18 +582,13 @@ __device__ __noinline__ void eval_loop_constraint(const Tables<T> &P, const SL &
     cptr<int32_t> dep = ip + 3 + n_ind;
     cptr<int32_t> payload = dep + rows;
     T kdq[3] = {0, 0, 0};
-#ifdef GRBDA_EXP_NO_CONSTRAINT
-    return;
-#endif
 
     for (int i = 0; i < k; i++) S.st1(lay.qs + i, L.q(c.q_index + i));
     for (int i = 0; i < rows * k; i++) S.st1(lay.K + i, T(0));
 
     // ---- K(q) ------------------------------------------------------------------------------------
     if (c.cons_type == 0) loop_position_K<T, N>(P, S, c, lay, payload, hdr0);
-#ifndef GRBDA_EXP_NO_TRIG
     else trig_poly_eval<T, N>(P, S, c, lay, payload, true, kdq);
-#endif
 
     // ---- G = P [1; -Kd^-1 Ki] ------------------------------------------------------------------
     T Kd[3][3], Kdi[3][3], X[3][N];
@@ -666,9 +636,7 @@ __device__ __noinline__ void eval_loop_constraint(const Tables<T> &P, const SL &
 
     // ---- k = -Kdot qd ; g = P [0; Kd^-1 k] ----------------------------------------------------------
     if (c.cons_type == 0) loop_position_Kdqd<T, N>(P, S, c, lay, payload, hdr0, kdq);
-#ifndef GRBDA_EXP_NO_TRIG
     else trig_poly_eval<T, N>(P, S, c, lay, payload, false, kdq);
-#endif
 #pragma unroll
     for (int r = 0; r < 3; r++)
         if (r < rows) S.st1(lay.G + dep[r] * (N + 1) + N, -(Kdi[r][0] * kdq[0] + Kdi[r][1] * kdq[1] + Kdi[r][2] * kdq[2]));
@@ -889,7 +857,7 @@ __device__ __forceinline__ void free_base_accel(const Tables<T> &P, const Cluste
 // ---------------------------------------------------------------------------------------------
 template <class T, int N, bool LOOP, bool GEN, class SL>
 __device__ __forceinline__ void aba_bwd_static(const Tables<T> &P, const SL &S, const ClusterRec &c,
-                                               const Lane<T> &L, Carry<T> &carry PROF_ARGS)
+                                               const Lane<T> &L, Carry<T> &carry)
 {
     T y[N], yd[N], u[N], F[6][N], D[N][N];
     // contribution of this cluster to its parent body when it is handed over in registers
@@ -937,10 +905,7 @@ __device__ __forceinline__ void aba_bwd_static(const Tables<T> &P, const SL &S, 
     }
 
     for (int i = c.k - 1; i >= 0; i--) {
-        PROF_ADD(5);  // (previous body) joint-space terms + push up the in-cluster chain
         const BodyRec b = load_body<GEN>(P.bodies + (c.first_body + i));
-        PROF_SYNC();
-        PROF_ADD(6);  // body record round trip
         cptr<T> C = P.consts + b.cofs;
         cptr<T> Ic = C + 12;
         T qi, gi;
@@ -949,8 +914,6 @@ __device__ __forceinline__ void aba_bwd_static(const Tables<T> &P, const SL &S, 
         const T qdi = rdot<T, N>(G, yd);
         T sc[2], E[9], v[6];
         body_kinematics<T>(P, S, b, C, qi, qdi, sc, E, v);
-        PROF_SYNC();
-        PROF_ADD(7);  // constants + kinematics (LDS v / parent v)
         T chat[6];
         vxaxis(b.axis, v, qdi, chat);
         add_axis(chat, b.axis, gi);
@@ -990,8 +953,6 @@ __device__ __forceinline__ void aba_bwd_static(const Tables<T> &P, const SL &S, 
             for (int j = 0; j < 21; j++) IA[j] = Ib[j];
         }
 
-        PROF_SYNC();
-        PROF_ADD(8);  // own bias + accumulator loads
         T h[6];
         column(IA, b.axis, h);
         const T d = pick(h, b.axis);
@@ -1035,8 +996,6 @@ __device__ __forceinline__ void aba_bwd_static(const Tables<T> &P, const SL &S, 
             }
         }
 
-        PROF_SYNC();
-        PROF_ADD(9);  // IA*c, force transform, congruence, hand-over / accumulate
         // joint-space terms: D += d G^T G, u -= G^T b, push h up the in-cluster chain
 #pragma unroll
         for (int a = 0; a < N; a++) {
@@ -1072,7 +1031,6 @@ __device__ __forceinline__ void aba_bwd_static(const Tables<T> &P, const SL &S, 
             for (int a = 0; a < N; a++) F[r][a] += f[r] * G[a];
     }
 
-    PROF_ADD(10);
     // D^-1 u', K = D^-1 F^T
     Chol<T, N> ch;
     ch.factor(D);
@@ -1119,8 +1077,6 @@ __device__ __forceinline__ void aba_bwd_static(const Tables<T> &P, const SL &S, 
             S.accK(c.parent_slot_IA, dI, c.corr_first_IA);
         }
     }
-    PROF_SYNC();
-    PROF_ADD(11);  // solve, K/y0 stores, parent correction
 }
 
 // Free root: S = 1, D = IA, c = 0 (FreeJoint.cpp:10-36)
@@ -1331,11 +1287,9 @@ __device__ __forceinline__ void aba_bwd_rev(const Tables<T> &P, const SL &S, con
 // acceleration sweep of the same shapes (ClusterTreeDynamics.cpp:131-152); a rotor has no children
 template <class T, class SL>
 __device__ __forceinline__ void aba_acc_rev(const Tables<T> &P, const SL &S, const ClusterRec &c,
-                                            const Lane<T> &L, const T (&kblk)[7], bool have_kblk PROF_ARGS)
+                                            const Lane<T> &L, const T (&kblk)[7], bool have_kblk)
 {
     T K[6], ap[6], ydd;
-    PROF_SYNCV();
-    PROF_ADD(13);  // drain of everything outstanding at step entry
     if (have_kblk) {  // [K 6][y0 1] fetched while the previous step ran
 #pragma unroll
         for (int r = 0; r < 6; r++) K[r] = kblk[r];
@@ -1345,25 +1299,17 @@ __device__ __forceinline__ void aba_acc_rev(const Tables<T> &P, const SL &S, con
         ydd = S.ldK1(c.slot_y0);
     }
     S.ld(c.parent_slot_a3, ap);
-    PROF_SYNCV();
-    PROF_ADD(14);  // K, y0, parent acceleration loads
 #pragma unroll
     for (int r = 0; r < 6; r++) ydd -= K[r] * ap[r];
     L.put(c.v_index, ydd);
-    PROF_SYNCV();
-    PROF_ADD(15);  // ydd + output store (acknowledged)
     if (!c.child_mask) return;
     const BodyRec b = load_rec(P.bodies + c.link_body);
-    PROF_SYNC();
-    PROF_ADD(16);  // body record
     cptr<T> C = P.consts + b.cofs;
     const T g0 = C[kBodyConstFixed];
     const T qdi = g0 * L.cyd(c, 0);
     T sn, cs, E[9], v[6], a[6];
     sincos_t(g0 * L.cy(c, 0), &sn, &cs);
     rotate_z(sn, cs, C, E);
-    PROF_SYNC();
-    PROF_ADD(17);  // constants, inputs, sincos, E
     {
         T vp[6];
         S.ld(b.parent_slot_v3, vp);
@@ -1411,13 +1357,8 @@ __device__ __forceinline__ void aba_acc_static(const Tables<T> &P, const SL &S, 
                                                const Lane<T> &L)
 {
     T K[6 * N], ydd[N], ap[6];
-#ifdef GRBDA_EXP_NOK
-    for (int j = 0; j < 6 * N; j++) K[j] = T(0.01) * j;
-    for (int j = 0; j < N; j++) ydd[j] = T(0.5);
-#else
     S.ldK(c.slot_K, K);
     S.ldK(c.slot_y0, ydd);
-#endif
     if (c.parent_slot_a3 >= 0) {
         S.ld(c.parent_slot_a3, ap);
     } else {
@@ -1764,16 +1705,9 @@ __device__ __forceinline__ void rnea_bwd_rev(const Tables<T> &P, const SL &S, co
 // HAS_LOOP is a kernel template parameter: models without implicit-loop clusters run a kernel that
 // does not contain the loop-constraint code at all (code size and register pressure matter: the
 // interpreter loop must stay resident in the instruction cache)
-#ifdef GRBDA_EXP_NMAX2
-#define GRBDA_EXP_BIG_N(FN, ...)
-#else
-#define GRBDA_EXP_BIG_N(FN, ...)                           \
+#define GRBDA_BIG_N(FN, ...)                           \
     case 3: FN<T, 3, false, HAS_LOOP>(__VA_ARGS__); break; \
     default: FN<T, 4, false, HAS_LOOP>(__VA_ARGS__); break;
-#endif
-#ifdef GRBDA_EXP_SHAPES_ONLY
-#define GRBDA_DISPATCH_N(c, FN, ...) {}
-#else
 #define GRBDA_DISPATCH_N(c, FN, ...)                                                        \
     if (HAS_LOOP && (c).kind == CK_LOOP) {                                                     \
         if constexpr (HAS_LOOP) {                                                              \
@@ -1787,10 +1721,9 @@ __device__ __forceinline__ void rnea_bwd_rev(const Tables<T> &P, const SL &S, co
         switch ((c).n) {                                                                       \
             case 1: FN<T, 1, false, HAS_LOOP>(__VA_ARGS__); break;                                       \
             case 2: FN<T, 2, false, HAS_LOOP>(__VA_ARGS__); break;                                       \
-            GRBDA_EXP_BIG_N(FN, __VA_ARGS__)                                                             \
+            GRBDA_BIG_N(FN, __VA_ARGS__)                                                             \
         }                                                                                      \
     }
-#endif
 
 // WPS: wavefronts per SIMD the kernel is register-allocated for.  f32: 2.  f64: the fast kernel exists for 1
 // (no spills; small batches that cannot fill two anyway) and for 2 (~280 spilled registers, still 4-12 %
@@ -1811,20 +1744,12 @@ __global__ __launch_bounds__(kWave, WPS) void aba_kernel(DevPlan<T> DP, const T 
     T *slab = scratch + (size_t)blockIdx.x * (size_t)(DP.n_glb_slots + P.nq + 2 * P.nv) * kWave;
     S.glb = slab + (size_t)(P.nq + 2 * P.nv) * kWave;
 
-#ifdef GRBDA_PROFILE
-    unsigned long long prof_acc[24] = {0};
-#endif
-    PROF_T0();
     const size_t n_tiles = (B + kWave - 1) / kWave;
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t r = tile * kWave + lane;
         const size_t left = B - tile * kWave;
         const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
-        PROF_SYNCV();
-        PROF_ADD(19);  // drain of the previous tile's result stores
         stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
-        PROF_SYNCV();
-        PROF_ADD(0);
         Lane<T> L;
         L.active = r < B;
         const size_t rr = L.active ? r : B - 1;
@@ -1844,8 +1769,6 @@ __global__ __launch_bounds__(kWave, WPS) void aba_kernel(DevPlan<T> DP, const T 
         for (int s = 0; s < P.n_steps; s++) {
             const Step st = load_rec(P.steps + s);
             const ClusterRec c = load_rec(P.clusters + st.cluster);
-            PROF_SYNC();
-            PROF_ADD(12);  // step + cluster record round trips
             if (use_shapes && (st.op & kOpSkipFast)) continue;
             const int op = st.op & kOpMask;
             if (op == OP_ABA_FWD) {
@@ -1856,7 +1779,6 @@ __global__ __launch_bounds__(kWave, WPS) void aba_kernel(DevPlan<T> DP, const T 
                 } else {
                     GRBDA_DISPATCH_N(c, aba_fwd_static, P, S, c, L)
                 }
-                PROF_ADD(2);
             } else if (op == OP_ABA_BWD) {
                 if (c.kind == CK_FREE) {
                     aba_bwd_free(P, S, c, L, carry);
@@ -1865,9 +1787,8 @@ __global__ __launch_bounds__(kWave, WPS) void aba_kernel(DevPlan<T> DP, const T 
                 } else if (use_shapes && c.shape == SHAPE_REV_ROTOR) {
                     aba_bwd_rev<T, true>(P, S, c, L, carry);
                 } else {
-                    GRBDA_DISPATCH_N(c, aba_bwd_static, P, S, c, L, carry PROF_PASS)
+                    GRBDA_DISPATCH_N(c, aba_bwd_static, P, S, c, L, carry)
                 }
-                PROF_ADD(3);
             } else {
                 if (use_shapes && !c.shape) {  // generic / free step: start the prefetch chain for a following shape step
                     const int knext = P.acc_k[s + 1];
@@ -1885,21 +1806,15 @@ __global__ __launch_bounds__(kWave, WPS) void aba_kernel(DevPlan<T> DP, const T 
                     const int knext = P.acc_k[s + 1];
                     kpre_valid = knext != -1;
                     if (kpre_valid) S.ldK(knext, kpre);
-                    aba_acc_rev<T>(P, S, c, L, kblk, have PROF_PASS);
+                    aba_acc_rev<T>(P, S, c, L, kblk, have);
                 } else {
                     GRBDA_DISPATCH_N(c, aba_acc_static, P, S, c, L)
                 }
-                PROF_ADD(4);
             }
         }
         write_outputs(slab + (size_t)(P.nq + P.nv) * kWave, ydd, tile, rows_valid, P.nv, lane);
         S.flush_bad(DP.bad_count, rows_valid);
-        PROF_ADD(18);  // tile epilogue
     }
-#ifdef GRBDA_PROFILE
-    if (lane == 0)
-        for (int i = 0; i < 24; i++) atomicAdd(&grbda_prof[i], prof_acc[i]);
-#endif
 }
 
 template <class T, bool HAS_LOOP, bool SPLIT = false>
@@ -2458,14 +2373,6 @@ __global__ __launch_bounds__(kWave, 1) void spanning_kernel(DevPlan<T> DP, int n
     }
 }
 
-#ifdef GRBDA_EXP_ONLY_ABA32
-// compile-time experiments (register budgets): only the fast f32 ABA kernel is instantiated
-#ifdef GRBDA_EXP_SPLIT
-template __global__ void aba_kernel<float, false, GRBDA_ABA32_WAVES, true>(DevPlan<float>, const float *, const float *, const float *, float *, size_t, float *);
-#else
-template __global__ void aba_kernel<float, false, GRBDA_ABA32_WAVES>(DevPlan<float>, const float *, const float *, const float *, float *, size_t, float *);
-#endif
-#else
 // ---------------------------------------------------------------------------------------------
 // host launchers (called by capi.cpp)
 // ---------------------------------------------------------------------------------------------
@@ -2473,7 +2380,7 @@ template <class T>
 hipError_t launch_aba(const DevPlan<T> &P, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch,
                       int grid, size_t lds_bytes, hipStream_t stream, bool two_waves_per_simd)
 {
-    constexpr int W32 = GRBDA_ABA32_WAVES;
+    constexpr int W32 = kAba32Waves;
     if constexpr (sizeof(T) == 4) {
         if (P.general)
             hipLaunchKernelGGL((aba_kernel<T, true, W32>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
@@ -2572,21 +2479,8 @@ template hipError_t launch_rnea<float>(const DevPlan<float> &, const float *, co
 template hipError_t launch_rnea<double>(const DevPlan<double> &, const double *, const double *, const double *,
                                         double *, size_t, double *, int, size_t, hipStream_t);
 
-#endif  // GRBDA_EXP_ONLY_ABA32
 
-#ifdef GRBDA_PROFILE
-extern "C" int grbda_debug_profile(unsigned long long *out, int reset)
-{
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(grbda_prof), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[32] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(grbda_prof), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
 
-#ifndef GRBDA_EXP_ONLY_ABA32
 hipError_t set_max_dynamic_lds()
 {
     const int maxb = 160 * 1024;
@@ -2596,10 +2490,10 @@ hipError_t set_max_dynamic_lds()
                          reinterpret_cast<const void *>(&state_kernel<double>),
                          reinterpret_cast<const void *>(&spanning_kernel<float>),
                          reinterpret_cast<const void *>(&spanning_kernel<double>),
-                         reinterpret_cast<const void *>(&aba_kernel<float, false, GRBDA_ABA32_WAVES>),
-                         reinterpret_cast<const void *>(&aba_kernel<float, false, GRBDA_ABA32_WAVES, true>),
+                         reinterpret_cast<const void *>(&aba_kernel<float, false, kAba32Waves>),
+                         reinterpret_cast<const void *>(&aba_kernel<float, false, kAba32Waves, true>),
                          reinterpret_cast<const void *>(&rnea_kernel<float, false, true>),
-                         reinterpret_cast<const void *>(&aba_kernel<float, true, GRBDA_ABA32_WAVES>),
+                         reinterpret_cast<const void *>(&aba_kernel<float, true, kAba32Waves>),
                          reinterpret_cast<const void *>(&aba_kernel<double, false, 1>),
                          reinterpret_cast<const void *>(&aba_kernel<double, false, 2>),
                          reinterpret_cast<const void *>(&aba_kernel<double, true, 1>),
@@ -2614,6 +2508,5 @@ hipError_t set_max_dynamic_lds()
     return hipSuccess;
 }
 
-#endif
 
 }  // namespace grbda_hip

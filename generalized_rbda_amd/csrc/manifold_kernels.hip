@@ -1039,11 +1039,7 @@ __global__ __launch_bounds__(kWave, 1) void manifold_project_kernel(DevPlan<T> D
                 // The floating base's columns: G e_a is a unit vector, so a column of the projected matrices is a column of the spanning
                 // ones contracted with G_I^T -- and every cluster is related to the base.  All FC columns at once: each entry of A_q / A_v / H_s
                 // in the base's columns is read ONCE (column by column it was the same rows of G_I against one entry at a time, six passes).
-#ifdef GRBDA_EXP_FC
-                constexpr int FC = GRBDA_EXP_FC;
-#else
                 constexpr int FC = 3;  // (six at once: 197 registers in fp32, two wavefronts per SIMD instead of three, 7 % slower)
-#endif
                 const int sv0 = span_v[J.first_body];
                 for (int a0 = 0; a0 < 6; a0 += FC) {
                     for (int cI = 0; cI < n_clusters; cI++) {
@@ -1117,11 +1113,7 @@ __global__ __launch_bounds__(kWave, 1) void manifold_project_kernel(DevPlan<T> D
             }
             // (J is a static or an implicit cluster here: the base's columns went above.)  NC columns at a time: the entries of A_q / A_v / H_s of
             // a cluster pair are read once per NC columns of J
-#ifdef GRBDA_EXP_NC
-            constexpr int NC = GRBDA_EXP_NC;
-#else
             constexpr int NC = sizeof(T) == 4 ? 2 : 1;  // (fp64 with two: 234 registers + scratch, one wavefront per SIMD)
-#endif
             for (int a0 = 0; a0 < nJ; a0 += NC) {
                 // column data over the spanning coordinates of cluster J: G e_a, G_a' yd, G_a' ydd + dg/dy_a, dg/dyd_a
                 T gJ[KB][NC], ayJ[KB][NC], byJ[KB][NC], bvJ[KB][NC];

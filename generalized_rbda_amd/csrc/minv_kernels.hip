@@ -507,31 +507,6 @@ template hipError_t launch_abi_factor<double>(const DevPlan<double> &, const Der
 // Fragment maps (cdna_hip_programming.md 3; the f64 instruction has the same A / B maps): A[l & 15][l >> 4], B[l >> 4][l & 15];
 // D f32: column l & 15, rows 4 (l >> 4) + 0..3;  D f64 (v_mfma_f64_16x16x4_f64): column l & 15, rows 4 r + (l >> 4), r = 0..3.
 // ---------------------------------------------------------------------------------------------------------------
-// optional in-kernel phase profile (make expv NAME=mvprof DEFS=-DGRBDA_EXP_MV_PROF, tools/time_solve.py; never in the shipped library)
-#ifdef GRBDA_EXP_MV_PROF
-__device__ unsigned long long mv_prof[8];
-#define MV_STAMP(i) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); prof_acc[i] += now_ - prof_t; prof_t = now_; }
-extern "C" int grbda_debug_mv_prof(unsigned long long *out, int reset)
-{
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(mv_prof), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[8] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(mv_prof), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#else
-#define MV_STAMP(i)
-#endif
-// phase ablation (experiment builds only: -DGRBDA_EXP_MV_ABL, GRBDA_MV_ABL=bits; wrong results): 1 no result stores, 2 no H^-1 store,
-// 4 no walk, 8 no second product, 16 no right-hand-side copy, 32 no first product, 64 no record copy
-#ifdef GRBDA_EXP_MV_ABL
-__device__ int mv_abl = 0;
-extern "C" int grbda_debug_mv_abl(int bits) { return hipMemcpyToSymbol(HIP_SYMBOL(mv_abl), &bits, sizeof bits) == hipSuccess ? 0 : -1; }
-#define MV_ABL(b) (mv_abl & (b))
-#else
-#define MV_ABL(b) 0
-#endif
 typedef float f32x4m __attribute__((ext_vector_type(4)));
 typedef double f64x4m __attribute__((ext_vector_type(4)));
 template <class T>
@@ -682,18 +657,14 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
         for (int t = 0; t < kMinvMaxDepth; t++) st[t] = col[3 + t];
     }
     const size_t n_groups = (B + G - 1) / G;
-#ifdef GRBDA_EXP_MV_PROF
-    unsigned long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_t = __builtin_amdgcn_s_memtime();
-#endif
     // prologue: the first group's record blocks
-    if (blockIdx.x < n_groups && !MV_ABL(64)) group_copy(rec + blockIdx.x * (size_t)G * n_entries, Rg, (size_t)G * n_entries);
+    if (blockIdx.x < n_groups) group_copy(rec + blockIdx.x * (size_t)G * n_entries, Rg, (size_t)G * n_entries);
     for (size_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
         const size_t s = grp * G + wave;
         const bool live = s < B;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         lds_barrier();  // barrier A
-        if (!MV_ABL(16))
-            for (int m = 0; m < n_mat; m++) group_copy(src[m] + grp * (size_t)G * nn, Pg + (size_t)m * G * nn, (size_t)G * nn);
+        for (int m = 0; m < n_mat; m++) group_copy(src[m] + grp * (size_t)G * nn, Pg + (size_t)m * G * nn, (size_t)G * nn);
         const size_t next = grp + gridDim.x;
         // clear the tile (16-byte stores, the tile is NVV * WS scalars)
         {
@@ -705,9 +676,8 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
             for (int i = lane * V; i < NVV * WS; i += kWave * V) *reinterpret_cast<TV *>(&A[i]) = z;
         }
         wave_lds_fence();
-        MV_STAMP(0)
         // ---- 1. W: lane j walks column j ----
-        if (!MV_ABL(4)) {
+        {
             const T *R = Rg + wave;
             const bool valid = (own_m >> 21) & 1;
             const int n_own = own_m & 15, e_own = (own_m >> 4) & 15, v_own = (own_m >> 8) & 63;
@@ -759,7 +729,6 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
             }
         }
         wave_lds_fence();
-        MV_STAMP(1)
         // ---- 2. H^-1 = W^T W (rows and columns nv .. NVV - 1 of the tile are zero) ----
         Acc hi[NT][NT];
 #pragma unroll
@@ -770,7 +739,6 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
                 for (int j = 0; j < 4; j++) hi[a][b][j] = T(0);
 #pragma unroll
         for (int k = 0; k < KS; k++) {
-            if (MV_ABL(32)) break;
             T w[NT];
 #pragma unroll
             // (row r of W reaches the columns from the first coordinate of r's own cluster on -- L^-1 is LOWER triangular inside the
@@ -782,10 +750,8 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
                 for (int b = 0; b < NT; b++)
                     if (16 * (a < b ? a : b) + 15 + kReach >= 4 * k) hi[a][b] = Mfma<T>::run(w[a], w[b], hi[a][b]);
         }
-        MV_STAMP(2)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         lds_barrier();  // barrier B
-        MV_STAMP(3)
 #pragma unroll
         for (int a = 0; a < NT; a++)
 #pragma unroll
@@ -795,8 +761,8 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
                     const int row = 16 * a + Mfma<T>::row(g, j), col = 16 * b + c16;
                     if (row < NVV && col < NVV) A[row * WS + col] = hi[a][b][j];
                 }
-        if (next < n_groups && !MV_ABL(64)) group_copy(rec + next * (size_t)G * n_entries, Rg, (size_t)G * n_entries);
-        if (Hinv && live && !MV_ABL(2)) {
+        if (next < n_groups) group_copy(rec + next * (size_t)G * n_entries, Rg, (size_t)G * n_entries);
+        if (Hinv && live) {
             T *hout = Hinv + s * (size_t)nn;
             if constexpr (sizeof(T) == 4) {
                 // H^-1 is symmetric: the four values a lane holds of tile (a, b) -- rows 16 a + 4 g + 0..3 of column 16 b + c16 -- are
@@ -829,7 +795,6 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
                         }
             }
         }
-        MV_STAMP(4)
         if (n_mat == 0) continue;
         wave_lds_fence();  // this wavefront's H^-1 is in its tile
         // ---- 3. X = -H^-1 [P1 | P2], taken transposed: (P^T H^-1)^T -- the right-hand-side fragment is the A operand ----
@@ -842,7 +807,6 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
                 for (int j = 0; j < 4; j++) acc[a][t][j] = T(0);
 #pragma unroll
         for (int k = 0; k < KS; k++) {
-            if (MV_ABL(8)) break;
             const int r = 4 * k + g;
             T av[NT], bv[NCT];
 #pragma unroll
@@ -861,9 +825,8 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
                     for (int a = 0; a < NT; a++) acc[a][t] = Mfma<T>::run(bv[t], av[a], acc[a][t]);
                 }
         }
-        MV_STAMP(5)
         // accumulator (a, t): X[row 16 a + c16][columns 16 t + Mfma::row(g, 0..3)] of [X1 | X2]
-        if (live && !MV_ABL(1)) {
+        if (live) {
 #pragma unroll
             for (int t = 0; t < NCT; t++)
                 if (t < nct) {
@@ -902,12 +865,7 @@ void minv_mfma_kernel(const T *__restrict__ rec, int n_entries, int r_il, const 
                     }
                 }
         }
-        MV_STAMP(6)
     }
-#ifdef GRBDA_EXP_MV_PROF
-    if (lane == 0)
-        for (int i = 0; i < 8; i++) atomicAdd(&mv_prof[i], prof_acc[i]);
-#endif
 }
 
 template <class T, int NVV>

@@ -21,10 +21,8 @@
 namespace grbda_hip {
 // Is the tree rotation Et (row-major at consts[cofs]) a cyclic permutation of the axes, (Et x)_i = x_((i + k) % 3), to rounding (1e-14)?
 // Returns the shift k, or -1.  The chain kernels then use the permutation-structured transforms (devmath.h, rzp_*).
-// GRBDA_NO_PERM_LINKS: A/B switch, every link on the general rotation path.
 static int cyclic_shift(const std::vector<double> &consts, int cofs)
 {
-    if (std::getenv("GRBDA_NO_PERM_LINKS")) return -1;
     for (int k = 0; k < 3; k++) {
         bool is = true;
         for (int i = 0; i < 3; i++)
@@ -75,9 +73,13 @@ int parse(const void *blob, size_t bytes, Blob &m, char *msg, size_t cap)
 
 }  // namespace
 
-int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep_mask, HostPlan &P, char *msg,
-                 size_t cap)
+int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPlan &P, char *msg, size_t cap)
 {
+    // LDS budgets per wavefront in slots (rows of 64 scalars)
+    const struct {
+        int aba32, aba64, rnea32, rnea64, chain32w;
+    } lds = {opt.lds_bytes_per_wave[0] / (4 * kWave), opt.lds_bytes_per_wave[1] / (8 * kWave), opt.lds_bytes_per_wave[2] / (4 * kWave),
+             opt.lds_bytes_per_wave[3] / (8 * kWave), opt.chain32w_lds_bytes / (4 * kWave)};
     Blob m;
     if (int rc = parse(blob, bytes, m, msg, cap)) return rc;
     const int nb = m.h->n_bodies, nc = m.h->n_clusters;
@@ -105,7 +107,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
         v_end += cl.n_vel;
         // clusters beyond the structured kernels' limits (kMaxClusterBodies, kMaxClusterDof) go through the spanning tree:
         // HostPlan::big_clusters, manifold_kernels.hip's wide variants
-        const bool no_big = std::getenv("GRBDA_NO_PROJECTION") != nullptr;
+        const bool no_big = opt.no_projection;
         if (cl.n_bodies > (no_big ? kMaxClusterBodies : kBigClusterBodies))
             return fail(msg, cap, GRBDA_EUNSUPPORTED, "cluster %d: %d bodies exceed the kernel limit", c, cl.n_bodies);
         const int max_dof = no_big ? kMaxClusterDof : kBigClusterDof;
@@ -187,7 +189,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                 if (cr.parent_body == -2) cr.parent_body = b.parent;
                 else if (cr.parent_body != b.parent) {
                     // several parent bodies: the structured recursions do not apply (plan.h, HostPlan::projection_only)
-                    if (std::getenv("GRBDA_NO_PROJECTION"))
+                    if (opt.no_projection)
                         return fail(msg, cap, GRBDA_EUNSUPPORTED,
                                     "cluster %d attaches to more than one body of its parent cluster (body %d)", c, gb);
                     P.projection_only = true;
@@ -689,15 +691,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
         cr.hot = cr.shape != SHAPE_GENERIC && cr.carry_out && bodies[cr.link_body].has_child && bodies[cr.link_body].carry_in;
     }
 
-    if (sweep_mask != 7) {  // profiling aid: drop whole sweeps (results are then meaningless)
-        std::vector<Step> kept;
-        for (const Step &st : P.aba_steps)
-            if (((st.op & kOpMask) == OP_ABA_FWD && (sweep_mask & 1)) || (st.op == OP_ABA_BWD && (sweep_mask & 2)) ||
-                (st.op == OP_ABA_ACC && (sweep_mask & 4)))
-                kept.push_back(st);
-        P.aba_steps = kept;
-    }
-
     // ---- live ranges + interval allocation --------------------------------------------------------
     struct Obj {
         int *field;  // where the slot number goes (index into a flat array of fields)
@@ -1117,17 +1110,15 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
         CP = ChainProgram();
         CP.n_waves = n_waves;
         const bool lm = n_waves > 1;  // latency mode (plan.h, ChainProgram::n_waves)
-        bool ok = sweep_mask == 7;
+        bool ok = true;
         // cluster classes: 0 free, 1 revolute, 2 revolute + axisymmetric rotor, 3 leaf pair (head of its parent link's backward
         // run), 4 revolute + general rotor, 5 two-rotor differential, 6 explicit pair with child clusters on link2 or in a
         // place class 3 does not cover (runs through the differential's segments with constant G), -1 unsupported
         // 7 generic cluster (plan.h, ChainGen): any other explicit cluster, URDF+ position loops, trig-polynomial constraints that
         // are not in the differential's shape; child clusters may hang off any of its bodies (tip = -2)
         std::vector<int> cls(nc, -1), tip(nc, -1), gen_rotor(nc, -1);
-        const bool no_gen = std::getenv("GRBDA_NO_CHAIN_GEN") != nullptr;  // A/B switch: such models keep the interpreter
         auto is_diff = [&](int c) { return cls[c] == 5 || cls[c] == 6; };
         auto make_gen = [&](int c) {
-            if (no_gen) { ok = false; return; }
             cls[c] = 7;
             tip[c] = -2;
         };
@@ -1193,7 +1184,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                     pair_rotors[c] = {r[0], r[1]};
                     pr.perm[0] = cyclic_shift(P.consts, pr.cofs[0]);
                     pr.perm[1] = cyclic_shift(P.consts, pr.cofs[1]);
-                    if (std::getenv("GRBDA_DEBUG_CHAIN")) std::fprintf(stderr, "chain: cluster %d pair perms %d %d\n", c, pr.perm[0], pr.perm[1]);
                 } else {
                     make_gen(c);
                 }
@@ -1206,7 +1196,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
             // (links may hang off the ground -- fixed-base models: the runs then start from v = 0, a = -gravity and hand
             // their inertia to nobody; pair and differential clusters need a parent body)
             if ((cls[c] == 3 || cls[c] == 5) && cr.parent_body < 0) make_gen(c);
-            if (!ok && std::getenv("GRBDA_DEBUG_CHAIN")) std::fprintf(stderr, "chain: cluster %d (k %d n %d kind %d shape %d) not covered\n", c, cr.k, cr.n, cr.kind, cr.shape);
         }
         // every child cluster must hang off the tip body of its parent cluster; a pair must be an only child of a link
         std::vector<std::vector<int>> ckids(nc);
@@ -1216,7 +1205,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
             const int pc = m.bodies[pb].cluster;
             if (tip[pc] != pb && tip[pc] != -2) {
                 // (a child cluster on a rotor, on the first link of a pair, ...: the parent runs as a generic cluster)
-                if (std::getenv("GRBDA_DEBUG_CHAIN")) std::fprintf(stderr, "chain: cluster %d hangs off body %d, not the tip %d of cluster %d\n", c, pb, tip[pc], pc);
                 if (cls[pc] == 0) { ok = false; break; }
                 make_gen(pc);
                 if (!ok) break;
@@ -1270,7 +1258,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                     l.glb_k = k_lds ? -1 : glb(10);  // [K 6][y0][sin][cos] (+ OSIM pass: 1 / D)
                     l.perm = cyclic_shift(P.consts, br.cofs);
                     l.rperm = l.rofs >= 0 && l.rpre < 0 ? cyclic_shift(P.consts, l.rofs) : -1;
-                    if (std::getenv("GRBDA_DEBUG_CHAIN")) std::fprintf(stderr, "chain: cluster %d class %d perm %d rotor perm %d\n", c, cls[c], l.perm, l.rperm);
                 } else if (is_diff(c)) {
                     const DiffShape &ds = diff_shape[c];
                     ChainDiff &d = diff_of[c];
@@ -1742,10 +1729,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                         if (o.size == 9 && !o.tag) { o.force = 0; o.prio = 1; o.slot = -1; }
                     rok = allocate(robjs, rnea_budget, rn_lds, rn_glb);
                 }
-                if (!rok && std::getenv("GRBDA_DEBUG_CHAIN")) {
-                    std::fprintf(stderr, "chain (rnea): LDS objects need more than %d slots (got to %d)\n", rnea_budget, rn_lds);
-                    for (const Obj &o : robjs) std::fprintf(stderr, "  obj size %d [%d, %d] slot %d\n", o.size, o.birth, o.death, o.slot);
-                }
                 if (rok) {
                     for (size_t id = 0; id < chains.size(); id++)
                         if (chains[id].diff) {
@@ -1804,13 +1787,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                             R.diffs.push_back(rd[ch.cl[0]]);
                         }
                         if (ch.gen) {
-                            if (std::getenv("GRBDA_DEBUG_CHAIN")) {
-                                const ChainGen &g = rg[ch.cl[0]];
-                                std::fprintf(stderr, "rnea gen cluster %d: k %d n %d kind %d lds_w %d blk %d keep %d pva %d pf %d segs %d/%d\n", ch.cl[0], g.k, g.n, g.kind,
-                                             g.lds_w, g.glb_k, g.keep, g.lds_pva, g.lds_acc_out, rt_fwd[id], rt_bwd[id]);
-                                for (const ChainGenBody &b : rgb[ch.cl[0]])
-                                    std::fprintf(stderr, "   body lam %d axisym %d acc_w %d up_w %d lds_va %d ind %d dep %d\n", b.lam, b.axisym, b.acc_w, b.up_w, b.lds_va, b.ind_a, b.dep_r);
-                            }
                             rg[ch.cl[0]].first = static_cast<int>(R.gbodies.size());
                             R.gbodies.insert(R.gbodies.end(), rgb[ch.cl[0]].begin(), rgb[ch.cl[0]].end());
                             R.segs[rt_fwd[id]].first = R.segs[rt_bwd[id]].first = static_cast<int>(R.gens.size());
@@ -1833,7 +1809,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                 }
                 R.ok = rok;
                 R.single_gen = rok && R.gens.size() == 1 && R.segs.size() == 2 && R.links.empty() && R.pairs.empty() && R.frees.empty() &&
-                               R.diffs.empty() && !R.gens[0].has_parent && R.n_glb == 0 && !std::getenv("GRBDA_NO_GEN1");
+                               R.diffs.empty() && !R.gens[0].has_parent && R.n_glb == 0 && !opt.no_gen1;
                 if (!rok) { R.segs.clear(); R.links.clear(); R.pairs.clear(); R.frees.clear(); R.diffs.clear(); R.gens.clear(); R.gbodies.clear(); }
             }
             // ---- LDS objects and their live ranges ----
@@ -1958,10 +1934,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                     if (o.slot >= 0 && (o.slot & kSlotGlobal)) *o.field = ((o.slot & ~kSlotGlobal) + n_glb) | kSlotGlobal;
                 n_glb += n_glb_unused;
             }
-            if (!ok && std::getenv("GRBDA_DEBUG_CHAIN")) {
-                std::fprintf(stderr, "chain: LDS objects need more than %d slots (got to %d)\n", lds_budget, n_lds);
-                for (const Obj &o : objs) std::fprintf(stderr, "  obj size %d [%d, %d] slot %d\n", o.size, o.birth, o.death, o.slot);
-            }
             if (!ok && !lm) {
                 // second try: the accumulators [IA 21][psi 6] of branching bodies -- touched once per child chain -- take
                 // what LDS the other objects leave and otherwise move to the wave's global slab (their slot numbers then
@@ -1977,10 +1949,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                         if (o.size == 8 && !o.tag) { o.force = 0; o.prio = 1; o.slot = -1; }
                     ok = allocate(objs, lds_budget, n_lds, n_glb_unused);
                     CP.sv_global = true;
-                    if (!ok && std::getenv("GRBDA_DEBUG_CHAIN")) {
-                        std::fprintf(stderr, "chain: third try failed, n_lds %d\n", n_lds);
-                        for (const Obj &o : objs) std::fprintf(stderr, "  obj size %d force %d [%d, %d] slot %d\n", o.size, o.force, o.birth, o.death, o.slot);
-                    }
                 }
                 for (Obj &o : objs)
                     if (o.slot & kSlotGlobal) *o.field = ((o.slot & ~kSlotGlobal) + n_glb) | kSlotGlobal;
@@ -2000,7 +1968,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                         if (op == SEG_FREE_ACC || op == SEG_RUN_ACC || op == SEG_PAIR_ACC || op == SEG_DIFF_ACC || op == SEG_GEN_ACC) { t_first = static_cast<int>(t2); break; }
                     }
                     const int nvr = P.nv;
-                    if (t_first >= 0 && nvr > 0 && !std::getenv("GRBDA_NO_LDS_RESULTS")) {
+                    if (t_first >= 0 && nvr > 0) {
                         std::vector<char> busy(static_cast<size_t>(lds_budget) + 1, 0);
                         for (const Obj &o : objs) {
                             if (o.slot < 0 || (o.slot & kSlotGlobal) || o.death < B0(t_first)) continue;
@@ -2018,7 +1986,6 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
                         }
                     }
                 }
-                if (std::getenv("GRBDA_DEBUG_CHAIN")) std::fprintf(stderr, "chain: result rows at LDS row %d (nv %d, %d rows in use of %d; %d slab rows, %d wavefronts per tile)\n", CP.out_lds, P.nv, n_lds, lds_budget, n_glb, CP.n_waves);
                 CP.n_lds = n_lds;
                 CP.n_glb = n_glb;
                 // parent velocity / (v, a) slots
@@ -2126,7 +2093,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
         }
         CP.ok = ok;
         CP.single_gen = ok && CP.gens.size() == 1 && CP.segs.size() == 2 && CP.links.empty() && CP.pairs.empty() && CP.frees.empty() &&
-                        CP.diffs.empty() && !CP.gens[0].has_parent && !std::getenv("GRBDA_NO_GEN1");
+                        CP.diffs.empty() && !CP.gens[0].has_parent && !opt.no_gen1;
         if (!ok) { CP.segs.clear(); CP.links.clear(); CP.pairs.clear(); CP.frees.clear(); CP.diffs.clear(); CP.gens.clear(); CP.gbodies.clear(); }
     };
     // the RNEA chain kernels run 8 wavefronts per CU like the ABA ones: the ABA budgets apply
@@ -2145,7 +2112,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
         if (!P.rchain64.ok) build_chain(scratch_cp, 2 * lds.aba64, &P.rchain64, 2 * lds.aba64);
     }
     // latency mode serves batches of at most one tile per SIMD, i.e. four tiles per CU: 40 KiB of LDS per tile
-    build_chain(P.chain32p, 40960 / (4 * kWave), &P.rchain32p, 40960 / (4 * kWave), 2, std::getenv("GRBDA_LM2_SLAB") == nullptr, true);  // (A/B switch: blocks in the slab)
+    build_chain(P.chain32p, 40960 / (4 * kWave), &P.rchain32p, 40960 / (4 * kWave), 2, true, true);
     build_chain(P.chain64p, 40960 / (8 * kWave), &P.rchain64p, 40960 / (8 * kWave), 2);
     // four wavefronts per tile: batches of at most two tiles per CU (one wavefront per SIMD in the two-wavefront mode), 80 KiB each
     build_chain(P.chain32q, 81920 / (4 * kWave), &P.rchain32q, 81920 / (4 * kWave), 4, true, true);
@@ -2155,7 +2122,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
     {
         CrbaProgram &CR = P.crba;
         CR = CrbaProgram();
-        CR.ok = sweep_mask == 7;
+        CR.ok = true;
         for (const ClusterRec &cr : clusters)
             if (cr.kind == CK_LOOP) CR.ok = false;
         CR.bodies.assign(nb, CrbaBody{0, -1, 0, 0});
@@ -2177,7 +2144,7 @@ int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep
     {
         DerivProgram &DV = P.deriv;
         DV = DerivProgram();
-        DV.ok = sweep_mask == 7;
+        DV.ok = true;
         for (const ClusterRec &cr : clusters) {
             if (cr.kind == CK_LOOP) DV.ok = false;
             if (cr.kind == CK_FREE && cr.first_body != 0) DV.ok = false;

@@ -479,11 +479,43 @@ struct DerivProgram {
     std::vector<uint64_t> related;
 };
 
-// LDS budget per wavefront, in slots, of each kernel (ABA / RNEA x f32 / f64).  Few slots mean more
-// wavefronts per CU and more state in the global slab; the best trade differs per kernel.
-struct LdsBudget {
-    int aba32 = 0, aba64 = 0, rnea32 = 0, rnea64 = 0;
-    int chain32w = 0;  // chain program at four wavefronts per SIMD
+// What a plan is built and launched with: the LDS budgets and launch shapes of the kernels and the route switches.  The member
+// initialisers are the defaults; capi.cpp (plan_options_from_env) reads the GRBDA_* variables of INTEGRATION.md into them once per plan.
+struct PlanOptions {
+    // launch shape per kernel, index = (rnea ? 2 : 0) + (f64 ? 1 : 0): LDS budget per wavefront for the slot store (bytes; few slots mean
+    // more wavefronts per CU and more state in the global slab, the best trade differs per kernel), and wavefronts launched per CU (the
+    // grid is persistent).  Defaults from sweeps on MI355X over the MIT humanoid, Mini Cheetah and JVRC-1 at 4096 tiles: the f32 RNEA
+    // kernel needs ~100 VGPRs and gains from 16 wavefronts per CU with 10 KiB each; the f64 RNEA kernel is register-bound to 8 per CU and
+    // prefers 6 with more LDS.  GRBDA_LDS_BYTES_PER_WAVE / GRBDA_WAVES_PER_CU set all four, the suffixed forms (_ABA32, _ABA64, _RNEA32,
+    // _RNEA64) one of them.
+    int lds_bytes_per_wave[4] = {20480, 20480, 10240, 26624};
+    int waves_per_cu[4] = {8, 8, 16, 6};
+    // fp64 forward dynamics OFF the plain chain kernels -- the cluster interpreter, and chain programs with generic segments (one wavefront
+    // per SIMD, 428 registers, chain_kernels.hip) -- runs best at one wavefront per SIMD (measured on the zoo, 131 072 states: interpreter
+    // 0.71-0.94 -> 0.46-0.66 ms; generic chain kernel even); GRBDA_WAVES_PER_CU / _ABA64 set it like the others
+    int waves_per_cu_f64_wide_regs = 4;
+    // the f32 chain programs laid out for four wavefronts per SIMD (HostPlan::chain32w / rchain32w): a quarter of the CU's 160 KiB per SIMD,
+    // in whole rows of 64 floats
+    int chain32w_lds_bytes = (160 * 1024 / 16) / 256 * 256;
+    int gen1_waves_cap = 0;       // GRBDA_GEN1_WAVES_PER_CU > 0: wavefronts per CU of the single-cluster kernels
+    int gen1_tiles_per_wave = 0;  // GRBDA_GEN1_TILES_PER_WAVE > 0: grid = tiles / this (the dispatcher balances the workgroups)
+    int lm_waves = 0;             // GRBDA_LM_WAVES=2: latency mode never takes four wavefronts per tile
+    int minv_wpc = 0;             // GRBDA_MINV_WPC: upper limit of the workgroups per CU of minv_mfma_kernel (0: what registers and LDS hold)
+    int deriv_waves = 0;          // GRBDA_DERIV_WAVES_PER_CU: grid of the inverse-dynamics derivative kernel (0: 3)
+    int crba_waves = 16;          // GRBDA_CRBA_WAVES_PER_CU: grid of the composite-rigid-body kernel (fp32: 99 registers, four wavefronts per
+                                  // SIMD: JVRC-1 mass matrix 1.95 -> 1.81 ms per 262 144 states against eight per CU; fp64 is capped at eight)
+    // routes
+    bool no_chain = false;             // GRBDA_NO_CHAIN=1: keep the general interpreter (tests of the general kernels)
+    bool no_latency_mode = false;      // GRBDA_NO_LATENCY_MODE=1: small batches keep the one-wavefront-per-tile kernel
+    bool no_gen1 = false;              // GRBDA_NO_GEN1 (set): single-cluster programs take the chain kernel (ChainProgram::single_gen)
+    bool no_crba = false;              // GRBDA_NO_CRBA=1: mass matrix through nv + 1 inverse-dynamics evaluations (the path of loop models)
+    bool no_minv = false;              // GRBDA_NO_MINV=1: the derivative pipeline keeps the dense factorisation of H
+    bool solve_f64 = false;            // GRBDA_SOLVE_F64=1: the SPD solve of the f32 derivative entry points computes in f64
+    bool no_analytic = false;          // GRBDA_NO_ANALYTIC=1: derivatives by the unit-vector / central-difference batches only
+    bool no_manifold = false;          // GRBDA_NO_MANIFOLD=1: implicit models keep the difference batches
+    bool no_small_constraint = false;  // GRBDA_NO_SMALL_CONSTRAINT=1: no half-size build of the constraint kernel
+    bool no_efpa = false;              // GRBDA_NO_EFPA=1: inverse OSIM through unit wrenches and the ABA / RNEA kernels
+    bool no_projection = false;        // GRBDA_NO_PROJECTION (set): no spanning-tree route; models that need it are refused
 };
 
 struct HostPlan {
@@ -522,8 +554,7 @@ struct HostPlan {
 
 // Compile a model-description blob (include/grbda_model_desc.h) into a HostPlan.
 // Returns 0 or a negative GRBDA_E* code (include/grbda_hip.h); msg receives a diagnostic.
-int compile_plan(const void *blob, size_t bytes, const LdsBudget &lds, int sweep_mask, HostPlan &out,
-                 char *msg, size_t msg_cap);
+int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPlan &out, char *msg, size_t msg_cap);
 
 // The spanning-tree model (every revolute body its own Revolute cluster) as a model-description blob; span_q / span_v: per body,
 // its first position / velocity index in that model (plan.cpp; capi.cpp manifold_derivs).

@@ -725,17 +725,10 @@ int main(int argc, char **argv)
             while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) blob.insert(blob.end(), buf, buf + n);
             std::fclose(f);
         }
-        // the budgets of capi.cpp (grbda_plan_create: lds_bytes_per_wave defaults, kChainWideLdsBytes); the latency-mode programs
-        // carry their own (plan.cpp)
-        LdsBudget lds;
-        lds.aba32 = 20480 / (4 * kWave);
-        lds.aba64 = 20480 / (8 * kWave);
-        lds.rnea32 = 10240 / (4 * kWave);
-        lds.rnea64 = 26624 / (8 * kWave);
-        lds.chain32w = 10240 / (4 * kWave);
+        // the library's default budgets (PlanOptions); the latency-mode programs carry their own (plan.cpp)
         HostPlan hp;
         char msg[512] = {0};
-        if (int rc = compile_plan(blob.data(), blob.size(), lds, 7, hp, msg, sizeof msg)) {
+        if (int rc = compile_plan(blob.data(), blob.size(), PlanOptions{}, hp, msg, sizeof msg)) {
             std::printf("%s: plan error %d %s\n", file.c_str(), rc, msg);
             n_find++;
             continue;

@@ -21,13 +21,7 @@ int urdf_to_blob(const char *const *paths, int n_paths, int ori_repr, std::vecto
 
 static int compile(const std::vector<unsigned char> &blob, grbda_hip::HostPlan &hp, char *msg, size_t cap)
 {
-    grbda_hip::LdsBudget lds;  // the defaults of capi.cpp: 20 KiB per wavefront f32, 40 KiB f64 ABA; 10 / 20 KiB RNEA
-    lds.aba32 = 20480 / (4 * 64);
-    lds.aba64 = 40960 / (8 * 64);
-    lds.rnea32 = 10240 / (4 * 64);
-    lds.rnea64 = 20480 / (8 * 64);
-    lds.chain32w = 10240 / (4 * 64);
-    return grbda_hip::compile_plan(blob.data(), blob.size(), lds, 7, hp, msg, cap);
+    return grbda_hip::compile_plan(blob.data(), blob.size(), grbda_hip::PlanOptions{}, hp, msg, cap);  // the library's defaults
 }
 
 int main(int argc, char **argv)

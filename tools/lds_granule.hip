@@ -1,5 +1,5 @@
 // tools/lds_granule.hip -- how many one-wavefront workgroups with N bytes of dynamic LDS does a CU of this GPU hold?
-// build: hipcc --offload-arch=gfx950 -O2 tools/lds_granule.hip -o build/exp/lds_granule
+// build: hipcc --offload-arch=gfx950 -O2 tools/lds_granule.hip -o build/tools/lds_granule
 // (a) what the runtime's occupancy query says, (b) measured: workgroups that spin a fixed time, grid = CUs x k, time vs k.
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -10,7 +10,7 @@ from generalized_rbda_amd.states import random_states
 for model in (sys.argv[1:] or ["mit_humanoid", "mini_cheetah"]):
     path = os.path.join(ROOT, "tests/golden/robot-models", model + ".urdf")
     plans = {}
-    for label, env in (("four", {}), ("two", {"GRBDA_LM_WAVES": "2"}), ("two, blocks in the slab", {"GRBDA_LM_WAVES": "2", "GRBDA_LM2_SLAB": "1"}),
+    for label, env in (("four", {}), ("two", {"GRBDA_LM_WAVES": "2"}),
                        ("one", {"GRBDA_NO_LATENCY_MODE": "1"})):
         os.environ.update(env)
         plans[label] = G.Plan.from_urdf(path)

@@ -17,4 +17,4 @@ for prec in precs:
     t0 = time.perf_counter()
     for _ in range(3): out = plan.fd_derivatives(tq, tqd, tt)
     torch.cuda.synchronize()
-    print(f"tello_with_arms B={B} {prec} fd_derivatives {(time.perf_counter() - t0) / 3 * 1e3:.3f} ms  (GRBDA_WORK_WANT_MB={os.environ.get('GRBDA_WORK_WANT_MB', '-')})", flush=True)
+    print(f"tello_with_arms B={B} {prec} fd_derivatives {(time.perf_counter() - t0) / 3 * 1e3:.3f} ms  (GRBDA_WORK_MAX_MB={os.environ.get('GRBDA_WORK_MAX_MB', '-')})", flush=True)
