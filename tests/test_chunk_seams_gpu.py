@@ -22,7 +22,7 @@ import oracle_py as O
 import generalized_rbda_amd as G
 from generalized_rbda_amd.states import random_states
 from graph_capture import capture
-from test_graph_capture_gpu import _dq_oracle, _fd_columns, _mass_oracle, _model, _rel, _states
+from entry_points import _dq_oracle, _fd_columns, _mass_oracle, _model, _rel, _states
 
 pytestmark = pytest.mark.gpu
 TOL64 = 1e-9
@@ -206,7 +206,7 @@ def _fixed_per_state(entry, plan):
 
 
 def _fixed_check(entry, blob, s, o, big):
-    from test_graph_capture_gpu import _chk_osim
+    from entry_points import _chk_osim
 
     tol32 = lambda a: max(a, TOL32) if s["dtype"] == "f32" else a
     if entry == "apply_test_force":
