@@ -36,6 +36,25 @@ int hip_err(hipError_t e, const char *what)
     return set_err(GRBDA_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// device copies of the tables of one chain program (plan.h, ChainProgram / RneaChainProgram)
+struct ChainTables {
+    ChainSeg *segs = nullptr;
+    ChainLink *links = nullptr;
+    ChainPair *pairs = nullptr;
+    ChainFree *frees = nullptr;
+    ChainDiff *diffs = nullptr;
+    ChainGen *gens = nullptr;
+    ChainGenBody *gbodies = nullptr;
+};
+struct RneaChainTables {
+    RneaSeg *segs = nullptr;
+    RneaLink *links = nullptr;
+    RneaPair *pairs = nullptr;
+    RneaFree *frees = nullptr;
+    RneaDiff *diffs = nullptr;
+    ChainGen *gens = nullptr;
+    ChainGenBody *gbodies = nullptr;
+};
 // per-(device) copies of the plan tables; per-(device, stream) scratch slabs
 struct DeviceTables {
     Step *aba_steps = nullptr, *rnea_steps = nullptr;
@@ -49,17 +68,10 @@ struct DeviceTables {
     BodyRec *rnea_bodies[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // RNEA slots
     double *consts64 = nullptr;
     float *consts32 = nullptr;
-    // chain program of the f32 fast path (plan.h, ChainProgram)
-    // [0] f32, two wavefronts per SIMD (HostPlan::chain32), [1] f32, four (chain32w), [2] f64 (chain64)
-    // chain programs: 0 f32, 1 f32 at four wavefronts per SIMD, 2 f64, 3 / 4 latency mode f32 / f64 (ChainProgram::n_waves = 2),
-    // 5 / 6 latency mode f32 / f64 with four wavefronts per tile
-    ChainSeg *chain_segs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainLink *chain_links[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainPair *chain_pairs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainFree *chain_frees[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainDiff *chain_diffs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainGen *chain_gens[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainGenBody *chain_gbodies[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // the chain programs HostPlan::chain[s] / rchain[s] that are ok, by ChainSlot (plan.h).  chain[SLOT_F32_WIDE] stays empty: forward
+    // dynamics at four wavefronts per SIMD has no route
+    ChainTables chain[kChainSlots];
+    RneaChainTables rchain[kChainSlots];
     CrbaBody *crba_bodies = nullptr;
     DerivBody *deriv_bodies = nullptr;
     uint64_t *deriv_related = nullptr;  // DerivProgram::related
@@ -67,15 +79,6 @@ struct DeviceTables {
     int32_t *minv_coltab = nullptr;     // ... and the column programs of minv_mfma_kernel
     int32_t *related_table = nullptr;   // HostPlan::related_table (plans of the wide route with more than 64 velocities)
     int32_t *span_q = nullptr, *span_v = nullptr, *crow = nullptr;  // grbda_plan::span_q / span_v / crow
-    // inverse dynamics on the chains: [0] f32 (HostPlan::rchain32), [1] f64, [2] f32 at four wavefronts per SIMD (rchain32w),
-    // [3] / [4] latency mode f32 / f64 with two wavefronts per tile (rchain32p / rchain64p), [5] / [6] with four (rchain32q / rchain64q)
-    RneaSeg *rchain_segs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    RneaLink *rchain_links[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    RneaPair *rchain_pairs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    RneaFree *rchain_frees[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    RneaDiff *rchain_diffs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainGen *rchain_gens[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ChainGenBody *rchain_gbodies[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int n_cu = 0;
     unsigned long long *bad_count = nullptr;  // this device's counter of states with a pivot that is not positive (deriv_kernels.hip)
 };
@@ -141,6 +144,37 @@ struct grbda_plan {
 
 namespace {
 
+hipError_t up(const void *src, size_t bytes, void **dst)
+{
+    hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
+    if (e != hipSuccess) return e;
+    return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+}
+template <class R>
+hipError_t up(const std::vector<R> &src, R **dst)
+{
+    return up(src.data(), src.size() * sizeof(R), reinterpret_cast<void **>(dst));
+}
+// upload and release of the tables of one chain program (either family) on the current device
+template <class Program, class Tables>
+int upload_chain_program(const Program &cp, Tables &ct)
+{
+    hipError_t e;
+    if ((e = up(cp.segs, &ct.segs)) != hipSuccess || (e = up(cp.links, &ct.links)) != hipSuccess || (e = up(cp.pairs, &ct.pairs)) != hipSuccess ||
+        (e = up(cp.frees, &ct.frees)) != hipSuccess || (e = up(cp.diffs, &ct.diffs)) != hipSuccess || (e = up(cp.gens, &ct.gens)) != hipSuccess ||
+        (e = up(cp.gbodies, &ct.gbodies)) != hipSuccess)
+        return hip_err(e, "plan upload");
+    if ((e = set_max_dynamic_lds_chain()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
+    return 0;
+}
+template <class Tables>
+void free_chain_tables(Tables &ct)
+{
+    for (void *ptr : {static_cast<void *>(ct.segs), static_cast<void *>(ct.links), static_cast<void *>(ct.pairs), static_cast<void *>(ct.frees),
+                      static_cast<void *>(ct.diffs), static_cast<void *>(ct.gens), static_cast<void *>(ct.gbodies)})
+        (void)hipFree(ptr);
+}
+
 int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
 {
     int count = 0;
@@ -157,11 +191,6 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
     }
     DeviceTables t;
     const HostPlan &h = p->host;
-    auto up = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
-        hipError_t e2 = hipMalloc(dst, bytes ? bytes : 16);
-        if (e2 != hipSuccess) return e2;
-        return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
     std::vector<float> c32(h.consts.begin(), h.consts.end());
     if ((e = up(h.aba_steps.data(), h.aba_steps.size() * sizeof(Step), (void **)&t.aba_steps)) != hipSuccess ||
         (e = up(h.rnea_steps.data(), h.rnea_steps.size() * sizeof(Step), (void **)&t.rnea_steps)) != hipSuccess ||
@@ -207,18 +236,11 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
             (e = up(L.acc_k.data(), L.acc_k.size() * sizeof(int32_t), (void **)&t.acc_k[w])) != hipSuccess)
             return hip_err(e, "plan upload");
     }
-    for (int w = 0; w < 7; w++) {
-        const RneaChainProgram &rp = w == 0 ? h.rchain32 : (w == 1 ? h.rchain64 : (w == 2 ? h.rchain32w : (w == 3 ? h.rchain32p : (w == 4 ? h.rchain64p : (w == 5 ? h.rchain32q : h.rchain64q)))));
-        if (!rp.ok) continue;
-        if ((e = up(rp.segs.data(), rp.segs.size() * sizeof(RneaSeg), (void **)&t.rchain_segs[w])) != hipSuccess ||
-            (e = up(rp.links.data(), rp.links.size() * sizeof(RneaLink), (void **)&t.rchain_links[w])) != hipSuccess ||
-            (e = up(rp.pairs.data(), rp.pairs.size() * sizeof(RneaPair), (void **)&t.rchain_pairs[w])) != hipSuccess ||
-            (e = up(rp.frees.data(), rp.frees.size() * sizeof(RneaFree), (void **)&t.rchain_frees[w])) != hipSuccess ||
-            (e = up(rp.diffs.data(), rp.diffs.size() * sizeof(RneaDiff), (void **)&t.rchain_diffs[w])) != hipSuccess ||
-            (e = up(rp.gens.data(), rp.gens.size() * sizeof(ChainGen), (void **)&t.rchain_gens[w])) != hipSuccess ||
-            (e = up(rp.gbodies.data(), rp.gbodies.size() * sizeof(ChainGenBody), (void **)&t.rchain_gbodies[w])) != hipSuccess)
-            return hip_err(e, "plan upload");
-        if ((e = set_max_dynamic_lds_chain()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
+    for (int s = 0; s < kChainSlots; s++) {
+        if (h.rchain[s].ok)
+            if (int rc = upload_chain_program(h.rchain[s], t.rchain[s])) return rc;
+        if (h.chain[s].ok && s != SLOT_F32_WIDE)
+            if (int rc = upload_chain_program(h.chain[s], t.chain[s])) return rc;
     }
     if (h.crba.ok && (e = up(h.crba.bodies.data(), h.crba.bodies.size() * sizeof(CrbaBody), (void **)&t.crba_bodies)) != hipSuccess)
         return hip_err(e, "plan upload");
@@ -236,19 +258,6 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
         ((e = up(h.deriv.minv.bodies.data(), h.deriv.minv.bodies.size() * sizeof(MinvBody), (void **)&t.minv_bodies)) != hipSuccess ||
          (e = up(h.deriv.minv.coltab.data(), h.deriv.minv.coltab.size() * sizeof(int32_t), (void **)&t.minv_coltab)) != hipSuccess))
         return hip_err(e, "plan upload");
-    for (int w = 0; w < 7; w++) {
-        const ChainProgram &cp = w == 0 ? h.chain32 : (w == 1 ? h.chain32w : (w == 2 ? h.chain64 : (w == 3 ? h.chain32p : (w == 4 ? h.chain64p : (w == 5 ? h.chain32q : h.chain64q)))));
-        if (!cp.ok) continue;
-        if ((e = up(cp.segs.data(), cp.segs.size() * sizeof(ChainSeg), (void **)&t.chain_segs[w])) != hipSuccess ||
-            (e = up(cp.links.data(), cp.links.size() * sizeof(ChainLink), (void **)&t.chain_links[w])) != hipSuccess ||
-            (e = up(cp.pairs.data(), cp.pairs.size() * sizeof(ChainPair), (void **)&t.chain_pairs[w])) != hipSuccess ||
-            (e = up(cp.frees.data(), cp.frees.size() * sizeof(ChainFree), (void **)&t.chain_frees[w])) != hipSuccess ||
-            (e = up(cp.diffs.data(), cp.diffs.size() * sizeof(ChainDiff), (void **)&t.chain_diffs[w])) != hipSuccess ||
-            (e = up(cp.gens.data(), cp.gens.size() * sizeof(ChainGen), (void **)&t.chain_gens[w])) != hipSuccess ||
-            (e = up(cp.gbodies.data(), cp.gbodies.size() * sizeof(ChainGenBody), (void **)&t.chain_gbodies[w])) != hipSuccess)
-            return hip_err(e, "plan upload");
-        if ((e = set_max_dynamic_lds_chain()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
-    }
     if (p->span) {
         if ((e = up(p->span_q.data(), p->span_q.size() * sizeof(int32_t), (void **)&t.span_q)) != hipSuccess ||
             (e = up(p->span_v.data(), p->span_v.size() * sizeof(int32_t), (void **)&t.span_v)) != hipSuccess ||
@@ -378,173 +387,237 @@ DevPlan<T> make_dev_plan(const grbda_plan *p, const DeviceTables &t, bool rnea, 
 }
 
 template <class T>
-bool chain_covers(const grbda_plan *p)
+const T *consts_of(const DeviceTables &t)
 {
-    if (p->opt.no_chain) return false;
-    if (sizeof(T) == 8) return p->host.chain64.ok;
-    return p->host.chain32.ok;
+    return sizeof(T) == 4 ? reinterpret_cast<const T *>(t.consts32) : reinterpret_cast<const T *>(t.consts64);
 }
 
-// which forward-dynamics kernel a batch of B states runs on a device with n_cu compute units: ONE definition, used by the launch
-// path below and by grbda_kernel_name (bench.py prints the name next to the roofline figures)
-enum AbaPath { ABA_GEN1, ABA_LM, ABA_LM4, ABA_CHAIN, ABA_INTERPRETER };
-template <class T>
-size_t lm_lds_bytes(const grbda_plan *p, int n_waves = 2)
+// ---- kernel argument blocks of the chain kernels: everything that follows from (plan, device, program slot) -----------------------
+// The call sites state only what is special to them.  The generic-cluster tables of a program without generic clusters are passed as
+// null (no_gens), the segment tables of a single-cluster launch likewise (gen1_only): the values these paths have always passed.
+template <class Dev, class Program, class Tables>
+void fill_chain_tables(Dev &d, const Program &cp, const Tables &ct)
 {
-    const HostPlan &h = p->host;
-    const ChainProgram &lp = n_waves == 4 ? (sizeof(T) == 8 ? h.chain64q : h.chain32q) : (sizeof(T) == 8 ? h.chain64p : h.chain32p);
-    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(h.nq + 2 * h.nv) * sizeof(T);
-    const size_t lds_lm = static_cast<size_t>(lp.n_lds) * kWave * sizeof(T);
-    return lds_lm < stage_all ? stage_all : lds_lm;
-}
-// the single-cluster kernels prefetch a state's positions into min(n + 3, 8) registers (implicit cluster: one per body) or n (explicit)
-static bool gen1_positions_fit(int nq, const ChainGen &g)
-{
-    const int room = g.kind ? std::min(g.n + 3, kMaxClusterBodies) : g.n;
-    return nq <= room && g.n <= 4;
-}
-template <class T>
-size_t gen1_lds_bytes(const grbda_plan *p)
-{
-    const HostPlan &h = p->host;
-    const ChainProgram &sp = sizeof(T) == 8 ? h.chain64 : h.chain32;
-    return static_cast<size_t>(sp.n_lds) * kWave * sizeof(T) + static_cast<size_t>(kWave) * static_cast<size_t>(h.nq + 2 * h.nv) * sizeof(T);
-}
-template <class T>
-AbaPath choose_aba(const grbda_plan *p, int n_cu, size_t B, bool f_ext)
-{
-    const HostPlan &h = p->host;
-    if (f_ext || !chain_covers<T>(p)) return ABA_INTERPRETER;
-    const size_t n_tiles = (B + kWave - 1) / kWave;
-    const ChainProgram &sp = sizeof(T) == 8 ? h.chain64 : h.chain32;
-    if (sp.ok && sp.single_gen && gen1_lds_bytes<T>(p) <= 65536 && gen1_positions_fit(h.nq, sp.gens[0])) return ABA_GEN1;
-    const ChainProgram &lp = sizeof(T) == 8 ? h.chain64p : h.chain32p;
-    // four wavefronts per tile while that still leaves at most two wavefronts per SIMD (two tiles per CU); GRBDA_LM_WAVES=2 keeps two
-    // (only the fp32 latency-mode kernels carry the differential segments: plan.cpp builds no fp64 program with them)
-    const ChainProgram &lq = sizeof(T) == 8 ? h.chain64q : h.chain32q;
-    if (lq.ok && (sizeof(T) == 4 || lq.diffs.empty()) && !p->opt.no_latency_mode && p->opt.lm_waves != 2 && n_tiles > 0 &&
-        n_tiles <= static_cast<size_t>(n_cu) * 2 && lm_lds_bytes<T>(p, 4) <= 81920)
-        return ABA_LM4;
-    if (lp.ok && (sizeof(T) == 4 || lp.diffs.empty()) && !p->opt.no_latency_mode && n_tiles <= static_cast<size_t>(n_cu) * 4 && n_tiles > 0 &&
-        lm_lds_bytes<T>(p) <= 40960)
-        return ABA_LM;
-    return ABA_CHAIN;
-}
-
-template <class T>
-int run_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *qd, const T *tau, T *ydd, size_t B,
-              int device, void *stream)
-{
-    const HostPlan &h = p->host;
-    const size_t n_tiles0 = (B + kWave - 1) / kWave;
-    const AbaPath path = choose_aba<T>(p, t.n_cu, B, false);
-    {   // single-cluster programs: the fused, slab-free kernel (chain_kernels.hip, aba_gen1_kernel)
-        const int w1 = sizeof(T) == 8 ? 2 : 0;
-        const ChainProgram &sp = sizeof(T) == 8 ? h.chain64 : h.chain32;
-        const size_t work = static_cast<size_t>(sp.n_lds) * kWave * sizeof(T);
-        const size_t lds_total = gen1_lds_bytes<T>(p);  // work area + the staged input rows
-        if (path == ABA_GEN1) {
-            ChainDev<T> d;
-            std::memset(&d, 0, sizeof d);
-            d.bad_count = t.bad_count;
-            d.gens = t.chain_gens[w1];
-            d.gbodies = t.chain_gbodies[w1];
-            d.n_gens = 1;
-            d.cints = t.cints;
-            d.consts = sizeof(T) == 4 ? reinterpret_cast<const T *>(t.consts32) : reinterpret_cast<const T *>(t.consts64);
-            d.nq = h.nq;
-            d.nv = h.nv;
-            d.ori_repr = h.ori_repr;
-            d.out_lds = -1;
-            d.lds_bytes = static_cast<int>(work);
-            for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
-            size_t per_cu = static_cast<size_t>(gen1_waves_per_simd<T>(sp.gens[0].n)) * 4;
-            const size_t fit = lds_workgroups_per_cu(lds_total);
-            if (fit < per_cu) per_cu = fit;
-            if (p->opt.gen1_waves_cap > 0 && static_cast<size_t>(p->opt.gen1_waves_cap) < per_cu) per_cu = static_cast<size_t>(p->opt.gen1_waves_cap);
-            size_t grid = static_cast<size_t>(t.n_cu) * per_cu;
-            if (p->opt.gen1_tiles_per_wave > 0) grid = (n_tiles0 + p->opt.gen1_tiles_per_wave - 1) / p->opt.gen1_tiles_per_wave;
-            if (grid > n_tiles0) grid = n_tiles0;
-            hipError_t e = launch_aba_gen1<T>(d, sp.gens[0].n, sp.gens[0].kind != 0, q, qd, tau, ydd, B, static_cast<int>(grid), lds_total,
-                                              static_cast<hipStream_t>(stream));
-            return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba single-cluster launch");
-        }
-    }
-    // Latency mode: a batch of at most one tile per SIMD would leave every SIMD with a single wavefront; a tile then goes
-    // to a workgroup of two wavefronts that split its limbs (chain_kernels.hip, aba_chain_lm_kernel).  GRBDA_NO_LATENCY_MODE=1
-    // keeps the ordinary kernel (A/B runs); results agree to rounding (the base sums one partial inertia per wavefront).
-    {
-        const int lm_waves = path == ABA_LM4 ? 4 : 2;
-        const ChainProgram &lp = lm_waves == 4 ? (sizeof(T) == 8 ? h.chain64q : h.chain32q) : (sizeof(T) == 8 ? h.chain64p : h.chain32p);
-        const size_t lds_lm = lm_lds_bytes<T>(p, lm_waves);
-        if (path == ABA_LM || path == ABA_LM4) {
-            const int w = lm_waves == 4 ? (sizeof(T) == 8 ? 6 : 5) : (sizeof(T) == 8 ? 4 : 3);
-            ChainDev<T> d;
-            d.bad_count = t.bad_count;
-            d.segs = t.chain_segs[w];
-            d.links = t.chain_links[w];
-            d.pairs = t.chain_pairs[w];
-            d.frees = t.chain_frees[w];
-            d.diffs = lp.diffs.empty() ? nullptr : t.chain_diffs[w];  // (fp32 programs only: plan.cpp)
-            d.n_diffs = static_cast<int>(lp.diffs.size());
-            d.gens = nullptr;
-            d.gbodies = nullptr;
-            d.n_gens = 0;
-            d.cints = t.cints;
-            d.consts = sizeof(T) == 4 ? reinterpret_cast<const T *>(t.consts32) : reinterpret_cast<const T *>(t.consts64);
-            d.n_segs = static_cast<int>(lp.segs.size());
-            d.nq = h.nq;
-            d.nv = h.nv;
-            d.n_glb_slots = lp.n_glb + 1;  // (+ the row that carries the other wavefronts' bad-pivot masks to wavefront 0, aba_chain_lm_kernel)
-            d.ori_repr = h.ori_repr;
-            d.debug = 0;
-            d.sv_global = 0;
-            d.fuse = d.stage_lds_v = d.stage_v_index = 0;
-            d.out_lds = lp.out_lds;
-            d.lds_bytes = static_cast<int>(lds_lm);
-            for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
-            const size_t grid = n_tiles0;  // (<= 4 workgroups per CU: all resident)
-            const size_t n_rows = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);
-            void *scratch = nullptr;
-            if (int rc = ensure_scratch(p, device, stream, grid * n_rows * kWave * sizeof(T) + 256, &scratch)) return rc;
-            hipError_t e = launch_aba_chain_lm<T>(d, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_lm,
-                                                  static_cast<hipStream_t>(stream), lm_waves);
-            return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba chain launch (latency mode)");
-        }
-    }
-    const int w = sizeof(T) == 8 ? 2 : 0;
-    const int kid = sizeof(T) == 8 ? 1 : 0;
-    const ChainProgram &cp = w == 2 ? h.chain64 : h.chain32;
-    const size_t waves_per_cu = static_cast<size_t>((sizeof(T) == 8 && !cp.gens.empty()) ? p->opt.waves_per_cu_f64_wide_regs : p->opt.waves_per_cu[kid]);
-    const size_t lds_budget = static_cast<size_t>(p->opt.lds_bytes_per_wave[kid]);
-    ChainDev<T> d;
-    d.bad_count = t.bad_count;
-    d.segs = t.chain_segs[w];
-    d.links = t.chain_links[w];
-    d.pairs = t.chain_pairs[w];
-    d.frees = t.chain_frees[w];
-    d.diffs = t.chain_diffs[w];
+    d.segs = ct.segs;
+    d.links = ct.links;
+    d.pairs = ct.pairs;
+    d.frees = ct.frees;
+    d.diffs = ct.diffs;
     d.n_diffs = static_cast<int>(cp.diffs.size());
-    d.gens = t.chain_gens[w];
-    d.gbodies = t.chain_gbodies[w];
+    d.gens = ct.gens;
+    d.gbodies = ct.gbodies;
     d.n_gens = static_cast<int>(cp.gens.size());
-    d.cints = t.cints;
-    d.consts = sizeof(T) == 4 ? reinterpret_cast<const T *>(t.consts32) : reinterpret_cast<const T *>(t.consts64);
     d.n_segs = static_cast<int>(cp.segs.size());
+    d.n_glb_slots = cp.n_glb;
+}
+template <class T, class Dev>
+void fill_chain_model(Dev &d, const HostPlan &h, const DeviceTables &t)
+{
+    d.cints = t.cints;
+    d.consts = consts_of<T>(t);
     d.nq = h.nq;
     d.nv = h.nv;
-    d.n_glb_slots = cp.n_glb;
     d.ori_repr = h.ori_repr;
-    d.debug = 0;
+    for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
+}
+template <class T>
+ChainDev<T> chain_dev(const grbda_plan *p, const DeviceTables &t, ChainSlot slot)
+{
+    const ChainProgram &cp = p->host.chain[slot];
+    ChainDev<T> d{};  // (debug, fuse, stage_*: 0)
+    fill_chain_tables(d, cp, t.chain[slot]);
+    fill_chain_model<T>(d, p->host, t);
     d.sv_global = cp.sv_global ? 1 : 0;
     d.out_lds = cp.out_lds;
-    d.fuse = d.stage_lds_v = d.stage_v_index = 0;
+    d.bad_count = t.bad_count;
+    return d;
+}
+template <class T>
+RneaChainDev<T> rnea_chain_dev(const grbda_plan *p, const DeviceTables &t, ChainSlot slot)
+{
+    RneaChainDev<T> d{};
+    fill_chain_tables(d, p->host.rchain[slot], t.rchain[slot]);
+    fill_chain_model<T>(d, p->host, t);
+    return d;
+}
+template <class Dev>
+void no_gens(Dev &d)
+{
+    d.gens = nullptr;
+    d.gbodies = nullptr;
+    d.n_gens = 0;
+}
+// the single-cluster kernels take their one cluster from gens[0]: no segment tables, no slab
+template <class Dev>
+void gen1_only(Dev &d)
+{
+    d.segs = nullptr;
+    d.links = nullptr;
+    d.pairs = nullptr;
+    d.frees = nullptr;
+    d.diffs = nullptr;
+    d.n_diffs = d.n_segs = d.n_glb_slots = 0;
+    d.n_gens = 1;
+}
+
+// ---- launch shapes ------------------------------------------------------------------------------------------------------------------
+template <class T>
+size_t stage_all_bytes(const HostPlan &h)  // the staging area of a tile's whole input: q, qd and tau / ydd transposed at once
+{
+    return static_cast<size_t>(kWave) * static_cast<size_t>(h.nq + 2 * h.nv) * sizeof(T);
+}
+// Persistent launch of one-wavefront workgroups, wavefronts_per_cu per CU and at most one per tile.  LDS per wavefront: the slot store, at
+// least the staging area of the longest input array, and that of all three at once when the budget holds it (stage_all_fits).
+// clamp_to_lds_fit: never more wavefronts than a CU's 160 KiB keep resident at once.  grid_unclamped is the grid before that clamp.
+struct LaunchShape {
+    size_t grid, grid_unclamped, lds_bytes;
+    bool stage_all_fits;
+};
+LaunchShape launch_shape(int n_cu, size_t n_tiles, size_t waves_per_cu, size_t store_bytes, int nq, int nv, size_t elem, size_t lds_budget,
+                         bool clamp_to_lds_fit)
+{
+    LaunchShape s;
+    s.grid = std::min(static_cast<size_t>(n_cu) * waves_per_cu, n_tiles);
+    s.grid_unclamped = s.grid;
+    const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(nq > nv ? nq : nv) * elem;
+    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(nq + 2 * nv) * elem;
+    s.lds_bytes = std::max(store_bytes, stage_one);
+    if (s.lds_bytes < stage_all && stage_all <= lds_budget) s.lds_bytes = stage_all;
+    s.stage_all_fits = s.lds_bytes >= stage_all;
+    const size_t fit = lds_workgroups_per_cu(s.lds_bytes);
+    if (clamp_to_lds_fit && fit >= 1 && fit < waves_per_cu) s.grid = std::min(s.grid, static_cast<size_t>(n_cu) * fit);
+    return s;
+}
+// the per-stream slab: rows of kWave scalars per resident wavefront (a program's global slots + the nq + 2 nv staged input rows)
+size_t scratch_bytes(size_t grid, size_t rows, size_t elem) { return grid * rows * kWave * elem + 256; }
+// grid of the single-cluster kernels: what registers (waves_per_simd) and LDS hold per CU, GRBDA_GEN1_WAVES_PER_CU / _TILES_PER_WAVE
+size_t gen1_grid(const grbda_plan *p, int n_cu, size_t n_tiles, int waves_per_simd, size_t lds_total)
+{
+    size_t per_cu = std::min(static_cast<size_t>(waves_per_simd) * 4, lds_workgroups_per_cu(lds_total));
+    if (p->opt.gen1_waves_cap > 0) per_cu = std::min(per_cu, static_cast<size_t>(p->opt.gen1_waves_cap));
+    size_t grid = static_cast<size_t>(n_cu) * per_cu;
+    if (p->opt.gen1_tiles_per_wave > 0) grid = (n_tiles + p->opt.gen1_tiles_per_wave - 1) / p->opt.gen1_tiles_per_wave;
+    return std::min(grid, n_tiles);
+}
+
+// ---- routes -------------------------------------------------------------------------------------------------------------------------
+// Which kernel a batch of B states runs on a device with n_cu compute units, and on which program: ONE definition per algorithm
+// (choose_aba, choose_rnea), which run() dispatches on, the launch functions take, and grbda_kernel_name formats (bench.py and the
+// tests read the name to know what they exercised).
+enum RoutePath { ROUTE_GEN1, ROUTE_LM, ROUTE_CHAIN, ROUTE_INTERPRETER };
+struct Route {
+    RoutePath path;
+    ChainSlot slot;  // the program of HostPlan::chain / rchain (not ROUTE_INTERPRETER)
+    int lm_waves;    // ROUTE_LM: wavefronts per tile, 2 or 4
+};
+// LDS of a latency-mode tile / of a single-cluster wavefront (work area + the staged input rows)
+template <class T, class Program>
+size_t lm_lds_bytes(const HostPlan &h, const Program &lp)
+{
+    return std::max(static_cast<size_t>(lp.n_lds) * kWave * sizeof(T), stage_all_bytes<T>(h));
+}
+template <class T, class Program>
+size_t gen1_lds_bytes(const HostPlan &h, const Program &sp)
+{
+    return static_cast<size_t>(sp.n_lds) * kWave * sizeof(T) + stage_all_bytes<T>(h);
+}
+// the single-cluster kernels prefetch a state's positions into min(n + 3, 8) registers (implicit cluster: one per body) or n (explicit)
+template <class T, class Program>
+bool gen1_usable(const HostPlan &h, const Program &sp)
+{
+    if (!sp.ok || !sp.single_gen || gen1_lds_bytes<T>(h, sp) > 65536) return false;
+    const ChainGen &g = sp.gens[0];
+    return h.nq <= (g.kind ? std::min(g.n + 3, kMaxClusterBodies) : g.n) && g.n <= 4;
+}
+// Latency mode: a batch of at most one tile per SIMD would leave every SIMD with a single wavefront; a tile then goes to a workgroup of two
+// wavefronts that split its limbs, and to four while that still leaves at most two wavefronts per SIMD (two tiles per CU; GRBDA_LM_WAVES=2
+// keeps two).  Only the fp32 latency-mode kernels carry the differential segments.  GRBDA_NO_LATENCY_MODE=1 keeps the ordinary kernels
+// (A/B runs); results agree to rounding (the base sums one partial inertia per wavefront).
+template <class T, class Program>
+bool lm_serves(const grbda_plan *p, const Program &lp, int waves, int n_cu, size_t n_tiles)
+{
+    return lp.ok && (sizeof(T) == 4 || lp.diffs.empty()) && !p->opt.no_latency_mode && !(waves == 4 && p->opt.lm_waves == 2) && n_tiles > 0 &&
+           n_tiles <= static_cast<size_t>(n_cu) * (waves == 4 ? 2 : 4) && lm_lds_bytes<T>(p->host, lp) <= static_cast<size_t>(lm_lds_limit(waves));
+}
+template <class T>
+Route choose_aba(const grbda_plan *p, int n_cu, size_t B, bool f_ext)
+{
+    const HostPlan &h = p->host;
+    constexpr bool f64 = sizeof(T) == 8;
+    const ChainSlot base = chain_slot(f64);
+    if (f_ext || p->opt.no_chain || !h.chain[base].ok) return {ROUTE_INTERPRETER, base, 0};
+    const size_t n_tiles = (B + kWave - 1) / kWave;
+    if (gen1_usable<T>(h, h.chain[base])) return {ROUTE_GEN1, base, 0};
+    for (const int waves : {4, 2})
+        if (lm_serves<T>(p, h.chain[chain_slot(f64, waves)], waves, n_cu, n_tiles)) return {ROUTE_LM, chain_slot(f64, waves), waves};
+    return {ROUTE_CHAIN, base, 0};
+}
+template <class T>
+Route choose_rnea(const grbda_plan *p, int n_cu, size_t B, bool f_ext)
+{
+    const HostPlan &h = p->host;
+    constexpr bool f64 = sizeof(T) == 8;
+    const ChainSlot base = chain_slot(f64);
+    if (f_ext || p->opt.no_chain || !h.rchain[base].ok) return {ROUTE_INTERPRETER, base, 0};
+    const size_t n_tiles = (B + kWave - 1) / kWave;
+    for (const int waves : {4, 2}) {
+        const RneaChainProgram &lp = h.rchain[chain_slot(f64, waves)];
+        if (lp.n_waves == waves && lm_serves<T>(p, lp, waves, n_cu, n_tiles)) return {ROUTE_LM, chain_slot(f64, waves), waves};
+    }
+    if (gen1_usable<T>(h, h.rchain[base])) return {ROUTE_GEN1, base, 0};
+    // f32: the inverse-dynamics kernel needs 109 VGPRs, so four wavefronts per SIMD fit; models whose blocks all fit the
+    // LDS of the two-per-SIMD shape (no global-slab fallback) run the program laid out for half the LDS per wavefront
+    // once the batch fills 16 wavefronts per CU (MIT humanoid 0.105 -> 0.095 ms, Mini Cheetah 0.079 -> 0.070 ms; JVRC-1,
+    // whose blocks spill already, loses)
+    if (!f64 && h.rchain[SLOT_F32_WIDE].ok && h.rchain[base].n_glb == 0 && h.rchain[base].gens.empty() && n_tiles > static_cast<size_t>(n_cu) * 8)
+        return {ROUTE_CHAIN, SLOT_F32_WIDE, 0};
+    return {ROUTE_CHAIN, base, 0};
+}
+
+template <class T>
+int run_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const T *q, const T *qd, const T *tau, T *ydd, size_t B, int device,
+              void *stream)
+{
+    const HostPlan &h = p->host;
+    const ChainProgram &cp = h.chain[r.slot];
+    const size_t n_tiles = (B + kWave - 1) / kWave;
+    const size_t in_rows = static_cast<size_t>(h.nq + 2 * h.nv);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    ChainDev<T> d = chain_dev<T>(p, t, r.slot);
+    void *scratch = nullptr;
+    if (r.path == ROUTE_GEN1) {  // single-cluster programs: the fused, slab-free kernel (chain_kernels.hip, aba_gen1_kernel)
+        gen1_only(d);
+        d.sv_global = 0;
+        d.out_lds = -1;
+        d.lds_bytes = static_cast<int>(static_cast<size_t>(cp.n_lds) * kWave * sizeof(T));
+        const size_t lds_total = gen1_lds_bytes<T>(h, cp);
+        const size_t grid = gen1_grid(p, t.n_cu, n_tiles, gen1_waves_per_simd<T>(cp.gens[0].n), lds_total);
+        hipError_t e = launch_aba_gen1<T>(d, cp.gens[0].n, cp.gens[0].kind != 0, q, qd, tau, ydd, B, static_cast<int>(grid), lds_total, hs);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba single-cluster launch");
+    }
+    if (r.path == ROUTE_LM) {  // (chain_kernels.hip, aba_chain_lm_kernel)
+        if (cp.diffs.empty()) d.diffs = nullptr;  // (fp32 programs only: plan.cpp)
+        no_gens(d);
+        d.n_glb_slots = cp.n_glb + 1;  // (+ the row that carries the other wavefronts' bad-pivot masks to wavefront 0, aba_chain_lm_kernel)
+        d.sv_global = 0;
+        const size_t lds_lm = lm_lds_bytes<T>(h, cp);
+        d.lds_bytes = static_cast<int>(lds_lm);
+        const size_t grid = n_tiles;  // (<= 4 workgroups per CU: all resident)
+        if (int rc = ensure_scratch(p, device, stream, scratch_bytes(grid, static_cast<size_t>(d.n_glb_slots) + in_rows, sizeof(T)), &scratch)) return rc;
+        hipError_t e = launch_aba_chain_lm<T>(d, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_lm, hs, r.lm_waves);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba chain launch (latency mode)");
+    }
+    const int kid = sizeof(T) == 8 ? 1 : 0;
+    const size_t waves_per_cu = static_cast<size_t>((sizeof(T) == 8 && !cp.gens.empty()) ? p->opt.waves_per_cu_f64_wide_regs : p->opt.waves_per_cu[kid]);
+    const LaunchShape s = launch_shape(t.n_cu, n_tiles, waves_per_cu, static_cast<size_t>(cp.n_lds) * kWave * sizeof(T), h.nq, h.nv, sizeof(T),
+                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[kid]), true);
     {   // the floating base's segments that only move data through the slab (devplan.h, ChainDev::fuse)
         int n_free_bwd = 0, at_bwd = -1;
-        for (size_t s = 0; s < cp.segs.size(); s++)
-            if (cp.segs[s].op == SEG_FREE_BWD) { n_free_bwd++; at_bwd = static_cast<int>(s); }
+        for (size_t i = 0; i < cp.segs.size(); i++)
+            if (cp.segs[i].op == SEG_FREE_BWD) { n_free_bwd++; at_bwd = static_cast<int>(i); }
         if (!cp.segs.empty() && cp.segs[0].op == SEG_FREE_FWD && n_free_bwd == 1 && cp.frees[cp.segs[0].first].lds_v >= 0) {
-            d.fuse |= 1;
+            // (without room for all three inputs the prologue stages one array at a time: the velocities are gone when it returns)
+            if (s.stage_all_fits) d.fuse |= 1;
             d.stage_lds_v = cp.frees[cp.segs[0].first].lds_v;
             d.stage_v_index = cp.frees[cp.segs[0].first].v_index;
         }
@@ -552,178 +625,51 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *q
             cp.segs[at_bwd + 1].first == cp.segs[at_bwd].first)
             d.fuse |= 2;
     }
-    for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
-    const size_t n_tiles = (B + kWave - 1) / kWave;
-    size_t grid = static_cast<size_t>(t.n_cu) * waves_per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    // LDS: the slot store, and at tile boundaries the staging area of the input transposition
-    size_t lds_bytes = static_cast<size_t>(cp.n_lds) * kWave * sizeof(T);
-    const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
-    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
-    if (lds_bytes < stage_one) lds_bytes = stage_one;
-    if (lds_bytes < stage_all && stage_all <= lds_budget) lds_bytes = stage_all;
-    d.lds_bytes = static_cast<int>(lds_bytes);
-    if (lds_bytes < stage_all) d.fuse &= ~1;  // (the prologue stages one array at a time: the velocities are gone when it returns)
-    const size_t fit = lds_workgroups_per_cu(lds_bytes);
-    if (fit >= 1 && fit < waves_per_cu) {
-        const size_t g2 = static_cast<size_t>(t.n_cu) * fit;
-        if (grid > g2) grid = g2;
-    }
-    const size_t n_rows = static_cast<size_t>(cp.n_glb) + static_cast<size_t>(d.nq + 2 * d.nv);
-    void *scratch = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, grid * n_rows * kWave * sizeof(T) + 256, &scratch)) return rc;
-    hipError_t e = launch_aba_chain<T>(d, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_bytes,
-                                           static_cast<hipStream_t>(stream));
+    d.lds_bytes = static_cast<int>(s.lds_bytes);
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, static_cast<size_t>(cp.n_glb) + in_rows, sizeof(T)), &scratch)) return rc;
+    hipError_t e = launch_aba_chain<T>(d, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba chain launch");
 }
 
 template <class T>
-size_t rnea_gen1_lds_bytes(const grbda_plan *p)
-{
-    const HostPlan &h = p->host;
-    const RneaChainProgram &rp = sizeof(T) == 8 ? h.rchain64 : h.rchain32;
-    return static_cast<size_t>(rp.n_lds) * kWave * sizeof(T) + static_cast<size_t>(kWave) * static_cast<size_t>(h.nq + 2 * h.nv) * sizeof(T);
-}
-template <class T>
-bool rnea_gen1_usable(const grbda_plan *p)
-{
-    const RneaChainProgram &rp = sizeof(T) == 8 ? p->host.rchain64 : p->host.rchain32;
-    return rp.ok && rp.single_gen && rnea_gen1_lds_bytes<T>(p) <= 65536 && gen1_positions_fit(p->host.nq, rp.gens[0]);
-}
-
-// latency mode of the inverse dynamics: wavefronts per tile for a batch of B states (0: the one-wavefront kernels); ONE definition, used by the launch path
-// and by grbda_kernel_name
-template <class T>
-int choose_rnea_lm(const grbda_plan *p, int n_cu, size_t B)
-{
-    const HostPlan &h = p->host;
-    const size_t n_tiles = (B + kWave - 1) / kWave;
-    if (p->opt.no_latency_mode || p->opt.no_chain || n_tiles == 0) return 0;
-    const bool kid = sizeof(T) == 8;
-    const RneaChainProgram &r4 = kid ? h.rchain64q : h.rchain32q, &r2 = kid ? h.rchain64p : h.rchain32p;
-    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(h.nq + 2 * h.nv) * sizeof(T);
-    if (r4.ok && r4.n_waves == 4 && (!kid || r4.diffs.empty()) && p->opt.lm_waves != 2 && n_tiles <= static_cast<size_t>(n_cu) * 2 &&
-        std::max(static_cast<size_t>(r4.n_lds) * kWave * sizeof(T), stage_all) <= 81920)
-        return 4;
-    if (r2.ok && r2.n_waves == 2 && (!kid || r2.diffs.empty()) && n_tiles <= static_cast<size_t>(n_cu) * 4 && std::max(static_cast<size_t>(r2.n_lds) * kWave * sizeof(T), stage_all) <= 40960)
-        return 2;
-    return 0;
-}
-
-template <class T>
-int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const T *q, const T *qd, const T *ydd, T *tau, size_t B, int device,
+int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const T *q, const T *qd, const T *ydd, T *tau, size_t B, int device,
                    void *stream)
 {
     const HostPlan &h = p->host;
-    const int kid = sizeof(T) == 8 ? 1 : 0;
+    const RneaChainProgram &rp = h.rchain[r.slot];
     const size_t n_tiles = (B + kWave - 1) / kWave;
-    // f32: the inverse-dynamics kernel needs 109 VGPRs, so four wavefronts per SIMD fit; models whose blocks all fit the
-    // LDS of the two-per-SIMD shape (no global-slab fallback) run the program laid out for half the LDS per wavefront
-    // once the batch fills 16 wavefronts per CU (MIT humanoid 0.105 -> 0.095 ms, Mini Cheetah 0.079 -> 0.070 ms; JVRC-1,
-    // whose blocks spill already, loses)
-    const bool wide = sizeof(T) == 4 && h.rchain32w.ok && h.rchain32.ok && h.rchain32.n_glb == 0 && h.rchain32.gens.empty() &&
-                      n_tiles > static_cast<size_t>(t.n_cu) * 8;
-    const int w = wide ? 2 : kid;
-    const RneaChainProgram &rp = wide ? h.rchain32w : (kid ? h.rchain64 : h.rchain32);
-    // Latency mode (as the forward dynamics': batches of at most one tile per SIMD go to workgroups of two wavefronts per tile, of at most two tiles per CU to
-    // workgroups of four when the base carries four limbs; chain_kernels.hip, rnea_chain_lm_kernel).  GRBDA_NO_LATENCY_MODE=1 / GRBDA_LM_WAVES=2 as there.
-    {
-        const RneaChainProgram &r4 = kid ? h.rchain64q : h.rchain32q, &r2 = kid ? h.rchain64p : h.rchain32p;
-        const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(h.nq + 2 * h.nv) * sizeof(T);
-        const int lm_waves = choose_rnea_lm<T>(p, t.n_cu, B);
-        const bool use4 = lm_waves == 4, use2 = lm_waves == 2;
-        if (use4 || use2) {
-            const RneaChainProgram &lp = use4 ? r4 : r2;
-            const int wi = use4 ? (kid ? 6 : 5) : (kid ? 4 : 3);
-            RneaChainDev<T> d;
-            std::memset(&d, 0, sizeof d);
-            d.segs = t.rchain_segs[wi];
-            d.links = t.rchain_links[wi];
-            d.pairs = t.rchain_pairs[wi];
-            d.frees = t.rchain_frees[wi];
-            d.diffs = lp.diffs.empty() ? nullptr : t.rchain_diffs[wi];  // (fp32 programs only)
-            d.n_diffs = static_cast<int>(lp.diffs.size());
-            d.cints = t.cints;
-            d.consts = sizeof(T) == 4 ? reinterpret_cast<const T *>(t.consts32) : reinterpret_cast<const T *>(t.consts64);
-            d.n_segs = static_cast<int>(lp.segs.size());
-            d.nq = h.nq;
-            d.nv = h.nv;
-            d.ori_repr = h.ori_repr;
-            for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
-            const size_t lds_bytes = std::max(static_cast<size_t>(lp.n_lds) * kWave * sizeof(T), stage_all);
-            d.lds_bytes = static_cast<int>(lds_bytes);
-            const size_t grid = n_tiles;  // (all resident)
-            void *scratch = nullptr;
-            if (int rc = ensure_scratch(p, device, stream, grid * static_cast<size_t>(h.nq + 2 * h.nv) * kWave * sizeof(T) + 256, &scratch)) return rc;
-            hipError_t e = launch_rnea_chain_lm<T>(d, q, qd, ydd, tau, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_bytes,
-                                                   static_cast<hipStream_t>(stream), use4 ? 4 : 2);
-            return e == hipSuccess ? GRBDA_OK : hip_err(e, "rnea chain launch (latency mode)");
-        }
+    const size_t in_rows = static_cast<size_t>(h.nq + 2 * h.nv);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    RneaChainDev<T> d = rnea_chain_dev<T>(p, t, r.slot);
+    void *scratch = nullptr;
+    if (r.path == ROUTE_LM) {  // (chain_kernels.hip, rnea_chain_lm_kernel)
+        if (rp.diffs.empty()) d.diffs = nullptr;  // (fp32 programs only)
+        no_gens(d);
+        d.n_glb_slots = 0;
+        const size_t lds_bytes = lm_lds_bytes<T>(h, rp);
+        d.lds_bytes = static_cast<int>(lds_bytes);
+        const size_t grid = n_tiles;  // (all resident)
+        if (int rc = ensure_scratch(p, device, stream, scratch_bytes(grid, in_rows, sizeof(T)), &scratch)) return rc;
+        hipError_t e = launch_rnea_chain_lm<T>(d, q, qd, ydd, tau, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_bytes, hs, r.lm_waves);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "rnea chain launch (latency mode)");
     }
-    if (rnea_gen1_usable<T>(p)) {  // single-cluster programs: the fused, slab-free kernel (chain_kernels.hip, rnea_gen1_kernel)
-        RneaChainDev<T> d;
-        std::memset(&d, 0, sizeof d);
-        d.gens = t.rchain_gens[kid];
-        d.gbodies = t.rchain_gbodies[kid];
-        d.n_gens = 1;
-        d.cints = t.cints;
-        d.consts = sizeof(T) == 4 ? reinterpret_cast<const T *>(t.consts32) : reinterpret_cast<const T *>(t.consts64);
-        d.nq = h.nq;
-        d.nv = h.nv;
-        d.ori_repr = h.ori_repr;
+    if (r.path == ROUTE_GEN1) {  // single-cluster programs: the fused, slab-free kernel (chain_kernels.hip, rnea_gen1_kernel)
+        gen1_only(d);
         d.lds_bytes = static_cast<int>(static_cast<size_t>(rp.n_lds) * kWave * sizeof(T));
-        for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
-        const size_t lds_total = rnea_gen1_lds_bytes<T>(p);  // work area + the staged input rows
-        size_t per_cu = static_cast<size_t>(rnea_gen1_waves_per_simd<T>(rp.gens[0].n)) * 4;
-        const size_t fit = lds_workgroups_per_cu(lds_total);
-        if (fit < per_cu) per_cu = fit;
-        if (p->opt.gen1_waves_cap > 0 && static_cast<size_t>(p->opt.gen1_waves_cap) < per_cu) per_cu = static_cast<size_t>(p->opt.gen1_waves_cap);
-        size_t grid = static_cast<size_t>(t.n_cu) * per_cu;
-        if (p->opt.gen1_tiles_per_wave > 0) grid = (n_tiles + p->opt.gen1_tiles_per_wave - 1) / p->opt.gen1_tiles_per_wave;
-        if (grid > n_tiles) grid = n_tiles;
-        hipError_t e = launch_rnea_gen1<T>(d, rp.gens[0].n, rp.gens[0].kind != 0, q, qd, ydd, tau, B, static_cast<int>(grid), lds_total,
-                                           static_cast<hipStream_t>(stream));
+        const size_t lds_total = gen1_lds_bytes<T>(h, rp);
+        const size_t grid = gen1_grid(p, t.n_cu, n_tiles, rnea_gen1_waves_per_simd<T>(rp.gens[0].n), lds_total);
+        hipError_t e = launch_rnea_gen1<T>(d, rp.gens[0].n, rp.gens[0].kind != 0, q, qd, ydd, tau, B, static_cast<int>(grid), lds_total, hs);
         return e == hipSuccess ? GRBDA_OK : hip_err(e, "rnea single-cluster launch");
     }
-    RneaChainDev<T> d;
-    d.segs = t.rchain_segs[w];
-    d.links = t.rchain_links[w];
-    d.pairs = t.rchain_pairs[w];
-    d.frees = t.rchain_frees[w];
-    d.diffs = t.rchain_diffs[w];
-    d.n_diffs = static_cast<int>(rp.diffs.size());
-    d.gens = t.rchain_gens[w];
-    d.gbodies = t.rchain_gbodies[w];
-    d.n_gens = static_cast<int>(rp.gens.size());
-    d.cints = t.cints;
-    d.consts = sizeof(T) == 4 ? reinterpret_cast<const T *>(t.consts32) : reinterpret_cast<const T *>(t.consts64);
-    d.n_segs = static_cast<int>(rp.segs.size());
-    d.nq = h.nq;
-    d.nv = h.nv;
-    d.n_glb_slots = rp.n_glb;
-    d.ori_repr = h.ori_repr;
-    for (int i = 0; i < 6; i++) d.a_root[i] = static_cast<T>(-h.gravity[i]);
-    // (wide: four wavefronts per SIMD; otherwise the ABA launch shape, 8 wavefronts per CU)
-    const size_t waves_per_cu = wide ? static_cast<size_t>(16) : static_cast<size_t>(p->opt.waves_per_cu[kid]);
-    const size_t lds_budget = static_cast<size_t>(wide ? p->opt.chain32w_lds_bytes : p->opt.lds_bytes_per_wave[kid]);
-    size_t grid = static_cast<size_t>(t.n_cu) * waves_per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    size_t lds_bytes = static_cast<size_t>(rp.n_lds) * kWave * sizeof(T);
-    const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
-    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
-    if (lds_bytes < stage_one) lds_bytes = stage_one;
-    if (lds_bytes < stage_all && stage_all <= lds_budget) lds_bytes = stage_all;
-    d.lds_bytes = static_cast<int>(lds_bytes);
-    const size_t fit = lds_workgroups_per_cu(lds_bytes);
-    if (fit >= 1 && fit < waves_per_cu) {
-        const size_t g2 = static_cast<size_t>(t.n_cu) * fit;
-        if (grid > g2) grid = g2;
-    }
-    const size_t n_rows = static_cast<size_t>(d.nq + 2 * d.nv) + static_cast<size_t>(rp.n_glb);
-    void *scratch = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, grid * n_rows * kWave * sizeof(T) + 256, &scratch)) return rc;
-    hipError_t e = launch_rnea_chain<T>(d, q, qd, ydd, tau, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_bytes,
-                                        static_cast<hipStream_t>(stream));
+    // (the four-wavefronts-per-SIMD program: 16 per CU; otherwise the ABA launch shape, 8 wavefronts per CU)
+    const bool wide = r.slot == SLOT_F32_WIDE;
+    const int kid = sizeof(T) == 8 ? 1 : 0;
+    const LaunchShape s = launch_shape(t.n_cu, n_tiles, wide ? static_cast<size_t>(16) : static_cast<size_t>(p->opt.waves_per_cu[kid]),
+                                       static_cast<size_t>(rp.n_lds) * kWave * sizeof(T), h.nq, h.nv, sizeof(T),
+                                       static_cast<size_t>(wide ? p->opt.chain32w_lds_bytes : p->opt.lds_bytes_per_wave[kid]), true);
+    d.lds_bytes = static_cast<int>(s.lds_bytes);
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, in_rows + static_cast<size_t>(rp.n_glb), sizeof(T)), &scratch)) return rc;
+    hipError_t e = launch_rnea_chain<T>(d, q, qd, ydd, tau, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "rnea chain launch");
 }
 
@@ -751,42 +697,29 @@ int run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, con
     }
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
-    // chain-structured fast path (chain_kernels.hip): forward dynamics of models the chain program covers
-    if (!rnea && !f_ext && chain_covers<T>(p)) return run_chain<T>(p, *t, q, qd, x, out, B, device, stream);
-    if (rnea && !f_ext && !p->opt.no_chain && (sizeof(T) == 8 ? p->host.rchain64.ok : p->host.rchain32.ok))
-        return run_rnea_chain<T>(p, *t, q, qd, x, out, B, device, stream);
+    // chain-structured fast path (chain_kernels.hip) of models the chain programs cover
+    const Route r = rnea ? choose_rnea<T>(p, t->n_cu, B, f_ext != nullptr) : choose_aba<T>(p, t->n_cu, B, f_ext != nullptr);
+    if (r.path != ROUTE_INTERPRETER)
+        return rnea ? run_rnea_chain<T>(p, *t, r, q, qd, x, out, B, device, stream) : run_chain<T>(p, *t, r, q, qd, x, out, B, device, stream);
     DevPlan<T> d = make_dev_plan<T>(p, *t, rnea, f_ext != nullptr);
     d.fext = f_ext;
-    const size_t n_tiles = (B + kWave - 1) / kWave;
     const int kid = (rnea ? 2 : 0) + (sizeof(T) == 8 ? 1 : 0);
-    const size_t waves_per_cu = static_cast<size_t>(kid == 1 ? p->opt.waves_per_cu_f64_wide_regs : p->opt.waves_per_cu[kid]);
-    size_t grid = static_cast<size_t>(t->n_cu) * waves_per_cu;
-    if (grid > n_tiles) grid = n_tiles;
+    const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, static_cast<size_t>(kid == 1 ? p->opt.waves_per_cu_f64_wide_regs : p->opt.waves_per_cu[kid]),
+                                       static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T), d.nq, d.nv, sizeof(T),
+                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[kid]), true);
+    d.lds_bytes = static_cast<int>(s.lds_bytes);
+    // (sized by the grid before the LDS-fit clamp: inherited, not chosen)
     const size_t n_glb = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);  // + staged inputs
-    const size_t scratch_bytes = grid * n_glb * kWave * sizeof(T) + 256;
     void *scratch = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, scratch_bytes, &scratch)) return rc;
-    // LDS: the slot store, and at tile boundaries the staging area of the input transposition
-    size_t lds_bytes = static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T);
-    const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
-    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
-    if (lds_bytes < stage_one) lds_bytes = stage_one;
-    if (lds_bytes < stage_all && stage_all <= static_cast<size_t>(p->opt.lds_bytes_per_wave[kid])) lds_bytes = stage_all;
-    d.lds_bytes = static_cast<int>(lds_bytes);
-    // a CU holds 160 KiB of LDS: never launch more persistent wavefronts than can be resident at once
-    const size_t fit = lds_workgroups_per_cu(lds_bytes);
-    if (fit >= 1 && fit < waves_per_cu) {
-        const size_t g2 = static_cast<size_t>(t->n_cu) * fit;
-        if (grid > g2) grid = g2;
-    }
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid_unclamped, n_glb, sizeof(T)), &scratch)) return rc;
     hipError_t e;
     if (rnea)
-        e = launch_rnea<T>(d, q, qd, x, out, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_bytes,
+        e = launch_rnea<T>(d, q, qd, x, out, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes,
                            static_cast<hipStream_t>(stream));
     else
         // (f64 only) the two-wavefronts-per-SIMD build pays for its spills only when the grid fills them
-        e = launch_aba<T>(d, q, qd, x, out, B, static_cast<T *>(scratch), static_cast<int>(grid), lds_bytes,
-                          static_cast<hipStream_t>(stream), grid > static_cast<size_t>(t->n_cu) * 4);
+        e = launch_aba<T>(d, q, qd, x, out, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes,
+                          static_cast<hipStream_t>(stream), s.grid > static_cast<size_t>(t->n_cu) * 4);
     if (e != hipSuccess) return hip_err(e, rnea ? "rnea launch" : "aba launch");
     return GRBDA_OK;
 }
@@ -850,22 +783,16 @@ int aux_setup(const grbda_plan *p, size_t B, int device, void *stream, DevPlan<T
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     d = make_dev_plan<T>(p, *t, false, false);
-    const int kid = sizeof(T) == 8 ? 1 : 0;
-    const size_t n_tiles = (B + kWave - 1) / kWave;
-    size_t g = static_cast<size_t>(t->n_cu) * 4;  // one wavefront per SIMD: these kernels are not register-tuned
-    if (g > n_tiles) g = n_tiles;
+    // one wavefront per SIMD: these kernels are not register-tuned (no LDS-fit clamp: inherited, not chosen)
+    const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, 4, static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T), d.nq, d.nv, sizeof(T),
+                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[sizeof(T) == 8 ? 1 : 0]), false);
     const size_t n_glb = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);
     void *sp = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, g * n_glb * kWave * sizeof(T) + 256, &sp)) return rc;
-    size_t lb = static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T);
-    const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
-    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
-    if (lb < stage_one) lb = stage_one;
-    if (lb < stage_all && stage_all <= static_cast<size_t>(p->opt.lds_bytes_per_wave[kid])) lb = stage_all;
-    d.lds_bytes = static_cast<int>(lb);
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, n_glb, sizeof(T)), &sp)) return rc;
+    d.lds_bytes = static_cast<int>(s.lds_bytes);
     *scratch = static_cast<T *>(sp);
-    *grid = static_cast<int>(g);
-    *lds_bytes = lb;
+    *grid = static_cast<int>(s.grid);
+    *lds_bytes = s.lds_bytes;
     return GRBDA_OK;
 }
 
@@ -1205,7 +1132,8 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
                    size_t B, int device, void *stream, const T *tf_force, T *tf_lambda, T *tf_dstate)
 {
     const HostPlan &h = p->host;
-    const ChainProgram &cp = sizeof(T) == 8 ? h.chain64 : h.chain32;
+    const ChainSlot slot = chain_slot(sizeof(T) == 8);
+    const ChainProgram &cp = h.chain[slot];
     // (programs with generic clusters -- plan.h, ChainGen -- have no walk steps in the force-propagation kernel: unit-wrench path)
     if (p->opt.no_chain || p->opt.no_efpa || !cp.ok || !cp.gens.empty() || n_contacts > kOsimMaxContacts) return 1;
     const Layout &L = h.lay64;
@@ -1314,46 +1242,22 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
         }
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
-    const int w = sizeof(T) == 8 ? 2 : 0;
-    const int kid = sizeof(T) == 8 ? 1 : 0;
     A.w_base = cp.n_glb;
     A.w_stride = 6 * max_rows;
-    ChainDev<T> d;
-    d.bad_count = t->bad_count;
-    d.segs = t->chain_segs[w];
-    d.links = t->chain_links[w];
-    d.pairs = t->chain_pairs[w];
-    d.frees = t->chain_frees[w];
-    d.diffs = t->chain_diffs[w];
-    d.n_diffs = static_cast<int>(cp.diffs.size());
-    d.gens = nullptr;
-    d.gbodies = nullptr;
-    d.n_gens = 0;
-    d.cints = t->cints;
-    d.consts = sizeof(T) == 4 ? reinterpret_cast<const T *>(t->consts32) : reinterpret_cast<const T *>(t->consts64);
-    d.n_segs = static_cast<int>(cp.segs.size());
-    d.nq = h.nq;
-    d.nv = h.nv;
+    ChainDev<T> d = chain_dev<T>(p, *t, slot);
+    no_gens(d);
     d.n_glb_slots = cp.n_glb + n_contacts * A.w_stride;
-    d.ori_repr = h.ori_repr;
-    d.debug = 0;
-    d.sv_global = cp.sv_global ? 1 : 0;
     d.out_lds = -1;  // (the force-propagation kernel keeps its result rows in the slab)
-    d.fuse = d.stage_lds_v = d.stage_v_index = 0;
     // (gravity enters the acceleration sweep only, which runs in applyTestForce mode alone -- there without it)
-    for (int i = 0; i < 6; i++) d.a_root[i] = tf_force ? T(0) : static_cast<T>(-h.gravity[i]);
-    const size_t n_tiles = (B + kWave - 1) / kWave;
-    size_t grid = static_cast<size_t>(t->n_cu) * 4;  // one wavefront per SIMD: the walk kernel is not register-tuned
-    if (grid > n_tiles) grid = n_tiles;
-    size_t lds_bytes = static_cast<size_t>(cp.n_lds) * kWave * sizeof(T);
-    const size_t stage_one = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq > d.nv ? d.nq : d.nv) * sizeof(T);
-    const size_t stage_all = static_cast<size_t>(kWave) * static_cast<size_t>(d.nq + 2 * d.nv) * sizeof(T);
-    if (lds_bytes < stage_one) lds_bytes = stage_one;
-    if (lds_bytes < stage_all && stage_all <= static_cast<size_t>(p->opt.lds_bytes_per_wave[kid])) lds_bytes = stage_all;
-    d.lds_bytes = static_cast<int>(lds_bytes);
-    const size_t n_rows = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);
+    if (tf_force)
+        for (int i = 0; i < 6; i++) d.a_root[i] = T(0);
+    // one wavefront per SIMD: the walk kernel is not register-tuned (no LDS-fit clamp: inherited, not chosen)
+    const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, 4, static_cast<size_t>(cp.n_lds) * kWave * sizeof(T), h.nq, h.nv, sizeof(T),
+                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[sizeof(T) == 8 ? 1 : 0]), false);
+    d.lds_bytes = static_cast<int>(s.lds_bytes);
+    const size_t n_rows = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(h.nq + 2 * h.nv);
     void *scratch = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, grid * n_rows * kWave * sizeof(T) + 256, &scratch)) return rc;
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, n_rows, sizeof(T)), &scratch)) return rc;
     // a block of zeros stands in for the velocities and torques of every tile (grown under ensure_work's capture rule)
     const size_t zneed = B * static_cast<size_t>(h.nv) * sizeof(T) + 256;
     void *zeros = nullptr;
@@ -1361,8 +1265,8 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
     hipStream_t hs = static_cast<hipStream_t>(stream);
     hipError_t e;
     if ((e = hipMemsetAsync(zeros, 0, zneed, hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    e = launch_osim_chain<T>(d, A, q, static_cast<const T *>(zeros), Linv, J, B, static_cast<T *>(scratch), static_cast<int>(grid),
-                             lds_bytes, hs);
+    e = launch_osim_chain<T>(d, A, q, static_cast<const T *>(zeros), Linv, J, B, static_cast<T *>(scratch), static_cast<int>(s.grid),
+                             s.lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "osim chain launch");
 }
 
@@ -2044,57 +1948,39 @@ int manifold_mass(const grbda_plan *p, const T *q, T *H, size_t B, int device, v
     return manifold_derivs<T>(p, q, nullptr, nullptr, nullptr, nullptr, nullptr, H, B, device, stream);
 }
 
+// the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
 template <class T>
 static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B)
 {
     const HostPlan &h = p->host;
     const char *tn = sizeof(T) == 4 ? "float" : "double";
+    const char *alg = kind == 0 ? "aba" : "rnea";
+    const Route r = kind == 0 ? choose_aba<T>(p, n_cu, B, false) : choose_rnea<T>(p, n_cu, B, false);
     char buf[160];
-    if (kind == 0) {
-        const ChainProgram &cp = sizeof(T) == 8 ? h.chain64 : h.chain32;
-        switch (choose_aba<T>(p, n_cu, B, false)) {
-            case ABA_GEN1:
-                std::snprintf(buf, sizeof buf, "grbda_hip::aba_gen1_kernel<%s, %d, %s, %d>", tn, cp.gens[0].n, cp.gens[0].kind ? "true" : "false",
-                              gen1_waves_per_simd<T>(cp.gens[0].n));
-                return buf;
-            case ABA_LM: {
-                const ChainProgram &lp = sizeof(T) == 8 ? h.chain64p : h.chain32p;
-                std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_lm_kernel<%s, 2%s>", tn, lp.diffs.empty() ? "" : ", true");
-                return buf;
-            }
-            case ABA_LM4:
-                std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_lm_kernel<%s, 4%s>", tn, (sizeof(T) == 8 ? h.chain64q : h.chain32q).diffs.empty() ? "" : ", true");
-                return buf;
-            case ABA_CHAIN:
-                std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_kernel<%s, %d, %d>", tn, (sizeof(T) == 8 && !cp.gens.empty()) ? 1 : 2,
-                              !cp.gens.empty() ? 2 : (!cp.diffs.empty() ? 1 : 0));
-                return buf;
-            default: break;
-        }
+    const auto format = [&](const auto &cp, int gen1_waves) {
+        const int segs = !cp.gens.empty() ? 2 : (!cp.diffs.empty() ? 1 : 0);
+        if (r.path == ROUTE_GEN1)
+            std::snprintf(buf, sizeof buf, "grbda_hip::%s_gen1_kernel<%s, %d, %s, %d>", alg, tn, cp.gens[0].n, cp.gens[0].kind ? "true" : "false", gen1_waves);
+        else if (r.path == ROUTE_LM)
+            std::snprintf(buf, sizeof buf, "grbda_hip::%s_chain_lm_kernel<%s, %d%s>", alg, tn, r.lm_waves, cp.diffs.empty() ? "" : ", true");
+        else if (kind == 0)
+            std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_kernel<%s, %d, %d>", tn, (sizeof(T) == 8 && !cp.gens.empty()) ? 1 : 2, segs);
+        else
+            std::snprintf(buf, sizeof buf, "grbda_hip::rnea_chain_kernel<%s, %d, %s>", tn, segs, cp.n_glb > 0 ? "true" : "false");
+    };
+    if (r.path == ROUTE_INTERPRETER) {
         bool loop = false;
         for (const ClusterRec &cr : h.lay64.clusters) loop = loop || cr.kind == CK_LOOP;
-        std::snprintf(buf, sizeof buf, "grbda_hip::aba_kernel<%s, %s>", tn, loop ? "true" : "false");
-        return buf;
+        std::snprintf(buf, sizeof buf, "grbda_hip::%s_kernel<%s, %s>", alg, tn, loop ? "true" : "false");
+    } else if (kind == 0) {
+        format(h.chain[r.slot], r.path == ROUTE_GEN1 ? gen1_waves_per_simd<T>(h.chain[r.slot].gens[0].n) : 0);
+    } else {
+        // (The four-wavefronts-per-SIMD route keeps the name of the two-per-SIMD program, as it always has: the batch-ladder tests compare
+        // the names either side of a threshold.  Its own program may spill where that one does not -- Mini Cheetah then runs
+        // rnea_chain_kernel<float, 0, true> under the name <float, 0, false>.)
+        const RneaChainProgram &rp = h.rchain[r.slot == SLOT_F32_WIDE ? SLOT_F32 : r.slot];
+        format(rp, r.path == ROUTE_GEN1 ? rnea_gen1_waves_per_simd<T>(rp.gens[0].n) : 0);
     }
-    const bool chain = !p->opt.no_chain && (sizeof(T) == 8 ? h.rchain64.ok : h.rchain32.ok);
-    if (chain) {
-        const RneaChainProgram &rp = sizeof(T) == 8 ? h.rchain64 : h.rchain32;
-        if (rnea_gen1_usable<T>(p)) {
-            std::snprintf(buf, sizeof buf, "grbda_hip::rnea_gen1_kernel<%s, %d, %s, %d>", tn, rp.gens[0].n, rp.gens[0].kind ? "true" : "false",
-                          rnea_gen1_waves_per_simd<T>(rp.gens[0].n));
-            return buf;
-        }
-        if (const int lmw = choose_rnea_lm<T>(p, n_cu, B)) {
-            const RneaChainProgram &lr = lmw == 4 ? (sizeof(T) == 8 ? h.rchain64q : h.rchain32q) : (sizeof(T) == 8 ? h.rchain64p : h.rchain32p);
-            std::snprintf(buf, sizeof buf, "grbda_hip::rnea_chain_lm_kernel<%s, %d%s>", tn, lmw, lr.diffs.empty() ? "" : ", true");
-            return buf;
-        }
-        std::snprintf(buf, sizeof buf, "grbda_hip::rnea_chain_kernel<%s, %d, %s>", tn, !rp.gens.empty() ? 2 : (rp.diffs.empty() ? 0 : 1), rp.n_glb > 0 ? "true" : "false");
-        return buf;
-    }
-    bool loop = false;
-    for (const ClusterRec &cr : h.lay64.clusters) loop = loop || cr.kind == CK_LOOP;
-    std::snprintf(buf, sizeof buf, "grbda_hip::rnea_kernel<%s, %s>", tn, loop ? "true" : "false");
     return buf;
 }
 
@@ -2423,8 +2309,10 @@ void grbda_plan_free(grbda_plan *p)
         (void)hipFree(t.aba_steps); (void)hipFree(t.rnea_steps); (void)hipFree(t.consts64); (void)hipFree(t.consts32);
         (void)hipFree(t.cints); (void)hipFree(t.dq_map); (void)hipFree(t.crba_bodies); (void)hipFree(t.deriv_bodies); (void)hipFree(t.deriv_related); (void)hipFree(t.related_table); (void)hipFree(t.minv_bodies); (void)hipFree(t.minv_coltab);
         (void)hipFree(t.span_q); (void)hipFree(t.span_v); (void)hipFree(t.crow);
-        for (int w = 0; w < 7; w++) { (void)hipFree(t.rchain_segs[w]); (void)hipFree(t.rchain_links[w]); (void)hipFree(t.rchain_pairs[w]); (void)hipFree(t.rchain_frees[w]); (void)hipFree(t.rchain_diffs[w]); (void)hipFree(t.rchain_gens[w]); (void)hipFree(t.rchain_gbodies[w]); }
-        for (int w = 0; w < 7; w++) { (void)hipFree(t.chain_segs[w]); (void)hipFree(t.chain_links[w]); (void)hipFree(t.chain_pairs[w]); (void)hipFree(t.chain_frees[w]); (void)hipFree(t.chain_diffs[w]); (void)hipFree(t.chain_gens[w]); (void)hipFree(t.chain_gbodies[w]); }
+        for (int w = 0; w < kChainSlots; w++) {
+            free_chain_tables(t.rchain[w]);
+            free_chain_tables(t.chain[w]);
+        }
         for (int w = 0; w < kLayouts; w++) { (void)hipFree(t.acc_k[w]); (void)hipFree(t.clusters[w]); (void)hipFree(t.rnea_clusters[w]); (void)hipFree(t.bodies[w]); (void)hipFree(t.rnea_bodies[w]); }
     }
     for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj})
@@ -2529,17 +2417,17 @@ int grbda_plan_info(const grbda_plan *p, grbda_plan_info_t *info)
     info->split_aba_f32 = p->host.lay32s.split_aba;
     info->split_rnea_f32 = p->host.lay32s.split_rnea;
     info->n_lds_slots_split_f32 = p->host.lay32s.n_lds_aba;
-    info->chain_aba_f32 = p->host.chain32.ok && !p->opt.no_chain;
-    info->n_lds_slots_chain_f32 = p->host.chain32.n_lds;
-    info->n_chain_segments = static_cast<int>(p->host.chain32.segs.size());
-    info->chain_aba_f64 = p->host.chain64.ok && !p->opt.no_chain;
-    info->chain_rnea_f32 = p->host.rchain32.ok && !p->opt.no_chain;
-    info->chain_rnea_f64 = p->host.rchain64.ok && !p->opt.no_chain;
+    info->chain_aba_f32 = p->host.chain[SLOT_F32].ok && !p->opt.no_chain;
+    info->n_lds_slots_chain_f32 = p->host.chain[SLOT_F32].n_lds;
+    info->n_chain_segments = static_cast<int>(p->host.chain[SLOT_F32].segs.size());
+    info->chain_aba_f64 = p->host.chain[SLOT_F64].ok && !p->opt.no_chain;
+    info->chain_rnea_f32 = p->host.rchain[SLOT_F32].ok && !p->opt.no_chain;
+    info->chain_rnea_f64 = p->host.rchain[SLOT_F64].ok && !p->opt.no_chain;
     info->analytic_derivatives = (analytic_covers<double>(p) || manifold_covers<double>(p)) ? 1 : 0;
-    info->n_chain_differentials = p->opt.no_chain ? 0 : static_cast<int>(p->host.chain32.diffs.size());
-    info->latency_mode_f32 = p->host.chain32p.ok && !p->opt.no_chain && !p->opt.no_latency_mode;
-    info->latency_mode_f64 = p->host.chain64p.ok && !p->opt.no_chain && !p->opt.no_latency_mode;
-    info->n_chain_generic = p->opt.no_chain ? 0 : static_cast<int>(p->host.chain32.gens.size());
+    info->n_chain_differentials = p->opt.no_chain ? 0 : static_cast<int>(p->host.chain[SLOT_F32].diffs.size());
+    info->latency_mode_f32 = p->host.chain[SLOT_LM2_F32].ok && !p->opt.no_chain && !p->opt.no_latency_mode;
+    info->latency_mode_f64 = p->host.chain[SLOT_LM2_F64].ok && !p->opt.no_chain && !p->opt.no_latency_mode;
+    info->n_chain_generic = p->opt.no_chain ? 0 : static_cast<int>(p->host.chain[SLOT_F32].gens.size());
     info->spanning_tree_route = p->host.projection_only ? 1 : 0;
     return GRBDA_OK;
 }

@@ -2097,26 +2097,26 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
         if (!ok) { CP.segs.clear(); CP.links.clear(); CP.pairs.clear(); CP.frees.clear(); CP.diffs.clear(); CP.gens.clear(); CP.gbodies.clear(); }
     };
     // the RNEA chain kernels run 8 wavefronts per CU like the ABA ones: the ABA budgets apply
-    build_chain(P.chain32, lds.aba32, &P.rchain32, lds.aba32);
-    build_chain(P.chain32w, lds.chain32w, &P.rchain32w, lds.chain32w);
-    build_chain(P.chain64, lds.aba64, &P.rchain64, lds.aba64);
+    build_chain(P.chain[SLOT_F32], lds.aba32, &P.rchain[SLOT_F32], lds.aba32);
+    build_chain(P.chain[SLOT_F32_WIDE], lds.chain32w, &P.rchain[SLOT_F32_WIDE], lds.chain32w);
+    build_chain(P.chain[SLOT_F64], lds.aba64, &P.rchain[SLOT_F64], lds.aba64);
     // Generic clusters (plan.h, ChainGen) keep their work area in LDS: large ones get a program laid out for twice the LDS per
     // wavefront (the launch then holds fewer wavefronts per CU, capi.cpp: still several times the interpreter's rate)
-    if (!P.chain32.ok) build_chain(P.chain32, 2 * lds.aba32, P.rchain32.ok ? nullptr : &P.rchain32, 2 * lds.aba32);
-    if (!P.chain64.ok) build_chain(P.chain64, 2 * lds.aba64, P.rchain64.ok ? nullptr : &P.rchain64, 2 * lds.aba64);
+    if (!P.chain[SLOT_F32].ok) build_chain(P.chain[SLOT_F32], 2 * lds.aba32, P.rchain[SLOT_F32].ok ? nullptr : &P.rchain[SLOT_F32], 2 * lds.aba32);
+    if (!P.chain[SLOT_F64].ok) build_chain(P.chain[SLOT_F64], 2 * lds.aba64, P.rchain[SLOT_F64].ok ? nullptr : &P.rchain[SLOT_F64], 2 * lds.aba64);
     // (the same for an inverse-dynamics program that did not fit: its generic clusters keep [f | sin, cos] of every body from the
     // forward to the backward segment)
     {
         ChainProgram scratch_cp;
-        if (!P.rchain32.ok) build_chain(scratch_cp, 2 * lds.aba32, &P.rchain32, 2 * lds.aba32);
-        if (!P.rchain64.ok) build_chain(scratch_cp, 2 * lds.aba64, &P.rchain64, 2 * lds.aba64);
+        if (!P.rchain[SLOT_F32].ok) build_chain(scratch_cp, 2 * lds.aba32, &P.rchain[SLOT_F32], 2 * lds.aba32);
+        if (!P.rchain[SLOT_F64].ok) build_chain(scratch_cp, 2 * lds.aba64, &P.rchain[SLOT_F64], 2 * lds.aba64);
     }
-    // latency mode serves batches of at most one tile per SIMD, i.e. four tiles per CU: 40 KiB of LDS per tile
-    build_chain(P.chain32p, 40960 / (4 * kWave), &P.rchain32p, 40960 / (4 * kWave), 2, true, true);
-    build_chain(P.chain64p, 40960 / (8 * kWave), &P.rchain64p, 40960 / (8 * kWave), 2);
-    // four wavefronts per tile: batches of at most two tiles per CU (one wavefront per SIMD in the two-wavefront mode), 80 KiB each
-    build_chain(P.chain32q, 81920 / (4 * kWave), &P.rchain32q, 81920 / (4 * kWave), 4, true, true);
-    build_chain(P.chain64q, 81920 / (8 * kWave), &P.rchain64q, 81920 / (8 * kWave), 4, true);
+    // latency mode serves batches of at most one tile per SIMD, i.e. four tiles per CU (40 KiB of LDS per tile), and with four
+    // wavefronts per tile batches of at most two tiles per CU (one wavefront per SIMD in the two-wavefront mode, 80 KiB each)
+    build_chain(P.chain[SLOT_LM2_F32], lm_lds_limit(2) / (4 * kWave), &P.rchain[SLOT_LM2_F32], lm_lds_limit(2) / (4 * kWave), 2, true, true);
+    build_chain(P.chain[SLOT_LM2_F64], lm_lds_limit(2) / (8 * kWave), &P.rchain[SLOT_LM2_F64], lm_lds_limit(2) / (8 * kWave), 2);
+    build_chain(P.chain[SLOT_LM4_F32], lm_lds_limit(4) / (4 * kWave), &P.rchain[SLOT_LM4_F32], lm_lds_limit(4) / (4 * kWave), 4, true, true);
+    build_chain(P.chain[SLOT_LM4_F64], lm_lds_limit(4) / (8 * kWave), &P.rchain[SLOT_LM4_F64], lm_lds_limit(4) / (8 * kWave), 4, true);
 
     // ---- composite-rigid-body program (crba_kernels.hip) ----------------------------------------------------------
     {

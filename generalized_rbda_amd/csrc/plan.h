@@ -401,6 +401,29 @@ struct ChainProgram {
     int n_waves = 1;
 };
 
+// The chain programs of a plan: HostPlan::chain[] (forward dynamics) and HostPlan::rchain[] (inverse dynamics) in ONE slot order, which the
+// device copies of their tables keep (capi.cpp, DeviceTables).  The f64 slots hold half as many LDS slots as their f32 siblings.
+enum ChainSlot : int {
+    SLOT_F32 = 0,   // two wavefronts per SIMD
+    SLOT_F32_WIDE,  // the same laid out for four wavefronts per SIMD (PlanOptions::chain32w_lds_bytes: half the LDS per wavefront)
+    SLOT_F64,
+    SLOT_LM2_F32,   // latency mode, two wavefronts per tile (ChainProgram::n_waves): batches of at most four tiles per CU
+    SLOT_LM2_F64,
+    SLOT_LM4_F32,   // latency mode, four wavefronts per tile: batches of at most two tiles per CU
+    SLOT_LM4_F64
+};
+constexpr int kChainSlots = 7;
+// (the inverse-dynamics programs: these with an r in front)
+constexpr const char *kChainSlotName[kChainSlots] = {"chain32", "chain32w", "chain64", "chain32p", "chain64p", "chain32q", "chain64q"};
+// the slot of a precision and a number of wavefronts per tile (0 / 1: the one-wavefront programs, 2 / 4: latency mode)
+constexpr ChainSlot chain_slot(bool f64, int lm_waves = 0)
+{
+    return lm_waves == 4 ? (f64 ? SLOT_LM4_F64 : SLOT_LM4_F32) : (lm_waves == 2 ? (f64 ? SLOT_LM2_F64 : SLOT_LM2_F32) : (f64 ? SLOT_F64 : SLOT_F32));
+}
+// LDS of a latency-mode tile: a CU's 160 KiB over the four (two) tiles it holds at most; the programs are built for it (plan.cpp) and
+// launched only when slot store and input staging fit it (capi.cpp)
+constexpr int lm_lds_limit(int lm_waves) { return lm_waves == 4 ? 81920 : 40960; }
+
 // composite-rigid-body algorithm (crba_kernels.hip): per body, where its per-state scratch rows live in the wave's slab
 struct CrbaBody {
     int32_t cluster;  // index of the containing cluster
@@ -494,7 +517,7 @@ struct PlanOptions {
     // per SIMD, 428 registers, chain_kernels.hip) -- runs best at one wavefront per SIMD (measured on the zoo, 131 072 states: interpreter
     // 0.71-0.94 -> 0.46-0.66 ms; generic chain kernel even); GRBDA_WAVES_PER_CU / _ABA64 set it like the others
     int waves_per_cu_f64_wide_regs = 4;
-    // the f32 chain programs laid out for four wavefronts per SIMD (HostPlan::chain32w / rchain32w): a quarter of the CU's 160 KiB per SIMD,
+    // the f32 chain programs laid out for four wavefronts per SIMD (SLOT_F32_WIDE): a quarter of the CU's 160 KiB per SIMD,
     // in whole rows of 64 floats
     int chain32w_lds_bytes = (160 * 1024 / 16) / 256 * 256;
     int gen1_waves_cap = 0;       // GRBDA_GEN1_WAVES_PER_CU > 0: wavefronts per CU of the single-cluster kernels
@@ -538,16 +561,10 @@ struct HostPlan {
     Layout lay32, lay64;      // fast path
     Layout lay32x, lay64x;    // with absolute transforms kept for external forces (TreeNode::Xa_)
     Layout lay32s;            // f32 fast path, split layout (used when split_aba / split_rnea)
-    ChainProgram chain32;     // f32 ABA, chain-structured fast path (chain_kernels.hip), two wavefronts per SIMD
-    ChainProgram chain32w;    // the same laid out for four wavefronts per SIMD (half the LDS per wavefront)
-    ChainProgram chain64;     // f64 ABA (slots are twice as large: the LDS budget holds half as many)
-    ChainProgram chain32p, chain64p;  // latency mode: two wavefronts per tile (ChainProgram::n_waves)
-    ChainProgram chain32q, chain64q;  // latency mode, four wavefronts per tile (batches of at most two tiles per CU)
+    ChainProgram chain[kChainSlots];       // forward dynamics on the chains (chain_kernels.hip), by ChainSlot
+    RneaChainProgram rchain[kChainSlots];  // inverse dynamics on the chains, the same slots
     CrbaProgram crba;
     DerivProgram deriv;
-    RneaChainProgram rchain32, rchain64;  // inverse dynamics on the chains
-    RneaChainProgram rchain32w;           // f32 laid out for four wavefronts per SIMD (half the LDS per wavefront)
-    RneaChainProgram rchain32p, rchain64p, rchain32q, rchain64q;  // latency mode: two / four wavefronts per tile (RneaChainProgram::n_waves)
     // statistics for DESIGN.md / bench.py
     double flops_aba = 0, flops_rnea = 0;
 };

@@ -735,14 +735,8 @@ int main(int argc, char **argv)
         }
         const Tree T = make_tree(hp);
         std::string model = file.substr(file.find_last_of('/') + 1);
-        struct AbaEntry { const char *name; ChainProgram *cp; bool klds; };
-        struct RneaEntry { const char *name; RneaChainProgram *rp; };
-        const AbaEntry abas[] = {{"chain32", &hp.chain32, false}, {"chain32w", &hp.chain32w, false}, {"chain64", &hp.chain64, false},
-                                 {"chain32p", &hp.chain32p, true}, {"chain64p", &hp.chain64p, false}, {"chain32q", &hp.chain32q, true},
-                                 {"chain64q", &hp.chain64q, true}};
-        const RneaEntry rneas[] = {{"rchain32", &hp.rchain32}, {"rchain32w", &hp.rchain32w}, {"rchain64", &hp.rchain64},
-                                   {"rchain32p", &hp.rchain32p}, {"rchain64p", &hp.rchain64p}, {"rchain32q", &hp.rchain32q},
-                                   {"rchain64q", &hp.rchain64q}};
+        // (the programs whose [K | y0] blocks are LDS objects: plan.cpp builds them with k_lds)
+        const auto klds_of = [](int s) { return s == SLOT_LM2_F32 || s == SLOT_LM4_F32 || s == SLOT_LM4_F64; };
         auto report = [&](const char *prog, bool ok, const Prog *P) {
             if (!ok) {
                 n_absent++;
@@ -765,25 +759,29 @@ int main(int argc, char **argv)
             if (F.total() > static_cast<int>(F.lines.size())) std::printf("    ... %zu more\n", F.total() - F.lines.size());
             n_find += F.total();
         };
-        for (const AbaEntry &e : abas) {
-            if (!e.cp->ok) { report(e.name, false, nullptr); continue; }
-            ChainProgram copy = *e.cp;
-            Prog P = build_aba(copy, hp, T, e.name, e.klds);
-            report(e.name, true, &P);
-            if (self && e.cp->n_waves > 1) {
-                const bool klds = e.klds;
-                const std::string nm = model + " " + e.name;
-                self_test(*e.cp, [&](ChainProgram &c) { return build_aba(c, hp, T, nm, klds); }, st, nm);
+        for (int s = 0; s < kChainSlots; s++) {
+            const char *name = kChainSlotName[s];
+            const ChainProgram &cp = hp.chain[s];
+            if (!cp.ok) { report(name, false, nullptr); continue; }
+            ChainProgram copy = cp;
+            const bool klds = klds_of(s);
+            Prog P = build_aba(copy, hp, T, name, klds);
+            report(name, true, &P);
+            if (self && cp.n_waves > 1) {
+                const std::string nm = model + " " + name;
+                self_test(cp, [&](ChainProgram &c) { return build_aba(c, hp, T, nm, klds); }, st, nm);
             }
         }
-        for (const RneaEntry &e : rneas) {
-            if (!e.rp->ok) { report(e.name, false, nullptr); continue; }
-            RneaChainProgram copy = *e.rp;
-            Prog P = build_rnea(copy, hp, T, e.name);
-            report(e.name, true, &P);
-            if (self && e.rp->n_waves > 1) {
-                const std::string nm = model + " " + e.name;
-                self_test(*e.rp, [&](RneaChainProgram &c) { return build_rnea(c, hp, T, nm); }, st, nm);
+        for (int s = 0; s < kChainSlots; s++) {
+            const std::string name = std::string("r") + kChainSlotName[s];
+            const RneaChainProgram &rp = hp.rchain[s];
+            if (!rp.ok) { report(name.c_str(), false, nullptr); continue; }
+            RneaChainProgram copy = rp;
+            Prog P = build_rnea(copy, hp, T, name);
+            report(name.c_str(), true, &P);
+            if (self && rp.n_waves > 1) {
+                const std::string nm = model + " " + name;
+                self_test(rp, [&](RneaChainProgram &c) { return build_rnea(c, hp, T, nm); }, st, nm);
             }
         }
     }

@@ -51,7 +51,7 @@ int main(int argc, char **argv)
             msg[0] = 0;
             rc = compile(blob, hp, msg, sizeof msg);
             std::printf("%s ori %d: %zu bytes, plan rc %d %s nq %d nv %d chain %d\n", argv[a], ori, blob.size(), rc, msg, hp.nq, hp.nv,
-                        hp.chain32.ok ? 1 : 0);
+                        hp.chain[grbda_hip::SLOT_F32].ok ? 1 : 0);
             if (rc) { bad++; continue; }
             // the oracle on a few states (zero positions are on every explicit model's manifold; implicit models: the
             // oracle's own Newton projection first)
