@@ -276,6 +276,9 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
     return 0;
 }
 
+// (Growing frees first, and hipFree waits for every stream of the device.  An entry point that sizes the slab more than once -- the
+// derivatives: the forward dynamics' share, then the recursion's -- grows it inside ONE call when the stream is new to the plan, so that
+// stream's first call is a device-wide synchronisation; later calls of the same or a smaller batch allocate nothing.)
 int ensure_scratch(const grbda_plan *p, int device, void *stream, size_t bytes, void **out)
 {
     std::lock_guard<std::recursive_mutex> lk(p->mu);

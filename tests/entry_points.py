@@ -275,10 +275,10 @@ def _host_inputs(blob, n_bodies, B, seed, dtype, max_cond=None):
     return s
 
 
-def _inputs(blob, plan, B, seed, dtype, gpu):
+def _inputs(blob, plan, B, seed, dtype, gpu, max_cond=None):
     import torch
 
-    s = dict(_host_inputs(blob, plan.n_bodies, B, seed, dtype))
+    s = dict(_host_inputs(blob, plan.n_bodies, B, seed, dtype, max_cond))
     x = {k: torch.as_tensor(np.ascontiguousarray(v), dtype=dtype, device=gpu) for k, v in s.items()}
     x["q_proj"] = x["q_start"].clone()
     return s, x
