@@ -80,7 +80,8 @@ int grbda_plan_release_work(grbda_plan *plan, unsigned long long *bytes_released
 int grbda_plan_dims(const grbda_plan *plan, int *nq, int *nv, int *n_bodies, int *n_clusters);
 
 /* TreeModel::setGravity / getGravity (TreeModel.h:56-57): linear part of the gravity vector.
- * Not thread safe against concurrent launches on the same plan. */
+ * Not thread safe against concurrent launches on the same plan.  Gravity is a kernel argument read at launch: every call after
+ * set_gravity uses the new value, and a captured graph keeps the gravity of its capture. */
 int grbda_plan_set_gravity(grbda_plan *plan, const double g[3]);
 int grbda_plan_get_gravity(const grbda_plan *plan, double g[3]);
 

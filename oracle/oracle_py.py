@@ -96,24 +96,51 @@ def forward_dynamics_mt(blob, q, qd, tau, n_threads):
 _lib32 = None
 
 
-def forward_dynamics_mt_f32(blob, q, qd, tau, n_threads):
-    """The same restatement compiled in single precision (_build/libgrbda_oracle_f32.so): the fp32 CPU baseline of
-    bench.py.  Not a parity checker."""
+def _f32():
     global _lib32
     if _lib32 is None:
         path = os.path.join(_HERE, "_build", "libgrbda_oracle_f32.so")
         if not os.path.exists(path):
             build()
-        _lib32 = ctypes.CDLL(path)
-        _lib32.grbda_oracle_forward_dynamics_mt.argtypes = [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                            c_size_t, c_int]
+        L = ctypes.CDLL(path)
+        L.grbda_oracle_forward_dynamics_mt.argtypes = [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_size_t, c_int]
+        for name in ("grbda_oracle_forward_dynamics", "grbda_oracle_inverse_dynamics"):
+            getattr(L, name).argtypes = [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
+        _lib32 = L
+    return _lib32
+
+
+def forward_dynamics_mt_f32(blob, q, qd, tau, n_threads):
+    """The same restatement compiled in single precision (_build/libgrbda_oracle_f32.so): the fp32 CPU baseline of
+    bench.py.  Not a parity checker."""
     q, qd, tau = (np.ascontiguousarray(a, dtype=np.float32) for a in (q, qd, tau))
     out = np.empty_like(tau)
-    rc = _lib32.grbda_oracle_forward_dynamics_mt(blob, len(blob), q.ctypes.data, qd.ctypes.data, tau.ctypes.data,
+    rc = _f32().grbda_oracle_forward_dynamics_mt(blob, len(blob), q.ctypes.data, qd.ctypes.data, tau.ctypes.data,
                                                  out.ctypes.data, q.shape[0], n_threads)
     if rc:
         raise RuntimeError(f"oracle error {rc}")
     return out
+
+
+def _run_f32(fn, blob, q, qd, x):
+    q, qd, x = (np.ascontiguousarray(a, dtype=np.float32) for a in (q, qd, x))
+    out = np.empty_like(x)
+    rc = fn(blob, len(blob), q.ctypes.data, qd.ctypes.data, x.ctypes.data, None, out.ctypes.data, q.shape[0])
+    if rc:
+        raise RuntimeError(f"oracle error {rc}")
+    return out
+
+
+def forward_dynamics_f32(blob, q, qd, tau):
+    """Forward dynamics of the single-precision build, float32 in and out: what single precision itself costs on these
+    inputs -- the yardstick of tests/term_states.py, never the reference of a comparison."""
+    return _run_f32(_f32().grbda_oracle_forward_dynamics, blob, q, qd, tau)
+
+
+def inverse_dynamics_f32(blob, q, qd, ydd):
+    """Inverse dynamics of the single-precision build (see forward_dynamics_f32)."""
+    return _run_f32(_f32().grbda_oracle_inverse_dynamics, blob, q, qd, ydd)
 
 
 def cluster_constraint(blob, cluster, q, qd, nsv, n, rows, big=False):
