@@ -1,6 +1,7 @@
 // capi.cpp -- implementation of include/grbda_hip.h on top of plan.cpp and kernels.hip.
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,6 +87,7 @@ struct Scratch {
     void *ptr = nullptr;
     size_t bytes = 0;
 };
+using SlabPool = std::map<std::pair<int, void *>, Scratch>;  // by (device, stream)
 
 // every entry point that may switch the calling thread's HIP device puts it back on return (torch and other users of the
 // runtime in the same thread keep their current device)
@@ -120,10 +122,10 @@ struct grbda_plan {
     // launches are in the stream (hipFree waits for them).  Recursive: the derived entry points call run().
     mutable std::recursive_mutex mu;
     mutable std::map<int, DeviceTables> dev;
-    mutable std::map<std::pair<int, void *>, Scratch> scratch;
-    mutable std::map<std::pair<int, void *>, Scratch> work;  // expanded batches of the derived quantities
-    mutable std::map<std::pair<int, void *>, Scratch> work_cvt;  // fp64 copies of fp32 inputs (grbda_fd_dq_f32)
-    mutable std::map<std::pair<int, void *>, Scratch> work_proj; // projection_run (called from inside the users of `work`)
+    mutable SlabPool scratch;
+    mutable SlabPool work;       // expanded batches of the derived quantities
+    mutable SlabPool work_cvt;   // fp64 copies of fp32 inputs (through_f64)
+    mutable SlabPool work_proj;  // projection_run (called from inside the users of `work`)
     // the chunk decision of the last eager analytic_derivs call per (device, stream): a capture of the same call replays it
     struct DerivChunk {
         size_t B = 0, per_state_bytes = 0, chunk = 0;
@@ -276,37 +278,48 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
     return 0;
 }
 
+bool is_capturing(void *stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// The slab of `pool` for (device, stream), grown on demand; `noun` names it in the refusal.
 // (Growing frees first, and hipFree waits for every stream of the device.  An entry point that sizes the slab more than once -- the
 // derivatives: the forward dynamics' share, then the recursion's -- grows it inside ONE call when the stream is new to the plan, so that
 // stream's first call is a device-wide synchronisation; later calls of the same or a smaller batch allocate nothing.)
-int ensure_scratch(const grbda_plan *p, int device, void *stream, size_t bytes, void **out)
+int ensure_slab(const grbda_plan *p, SlabPool &pool, const char *noun, int device, void *stream, size_t bytes, void **out)
 {
     std::lock_guard<std::recursive_mutex> lk(p->mu);
-    Scratch &s = p->scratch[{device, stream}];
+    Scratch &s = pool[{device, stream}];
     if (s.bytes < bytes) {
         // A stream under capture must not see hipFree / hipMalloc, and a graph captured earlier on this (device, stream)
         // holds the slab's address: growing is refused while the stream captures (reserve with one eager call of the
         // largest batch first, include/grbda_hip.h "Graph capture")
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return set_err(GRBDA_EINVAL, "the per-stream scratch slab would have to grow during stream capture: run the largest "
-                                         "batch once on this stream before capturing");
-        if (s.ptr) {
-            hipError_t e = hipFree(s.ptr);
-            if (e != hipSuccess) return hip_err(e, "hipFree");
-            s.ptr = nullptr;
-            s.bytes = 0;
-        }
-        hipError_t e = hipMalloc(&s.ptr, bytes);
-        if (e != hipSuccess) return hip_err(e, "hipMalloc(scratch)");
+        if (is_capturing(stream))
+            return set_err(GRBDA_EINVAL, std::string(noun) + " would have to grow during stream capture: run the largest batch once on "
+                                                             "this stream before capturing");
+        hipError_t e;
+        if (s.ptr && (e = hipFree(s.ptr)) != hipSuccess) return hip_err(e, "hipFree");
+        s.ptr = nullptr;
+        s.bytes = 0;
+        if ((e = hipMalloc(&s.ptr, bytes)) != hipSuccess) return hip_err(e, "hipMalloc(slab)");
         s.bytes = bytes;
     }
     *out = s.ptr;
     return 0;
 }
-
-// The per-(device, stream) work slab of the derived quantities, grown on demand under the same rule as ensure_scratch: never
+int ensure_scratch(const grbda_plan *p, int device, void *stream, size_t bytes, void **out)
+{
+    return ensure_slab(p, p->scratch, "the per-stream scratch slab", device, stream, bytes, out);
+}
+// The per-(device, stream) work slab of the derived quantities, grown on demand under the same rule as the scratch slab: never
 // while the stream captures (a graph captured earlier holds the old address).
+int ensure_work(const grbda_plan *p, SlabPool &pool, int device, void *stream, size_t bytes, void **out)
+{
+    return ensure_slab(p, pool, "a per-stream work buffer", device, stream, bytes, out);
+}
+
 // Upper bound of a work-slab request of the chunked pipelines (derivatives, projection): what the call site asks for (1-16 GiB, sized so that a
 // million states go through in a few chunks), cut to GRBDA_WORK_MAX_MB when that is set and to
 //     max(the slab this (device, stream) already holds, a quarter of the memory that is FREE on the device right now, 256 MiB)
@@ -314,7 +327,7 @@ int ensure_scratch(const grbda_plan *p, int device, void *stream, size_t bytes, 
 // else has been allocated since -- and (b) a stream that is being CAPTURED derives its chunk from the held slab alone (no hipMemGetInfo, no
 // growth: INTEGRATION.md's rule "run the largest batch once on the stream before capturing" then always suffices).  The slabs are kept per
 // (device, stream) and never shrink by themselves; grbda_plan_release_work() hands them back.
-static size_t work_budget(const grbda_plan *p, const std::map<std::pair<int, void *>, Scratch> &pool, int device, void *stream, size_t want)
+size_t work_budget(const grbda_plan *p, const SlabPool &pool, int device, void *stream, size_t want)
 {
     size_t cap = want;
     size_t held = 0;
@@ -323,8 +336,7 @@ static size_t work_budget(const grbda_plan *p, const std::map<std::pair<int, voi
         const auto it = pool.find({device, stream});
         if (it != pool.end()) held = it->second.bytes > 256 ? it->second.bytes - 256 : 0;
     }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+    const bool capturing = is_capturing(stream);
     if (capturing && held > 0) return cap < held ? cap : held;
     size_t free_b = 0, total_b = 0;
     if (!capturing && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) {
@@ -336,26 +348,6 @@ static size_t work_budget(const grbda_plan *p, const std::map<std::pair<int, voi
     const int mb = env_int("GRBDA_WORK_MAX_MB", 0);
     if (mb > 0 && cap > (static_cast<size_t>(mb) << 20)) cap = static_cast<size_t>(mb) << 20;
     return cap;
-}
-
-int ensure_work(const grbda_plan *p, std::map<std::pair<int, void *>, Scratch> &pool, int device, void *stream, size_t bytes, void **out)
-{
-    std::lock_guard<std::recursive_mutex> lk(p->mu);
-    Scratch &s = pool[{device, stream}];
-    if (s.bytes < bytes) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return set_err(GRBDA_EINVAL, "a per-stream work buffer would have to grow during stream capture: run the largest batch once on "
-                                         "this stream before capturing");
-        hipError_t e;
-        if (s.ptr && (e = hipFree(s.ptr)) != hipSuccess) return hip_err(e, "hipFree");
-        s.ptr = nullptr;
-        s.bytes = 0;
-        if ((e = hipMalloc(&s.ptr, bytes)) != hipSuccess) return hip_err(e, "hipMalloc(work)");
-        s.bytes = bytes;
-    }
-    *out = s.ptr;
-    return 0;
 }
 
 template <class T>
@@ -502,6 +494,67 @@ size_t gen1_grid(const grbda_plan *p, int n_cu, size_t n_tiles, int waves_per_si
     if (p->opt.gen1_tiles_per_wave > 0) grid = (n_tiles + p->opt.gen1_tiles_per_wave - 1) / p->opt.gen1_tiles_per_wave;
     return std::min(grid, n_tiles);
 }
+// grid of the element-wise kernels of this file: 256 threads per block in a grid-stride loop over n elements
+int blocks_for(size_t n) { return static_cast<int>((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535); }
+// persistent launch of an auxiliary kernel: per_cu one-wavefront workgroups per CU, at most one per tile of the B states
+size_t tile_grid(int n_cu, size_t per_cu, size_t B) { return std::min(static_cast<size_t>(n_cu) * per_cu, (B + kWave - 1) / kWave); }
+
+// ---- chunks: a batch goes through its work slab so many states at a time ----------------------------------------------------------
+struct Chunk {
+    size_t chunk;  // states per pass
+    size_t bytes;  // the slab that holds them
+};
+// as many states as `cap_bytes` hold, at least one, at most the batch
+Chunk fixed_chunk(size_t cap_bytes, size_t per_state_bytes, size_t B)
+{
+    size_t chunk = cap_bytes / per_state_bytes;
+    if (chunk < 1) chunk = 1;
+    if (chunk > B) chunk = B;
+    return {chunk, chunk * per_state_bytes + 256};
+}
+size_t whole_tiles(size_t chunk)  // rounded down to tiles of kWave states, at least one
+{
+    chunk &= ~static_cast<size_t>(kWave - 1);
+    return chunk < static_cast<size_t>(kWave) ? kWave : chunk;
+}
+// as many whole tiles as the budget of `pool` gives a request of `want_bytes` (work_budget), at most the batch rounded up to tiles
+Chunk budgeted_chunk(const grbda_plan *p, const SlabPool &pool, int device, void *stream, size_t want_bytes, size_t per_state_bytes, size_t B)
+{
+    size_t chunk = whole_tiles(work_budget(p, pool, device, stream, want_bytes) / per_state_bytes);
+    const size_t b_round = (B + kWave - 1) / kWave * kWave;
+    if (chunk > b_round) chunk = b_round;
+    return {chunk, chunk * per_state_bytes + 256};
+}
+// for (const auto [b0, nb] : ChunkWalk{B, chunk}): the passes over a batch of B states, nb of them from state b0 on
+struct ChunkWalk {
+    size_t B, chunk;
+    struct Pass {
+        size_t b0, nb;
+    };
+    struct Iter {
+        size_t b0, B, chunk;
+        Pass operator*() const { return {b0, B - b0 < chunk ? B - b0 : chunk}; }
+        void operator++() { b0 += chunk; }
+        bool operator!=(const Iter &) const { return b0 < B; }
+    };
+    Iter begin() const { return {0, B, chunk}; }
+    Iter end() const { return {B, B, chunk}; }
+};
+// Typed cursor over a slab sized for `cap` scalars: take(count) hands out the next `count` of them.  A site whose per-state size is the sum
+// of what it takes ends with assert(w.taken == w.cap), so that the size and the pointers cannot drift apart.
+template <class T>
+struct Carver {
+    T *base;
+    size_t cap, taken = 0;
+    Carver(void *slab, size_t cap_) : base(static_cast<T *>(slab)), cap(cap_) {}
+    T *take(size_t count)
+    {
+        assert(taken + count <= cap);
+        T *r = base + taken;
+        taken += count;
+        return r;
+    }
+};
 
 // ---- routes -------------------------------------------------------------------------------------------------------------------------
 // Which kernel a batch of B states runs on a device with n_cu compute units, and on which program: ONE definition per algorithm
@@ -687,7 +740,7 @@ int run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, con
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !qd || !x || !out) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !qd || !x || !out) return set_err(GRBDA_EINVAL, "null argument");
     if (B == 0) return GRBDA_OK;
     if (p->host.projection_only) {
         // (external forces: world-frame wrenches on the BODIES, which the spanning model shares with this one -- they enter its inverse dynamics)
@@ -727,44 +780,74 @@ int run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, con
     return GRBDA_OK;
 }
 
+// ---- host arrays: the staging of the *_host_f64 entry points (single-state facade calls) -----------------------------------------
+// in() / out() / inout() allocate a device array each, as they are called; run() then copies the inputs in, makes the call (which
+// enqueues on the null stream), waits for the device and copies the outputs back, all in the order of declaration.  The arrays are
+// freed when the stage goes out of scope, whatever failed.
+class HostStage {
+    struct Array {
+        void *dev;
+        const void *src;  // host array copied in before the call (null: none)
+        void *dst;        // host array the result is copied to (null: none)
+        size_t bytes;
+    };
+    std::vector<Array> arrays_;
+    int rc_ = GRBDA_OK;
+    template <class T>
+    T *add(const T *src, T *dst, size_t count)
+    {
+        Array a{nullptr, src, dst, count * sizeof(T)};
+        hipError_t e;
+        if (rc_ == GRBDA_OK && (e = hipMalloc(&a.dev, a.bytes ? a.bytes : 16)) != hipSuccess) rc_ = hip_err(e, "hipMalloc");
+        arrays_.push_back(a);
+        return static_cast<T *>(a.dev);
+    }
+
+public:
+    HostStage() = default;
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+    ~HostStage()
+    {
+        for (const Array &a : arrays_)
+            if (a.dev) (void)hipFree(a.dev);
+    }
+    template <class T>
+    const T *in(const T *src, size_t count) { return add<T>(src, nullptr, count); }
+    template <class T>
+    T *out(T *dst, size_t count) { return add<T>(nullptr, dst, count); }  // (dst null: a device array nobody reads back)
+    template <class T>
+    T *inout(T *io, size_t count) { return add<T>(io, io, count); }
+    template <class Call>
+    int run(Call call)
+    {
+        if (rc_) return rc_;
+        hipError_t e;
+        for (const Array &a : arrays_)
+            if (a.src && (e = hipMemcpy(a.dev, a.src, a.bytes, hipMemcpyHostToDevice)) != hipSuccess) return hip_err(e, "hipMemcpy H2D");
+        if (int rc = call()) return rc;
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_err(e, "kernel execution");
+        for (const Array &a : arrays_)
+            if (a.dst && (e = hipMemcpy(a.dst, a.dev, a.bytes, hipMemcpyDeviceToHost)) != hipSuccess) return hip_err(e, "hipMemcpy D2H");
+        return GRBDA_OK;
+    }
+};
+
 int run_host_f64(const grbda_plan *p, bool rnea, const double *q, const double *qd, const double *x,
                  const double *f_ext, double *out, size_t B, int device)
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !qd || !x || !out) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !qd || !x || !out) return set_err(GRBDA_EINVAL, "null argument");
     if (B == 0) return GRBDA_OK;
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    double *dq = nullptr, *dqd = nullptr, *dx = nullptr, *dout = nullptr, *dfe = nullptr;
-    const size_t nfe = static_cast<size_t>(p->host.n_bodies) * 6;
-    hipError_t e;
-    int rc = GRBDA_OK;
-    if (f_ext) {
-        if ((e = hipMalloc((void **)&dfe, B * nfe * 8)) != hipSuccess) return hip_err(e, "hipMalloc");
-        if ((e = hipMemcpy(dfe, f_ext, B * nfe * 8, hipMemcpyHostToDevice)) != hipSuccess) { (void)hipFree(dfe); return hip_err(e, "hipMemcpy H2D"); }
-    }
-    if ((e = hipMalloc((void **)&dq, B * nq * 8)) != hipSuccess || (e = hipMalloc((void **)&dqd, B * nv * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&dx, B * nv * 8)) != hipSuccess || (e = hipMalloc((void **)&dout, B * nv * 8)) != hipSuccess) {
-        rc = hip_err(e, "hipMalloc");
-    } else if ((e = hipMemcpy(dq, q, B * nq * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-               (e = hipMemcpy(dqd, qd, B * nv * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-               (e = hipMemcpy(dx, x, B * nv * 8, hipMemcpyHostToDevice)) != hipSuccess) {
-        rc = hip_err(e, "hipMemcpy H2D");
-    } else {
-        rc = run<double>(p, rnea, dq, dqd, dx, dfe, dout, B, device, nullptr);
-        if (rc == GRBDA_OK) {
-            if ((e = hipDeviceSynchronize()) != hipSuccess) rc = hip_err(e, "kernel execution");
-            else if ((e = hipMemcpy(out, dout, B * nv * 8, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
-        }
-    }
-    if (dq) (void)hipFree(dq);
-    if (dqd) (void)hipFree(dqd);
-    if (dx) (void)hipFree(dx);
-    if (dout) (void)hipFree(dout);
-    if (dfe) (void)hipFree(dfe);
-    return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, nfe = static_cast<size_t>(p->host.n_bodies) * 6;
+    HostStage st;
+    const double *dfe = f_ext ? st.in(f_ext, B * nfe) : nullptr;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dx = st.in(x, B * nv);
+    double *dout = st.out(out, B * nv);
+    return st.run([&] { return run<double>(p, rnea, dq, dqd, dx, dfe, dout, B, device, nullptr); });
 }
 
 // ---- steps either side of the path: Newton projection, spanning recovery (kernels.hip) -----------------------
@@ -804,14 +887,13 @@ int project(const grbda_plan *p, T *q, int32_t *ok, size_t B, int max_iter, doub
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || max_iter < 0) return set_err(GRBDA_EINVAL, "bad argument");
+    if (!q || max_iter < 0) return set_err(GRBDA_EINVAL, "bad argument");
     if (B == 0) return GRBDA_OK;
     if (p->host.big_clusters) {  // (clusters beyond the structured limits: the wide Newton kernel of manifold_kernels.hip)
         DeviceTables *t = nullptr;
         if (int rc = ensure_device(p, device, &t)) return rc;
         DevPlan<T> dp = make_dev_plan<T>(p, *t, false, false);
-        size_t g = static_cast<size_t>(t->n_cu) * 4;
-        if (g > (B + kWave - 1) / kWave) g = (B + kWave - 1) / kWave;
+        const size_t g = tile_grid(t->n_cu, 4, B);
         hipError_t e = launch_manifold_newton<T>(dp, p->host.n_clusters, q, ok, B, max_iter, static_cast<T>(tol), static_cast<int>(g),
                                                  static_cast<hipStream_t>(stream));
         return e == hipSuccess ? GRBDA_OK : hip_err(e, "projection launch");
@@ -832,7 +914,7 @@ int spanning(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *qd_s
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !qd || !ydd || !qdd_span) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !qd || !ydd || !qdd_span) return set_err(GRBDA_EINVAL, "null argument");
     if (B == 0) return GRBDA_OK;
     if (p->host.big_clusters) {
         // clusters beyond the structured limits: qd_s = G yd, qdd_s = G ydd + g from the wide constraint kernel of the spanning-tree route
@@ -843,19 +925,15 @@ int spanning(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *qd_s
         const size_t nq = p->host.nq, nv = p->host.nv, nq_s = p->span->host.nq, nv_s = p->span->host.nv;
         if (static_cast<size_t>(span_count(p)) != nv_s) return set_err(GRBDA_EUNSUPPORTED, "spanning layout mismatch");
         const size_t per_state = nq_s + nv_s + static_cast<size_t>(p->n_cpl_rows);
-        size_t chunk = work_budget(p, p->work_proj, device, stream, 1024ull << 20) / (per_state * sizeof(T));
-        chunk &= ~static_cast<size_t>(kWave - 1);
-        if (chunk < static_cast<size_t>(kWave)) chunk = kWave;
-        const size_t b_round = (B + kWave - 1) / kWave * kWave;
-        if (chunk > b_round) chunk = b_round;
+        const Chunk c = budgeted_chunk(p, p->work_proj, device, stream, 1024ull << 20, per_state * sizeof(T), B);
         void *wptr = nullptr;
-        if (int rc = ensure_work(p, p->work_proj, device, stream, chunk * per_state * sizeof(T) + 256, &wptr)) return rc;
-        T *q_s = static_cast<T *>(wptr), *v_tmp = q_s + chunk * nq_s, *cpl = v_tmp + chunk * nv_s;
+        if (int rc = ensure_work(p, p->work_proj, device, stream, c.bytes, &wptr)) return rc;
+        Carver<T> w(wptr, c.chunk * per_state);
+        T *q_s = w.take(c.chunk * nq_s), *v_tmp = w.take(c.chunk * nv_s), *cpl = w.take(c.chunk * p->n_cpl_rows);
+        assert(w.taken == w.cap);
         DevPlan<T> dp = make_dev_plan<T>(p, *t, false, false);
-        for (size_t b0 = 0; b0 < B; b0 += chunk) {
-            const size_t nb = B - b0 < chunk ? B - b0 : chunk;
-            size_t g = static_cast<size_t>(t->n_cu) * 4;
-            if (g > (nb + kWave - 1) / kWave) g = (nb + kWave - 1) / kWave;
+        for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+            const size_t g = tile_grid(t->n_cu, 4, nb);
             hipError_t e = launch_manifold_constraint<T>(dp, p->host.n_clusters, t->span_q, t->span_v, t->crow, static_cast<int>(nq_s),
                                                          static_cast<int>(nv_s), p->n_cpl_rows, 0, q + b0 * nq, qd + b0 * nv, ydd + b0 * nv, q_s,
                                                          qd_span ? qd_span + b0 * nv_s : v_tmp, qdd_span + b0 * nv_s, cpl, nb, static_cast<int>(g),
@@ -915,8 +993,7 @@ int state_convert(const grbda_plan *p, const uint8_t *pos_sp, const uint8_t *vel
         DeviceTables *t = nullptr;
         if (int rc = ensure_device(p, device, &t)) return rc;
         DevPlan<T> dp = make_dev_plan<T>(p, *t, false, false);
-        size_t g = static_cast<size_t>(t->n_cu) * 4;
-        if (g > (B + kWave - 1) / kWave) g = (B + kWave - 1) / kWave;
+        const size_t g = tile_grid(t->n_cu, 4, B);
         hipError_t e = launch_manifold_state<T>(dp, p->host.n_clusters, F, q_in, qd_in, in_nq, in_nv, q, qd, status, cond, B, static_cast<T>(tol),
                                                 static_cast<int>(g), static_cast<hipStream_t>(stream));
         return e == hipSuccess ? GRBDA_OK : hip_err(e, "state conversion launch");
@@ -937,13 +1014,12 @@ int poses(const grbda_plan *p, const T *q, T *Xa, size_t B, int device, void *st
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !Xa) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !Xa) return set_err(GRBDA_EINVAL, "null argument");
     if (B == 0) return GRBDA_OK;
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
-    const size_t n_tiles = (B + kWave - 1) / kWave;
-    const size_t g = n_tiles < static_cast<size_t>(t->n_cu) * 8 ? n_tiles : static_cast<size_t>(t->n_cu) * 8;
+    const size_t g = tile_grid(t->n_cu, 8, B);
     hipError_t e = launch_poses<T>(d, p->host.n_clusters, q, Xa, B, static_cast<int>(g), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "poses launch");
 }
@@ -962,11 +1038,11 @@ int twists(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *V, siz
     const size_t ns = static_cast<size_t>(span_count(p));
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, 2 * B * ns * sizeof(T) + 256, &wptr)) return rc;
-    T *vs = static_cast<T *>(wptr), *as = vs + B * ns;
+    Carver<T> w(wptr, 2 * B * ns);
+    T *vs = w.take(B * ns), *as = w.take(B * ns);
     if (int rc = spanning<T>(p, q, qd, ydd, vs, as, B, device, stream)) return rc;
     DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
-    const size_t n_tiles = (B + kWave - 1) / kWave;
-    const size_t g = n_tiles < static_cast<size_t>(t->n_cu) * 8 ? n_tiles : static_cast<size_t>(t->n_cu) * 8;
+    const size_t g = tile_grid(t->n_cu, 8, B);
     hipError_t e = launch_twists<T>(d, p->host.n_clusters, static_cast<int>(ns), q, vs, as, V, B, static_cast<int>(g),
                                     static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "twists launch");
@@ -1022,7 +1098,7 @@ int test_force(const grbda_plan *p, const T *q, int body, const double *offset, 
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !offset || !force || !lambda_inv || !dstate) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !offset || !force || !lambda_inv || !dstate) return set_err(GRBDA_EINVAL, "null argument");
     if (body < 0 || body >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
     if (B == 0) return GRBDA_OK;
     {   // models the chain program covers: one launch of the force-propagation kernel (osim_chain_kernel, applyTestForce mode)
@@ -1033,23 +1109,21 @@ int test_force(const grbda_plan *p, const T *q, int body, const double *offset, 
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies;
     const size_t per_state = nbod * 18 + 5 * nv;  // poses, wrenches, zeros, four results
-    size_t chunk = (256u << 20) / (per_state * sizeof(T));
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
+    const Chunk c = fixed_chunk(256u << 20, per_state * sizeof(T), B);
+    const size_t chunk = c.chunk;
     void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, chunk * per_state * sizeof(T) + 256, &wptr)) return rc;
-    T *Xa = static_cast<T *>(wptr);
-    T *fext = Xa + chunk * nbod * 12;
-    T *zero = fext + chunk * nbod * 6;
-    T *a1 = zero + chunk * nv, *a0 = a1 + chunk * nv, *t1 = a0 + chunk * nv, *t0 = t1 + chunk * nv;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, chunk * per_state);
+    T *Xa = w.take(chunk * nbod * 12), *fext = w.take(chunk * nbod * 6), *zero = w.take(chunk * nv);
+    T *a1 = w.take(chunk * nv), *a0 = w.take(chunk * nv), *t1 = w.take(chunk * nv), *t0 = w.take(chunk * nv);
+    assert(w.taken == w.cap);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(zero, 0, chunk * nv * sizeof(T), hs);
     if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
+    for (const auto [b0, nb] : ChunkWalk{B, chunk}) {
         const T *qc = q + b0 * nq;
         if (int rc = poses<T>(p, qc, Xa, nb, device, stream)) return rc;
-        const int blocks = static_cast<int>((nb + 255) / 256 < 65535 ? (nb + 255) / 256 : 65535);
+        const int blocks = blocks_for(nb);
         hipLaunchKernelGGL((wrench_kernel<T>), dim3(blocks), dim3(256), 0, hs, Xa, force + 3 * b0, static_cast<int>(nbod),
                            body, static_cast<T>(offset[0]), static_cast<T>(offset[1]), static_cast<T>(offset[2]), nb, fext);
         if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "wrench launch");
@@ -1279,7 +1353,7 @@ int inv_osim(const grbda_plan *p, const T *q, int n_contacts, const int *bodies,
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !bodies || !offsets || !Linv) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !bodies || !offsets || !Linv) return set_err(GRBDA_EINVAL, "null argument");
     if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact frames per call");
     ContactSet<T> cs;
     cs.n = n_contacts;
@@ -1298,35 +1372,28 @@ int inv_osim(const grbda_plan *p, const T *q, int n_contacts, const int *bodies,
     const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies;
     const size_t m = 6 * static_cast<size_t>(n_contacts), R = m + 1;
     const size_t per_state = nbod * 12 + R * (nq + nbod * 6 + 3 * nv);  // poses; per row q, wrenches, zeros, 2 results
-    size_t chunk = (256u << 20) / (per_state * sizeof(T));
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
+    const Chunk c = fixed_chunk(256u << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, chunk * per_state * sizeof(T) + 256, &wptr)) return rc;
-    const size_t rows = chunk * R;
-    T *Xa = static_cast<T *>(wptr);
-    T *qx = Xa + chunk * nbod * 12;
-    T *fext = qx + rows * nq;
-    T *zero = fext + rows * nbod * 6;
-    T *acc = zero + rows * nv, *tau = acc + rows * nv;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    const size_t rows = c.chunk * R;
+    Carver<T> w(wptr, c.chunk * per_state);
+    T *Xa = w.take(c.chunk * nbod * 12), *qx = w.take(rows * nq), *fext = w.take(rows * nbod * 6), *zero = w.take(rows * nv);
+    T *acc = w.take(rows * nv), *tau = w.take(rows * nv);
+    assert(w.taken == w.cap);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(zero, 0, rows * nv * sizeof(T), hs);
     if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         const size_t nrows = nb * R;
         if (int rc = poses<T>(p, q + b0 * nq, Xa, nb, device, stream)) return rc;
-        int blocks = static_cast<int>((nrows + 255) / 256 < 65535 ? (nrows + 255) / 256 : 65535);
-        hipLaunchKernelGGL((osim_expand_kernel<T>), dim3(blocks), dim3(256), 0, hs, cs, q + b0 * nq, Xa, static_cast<int>(nq),
+        hipLaunchKernelGGL((osim_expand_kernel<T>), dim3(blocks_for(nrows)), dim3(256), 0, hs, cs, q + b0 * nq, Xa, static_cast<int>(nq),
                            static_cast<int>(nbod), nb, qx, fext);
         if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "expand launch");
         int rc;
         if ((rc = run<T>(p, false, qx, zero, zero, fext, acc, nrows, device, stream)) ||
             (rc = run<T>(p, true, qx, zero, zero, fext, tau, nrows, device, stream)))
             return rc;
-        const size_t tot = nb * m * m;
-        blocks = static_cast<int>((tot + 255) / 256 < 65535 ? (tot + 255) / 256 : 65535);
-        hipLaunchKernelGGL((osim_combine_kernel<T>), dim3(blocks), dim3(256), 0, hs, acc, tau, static_cast<int>(nv),
+        hipLaunchKernelGGL((osim_combine_kernel<T>), dim3(blocks_for(nb * m * m)), dim3(256), 0, hs, acc, tau, static_cast<int>(nv),
                            static_cast<int>(m), nb, Linv + b0 * m * m, J ? J + b0 * m * nv : nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "combine launch");
     }
@@ -1429,7 +1496,7 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !out) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !out) return set_err(GRBDA_EINVAL, "null argument");
     if ((mode == DM_BIAS || mode == DM_DQD || mode == DM_DQ) && !qd) return set_err(GRBDA_EINVAL, "null argument");
     if ((mode == DM_DQD || mode == DM_DQ) && !tau) return set_err(GRBDA_EINVAL, "null argument");
     bool reproject = false;
@@ -1444,13 +1511,10 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
     if (mode == DM_MASS && p->host.crba.ok && !p->opt.no_crba) {
         // composite-rigid-body kernel (crba_kernels.hip): one launch instead of nv + 1 inverse-dynamics evaluations
         DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
-        const size_t n_tiles = (B + kWave - 1) / kWave;
         const size_t crba_waves = static_cast<size_t>(sizeof(T) == 4 ? p->opt.crba_waves : std::min(p->opt.crba_waves, 8));  // (fp64: 256 registers, two per SIMD)
-        size_t grid = static_cast<size_t>(t->n_cu) * crba_waves;
-        if (grid > n_tiles) grid = n_tiles;
+        const size_t grid = tile_grid(t->n_cu, crba_waves, B);
         void *scratch = nullptr;
-        if (int rc = ensure_scratch(p, device, stream, grid * static_cast<size_t>(p->host.crba.n_rows) * kWave * sizeof(T) + 256, &scratch))
-            return rc;
+        if (int rc = ensure_scratch(p, device, stream, scratch_bytes(grid, p->host.crba.n_rows, sizeof(T)), &scratch)) return rc;
         hipStream_t hs = static_cast<hipStream_t>(stream);
         hipError_t e;
         if (t->deriv_related) {
@@ -1464,8 +1528,7 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
                 const size_t b0 = part == 0 ? 0 : Bg, nbp = part == 0 ? Bg : B - Bg;
                 if (nbp == 0) continue;
                 const int ilp = part == 0 ? il : 1;
-                size_t gp = static_cast<size_t>(t->n_cu) * crba_waves;
-                if (gp > (nbp + kWave - 1) / kWave) gp = (nbp + kWave - 1) / kWave;
+                const size_t gp = tile_grid(t->n_cu, crba_waves, nbp);
                 e = launch_crba<T>(d, t->crba_bodies, p->host.n_clusters, p->host.crba.n_rows, q + b0 * nq, out + b0 * static_cast<size_t>(nv) * nv, nbp,
                                    static_cast<T *>(scratch), static_cast<int>(gp), hs, true, ilp);
                 if (e != hipSuccess) return hip_err(e, "crba launch");
@@ -1485,24 +1548,18 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
     }
     const int R = mode == DM_BIAS ? 1 : ((mode == DM_DQD || mode == DM_DQ) ? 2 * nv : nv + 1);
     const size_t row_scalars = static_cast<size_t>(nq) + 3 * static_cast<size_t>(nv);  // q, qd, x, result
-    size_t chunk = (256u << 20) / (row_scalars * sizeof(T) * static_cast<size_t>(R));
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
-    const size_t rows = chunk * static_cast<size_t>(R);
+    const Chunk c = fixed_chunk(256u << 20, row_scalars * sizeof(T) * static_cast<size_t>(R), B);
+    const size_t rows = c.chunk * static_cast<size_t>(R);
     void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, rows * row_scalars * sizeof(T) + 256, &wptr)) return rc;
-    T *qx = static_cast<T *>(wptr);
-    T *qdx = qx + rows * nq;
-    T *xx = qdx + rows * nv;
-    T *res = xx + rows * nv;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, rows * row_scalars);
+    T *qx = w.take(rows * nq), *qdx = w.take(rows * nv), *xx = w.take(rows * nv), *res = w.take(rows * nv);
+    assert(w.taken == w.cap);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     const bool via_rnea = mode == DM_BIAS || mode == DM_MASS;
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         const size_t nrows = nb * static_cast<size_t>(R);
-        const size_t total = nrows * static_cast<size_t>(nq + 2 * nv);
-        int blocks = static_cast<int>((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-        hipLaunchKernelGGL((expand_kernel<T>), dim3(blocks), dim3(256), 0, hs, mode, q + b0 * nq,
+        hipLaunchKernelGGL((expand_kernel<T>), dim3(blocks_for(nrows * static_cast<size_t>(nq + 2 * nv))), dim3(256), 0, hs, mode, q + b0 * nq,
                            qd ? qd + b0 * nv : nullptr, tau ? tau + b0 * nv : nullptr, nq, nv, R, nb, qx, qdx, xx, t->dq_map,
                            static_cast<T>(step));
         hipError_t e = hipGetLastError();
@@ -1516,9 +1573,7 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
         T *dst = mode == DM_BIAS ? out + b0 * nv : res;
         if (int rc = run<T>(p, via_rnea, qx, qdx, xx, fe, dst, nrows, device, stream)) return rc;
         if (mode != DM_BIAS) {
-            const size_t tot2 = nb * static_cast<size_t>(nv) * nv;
-            blocks = static_cast<int>((tot2 + 255) / 256 < 65535 ? (tot2 + 255) / 256 : 65535);
-            hipLaunchKernelGGL((combine_kernel<T>), dim3(blocks), dim3(256), 0, hs, mode, res, nv, R, nb,
+            hipLaunchKernelGGL((combine_kernel<T>), dim3(blocks_for(nb * static_cast<size_t>(nv) * nv)), dim3(256), 0, hs, mode, res, nv, R, nb,
                                out + b0 * static_cast<size_t>(nv) * nv, static_cast<T>(step));
             if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "combine launch");
         }
@@ -1552,15 +1607,11 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
     // (forward dynamics: H_s alone of the spanning recursion's three matrices is stored)
     const size_t per_state = nq_s + 3 * nv_s + static_cast<size_t>(p->n_cpl_rows) + (rnea ? 0 : nn_s + 2 * nn);  // (wide: nn + nv would do)
     // (plans with big clusters: 40-50 KB per state; a chunk that leaves most SIMDs without a tile costs more than the memory)
-    size_t chunk = work_budget(p, p->work_proj, device, stream, (big ? 4096ull : 1024ull) << 20) / (per_state * sizeof(T));
-    chunk &= ~static_cast<size_t>(kWave - 1);
-    if (chunk < static_cast<size_t>(kWave)) chunk = kWave;
-    const size_t b_round = (B + kWave - 1) / kWave * kWave;
-    if (chunk > b_round) chunk = b_round;
+    const Chunk c = budgeted_chunk(p, p->work_proj, device, stream, (big ? 4096ull : 1024ull) << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work_proj, device, stream, chunk * per_state * sizeof(T) + 256, &wptr)) return rc;
-    T *w = static_cast<T *>(wptr);
-    auto take = [&](size_t per) { T *r = w; w += chunk * per; return r; };
+    if (int rc = ensure_work(p, p->work_proj, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, c.chunk * per_state);
+    auto take = [&](size_t per) { return w.take(c.chunk * per); };
     T *q_s = take(nq_s), *qd_s = take(nv_s), *qdd_s = take(nv_s), *x_s = take(nv_s), *cpl = take(p->n_cpl_rows);
     T *Aq = nullptr, *Av = nullptr, *Hs = rnea ? nullptr : take(nn_s);
     // (more than 64 velocities: related-coordinate TABLES instead of one-word masks, and the workgroup-per-state solve on the one right-hand
@@ -1571,11 +1622,8 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
     DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
     DevPlan<T> ds = make_dev_plan<T>(sp, *ts, false, false);
     hipError_t e;
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
-        const size_t n_tiles = (nb + kWave - 1) / kWave;
-        size_t grid = static_cast<size_t>(t->n_cu) * 4;
-        if (grid > n_tiles) grid = n_tiles;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        const size_t grid = tile_grid(t->n_cu, 4, nb);
         // inverse dynamics: qdd_s = G ydd + g; forward dynamics: qdd_s = g (the bias of the spanning tree with the constraint's own acceleration)
         e = launch_manifold_constraint<T>(d, p->host.n_clusters, t->span_q, t->span_v, t->crow, static_cast<int>(nq_s), static_cast<int>(nv_s),
                                           p->n_cpl_rows, 0, q + b0 * nq, qd + b0 * nv, rnea ? x + b0 * nv : nullptr, q_s, qd_s, qdd_s, cpl, nb,
@@ -1589,10 +1637,9 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
             if (e != hipSuccess) return hip_err(e, "manifold apply launch");
             continue;
         }
-        size_t g2 = static_cast<size_t>(ts->n_cu) * 4;
-        if (g2 > n_tiles) g2 = n_tiles;
+        const size_t g2 = tile_grid(ts->n_cu, 4, nb);
         void *scratch = nullptr;
-        if (int rc = ensure_scratch(sp, device, stream, g2 * static_cast<size_t>(sp->host.deriv.n_rows) * kWave * sizeof(T) + 256, &scratch)) return rc;
+        if (int rc = ensure_scratch(sp, device, stream, scratch_bytes(g2, sp->host.deriv.n_rows, sizeof(T)), &scratch)) return rc;
         e = launch_rnea_deriv<T>(ds, ts->deriv_bodies, sp->host.n_clusters, sp->host.deriv.n_rows, sp->host.deriv.n_max, q_s, qd_s, qdd_s, Aq, Av, Hs,
                                  nb, static_cast<T *>(scratch), static_cast<int>(g2), hs, kWave);
         if (e != hipSuccess) return hip_err(e, "spanning derivative launch");
@@ -1631,31 +1678,50 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
     return GRBDA_OK;
 }
 
-int projection_run_f32_through_f64(const grbda_plan *p, bool rnea, const float *q, const float *qd, const float *x, const float *f_ext, float *out,
-                                   size_t B, int device, void *stream)
+// fp32 entry points that compute in fp64.  Chunk by chunk (at most `cap_bytes` of fp64 copies in the plan's work_cvt slab): the arrays with a
+// `src` are converted, call(a, nb) runs the fp64 routine on the chunk's arrays a[i] (null where the caller gave none), the arrays with a
+// `dst` are converted back.  `width`: scalars per state.
+struct CvtArray {
+    const float *src;
+    float *dst;
+    size_t width;
+};
+template <size_t N, class Call>
+int through_f64(const grbda_plan *p, size_t cap_bytes, const CvtArray (&arrays)[N], size_t B, int device, void *stream, Call call)
 {
-    const size_t nq = p->host.nq, nv = p->host.nv, nfe = f_ext ? static_cast<size_t>(p->host.n_bodies) * 6 : 0;
-    const size_t per_state = nq + 3 * nv + nfe;
-    size_t chunk = (256u << 20) / (per_state * sizeof(double));
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
+    size_t per_state = 0;
+    for (const CvtArray &a : arrays) per_state += (a.src || a.dst) ? a.width : 0;
+    const Chunk c = fixed_chunk(cap_bytes, per_state * sizeof(double), B);
     void *cvt = nullptr;
-    if (int rc = ensure_work(p, p->work_cvt, device, stream, chunk * per_state * sizeof(double) + 256, &cvt)) return rc;
-    double *q64 = static_cast<double *>(cvt), *qd64 = q64 + chunk * nq, *x64 = qd64 + chunk * nv, *o64 = x64 + chunk * nv, *fe64 = o64 + chunk * nv;
+    if (int rc = ensure_work(p, p->work_cvt, device, stream, c.bytes, &cvt)) return rc;
+    Carver<double> w(cvt, c.chunk * per_state);
+    double *a64[N];
+    for (size_t i = 0; i < N; i++) a64[i] = (arrays[i].src || arrays[i].dst) ? w.take(c.chunk * arrays[i].width) : nullptr;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    auto blocks = [](size_t n) { return static_cast<int>((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535); };
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
-        hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks(nb * nq)), dim3(256), 0, hs, q + b0 * nq, q64, nb * nq);
-        hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks(nb * nv)), dim3(256), 0, hs, qd + b0 * nv, qd64, nb * nv);
-        hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks(nb * nv)), dim3(256), 0, hs, x + b0 * nv, x64, nb * nv);
-        if (f_ext) hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks(nb * nfe)), dim3(256), 0, hs, f_ext + b0 * nfe, fe64, nb * nfe);
-        if (int rc = projection_run<double>(p, rnea, q64, qd64, x64, f_ext ? fe64 : nullptr, o64, nb, device, stream)) return rc;
-        hipLaunchKernelGGL((convert_kernel<double, float>), dim3(blocks(nb * nv)), dim3(256), 0, hs, o64, out + b0 * nv, nb * nv);
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        for (size_t i = 0; i < N; i++) {
+            const size_t n = nb * arrays[i].width;
+            if (arrays[i].src) hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks_for(n)), dim3(256), 0, hs, arrays[i].src + b0 * arrays[i].width, a64[i], n);
+        }
+        if (int rc = call(a64, nb)) return rc;
+        for (size_t i = 0; i < N; i++) {
+            const size_t n = nb * arrays[i].width;
+            if (arrays[i].dst) hipLaunchKernelGGL((convert_kernel<double, float>), dim3(blocks_for(n)), dim3(256), 0, hs, a64[i], arrays[i].dst + b0 * arrays[i].width, n);
+        }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_err(e, "convert launch");
     }
     return GRBDA_OK;
+}
+
+int projection_run_f32_through_f64(const grbda_plan *p, bool rnea, const float *q, const float *qd, const float *x, const float *f_ext, float *out,
+                                   size_t B, int device, void *stream)
+{
+    const size_t nq = p->host.nq, nv = p->host.nv, nfe = static_cast<size_t>(p->host.n_bodies) * 6;
+    const CvtArray arrays[] = {{q, nullptr, nq}, {qd, nullptr, nv}, {x, nullptr, nv}, {nullptr, out, nv}, {f_ext, nullptr, nfe}};
+    return through_f64(p, 256u << 20, arrays, B, device, stream, [&](double *const *a, size_t nb) {
+        return projection_run<double>(p, rnea, a[0], a[1], a[2], a[4], a[3], nb, device, stream);
+    });
 }
 
 // Models with implicit clusters (manifold_kernels.hip): ydd = FD; spanning state and the first-order parts of G, g per state;
@@ -1693,24 +1759,21 @@ int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     // (16 GiB, cut to a quarter of the free memory: TelloWithArms takes 33 KB per state; a 4 GiB chunk -- 131 072 states, 2 048 tiles -- left half
     // of the projection kernel's wavefront slots empty: 13.3 -> 10.8 ms per 262 144 states, 55 -> 44 ms per 1 048 576)
     // (up to 16 GiB -- but no more than the batch itself needs: a small batch does not pin a large slab)
-    size_t chunk = work_budget(p, p->work, device, stream, std::min<size_t>(16384ull << 20, ((B + kWave - 1) / kWave * kWave) * per_state * sizeof(T) + (1u << 20))) / (per_state * sizeof(T));
-    chunk &= ~static_cast<size_t>(kWave - 1);
-    if (chunk < static_cast<size_t>(kWave)) chunk = kWave;
-    const size_t b_round = (B + kWave - 1) / kWave * kWave;
-    if (chunk > b_round) chunk = b_round;
+    const size_t want = std::min<size_t>(16384ull << 20, ((B + kWave - 1) / kWave * kWave) * per_state * sizeof(T) + (1u << 20));
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, want, per_state * sizeof(T), B);
+    const size_t chunk = c.chunk;
     void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, chunk * per_state * sizeof(T) + 256, &wptr)) return rc;
-    T *w = static_cast<T *>(wptr);
-    auto take = [&](size_t per) { T *r = w; w += chunk * per; return r; };
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, chunk * per_state);
+    auto take = [&](size_t per) { return w.take(chunk * per); };
     T *q_s = take(nq_s), *qd_s = take(nv_s), *qdd_s = take(nv_s), *tau_s = take(nv_s), *zeros = take(nv), *cpl = take(p->n_cpl_rows);
     T *Aq = take(nn_s), *Av = take(nn_s), *Hs = take(nn_s), *Dq = take(nn), *Dqd = take(nn), *Hw = take(nn), *ydd = take(nv);
+    assert(w.taken == w.cap);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
     DevPlan<T> ds = make_dev_plan<T>(sp, *ts, false, false);
     hipError_t e;
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
-        const size_t n_tiles = (nb + kWave - 1) / kWave;
+    for (const auto [b0, nb] : ChunkWalk{B, chunk}) {
         const T *qc = q + b0 * nq, *qdc = qd ? qd + b0 * nv : zeros, *yddc = nullptr;
         if (!qd && (e = hipMemsetAsync(zeros, 0, nb * nv * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
         if (need_d) {
@@ -1720,8 +1783,7 @@ int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
             // H only: the recursion runs at zero velocity and acceleration (its H does not depend on them)
             if ((e = hipMemsetAsync(qd_s, 0, 2 * chunk * nv_s * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
         }
-        size_t grid = static_cast<size_t>(t->n_cu) * 4;
-        if (grid > n_tiles) grid = n_tiles;
+        const size_t grid = tile_grid(t->n_cu, 4, nb);
         e = launch_manifold_constraint<T>(d, p->host.n_clusters, t->span_q, t->span_v, t->crow, static_cast<int>(nq_s), static_cast<int>(nv_s),
                                           p->n_cpl_rows, need_d ? 1 : 0, qc, qdc, yddc, q_s, qd_s, need_d ? qdd_s : nullptr, cpl, nb,
                                           static_cast<int>(grid), hs, p->constraint_shape, p->has_trig);
@@ -1730,12 +1792,9 @@ int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
         if (need_d)
             if (int rc = run<T>(sp, true, q_s, qd_s, qdd_s, nullptr, tau_s, nb, device, stream)) return rc;
         {
-            const size_t deriv_waves = 4;
-            size_t g2 = static_cast<size_t>(ts->n_cu) * deriv_waves;
-            if (g2 > n_tiles) g2 = n_tiles;
+            const size_t g2 = tile_grid(ts->n_cu, 4, nb);
             void *scratch = nullptr;
-            if (int rc = ensure_scratch(sp, device, stream, g2 * static_cast<size_t>(sp->host.deriv.n_rows) * kWave * sizeof(T) + 256, &scratch))
-                return rc;
+            if (int rc = ensure_scratch(sp, device, stream, scratch_bytes(g2, sp->host.deriv.n_rows, sizeof(T)), &scratch)) return rc;
             e = launch_rnea_deriv<T>(ds, ts->deriv_bodies, sp->host.n_clusters, sp->host.deriv.n_rows, sp->host.deriv.n_max, q_s, qd_s, qdd_s,
                                      need_d ? Aq : nullptr, need_d ? Av : nullptr, Hs, nb, static_cast<T *>(scratch), static_cast<int>(g2), hs, kWave);
             if (e != hipSuccess) return hip_err(e, "spanning derivative launch");
@@ -1815,8 +1874,7 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     const size_t B_groups = (B + kDerivGroup - 1) / kDerivGroup * kDerivGroup;  // (the last group of the workspace is allocated whole)
     size_t chunk = 0;
     bool ydd_all = false;
-    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
-    const bool capturing = stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cst) == hipSuccess && cst != hipStreamCaptureStatusNone;
+    const bool capturing = is_capturing(stream);
     {
         const auto it = p->deriv_chunk.find({device, stream});
         if (capturing && it != p->deriv_chunk.end() && it->second.B == B && it->second.per_state_bytes == ps_bytes && it->second.need_d == need_d) {
@@ -1832,9 +1890,7 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
         } else {
             // (room for the whole batch's ydd and a tile of states besides; otherwise the forward dynamics runs per chunk)
             ydd_all = need_d && budget >= ydd_bytes + tile;
-            chunk = (budget - (ydd_all ? ydd_bytes : 0)) / (ps_bytes ? ps_bytes : 1);
-            chunk &= ~static_cast<size_t>(kWave - 1);  // whole tiles, whole groups of the interleaved workspace
-            if (chunk < static_cast<size_t>(kWave)) chunk = kWave;
+            chunk = whole_tiles((budget - (ydd_all ? ydd_bytes : 0)) / (ps_bytes ? ps_bytes : 1));  // (and with them whole groups of the interleaved workspace)
             // whole ROUNDS of the one-state-per-lane kernels: a chunk of 2.4 rounds of wavefront slots takes as long as 3 (measured: 159 488-state
             // chunks of JVRC-1, 2 492 tiles on 1 024 slots of the recursion and 2 048 of the factor kernel / the ABA: 19 % and 40 % of the
             // slots idle in the last round).  n_cu * 8 wavefronts = one round at two per SIMD, two rounds of the recursion's four per CU.
@@ -1851,25 +1907,18 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     // (deriv_kernels.hip); every other combination keeps the state-major layout (il, above)
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, (chunk * per_state + (ydd_all ? B * nv : 0)) * sizeof(T) + 256, &wptr)) return rc;
-    T *wnext = static_cast<T *>(wptr);
-    auto take = [&](bool wanted) -> T * {
-        if (!wanted) return nullptr;
-        T *r = wnext;
-        wnext += chunk * nn;
-        return r;
-    };
-    T *wH = take(!minv && !h_in_place), *Dq = take(need_d), *Dqd = take(need_d);
-    T *ydd_chunk = wnext;
-    T *recs = minv ? ydd_chunk + (need_d ? chunk * nv : 0) : nullptr;
-    T *ydd_whole = ydd_all ? static_cast<T *>(wptr) + chunk * per_state : nullptr;
+    Carver<T> w(wptr, chunk * per_state + (ydd_all ? B * nv : 0));
+    T *wH = (!minv && !h_in_place) ? w.take(chunk * nn) : nullptr, *Dq = need_d ? w.take(chunk * nn) : nullptr, *Dqd = need_d ? w.take(chunk * nn) : nullptr;
+    T *ydd_chunk = w.take(need_d ? chunk * nv : 0);
+    T *recs = minv ? w.take(chunk * mv.n_entries) : nullptr;
+    assert(w.taken == chunk * per_state);
+    T *ydd_whole = ydd_all ? w.take(B * nv) : nullptr;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
     if (ydd_all)
         if (int rc = run<T>(p, false, q, qd, tau, nullptr, ydd_whole, B, device, stream)) return rc;
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
+    for (const auto [b0, nb] : ChunkWalk{B, chunk}) {
         T *ydd = ydd_all ? ydd_whole + b0 * nv : ydd_chunk;
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
-        const size_t n_tiles = (nb + kWave - 1) / kWave;
         // (an interleaved H block spans the slots of a whole group: when the batch does not end on a group boundary the last
         // group would reach past the caller's d/dtau array, so that H goes to the workspace)
         T *H = h_in_place ? dtau + b0 * nn : wH;
@@ -1878,18 +1927,16 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
         // nothing is cleared)
         if (need_d && !ydd_all)
             if (int rc = run<T>(p, false, q + b0 * nq, qd + b0 * nv, tau + b0 * nv, nullptr, ydd, nb, device, stream)) return rc;
-        size_t grid = static_cast<size_t>(t->n_cu) * 8;
-        if (grid > n_tiles) grid = n_tiles;
+        const size_t grid = tile_grid(t->n_cu, 8, nb);
         const size_t rows = std::max(p->host.crba.n_rows, (need_d || minv) ? p->host.deriv.n_rows : 0);  // (the factor kernel of the minv route uses the recursion's rows)
         // (state-major results: three wavefronts per CU -- a fourth only adds open cache lines; interleaved: one per SIMD)
         const size_t deriv_waves = p->opt.deriv_waves ? static_cast<size_t>(p->opt.deriv_waves) : (il > 1 ? 4 : 3);
         const size_t slabs = std::max(grid, static_cast<size_t>(t->n_cu) * deriv_waves);  // (the factor kernel of the minv route runs n_cu * 8 wavefronts, as `grid`)
         void *scratch = nullptr;
-        if (int rc = ensure_scratch(p, device, stream, slabs * rows * kWave * sizeof(T) + 256, &scratch)) return rc;
+        if (int rc = ensure_scratch(p, device, stream, scratch_bytes(slabs, rows, sizeof(T)), &scratch)) return rc;
         if (need_d) {
             // (the derivative recursion carries the composite inertias in a common frame: H comes out of the same launch)
-            size_t g2 = static_cast<size_t>(t->n_cu) * deriv_waves;
-            if (g2 > n_tiles) g2 = n_tiles;
+            const size_t g2 = tile_grid(t->n_cu, deriv_waves, nb);
             e = launch_rnea_deriv<T>(d, t->deriv_bodies, p->host.n_clusters, p->host.deriv.n_rows, p->host.deriv.n_max, q + b0 * nq,
                                      qd + b0 * nv, ydd, Dq, Dqd, minv ? nullptr : H, nb, static_cast<T *>(scratch), static_cast<int>(g2), hs, il);
             if (e != hipSuccess) return hip_err(e, "rnea derivative launch");
@@ -1993,7 +2040,7 @@ int run_sharded(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !qd || !x || !out) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !qd || !x || !out) return set_err(GRBDA_EINVAL, "null argument");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         return set_err(GRBDA_ENODEVICE, "no HIP device available (there is no CPU fallback)");
@@ -2118,15 +2165,6 @@ int run_sharded_dev(const grbda_plan *p, bool rnea, int n_gpus, const int *devic
     }
     return GRBDA_OK;
 }
-
-// ---- host-pointer convenience for the contact-side entry points (single-state facade calls) ----------------------
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { hipError_t e = hipMalloc(&p, bytes ? bytes : 16); return e == hipSuccess ? 0 : hip_err(e, "hipMalloc"); }
-    int put(const void *src, size_t bytes) { hipError_t e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice); return e == hipSuccess ? 0 : hip_err(e, "hipMemcpy H2D"); }
-    int get(void *dst, size_t bytes) const { hipError_t e = hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost); return e == hipSuccess ? 0 : hip_err(e, "hipMemcpy D2H"); }
-};
 
 }  // namespace
 
@@ -2331,12 +2369,8 @@ void grbda_plan_free(grbda_plan *p)
 static bool holds_capturing_slab(const grbda_plan *p)
 {
     for (auto *m : {&p->work, &p->work_cvt, &p->work_proj})
-        for (auto &kv : *m) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (kv.second.ptr && kv.first.second && hipStreamIsCapturing(static_cast<hipStream_t>(kv.first.second), &cs) == hipSuccess &&
-                cs != hipStreamCaptureStatusNone)
-                return true;
-        }
+        for (auto &kv : *m)
+            if (kv.second.ptr && is_capturing(kv.first.second)) return true;
     return p->span && holds_capturing_slab(p->span);
 }
 
@@ -2523,26 +2557,10 @@ int grbda_fd_dq_f32(const grbda_plan *p, const float *q, const float *qd, const 
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nv = p->host.nv;
-    const size_t per_state = nq + 2 * nv + nv * nv;
-    size_t chunk = (64u << 20) / (per_state * sizeof(double));
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
-    void *cvt = nullptr;
-    if (int rc = ensure_work(p, p->work_cvt, device, stream, chunk * per_state * sizeof(double) + 256, &cvt)) return rc;
-    double *q64 = static_cast<double *>(cvt), *qd64 = q64 + chunk * nq, *tau64 = qd64 + chunk * nv, *J64 = tau64 + chunk * nv;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    auto blocks = [](size_t n) { return static_cast<int>((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535); };
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = B - b0 < chunk ? B - b0 : chunk;
-        hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks(nb * nq)), dim3(256), 0, hs, q + b0 * nq, q64, nb * nq);
-        hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks(nb * nv)), dim3(256), 0, hs, qd + b0 * nv, qd64, nb * nv);
-        hipLaunchKernelGGL((convert_kernel<float, double>), dim3(blocks(nb * nv)), dim3(256), 0, hs, tau + b0 * nv, tau64, nb * nv);
-        if (int rc = derived<double>(p, DM_DQ, q64, qd64, tau64, nullptr, J64, nb, device, stream, step)) return rc;
-        hipLaunchKernelGGL((convert_kernel<double, float>), dim3(blocks(nb * nv * nv)), dim3(256), 0, hs, J64, J + b0 * nv * nv, nb * nv * nv);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_err(e, "convert launch");
-    }
-    return GRBDA_OK;
+    const CvtArray arrays[] = {{q, nullptr, nq}, {qd, nullptr, nv}, {tau, nullptr, nv}, {nullptr, J, nv * nv}};
+    return through_f64(p, 64u << 20, arrays, B, device, stream, [&](double *const *a, size_t nb) {
+        return derived<double>(p, DM_DQ, a[0], a[1], a[2], nullptr, a[3], nb, device, stream, step);
+    });
 }
 int grbda_fd_derivatives_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double *dq, double *dqd,
                              double *dtau, size_t B, int device, void *stream)
@@ -2669,16 +2687,14 @@ int grbda_body_poses_host_f64(const grbda_plan *p, const double *q, double *Xa, 
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !Xa) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !Xa) return set_err(GRBDA_EINVAL, "null argument");
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nb = p->host.n_bodies;
-    DevBuf dq, dX;
-    int rc;
-    if ((rc = dq.alloc(B * nq * 8)) || (rc = dX.alloc(B * nb * 12 * 8)) || (rc = dq.put(q, B * nq * 8))) return rc;
-    if ((rc = poses<double>(p, static_cast<double *>(dq.p), static_cast<double *>(dX.p), B, device, nullptr))) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    return dX.get(Xa, B * nb * 12 * 8);
+    HostStage st;
+    const double *dq = st.in(q, B * nq);
+    double *dX = st.out(Xa, B * nb * 12);
+    return st.run([&] { return poses<double>(p, dq, dX, B, device, nullptr); });
 }
 int grbda_body_twists_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double *V, size_t B, int device)
 {
@@ -2688,59 +2704,39 @@ int grbda_body_twists_host_f64(const grbda_plan *p, const double *q, const doubl
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nv = p->host.nv, nb = p->host.n_bodies;
-    DevBuf dq, dqd, dy, dV;
-    int rc;
-    if ((rc = dq.alloc(B * nq * 8)) || (rc = dqd.alloc(B * nv * 8)) || (rc = dy.alloc(B * nv * 8)) || (rc = dV.alloc(B * nb * 12 * 8)) ||
-        (rc = dq.put(q, B * nq * 8)) || (rc = dqd.put(qd, B * nv * 8)) || (rc = dy.put(ydd, B * nv * 8)))
-        return rc;
-    if ((rc = twists<double>(p, static_cast<double *>(dq.p), static_cast<double *>(dqd.p), static_cast<double *>(dy.p),
-                             static_cast<double *>(dV.p), B, device, nullptr)))
-        return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    return dV.get(V, B * nb * 12 * 8);
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dy = st.in(ydd, B * nv);
+    double *dV = st.out(V, B * nb * 12);
+    return st.run([&] { return twists<double>(p, dq, dqd, dy, dV, B, device, nullptr); });
 }
 int grbda_apply_test_force_host_f64(const grbda_plan *p, const double *q, int body, const double offset[3],
                                     const double *force, double *lambda_inv, double *dstate, size_t B, int device)
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !force || !lambda_inv || !dstate) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !force || !lambda_inv || !dstate) return set_err(GRBDA_EINVAL, "null argument");
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nv = p->host.nv;
-    DevBuf dq, df, dl, dd;
-    int rc;
-    if ((rc = dq.alloc(B * nq * 8)) || (rc = df.alloc(B * 3 * 8)) || (rc = dl.alloc(B * 8)) || (rc = dd.alloc(B * nv * 8)) ||
-        (rc = dq.put(q, B * nq * 8)) || (rc = df.put(force, B * 3 * 8)))
-        return rc;
-    if ((rc = test_force<double>(p, static_cast<double *>(dq.p), body, offset, static_cast<double *>(df.p),
-                                 static_cast<double *>(dl.p), static_cast<double *>(dd.p), B, device, nullptr)))
-        return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    if ((rc = dl.get(lambda_inv, B * 8))) return rc;
-    return dd.get(dstate, B * nv * 8);
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *df = st.in(force, B * 3);
+    double *dl = st.out(lambda_inv, B), *dd = st.out(dstate, B * nv);
+    return st.run([&] { return test_force<double>(p, dq, body, offset, df, dl, dd, B, device, nullptr); });
 }
 int grbda_inv_osim_host_f64(const grbda_plan *p, const double *q, int n_contacts, const int *bodies, const double *offsets,
                             double *Linv, double *J, size_t B, int device)
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!p || !q || !Linv) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !Linv) return set_err(GRBDA_EINVAL, "null argument");
     if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact frames per call");
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nv = p->host.nv, m = 6 * static_cast<size_t>(n_contacts);
-    DevBuf dq, dL, dJ;
-    int rc;
-    if ((rc = dq.alloc(B * nq * 8)) || (rc = dL.alloc(B * m * m * 8)) || (J && (rc = dJ.alloc(B * m * nv * 8))) ||
-        (rc = dq.put(q, B * nq * 8)))
-        return rc;
-    if ((rc = inv_osim<double>(p, static_cast<double *>(dq.p), n_contacts, bodies, offsets, static_cast<double *>(dL.p),
-                               J ? static_cast<double *>(dJ.p) : nullptr, B, device, nullptr)))
-        return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    if ((rc = dL.get(Linv, B * m * m * 8))) return rc;
-    return J ? dJ.get(J, B * m * nv * 8) : GRBDA_OK;
+    HostStage st;
+    const double *dq = st.in(q, B * nq);
+    double *dL = st.out(Linv, B * m * m), *dJ = J ? st.out(J, B * m * nv) : nullptr;
+    return st.run([&] { return inv_osim<double>(p, dq, n_contacts, bodies, offsets, dL, dJ, B, device, nullptr); });
 }
 // host arrays: mass matrix and the derivatives of the forward dynamics (facade: getMassMatrix, forwardDynamicsDerivativesBatch)
 int grbda_mass_matrix_host_f64(const grbda_plan *p, const double *q, double *H, size_t B, int device)
@@ -2751,12 +2747,10 @@ int grbda_mass_matrix_host_f64(const grbda_plan *p, const double *q, double *H, 
     DeviceTables *t = nullptr;
     if (int rc0 = ensure_device(p, device, &t)) return rc0;  // `device` current before anything is allocated on it
     const size_t nq = p->host.nq, nv = p->host.nv;
-    DevBuf dq, dH;
-    int rc;
-    if ((rc = dq.alloc(B * nq * 8)) || (rc = dH.alloc(B * nv * nv * 8)) || (rc = dq.put(q, B * nq * 8))) return rc;
-    if ((rc = grbda_mass_matrix_f64(p, static_cast<double *>(dq.p), static_cast<double *>(dH.p), B, device, nullptr))) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    return dH.get(H, B * nv * nv * 8);
+    HostStage st;
+    const double *dq = st.in(q, B * nq);
+    double *dH = st.out(H, B * nv * nv);
+    return st.run([&] { return grbda_mass_matrix_f64(p, dq, dH, B, device, nullptr); });
 }
 int grbda_fd_derivatives_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double *dq, double *dqd,
                                   double *dtau, size_t B, int device)
@@ -2767,20 +2761,10 @@ int grbda_fd_derivatives_host_f64(const grbda_plan *p, const double *q, const do
     DeviceTables *t = nullptr;
     if (int rc0 = ensure_device(p, device, &t)) return rc0;  // `device` current before anything is allocated on it
     const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
-    DevBuf bq, bqd, bt, b1, b2, b3;
-    int rc;
-    if ((rc = bq.alloc(B * nq * 8)) || (rc = bqd.alloc(B * nv * 8)) || (rc = bt.alloc(B * nv * 8)) || (dq && (rc = b1.alloc(B * nn * 8))) ||
-        (dqd && (rc = b2.alloc(B * nn * 8))) || (dtau && (rc = b3.alloc(B * nn * 8))) || (rc = bq.put(q, B * nq * 8)) ||
-        (rc = bqd.put(qd, B * nv * 8)) || (rc = bt.put(tau, B * nv * 8)))
-        return rc;
-    if ((rc = grbda_fd_derivatives_f64(p, static_cast<double *>(bq.p), static_cast<double *>(bqd.p), static_cast<double *>(bt.p),
-                                       dq ? static_cast<double *>(b1.p) : nullptr, dqd ? static_cast<double *>(b2.p) : nullptr,
-                                       dtau ? static_cast<double *>(b3.p) : nullptr, B, device, nullptr)))
-        return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    if (dq && (rc = b1.get(dq, B * nn * 8))) return rc;
-    if (dqd && (rc = b2.get(dqd, B * nn * 8))) return rc;
-    return dtau ? b3.get(dtau, B * nn * 8) : GRBDA_OK;
+    HostStage st;
+    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bt = st.in(tau, B * nv);
+    double *b1 = dq ? st.out(dq, B * nn) : nullptr, *b2 = dqd ? st.out(dqd, B * nn) : nullptr, *b3 = dtau ? st.out(dtau, B * nn) : nullptr;
+    return st.run([&] { return grbda_fd_derivatives_f64(p, bq, bqd, bt, b1, b2, b3, B, device, nullptr); });
 }
 int grbda_plan_span_dims(const grbda_plan *p, int *n_span_vel)
 {
@@ -2807,13 +2791,10 @@ int grbda_project_positions_host_f64(const grbda_plan *p, double *q, int32_t *ok
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq;
-    DevBuf dq, dok;
-    int rc;
-    if ((rc = dq.alloc(B * nq * 8)) || (rc = dok.alloc(B * sizeof(int32_t))) || (rc = dq.put(q, B * nq * 8))) return rc;
-    if ((rc = project<double>(p, static_cast<double *>(dq.p), static_cast<int32_t *>(dok.p), B, max_iter, tol, device, nullptr))) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    if ((rc = dq.get(q, B * nq * 8))) return rc;
-    return ok ? dok.get(ok, B * sizeof(int32_t)) : GRBDA_OK;
+    HostStage st;
+    double *dq = st.inout(q, B * nq);
+    int32_t *dok = st.out(ok, B);  // (the kernel always writes the flags; a null `ok` only drops the copy)
+    return st.run([&] { return project<double>(p, dq, dok, B, max_iter, tol, device, nullptr); });
 }
 int grbda_state_input_dims(const grbda_plan *p, const uint8_t *pos_is_spanning, const uint8_t *vel_is_spanning, int *in_nq, int *in_nv)
 {
@@ -2845,21 +2826,16 @@ int grbda_state_to_independent_host_f64(const grbda_plan *p, const uint8_t *pos_
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nv = p->host.nv;
-    DevBuf bqi, bvi, bq, bv, bs;
-    int rc;
-    if ((rc = bqi.alloc(B * in_nq * 8)) || (rc = bvi.alloc(B * in_nv * 8)) || (rc = bq.alloc(B * nq * 8)) || (rc = bv.alloc(B * nv * 8)) ||
-        (rc = bs.alloc(B * 4)) || (rc = bqi.put(q_in, B * in_nq * 8)) || (rc = bvi.put(qd_in, B * in_nv * 8)))
+    std::vector<int32_t> status(B);
+    HostStage st;
+    const double *bqi = st.in(q_in, B * in_nq), *bvi = st.in(qd_in, B * in_nv);
+    int32_t *bs = st.out(status.data(), B);  // (read back first, as it always was)
+    double *bq = st.out(q, B * nq), *bv = st.out(qd, B * nv);
+    if (int rc = st.run([&] { return state_convert<double>(p, pos_is_spanning, vel_is_spanning, bqi, bvi, bq, bv, bs, nullptr, B, tol, device, nullptr); }))
         return rc;
-    if ((rc = state_convert<double>(p, pos_is_spanning, vel_is_spanning, static_cast<const double *>(bqi.p), static_cast<const double *>(bvi.p),
-                                    static_cast<double *>(bq.p), static_cast<double *>(bv.p), static_cast<int32_t *>(bs.p), nullptr, B, tol,
-                                    device, nullptr)))
-        return rc;
-    if (hipDeviceSynchronize() != hipSuccess) return set_err(GRBDA_EHIP, "kernel execution");
-    std::vector<int32_t> st(B);
-    if ((rc = bs.get(st.data(), B * 4)) || (rc = bq.get(q, B * nq * 8)) || (rc = bv.get(qd, B * nv * 8))) return rc;
     for (size_t b = 0; b < B; b++)
-        if (st[b]) {
-            const int code = st[b] & 255, cluster = st[b] >> 8;
+        if (status[b]) {
+            const int code = status[b] & 255, cluster = status[b] >> 8;
             return set_err(GRBDA_ESTATE, "state " + std::to_string(b) + ", cluster " + std::to_string(cluster) + ": " +
                                              (code == 1 ? "Spanning position is not valid" : "Spanning velocity is not valid"));
         }
