@@ -198,33 +198,41 @@ __device__ __forceinline__ void bias_force(const I21 &I, const T (&v)[6], T (&p)
     crf(v, Iv, p);
 }
 
-// Axisymmetric rotor evaluated at q = 0 (plan.cpp): a body whose inertia is invariant under rotation about its joint
-// axis z has the spatial inertia  [[A,0,0,0,k,0],[0,A,0,-k,0,0],[0,0,B,0,0,0],[0,-k,0,m,0,0],[k,0,0,0,m,0],[0,0,0,0,0,m]]
-// (k = m c_z), so I v and I c cost 10 / 8 operations instead of 36 / 24, h = I[:, z] = B e_z makes the joint-space
-// bias b = pA_z, and the force per unit rotor acceleration X0^T h is a plan constant (ChainLink::rpre).
-// In: parent velocity vp, rotor rate qdr.  Out: b (bias torque about the rotor axis), tp = X0^T (pA + I c) at the parent.
+// Axisymmetric rotor in closed form (plan.cpp marks a leaf body axisymmetric when its inertia is invariant under rotation about
+// its joint axis z to 1e-12 relative).  Such a body has the spatial inertia
+//   I = [[A,0,0,0,k,0],[0,A,0,-k,0,0],[0,0,B,0,0,0],[0,-k,0,m,0,0],[k,0,0,0,m,0],[0,0,0,0,0,m]]   (k = m c_z),
+// so h = I z = B z, and the invariance reads  z x* I = I z x  (x* the force cross product crf, x the motion cross product).
+// With w = X0 vp the parent body's velocity in the rotor frame, om the rotor rate, v = w + om z and c = v x (om z) = om (w x z),
+// what the ABA needs from the rotor is (ClusterTreeDynamics.cpp:94-129)
+//   pA + I c = v x* I v + I c
+//            = w x* I w + om B (w x* z) + om (z x* I w) + om^2 B (z x* z) + om I (w x z)
+//            = w x* I w + om B (w x* z)                         (z x* I w = I (z x w) = -I (w x z);  z x* z = 0)
+//   b  = z . (pA + I c) = 0                                    (identically: (w x* I w)_z = -k w3 w0 - k w4 w1 + k w1 w4 + k w0 w3 = 0
+//                                                                for the I above, and w x* z has no z torque)
+//   tp = X0^T (pA + I c) = vp x* (X0^T I X0) vp + om (vp x* X0^T h)         (X^T ((X a) x* f) = a x* X^T f)
+// The first term of tp is what the bias force of the body the rotor hangs off produces when it is evaluated with that body's inertia
+// PLUS the rotor's constant X0^T I X0 -- the plan constant `bofs` of every record (plan.cpp, bias_inertia) -- so it costs nothing here;
+// the second is one cross product with the plan constant X0^T h (ChainLink::rpre [0..5]).  Nothing is approximated: the terms left out
+// cancel identically, and the joint-space bias b of the rotor is zero (no update of u).
+// In: parent velocity vp, rotor rate qdr, Rp = [X0^T h (6)].  Out: tp.
 template <class T>
-__device__ __forceinline__ void rotor_terms(cptr<T> Cr, const T (&vp)[6], T qdr, T &b, T (&tp)[6])
+__device__ __forceinline__ void rotor_terms(cptr<T> Rp, const T (&vp)[6], T qdr, T (&tp)[6])
 {
-    cptr<T> Ir = Cr + 12;
-    const T A0 = Ir[sidx(0, 0)], A1 = Ir[sidx(1, 1)], Bz = Ir[sidx(2, 2)], k04 = Ir[sidx(0, 4)], k13 = Ir[sidx(1, 3)];
-    const T m3 = Ir[sidx(3, 3)], m4 = Ir[sidx(4, 4)], m5 = Ir[sidx(5, 5)];
-    T E0[9], vr[6];
+    T f[6], t[6];
 #pragma unroll
-    for (int j = 0; j < 9; j++) E0[j] = Cr[j];
-    xmotion(E0, Cr + 9, vp, vr);
-    vr[2] += qdr;
-    // I v
-    const T Iv[6] = {A0 * vr[0] + k04 * vr[4], A1 * vr[1] + k13 * vr[3], Bz * vr[2],
-                     m3 * vr[3] + k13 * vr[1], m4 * vr[4] + k04 * vr[0], m5 * vr[5]};
-    T pA[6];
-    crf(vr, Iv, pA);
-    b = pA[2];
-    // c = v x (z qdr) = (v1, -v0, 0, v4, -v3, 0) qdr ;  t = pA + I c
-    const T c0 = vr[1] * qdr, c1 = -vr[0] * qdr, c3 = vr[4] * qdr, c4 = -vr[3] * qdr;
-    T t[6] = {pA[0] + A0 * c0 + k04 * c4, pA[1] + A1 * c1 + k13 * c3, pA[2],
-              pA[3] + m3 * c3 + k13 * c1, pA[4] + m4 * c4 + k04 * c0, pA[5]};
-    xforce_inv(E0, Cr + 9, t, tp);
+    for (int j = 0; j < 6; j++) f[j] = Rp[j];
+    crf(vp, f, t);
+#pragma unroll
+    for (int j = 0; j < 6; j++) tp[j] = qdr * t[j];
+}
+// a rotor on a body of a generic cluster (ChainLink::rquad): that body's bias force does not carry vp x* (X0^T I X0) vp
+template <class T>
+__device__ __forceinline__ void rotor_quad(cptr<T> Q, const T (&vp)[6], T (&tp)[6])
+{
+    T t[6];
+    bias_force(Q, vp, t);
+#pragma unroll
+    for (int j = 0; j < 6; j++) tp[j] += t[j];
 }
 
 // E-dependent part of one link of the backward run: F = X^T h, psic = X^T t, IAc = X^T IA X.  perm >= 0: the tree rotation is the
@@ -543,16 +551,15 @@ __device__ __forceinline__ void pair_bwd_k(const ChainTables<T> &P, const ChainM
         congruence_k<T, K1>(s1, c1, E1, C1, IA1, IA);
         xforce_inv_k<T, K1>(s1, c1, E1, C1, h1, F0);
     }
-    // ---- rotors (q = 0): bias to P, joint-space terms with their G rows ----
+    // ---- rotors (closed form): bias to P (its quadratic part comes from P's own bias force, ChainLink::bofs), joint-space terms with
+    // their G rows ----
 #pragma unroll
     for (int r = 0; r < 2; r++) {
         cptr<T> Cr = P.consts + pr.cofs[2 + r];
         cptr<T> Rp = P.consts + pr.rpre[r];
         const T ga = Cr[kBodyConstFixed], gb = Cr[kBodyConstFixed + 1];
-        T bj, tp[6];
-        rotor_terms(Cr, vp, ga * yd1 + gb * yd2, bj, tp);
-        u[0] -= ga * bj;
-        u[1] -= gb * bj;
+        T tp[6];
+        rotor_terms(Rp, vp, ga * yd1 + gb * yd2, tp);  // (joint-space bias of the rotor: zero, see rotor_terms)
         D00 += Rp[6] * ga * ga;
         D01 += Rp[6] * ga * gb;
         D11 += Rp[6] * gb * gb;
@@ -850,7 +857,7 @@ __device__ __forceinline__ void diff_bwd(const ChainTables<T> &P, const ChainMem
     {   // ---- link2 ----
         cptr<T> Ib = P.consts + d.iofs;
         T IA2[21], p2[6], h2[6];
-        bias_force(C2 + 12, v2, p2);
+        bias_force(P.consts + d.bofs, v2, p2);  // (with the closed-form rotors on link2: rotor_terms)
         if (d.lds_acc != -1) {
             T acc[27];
             M.acc_ld(d.lds_acc, acc);
@@ -922,15 +929,14 @@ __device__ __forceinline__ void diff_bwd(const ChainTables<T> &P, const ChainMem
             F1[j] += Fc[j] * X01;
         }
     }
-    // ---- rotors (q = 0); their G rows are (1, 0), (0, 1) in a differential, the gear / belt products in an explicit pair ----
+    // ---- rotors (closed form, rotor_terms); their G rows are (1, 0), (0, 1) in a differential, the gear / belt products in an explicit pair ----
 #pragma unroll
     for (int r = 0; r < 2; r++) {
-        T bj, tp[6];
+        T tp[6];
         cptr<T> Rp = P.consts + d.rpre[r];
         const T ga = P.consts[d.gofs + 2 * r], gb = P.consts[d.gofs + 2 * r + 1];
-        rotor_terms(P.consts + d.cofs[2 + r], vp, ga * yd0 + gb * yd1, bj, tp);
-        u0 -= ga * bj;
-        u1 -= gb * bj;
+        rotor_terms(Rp, vp, ga * yd0 + gb * yd1, tp);
+        if (d.rquad[r] >= 0) rotor_quad(P.consts + d.rquad[r], vp, tp);
         D00 += Rp[6] * ga * ga;
         D01 += Rp[6] * ga * gb;
         D11 += Rp[6] * gb * gb;
@@ -1088,7 +1094,7 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
             M.lds_ld(l.lds_sv, blk);
         }
         cptr<T> C = P.consts + l.cofs;
-        cptr<T> Ic = C + 12;
+        cptr<T> Ic = P.consts + l.bofs;  // bias inertia: the link's own plus X0^T I X0 of the closed-form rotors on it (rotor_terms)
         cptr<T> Ib = P.consts + l.iofs;
         const T g0 = C[kBodyConstFixed];
         const T qdi = g0 * yd;
@@ -1173,9 +1179,9 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<
 #pragma unroll
                 for (int j = 0; j < 6; j++) vp[j] = 0;
             }
-            T bjr, tp[6];
-            rotor_terms(Cr, vp, gr * yd, bjr, tp);
-            u -= gr * bjr;
+            T tp[6];
+            rotor_terms(Rp, vp, gr * yd, tp);  // (no joint-space bias: b = 0)
+            if (ROT == 0 && l.rquad >= 0) rotor_quad(P.consts + l.rquad, vp, tp);
             D += Rp[6] * gr * gr;
 #pragma unroll
             for (int r = 0; r < 6; r++) F[r] += Rp[r] * gr;
@@ -1422,7 +1428,7 @@ __device__ __forceinline__ void free_acc_core(const ChainTables<T> &P, const Cha
 template <class T, bool OSIM>
 __device__ __forceinline__ void free_bwd(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f, bool fuse_acc = false)
 {
-    cptr<T> Ic = P.consts + f.cofs + 12;
+    cptr<T> Ic = P.consts + f.bofs;  // bias inertia (ChainLink::bofs)
     cptr<T> Ib = P.consts + f.iofs;
     T v[6], psi[6], IA[21];
 #pragma unroll

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
 
 #include "../../include/grbda_hip.h"
 #include "../../include/grbda_model_desc.h"
@@ -387,6 +388,9 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
     // inertias) then X(q)^T I X(q), X(q)^T I s and X(q)^T (v x* I v) are independent of q: the body is
     // evaluated at q = 0, and its inertia contribution to the parent is the constant X0^T I X0.
     for (int b = 0; b < nb; b++) bodies[b].xofs = -1;
+    // X0^T I X0 of every axisymmetric leaf that is folded into its parent's constants (empty: not folded), kept per body: the chain
+    // programs build the parents' BIAS inertias from them (bias_inertia below)
+    std::vector<std::vector<double>> leaf_fold(nb);
     {
         std::vector<std::vector<double>> extra(nb);
         auto at = [](const double *M, int i, int j) { return M[i * 6 + j]; };
@@ -432,6 +436,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
             if (bd.parent < 0) continue;  // a rotor on the ground: nobody to hand X0^T I X0 to
             std::vector<double> &ex = extra[bd.parent];
             if (ex.empty()) ex.assign(21, 0.0);
+            leaf_fold[b].assign(21, 0.0);
             int idx = 0;
             for (int i = 0; i < 6; i++)
                 for (int j = i; j < 6; j++, idx++) {
@@ -439,6 +444,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     for (int k2 = 0; k2 < 6; k2++)
                         for (int l2 = 0; l2 < 6; l2++) sacc += X[k2 * 6 + i] * at(bd.inertia, k2, l2) * X[l2 * 6 + j];
                     ex[idx] += sacc;
+                    leaf_fold[b][idx] = sacc;
                 }
         }
         for (int b = 0; b < nb; b++)
@@ -1002,6 +1008,41 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
         P.consts.push_back(h[2]);
         return rotor_pre[b];
     };
+    // The axisymmetric rotors of a chain program are evaluated in closed form (chain_kernels.hip, rotor_terms): the part of a rotor's
+    // bias that is quadratic in the velocity vp of the body it hangs off, vp x* (X0^T I X0) vp, is produced by THAT body's own bias
+    // force, v x* (I_bias v) with I_bias = I_body + sum over exactly those rotors of X0^T I X0.  BodyRec::xofs holds that sum over ALL
+    // axisymmetric leaf children, the ones other routes evaluate with their full bias included (leaves of generic clusters), so it
+    // serves only when the two sets are the same; otherwise the constant is emitted here (once per body and set of rotors).
+    std::vector<int> n_folded(nb, 0);
+    for (int b = 0; b < nb; b++)
+        if (!leaf_fold[b].empty()) n_folded[bodies[b].parent]++;
+    std::map<std::vector<int>, int> bias_memo;
+    auto bias_inertia = [&](int b, std::vector<int> rotors) {
+        if (rotors.empty()) return bodies[b].cofs + 12;
+        std::sort(rotors.begin(), rotors.end());
+        if (static_cast<int>(rotors.size()) == n_folded[b]) return bodies[b].xofs;
+        std::vector<int> key = rotors;
+        key.push_back(b);
+        auto it = bias_memo.find(key);
+        if (it != bias_memo.end()) return it->second;
+        const int at = static_cast<int>(P.consts.size());
+        for (int j = 0; j < 21; j++) {
+            double sacc = P.consts[bodies[b].cofs + 12 + j];
+            for (int r : rotors) sacc += leaf_fold[r][j];
+            P.consts.push_back(sacc);
+        }
+        bias_memo[key] = at;
+        return at;
+    };
+    // ... and where the body the rotor hangs off cannot take the term (a body of a generic cluster), the rotor's record points at its own
+    // X0^T I X0 and the term is evaluated with the rotor (ChainLink::rquad, ChainDiff::rquad)
+    std::vector<int> rotor_quad(nb, -1);
+    auto rotor_quadratic = [&](int r) {
+        if (rotor_quad[r] >= 0) return rotor_quad[r];
+        rotor_quad[r] = static_cast<int>(P.consts.size());
+        P.consts.insert(P.consts.end(), leaf_fold[r].begin(), leaf_fold[r].end());
+        return rotor_quad[r];
+    };
     // ---- two-rotor differential clusters (plan.h, ChainDiff): shape test and constraint program -----------------------
     // ints   [n_args, n_atoms, tofs_d, 0] [per argument: W offset of its sin, cos, id atom or -1]
     //        per row: [n1, n2, n3] then the atoms' W offsets of the 1-, 2- and 3-factor terms
@@ -1220,6 +1261,16 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     tip[k] = diff_shape[k].l2;
                 }
         }
+        // closed-form rotors of this program, by the body they hang off (rotor_terms): class 2 links, pairs and differentials; the
+        // ones on a body of a generic cluster carry their quadratic term themselves (on_gen)
+        std::vector<std::vector<int>> closed_rotors(nb);
+        auto on_gen = [&](int c) { return clusters[c].parent_body >= 0 && cls[m.bodies[clusters[c].parent_body].cluster] == 7; };
+        for (int c = 0; c < nc && ok; c++) {
+            if (on_gen(c) || clusters[c].parent_body < 0) continue;  // (on the ground: vp = 0, the term vanishes)
+            if (cls[c] == 2) closed_rotors[bodies[clusters[c].rotor_body].parent].push_back(clusters[c].rotor_body);
+            else if (cls[c] == 3) for (int r : pair_rotors[c]) closed_rotors[bodies[r].parent].push_back(r);
+            else if (is_diff(c)) for (int r : diff_shape[c].r) closed_rotors[bodies[r].parent].push_back(r);
+        }
         if (ok) {
             // per-cluster master records
             std::vector<ChainLink> link_of(nc);
@@ -1243,6 +1294,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     f = ChainFree();
                     const BodyRec &br = bodies[cr.first_body];
                     f.q_index = cr.q_index; f.v_index = cr.v_index; f.cofs = br.cofs; f.iofs = br.xofs >= 0 ? br.xofs : br.cofs + 12;
+                    f.bofs = bias_inertia(cr.first_body, closed_rotors[cr.first_body]);
                     f.lds_v = f.lds_acc = f.lds_va = f.lds_acc2 = f.lds_acc3 = f.lds_acc4 = -1;
                     f.glb_y0 = k_lds ? -1 : glb(33);  // [y0 6] (+ OSIM pass: Cholesky factor of the base's articulated inertia, L 21 + 1/diag 6)
                 } else if (cls[c] == 1 || cls[c] == 2 || cls[c] == 4) {
@@ -1253,6 +1305,8 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     l.rofs = cls[c] == 2 ? bodies[cr.rotor_body].cofs : (cls[c] == 4 ? bodies[gen_rotor[c]].cofs : -1);
                     l.rpre = cls[c] == 2 ? rotor_constants(cr.rotor_body) : -1;  // rofs >= 0 with rpre < 0: a general rotor
                     l.iofs = br.xofs >= 0 ? br.xofs : br.cofs + 12;
+                    l.bofs = bias_inertia(tip[c], closed_rotors[tip[c]]);
+                    l.rquad = cls[c] == 2 && on_gen(c) ? rotor_quadratic(cr.rotor_body) : -1;
                     l.has_child = br.has_child;
                     l.lds_sv = l.lds_pv = l.lds_va = -1;
                     l.glb_k = k_lds ? -1 : glb(10);  // [K 6][y0][sin][cos] (+ OSIM pass: 1 / D)
@@ -1278,6 +1332,9 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     d.rpre[0] = rotor_constants(ds.r[0]);
                     d.rpre[1] = rotor_constants(ds.r[1]);
                     d.iofs = bodies[ds.l2].xofs >= 0 ? bodies[ds.l2].xofs : bodies[ds.l2].cofs + 12;
+                    d.bofs = bias_inertia(ds.l2, closed_rotors[ds.l2]);
+                    d.rquad[0] = on_gen(c) ? rotor_quadratic(ds.r[0]) : -1;
+                    d.rquad[1] = on_gen(c) ? rotor_quadratic(ds.r[1]) : -1;
                     d.lds_pv = d.lds_sv = d.lds_acc = d.lds_acc_out = d.lds_pva = d.lds_va = d.lds_w = -1;
                     d.tofs_i = ds.tofs_i;
                     d.tofs_d = ds.tofs_i >= 0 ? P.cints[ds.tofs_i + 2] : 0;
@@ -2038,7 +2095,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     bool all_axi = true, none = true;
                     for (int c : r.cl) {
                         CP.links.push_back(link_of[c]);
-                        all_axi = all_axi && link_of[c].rofs >= 0 && link_of[c].rpre >= 0;
+                        all_axi = all_axi && link_of[c].rofs >= 0 && link_of[c].rpre >= 0 && link_of[c].rquad < 0;
                         none = none && link_of[c].rofs < 0;
                     }
                     sg.rot_kind = all_axi ? 1 : (none ? 2 : 0);

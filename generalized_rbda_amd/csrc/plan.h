@@ -197,7 +197,12 @@ struct ChainLink {
     int32_t perm;       // 0, 1, 2: the tree rotation Et is the cyclic axis permutation (Et x)_i = x_((i + perm) % 3), the kernels use
                         // the permutation-structured transforms (devmath.h, rzp_*); -1: general rotation
     int32_t rperm;      // the same for the tree rotation of a general rotor (rofs >= 0, rpre < 0)
-    int32_t reserved[3];
+    int32_t bofs;       // the 21 constants of the BIAS inertia, pA = v x* (I_bias v): I_link + sum of X0^T I X0 over exactly the
+                        // axisymmetric rotors on this body that the chain program evaluates in closed form (chain_kernels.hip, rotor_terms);
+                        // equals iofs when those are all its axisymmetric leaf children, cofs + 12 when there are none
+    int32_t rquad;      // -1; else the rotor's own X0^T I X0 (21): the body it hangs off belongs to a generic cluster, whose bias force
+                        // does not carry the rotor's quadratic term, and the run adds vp x* (X0^T I X0) vp itself
+    int32_t reserved[1];
 };
 
 // a RevolutePairWithRotor-shaped leaf cluster (32 ints)
@@ -235,7 +240,9 @@ struct ChainDiff {
                              // cluster of the same shape -- RevolutePairWithRotor with child clusters on link2 or in a place the
                              // leaf-pair head of a run does not cover: the link angles are the coordinates (X = 1, g = 0)
     int32_t gofs;            // consts[]: G rows of the two rotors, (1, 0, 0, 1) for a differential
-    int32_t reserved[7];
+    int32_t bofs;            // link2: bias inertia (ChainLink::bofs)
+    int32_t rquad[2];        // rotor1, rotor2: ChainLink::rquad
+    int32_t reserved[4];
 };
 // ---------------------------------------------------------------------------------------------------------------
 // Generic cluster inside a chain program (chain_kernels.hip, gen_segments.h): k <= 8 revolute bodies in any in-cluster tree,
@@ -324,7 +331,8 @@ struct ChainFree {      // 16 ints
     int32_t lds_va;     // acceleration sweep: own [v 6][a 6], -1 when no children
     int32_t lds_acc2;   // latency-mode programs: the accumulator the SECOND wavefront's limbs add into (-1: none)
     int32_t lds_acc3, lds_acc4;  // ... the third's and the fourth's (ChainProgram::n_waves = 4)
-    int32_t reserved[5];
+    int32_t bofs;       // bias inertia (ChainLink::bofs)
+    int32_t reserved[4];
 };
 
 // ---- inverse dynamics on the same chains (chain_kernels.hip, rnea_chain_kernel) ------------------------------------
