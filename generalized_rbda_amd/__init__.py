@@ -36,6 +36,7 @@ C_ABI_SYMBOLS = [
     "grbda_body_twists_f64", "grbda_body_twists_f32", "grbda_body_twists_host_f64",
     "grbda_state_input_dims", "grbda_state_to_independent_f64", "grbda_state_to_independent_f32",
     "grbda_state_to_independent_host_f64", "grbda_spd_bad_pivots", "grbda_kernel_name", "grbda_project_positions_host_f64",
+    "grbda_rnea_derivatives_f64", "grbda_rnea_derivatives_f32", "grbda_rnea_derivatives_host_f64",
 ]
 
 
@@ -123,6 +124,11 @@ def lib() -> ctypes.CDLL:
     for sfx in ("f64", "f32"):
         getattr(L, "grbda_fd_derivatives_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                               c_void_p, c_size_t, c_int, c_void_p]
+    for sfx in ("f64", "f32"):
+        getattr(L, "grbda_rnea_derivatives_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
+                                                                c_void_p, c_size_t, c_int, c_void_p]
+    L.grbda_rnea_derivatives_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
+                                                  c_size_t, c_int]
     for sfx in ("f64", "f32"):
         getattr(L, "grbda_project_positions_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int,
                                                                  c_double, c_int, c_void_p]
@@ -495,6 +501,31 @@ class Plan:
         fn = getattr(lib(), f"grbda_fd_derivatives_{'f32' if q.dtype == torch.float32 else 'f64'}")
         ptr = lambda k: out[k].data_ptr() if k in out else None
         _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), ptr("dq"), ptr("dqd"), ptr("dtau"), B,
+                  q.device.index or 0, c_void_p(s.cuda_stream)))
+        return out
+
+    def id_derivatives(self, q, qd, ydd, want=("dq", "dqd", "dydd"), step: float = 1e-6, stream=None):
+        """d tau / d q, d tau / d qd, d tau / d ydd (= H) of the inverse dynamics at (q, qd, ydd) (grbda_rnea_derivatives_*): a dict
+        of [B, nv, nv] tensors for the names in `want`, out[b, i, j] = d tau_i / d x_j, the columns of "dq" along the tangent step of
+        fd_dq.  Explicit models with nv <= 64: the analytic recursion alone, no forward dynamics and no solve (`step` unused); the
+        others: difference batches over the inverse dynamics, "dq" with `step`."""
+        import torch
+
+        self._floating(q, qd, ydd)
+        B = q.shape[0]
+        if q.shape != (B, self.nq) or qd.shape != (B, self.nv) or ydd.shape != (B, self.nv):
+            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}]")
+        names = [k for k in ("dq", "dqd", "dydd") if k in want]
+        if not names or any(k not in ("dq", "dqd", "dydd") for k in want):
+            raise ValueError('want must name at least one of "dq", "dqd", "dydd" and nothing else')
+        q, qd, ydd = q.contiguous(), qd.contiguous(), ydd.contiguous()
+        out = {k: torch.empty((B, self.nv, self.nv), dtype=q.dtype, device=q.device) for k in names}
+        if B == 0:
+            return out
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        fn = getattr(lib(), f"grbda_rnea_derivatives_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), ydd.data_ptr(), step, ptr("dq"), ptr("dqd"), ptr("dydd"), B,
                   q.device.index or 0, c_void_p(s.cuda_stream)))
         return out
 

@@ -1401,7 +1401,10 @@ int inv_osim(const grbda_plan *p, const T *q, int n_contacts, const int *bodies,
 }
 
 // ---- derived quantities: expanded batches over the two kernels (include/grbda_hip.h) ---------------------
-enum DerivedMode { DM_BIAS = 0, DM_MASS = 1, DM_DTAU = 2, DM_DQD = 3, DM_DQ = 4 };
+// (DM_ID_DQD, DM_ID_DQ: the same difference batches as DM_DQD, DM_DQ over the INVERSE dynamics, `tau` holding ydd -- grbda_rnea_derivatives_*)
+enum DerivedMode { DM_BIAS = 0, DM_MASS = 1, DM_DTAU = 2, DM_DQD = 3, DM_DQ = 4, DM_ID_DQD = 5, DM_ID_DQ = 6 };
+__host__ __device__ inline bool dm_steps_q(int mode) { return mode == DM_DQ || mode == DM_ID_DQ; }
+__host__ __device__ inline bool dm_steps_qd(int mode) { return mode == DM_DQD || mode == DM_ID_DQD; }
 
 // row (b, j) of the expanded batch: state b with the j-th unit vector (or none) applied
 // position col of state q0 after the tangent step `d` along velocity coordinate k (testHelpers.hpp:50-112)
@@ -1448,19 +1451,19 @@ __global__ void expand_kernel(int mode, const T *__restrict__ q, const T *__rest
         const size_t b = row / R;
         const int j = (int)(row % R);
         if (col < nq) {
-            qx[row * nq + col] = mode == DM_DQ ? perturbed_position(q + b * nq, col, dq_map, j >> 1, (j & 1) ? -step : step)
+            qx[row * nq + col] = dm_steps_q(mode) ? perturbed_position(q + b * nq, col, dq_map, j >> 1, (j & 1) ? -step : step)
                                                : q[b * nq + col];
         } else if (col < nq + nv) {
             const int k = col - nq;
             T v = 0;
-            if (mode == DM_BIAS || mode == DM_DQ) v = qd[b * nv + k];
-            else if (mode == DM_DQD) v = qd[b * nv + k] + ((j >> 1) == k ? ((j & 1) ? T(-1) : T(1)) : T(0));
+            if (mode == DM_BIAS || dm_steps_q(mode)) v = qd[b * nv + k];
+            else if (dm_steps_qd(mode)) v = qd[b * nv + k] + ((j >> 1) == k ? ((j & 1) ? T(-1) : T(1)) : T(0));
             qdx[row * nv + k] = v;
         } else {
             const int k = col - nq - nv;
             T v = 0;
             if (mode == DM_MASS || mode == DM_DTAU) v = (j == k) ? T(1) : T(0);
-            else if (mode == DM_DQD || mode == DM_DQ) v = tau[b * nv + k];
+            else if (dm_steps_qd(mode) || dm_steps_q(mode)) v = tau[b * nv + k];
             xx[row * nv + k] = v;
         }
     }
@@ -1483,8 +1486,8 @@ __global__ void combine_kernel(int mode, const T *__restrict__ r, int nv, int R,
         const int i = (int)((t / nv) % nv), j = (int)(t % nv);
         const T *rb = r + b * (size_t)R * nv;
         T v;
-        if (mode == DM_DQD || mode == DM_DQ)
-            v = (rb[(size_t)(2 * j) * nv + i] - rb[(size_t)(2 * j + 1) * nv + i]) / (T(2) * (mode == DM_DQ ? step : T(1)));
+        if (dm_steps_qd(mode) || dm_steps_q(mode))
+            v = (rb[(size_t)(2 * j) * nv + i] - rb[(size_t)(2 * j + 1) * nv + i]) / (T(2) * (dm_steps_q(mode) ? step : T(1)));
         else v = rb[(size_t)j * nv + i] - rb[(size_t)nv * nv + i];
         out[t] = v;
     }
@@ -1497,10 +1500,11 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
     if (!q || !out) return set_err(GRBDA_EINVAL, "null argument");
-    if ((mode == DM_BIAS || mode == DM_DQD || mode == DM_DQ) && !qd) return set_err(GRBDA_EINVAL, "null argument");
-    if ((mode == DM_DQD || mode == DM_DQ) && !tau) return set_err(GRBDA_EINVAL, "null argument");
+    const bool differences = dm_steps_qd(mode) || dm_steps_q(mode);
+    if ((mode == DM_BIAS || differences) && !qd) return set_err(GRBDA_EINVAL, "null argument");
+    if (differences && !tau) return set_err(GRBDA_EINVAL, "null argument");
     bool reproject = false;
-    if (mode == DM_DQ) {
+    if (dm_steps_q(mode)) {
         if (!(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
         for (const ClusterRec &c : p->host.lay64.clusters) reproject |= c.kind == CK_LOOP;
     }
@@ -1546,7 +1550,7 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
                            static_cast<int>(grid), hs, false, 1);
         return e == hipSuccess ? GRBDA_OK : hip_err(e, "crba launch");
     }
-    const int R = mode == DM_BIAS ? 1 : ((mode == DM_DQD || mode == DM_DQ) ? 2 * nv : nv + 1);
+    const int R = mode == DM_BIAS ? 1 : (differences ? 2 * nv : nv + 1);
     const size_t row_scalars = static_cast<size_t>(nq) + 3 * static_cast<size_t>(nv);  // q, qd, x, result
     const Chunk c = fixed_chunk(256u << 20, row_scalars * sizeof(T) * static_cast<size_t>(R), B);
     const size_t rows = c.chunk * static_cast<size_t>(R);
@@ -1556,7 +1560,7 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
     T *qx = w.take(rows * nq), *qdx = w.take(rows * nv), *xx = w.take(rows * nv), *res = w.take(rows * nv);
     assert(w.taken == w.cap);
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    const bool via_rnea = mode == DM_BIAS || mode == DM_MASS;
+    const bool via_rnea = mode == DM_BIAS || mode == DM_MASS || mode == DM_ID_DQD || mode == DM_ID_DQ;
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         const size_t nrows = nb * static_cast<size_t>(R);
         hipLaunchKernelGGL((expand_kernel<T>), dim3(blocks_for(nrows * static_cast<size_t>(nq + 2 * nv))), dim3(256), 0, hs, mode, q + b0 * nq,
@@ -1999,6 +2003,108 @@ int manifold_mass(const grbda_plan *p, const T *q, T *H, size_t B, int device, v
 }
 
 // the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
+// ---- first-order derivatives of the INVERSE dynamics (grbda_rnea_derivatives_*, include/grbda_hip.h) ------------------------------------
+// [a, a + n) and [b, b + m) share a byte
+bool ranges_overlap(const void *a, size_t n, const void *b, size_t m)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && n && m && x < y + m && y < x + n;
+}
+// d tau / d q and d tau / d qd at (q, qd, ydd).  Plans the analytic recursion covers: rnea_deriv_kernel on the caller's ydd (no forward
+// dynamics, no solve) writes its run layout STRAIGHT INTO dq / dqd -- whole groups of kDerivGroup states interleaved where
+// unpack_runs_interleave allows, the tail of the batch state-major, as the CRBA path of derived() lays out H -- and unpack_runs_kernel turns
+// every block into row-major in place: the scratch slab, no work slab, the same launches for the same B (capturable).  Every other plan:
+// the difference batches of derived() over the inverse dynamics.
+template <class T>
+int id_derivs(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double step, T *dq, T *dqd, size_t B, int device, void *stream)
+{
+    if (!analytic_covers<T>(p)) {
+        if (dqd)
+            if (int rc = derived<T>(p, DM_ID_DQD, q, qd, ydd, nullptr, dqd, B, device, stream)) return rc;
+        if (!dq) return GRBDA_OK;
+        if constexpr (sizeof(T) == 8) {
+            return derived<T>(p, DM_ID_DQ, q, qd, ydd, nullptr, dq, B, device, stream, step);
+        } else {
+            // (a central difference has no usable step in fp32 -- grbda_fd_dq_f32: taken in fp64 on the converted inputs)
+            if (!(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+            const size_t nq = p->host.nq, nv = p->host.nv;
+            const CvtArray arrays[] = {{q, nullptr, nq}, {qd, nullptr, nv}, {ydd, nullptr, nv}, {nullptr, dq, nv * nv}};
+            return through_f64(p, 64u << 20, arrays, B, device, stream, [&](double *const *a, size_t nb) {
+                return derived<double>(p, DM_ID_DQ, a[0], a[1], a[2], nullptr, a[3], nb, device, stream, step);
+            });
+        }
+    }
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    if (!t->deriv_related) return set_err(GRBDA_EUNSUPPORTED, "the plan has no related-coordinate masks on the device");
+    const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
+    const int nvi = static_cast<int>(nv);
+    const int il = unpack_runs_interleave(nvi, sizeof(T));
+    const size_t Bg = il > 1 ? B / il * il : 0;
+    // (interleaved results: one wavefront per SIMD; state-major: three per CU -- analytic_derivs)
+    const size_t waves_il = p->opt.deriv_waves ? static_cast<size_t>(p->opt.deriv_waves) : 4, waves_sm = p->opt.deriv_waves ? waves_il : 3;
+    void *scratch = nullptr;
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(tile_grid(t->n_cu, std::max(waves_il, waves_sm), B), p->host.deriv.n_rows, sizeof(T)), &scratch))
+        return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
+    T *o0 = dq ? dq : dqd, *o1 = dq ? dqd : nullptr;  // (the unpack's first matrix is never null)
+    for (int part = 0; part < 2; part++) {
+        const size_t b0 = part == 0 ? 0 : Bg, nbp = part == 0 ? Bg : B - Bg;
+        if (nbp == 0) continue;
+        const int ilp = part == 0 ? il : 1;
+        const size_t g = tile_grid(t->n_cu, ilp > 1 ? waves_il : waves_sm, nbp);
+        hipError_t e = launch_rnea_deriv<T>(d, t->deriv_bodies, p->host.n_clusters, p->host.deriv.n_rows, p->host.deriv.n_max, q + b0 * nq, qd + b0 * nv,
+                                            ydd + b0 * nv, dq ? dq + b0 * nn : nullptr, dqd ? dqd + b0 * nn : nullptr, nullptr, nbp, static_cast<T *>(scratch),
+                                            static_cast<int>(g), hs, ilp);
+        if (e != hipSuccess) return hip_err(e, "rnea derivative launch");
+        // (a persistent grid: as many workgroups of 256 threads as a CU holds, eight at the most)
+        const size_t units = nbp / ilp;
+        size_t g2 = static_cast<size_t>(t->n_cu) * std::min<size_t>(8, lds_workgroups_per_cu(unpack_runs_lds_bytes(nvi, sizeof(T), ilp) + 512));
+        if (g2 > units) g2 = units;
+        e = launch_unpack_runs<T>(o0 + b0 * nn, o1 ? o1 + b0 * nn : nullptr, t->deriv_related, nvi, nbp, static_cast<int>(g2), hs, ilp);
+        if (e != hipSuccess) return hip_err(e, "run unpack launch");
+    }
+    return GRBDA_OK;
+}
+template <class T>
+int mass_matrix(const grbda_plan *p, const T *q, T *H, size_t B, int device, void *stream)
+{
+    if (const int rc = manifold_mass<T>(p, q, H, B, device, stream); rc != 1) return rc;
+    return derived<T>(p, DM_MASS, q, nullptr, nullptr, nullptr, H, B, device, stream);
+}
+// the argument rules of grbda_rnea_derivatives_* (device and host arrays alike)
+template <class T>
+int rnea_derivatives_args(const grbda_plan *p, const T *q, const T *qd, const T *ydd, const T *dq, const T *dqd, const T *dydd, size_t B)
+{
+    if (!q || !qd || !ydd) return set_err(GRBDA_EINVAL, "null argument");
+    if (!dq && !dqd && !dydd) return set_err(GRBDA_EINVAL, "no output asked for");
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    const void *in[3] = {q, qd, ydd}, *out[3] = {dq, dqd, dydd};
+    const size_t in_bytes[3] = {B * nq * sizeof(T), B * nv * sizeof(T), B * nv * sizeof(T)}, out_bytes = B * nv * nv * sizeof(T);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++)
+            if (ranges_overlap(out[i], out_bytes, in[j], in_bytes[j])) return set_err(GRBDA_EINVAL, "an output array overlaps an input array");
+        for (int j = i + 1; j < 3; j++)
+            if (ranges_overlap(out[i], out_bytes, out[j], out_bytes)) return set_err(GRBDA_EINVAL, "two output arrays overlap");
+    }
+    return GRBDA_OK;
+}
+template <class T>
+int rnea_derivatives(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double step, T *dq, T *dqd, T *dydd, size_t B, int device,
+                     void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = rnea_derivatives_args<T>(p, q, qd, ydd, dq, dqd, dydd, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    // d tau / d ydd = H(q): the mass-matrix entry point, whatever else is asked for (the same bits in every subset of the outputs)
+    if (dydd)
+        if (int rc = mass_matrix<T>(p, q, dydd, B, device, stream)) return rc;
+    if (!dq && !dqd) return GRBDA_OK;
+    return id_derivs<T>(p, q, qd, ydd, step, dq, dqd, B, device, stream);
+}
+
 template <class T>
 static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B)
 {
@@ -2584,6 +2690,16 @@ int grbda_fd_derivatives_f32(const grbda_plan *p, const float *q, const float *q
     if (dq) if (const int r2 = grbda_fd_dq_f32(p, q, qd, tau, 1e-6, dq, B, device, stream)) return r2;
     return GRBDA_OK;
 }
+int grbda_rnea_derivatives_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double step, double *dtau_dq,
+                               double *dtau_dqd, double *dtau_dydd, size_t B, int device, void *stream)
+{
+    return rnea_derivatives<double>(p, q, qd, ydd, step, dtau_dq, dtau_dqd, dtau_dydd, B, device, stream);
+}
+int grbda_rnea_derivatives_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, double step, float *dtau_dq,
+                               float *dtau_dqd, float *dtau_dydd, size_t B, int device, void *stream)
+{
+    return rnea_derivatives<float>(p, q, qd, ydd, step, dtau_dq, dtau_dqd, dtau_dydd, B, device, stream);
+}
 int grbda_kernel_name(const grbda_plan *p, int kind, int precision, size_t B, int device, char *buf, size_t cap)
 {
     if (!p || !buf || cap == 0 || (kind != 0 && kind != 1) || (precision != 32 && precision != 64)) return set_err(GRBDA_EINVAL, "bad argument");
@@ -2765,6 +2881,22 @@ int grbda_fd_derivatives_host_f64(const grbda_plan *p, const double *q, const do
     const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bt = st.in(tau, B * nv);
     double *b1 = dq ? st.out(dq, B * nn) : nullptr, *b2 = dqd ? st.out(dqd, B * nn) : nullptr, *b3 = dtau ? st.out(dtau, B * nn) : nullptr;
     return st.run([&] { return grbda_fd_derivatives_f64(p, bq, bqd, bt, b1, b2, b3, B, device, nullptr); });
+}
+int grbda_rnea_derivatives_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double step, double *dtau_dq,
+                                    double *dtau_dqd, double *dtau_dydd, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = rnea_derivatives_args<double>(p, q, qd, ydd, dtau_dq, dtau_dqd, dtau_dydd, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
+    DeviceTables *t = nullptr;
+    if (int rc0 = ensure_device(p, device, &t)) return rc0;  // `device` current before anything is allocated on it
+    HostStage st;
+    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *by = st.in(ydd, B * nv);
+    double *b1 = dtau_dq ? st.out(dtau_dq, B * nn) : nullptr, *b2 = dtau_dqd ? st.out(dtau_dqd, B * nn) : nullptr,
+           *b3 = dtau_dydd ? st.out(dtau_dydd, B * nn) : nullptr;
+    return st.run([&] { return grbda_rnea_derivatives_f64(p, bq, bqd, by, step, b1, b2, b3, B, device, nullptr); });
 }
 int grbda_plan_span_dims(const grbda_plan *p, int *n_span_vel)
 {

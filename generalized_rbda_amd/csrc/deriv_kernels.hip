@@ -1479,4 +1479,85 @@ size_t spd_solve_lds_bytes(int nv, size_t elem, int n_rhs)
     return static_cast<size_t>(nvb) * nvb * elem;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Run layout of rnea_deriv_kernel -> plain row-major nv x nv, IN PLACE: the last step of grbda_rnea_derivatives_*, whose recursion
+// writes d ID / d q and d ID / d qd straight into the caller's arrays.  A unit is IL states (IL = kDerivGroup: one interleaved group,
+// [entry][IL]; IL = 1: one state), IL nv^2 consecutive elements, and a permutation of what the caller gets: entry (i, j) sits in the
+// run of max(i, j) (see the kernel above).  One unit per workgroup at a time: the unit is read into LDS with consecutive lanes on
+// consecutive addresses, the workgroup meets, and the unit is written row-major the same way, state by state -- one read and one write
+// of every element, nothing else.  In LDS the states of a group lie one after the other, kUnpackStride apart: the stride puts the IL
+// lanes that share an entry at the load on different banks, and the row-major pass reads runs of consecutive words.  Entries between
+// coordinates that are not on one root path (DerivProgram::related) are WRITTEN AS ZERO: the recursion never stores them and the
+// caller's array is not cleared.  D1: a second matrix (blockIdx.y = 1) or null.  nv <= 64 (one-word masks).
+constexpr int kUnpackThreads = 256;
+// elements between two states of a group in LDS: nv^2 rounded up so that the stride is 16 banks (of 64, four bytes each) past a multiple of 64
+__host__ __device__ inline int unpack_runs_stride(int nv, int elem, int il)
+{
+    const int nn = nv * nv;
+    if (il == 1) return nn;
+    const int per = 256 / elem, want = 64 / elem;  // elements per sweep of the banks; the offset asked for
+    return nn + (want - nn % per + per) % per;
+}
+template <class T, int IL>
+__global__ __launch_bounds__(kUnpackThreads) void unpack_runs_kernel(T *__restrict__ D0, T *__restrict__ D1, const uint64_t *__restrict__ related,
+                                                                     int nv, size_t n_units)
+{
+    T *blk = reinterpret_cast<T *>(deriv_smem);  // [IL][stride]
+    __shared__ uint64_t rel_rows[kWave];
+    const int tid = threadIdx.x, nn = nv * nv, total = nn * IL, stride = unpack_runs_stride(nv, (int)sizeof(T), IL);
+    T *D = blockIdx.y == 0 ? D0 : D1;
+    if (tid < kWave) rel_rows[tid] = tid < nv ? related[tid] : 0;
+    const int r0 = tid / nv, c0 = tid % nv, step_r = kUnpackThreads / nv, step_c = kUnpackThreads % nv;
+    for (size_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        T *Dg = D + u * (size_t)total;
+        __syncthreads();  // the previous unit's reads of the block are done (first unit: the masks are in place)
+        for (int i = tid; i < total; i += kUnpackThreads) blk[(i % IL) * stride + i / IL] = Dg[i];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < IL; s++) {
+            T *Ds = Dg + (size_t)s * nn;
+            const T *bs = blk + s * stride;
+            int r = r0, c = c0;
+            for (int i = tid; i < nn; i += kUnpackThreads) {
+                const int src = c <= r ? r * r + c : c * c + c + 1 + r;
+                const bool rel = (rel_rows[r] >> c) & 1;
+                Ds[i] = rel ? bs[src] : T(0);
+                r += step_r;
+                c += step_c;
+                if (c >= nv) {
+                    c -= nv;
+                    r++;
+                }
+            }
+        }
+    }
+}
+// Interleave factor grbda_rnea_derivatives_* gives the recursion's results: whole groups of kDerivGroup states where a group's block
+// (padding included) takes at most 32 KiB of LDS -- the size of the largest state-major block (nv = 64, fp64), so that a CU always holds
+// four workgroups of the unpack, 1024 threads with a load each in flight -- else 1.  f32: nv <= 44; f64: nv <= 31.
+size_t unpack_runs_lds_bytes(int nv, size_t elem, int il);
+int unpack_runs_interleave(int nv, size_t elem)
+{
+    return unpack_runs_lds_bytes(nv, elem, kDerivGroup) <= 32u * 1024u ? kDerivGroup : 1;
+}
+size_t unpack_runs_lds_bytes(int nv, size_t elem, int il)
+{
+    return static_cast<size_t>(il) * unpack_runs_stride(nv, static_cast<int>(elem), il) * elem;
+}
+// B a multiple of il (1 or kDerivGroup); D0 not null
+template <class T>
+hipError_t launch_unpack_runs(T *D0, T *D1, const uint64_t *related, int nv, size_t B, int grid, hipStream_t stream, int il)
+{
+    if (nv < 1 || nv > kWave || !related || !D0 || (il != 1 && il != kDerivGroup) || B % il != 0 || grid < 1) return hipErrorInvalidValue;
+    const size_t lds = unpack_runs_lds_bytes(nv, sizeof(T), il);
+    if (lds > 32u * 1024u) return hipErrorInvalidValue;
+    const dim3 g(grid, D1 ? 2 : 1);
+    if (il == 1) hipLaunchKernelGGL((unpack_runs_kernel<T, 1>), g, dim3(kUnpackThreads), lds, stream, D0, D1, related, nv, B);
+    else hipLaunchKernelGGL((unpack_runs_kernel<T, kDerivGroup>), g, dim3(kUnpackThreads), lds, stream, D0, D1, related, nv, B / il);
+    return hipGetLastError();
+}
+template hipError_t launch_unpack_runs<float>(float *, float *, const uint64_t *, int, size_t, int, hipStream_t, int);
+template hipError_t launch_unpack_runs<double>(double *, double *, const uint64_t *, int, size_t, int, hipStream_t, int);
+
 }  // namespace grbda_hip

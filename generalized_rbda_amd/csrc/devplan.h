@@ -207,6 +207,12 @@ template <class TIO, class TC>
 hipError_t launch_spd_solve(const TIO *H, int h_packed, const TIO *P1, const TIO *P2, TIO *Hinv, TIO *X1, TIO *X2, const uint64_t *related,
                             int nv, size_t B, int grid, hipStream_t stream, int interleave);
 size_t spd_solve_lds_bytes(int nv, size_t elem, int n_rhs);
+// rnea_deriv_kernel's run layout (state-major, or groups of kDerivGroup states where unpack_runs_interleave says so) -> row-major nv x nv in
+// place, structural zeros written; D1 may be null; B a multiple of il (deriv_kernels.hip, unpack_runs_kernel)
+template <class T>
+hipError_t launch_unpack_runs(T *D0, T *D1, const uint64_t *related, int nv, size_t B, int grid, hipStream_t stream, int il);
+int unpack_runs_interleave(int nv, size_t elem);
+size_t unpack_runs_lds_bytes(int nv, size_t elem, int il);
 
 // analytic derivatives of models with implicit clusters through the spanning tree (manifold_kernels.hip)
 template <class T>

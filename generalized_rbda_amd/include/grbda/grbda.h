@@ -1257,6 +1257,15 @@ public:
         check(grbda_fd_derivatives_host_f64(plan(), q, qd, tau, dydd_dq, dydd_dqd, dydd_dtau, B, device));
     }
 
+    // d tau / d q, d tau / d qd, d tau / d ydd (= H) of inverseDynamics at (q, qd, ydd) for B states on HOST arrays, each [B][nv][nv]
+    // row-major, any of them (not all) may be null (grbda_rnea_derivatives_*: analytic for explicit models, `step` then unused; no
+    // external forces).  Pinocchio's computeRNEADerivatives; the reference has no counterpart.
+    void inverseDynamicsDerivativesBatch(const double *q, const double *qd, const double *ydd, double *dtau_dq, double *dtau_dqd,
+                                         double *dtau_dydd, size_t B, int device = 0, double step = 1e-6)
+    {
+        check(grbda_rnea_derivatives_host_f64(plan(), q, qd, ydd, step, dtau_dq, dtau_dqd, dtau_dydd, B, device));
+    }
+
     // batched entry points on HOST arrays (row-major q[B][nq], qd[B][nv], tau[B][nv] -> ydd[B][nv])
     void forwardDynamicsBatch(const double *q, const double *qd, const double *tau, double *ydd, size_t B, int device = 0)
     {
@@ -1294,6 +1303,15 @@ public:
         if constexpr (std::is_same<Scalar, float>::value)
             check(grbda_fd_derivatives_f32(plan(), q, qd, tau, dydd_dq, dydd_dqd, dydd_dtau, B, device, stream));
         else check(grbda_fd_derivatives_f64(plan(), q, qd, tau, dydd_dq, dydd_dqd, dydd_dtau, B, device, stream));
+    }
+    // d tau / d q, d qd, d ydd on device arrays, each [B][nv][nv] row-major, any of them (not all) may be null (grbda_rnea_derivatives_f32 / _f64)
+    void inverseDynamicsDerivativesBatch(const Scalar *q, const Scalar *qd, const Scalar *ydd, Scalar *dtau_dq, Scalar *dtau_dqd,
+                                         Scalar *dtau_dydd, size_t B, int device, void *stream, double step = 1e-6)
+    {
+        static_assert(std::is_same<Scalar, float>::value || std::is_same<Scalar, double>::value, "device batches are float or double");
+        if constexpr (std::is_same<Scalar, float>::value)
+            check(grbda_rnea_derivatives_f32(plan(), q, qd, ydd, step, dtau_dq, dtau_dqd, dtau_dydd, B, device, stream));
+        else check(grbda_rnea_derivatives_f64(plan(), q, qd, ydd, step, dtau_dq, dtau_dqd, dtau_dydd, B, device, stream));
     }
     // the immutable compiled plan, for the device-pointer C ABI (grbda_aba_f32 / _f64, grbda_rnea_*)
     const grbda_plan *plan()

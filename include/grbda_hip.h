@@ -202,6 +202,39 @@ int grbda_fd_derivatives_f64(const grbda_plan *plan, const double *q, const doub
                              double *dydd_dqd, double *dydd_dtau, size_t B, int device, void *stream);
 int grbda_fd_derivatives_f32(const grbda_plan *plan, const float *q, const float *qd, const float *tau, float *dydd_dq,
                              float *dydd_dqd, float *dydd_dtau, size_t B, int device, void *stream);
+/* ---- first-order derivatives of the INVERSE dynamics -----------------------------------------------------------------------
+ * tau = ID(q, qd, ydd) = H(q) ydd + C(q, qd).  For B states at (q, qd, ydd), each output [B][nv][nv] row-major with
+ * out[b][i][j] = d tau_i / d x_j:
+ *     dtau_dq    d ID / d q     columns along the tangent step grbda_fd_dq_* documents (testHelpers.hpp:50-112: a quaternion base takes
+ *                               pos += R^T d, quat += quat x (0, d) / 2; a roll-pitch-yaw base plain q + dq; implicit-loop models move an
+ *                               INDEPENDENT position and re-project the dependent ones onto phi(q) = 0)
+ *     dtau_dqd   d ID / d qd
+ *     dtau_dydd  d ID / d ydd = H(q), full and symmetric: asked for alone, the call IS grbda_mass_matrix_*; asked for with the
+ *                               others it is computed by that entry point too (the same bits either way)
+ * Any output may be NULL, not all three; the outputs must not overlap the inputs or each other (GRBDA_EINVAL).  These are the
+ * matrices of inverse-dynamics-based trajectory optimisation, computed-torque linearisation and identification (Pinocchio:
+ * computeRNEADerivatives); with ydd = FD(q, qd, tau) they are related to grbda_fd_derivatives_* by d ydd / d q = -H^-1 d tau / d q,
+ * d ydd / d qd = -H^-1 d tau / d qd, but nothing is inverted or factorised here, and no forward dynamics runs.
+ *
+ * Plans with grbda_plan_info.analytic_derivatives == 1 made of explicit clusters (nv <= 64): the analytic recursion of
+ * deriv_kernels.hip, ONE pass per state, writes d ID / d q and d ID / d qd projected with G into the caller's arrays and a second
+ * kernel puts them into row-major order in place (entries between coordinates that are not on one root path are structural zeros and
+ * are written as 0.0); `step` is not used and the call needs no work space beyond the per-stream scratch slab.  Every other plan
+ * (implicit clusters, nv > 64, the spanning-tree route, GRBDA_NO_ANALYTIC=1): difference batches over grbda_rnea_* -- d tau / d qd
+ * by central differences with unit step (exact: the inverse dynamics are quadratic in qd), d tau / d q by central differences with
+ * `step` (> 0; 1e-6 suits fp64) along the tangent step above, implicit clusters re-projected by Newton; the _f32 entry point takes those
+ * position differences in fp64 on the converted inputs, as grbda_fd_dq_f32 does.
+ *
+ * Device pointers; the call enqueues on `stream` and does not synchronise; it can be captured after one eager call of the same B on
+ * that stream; gravity is read at launch.  There is NO f_ext argument: world-frame external forces make d tau / d q depend on the
+ * body poses (the force on a body turns with every joint between it and the world), which the recursion does not carry.
+ * B == 0: GRBDA_OK.  The _host_ variant takes host arrays (allocates, copies and synchronises per call). */
+int grbda_rnea_derivatives_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, double step,
+                               double *dtau_dq, double *dtau_dqd, double *dtau_dydd, size_t B, int device, void *stream);
+int grbda_rnea_derivatives_f32(const grbda_plan *plan, const float *q, const float *qd, const float *ydd, double step,
+                               float *dtau_dq, float *dtau_dqd, float *dtau_dydd, size_t B, int device, void *stream);
+int grbda_rnea_derivatives_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, double step,
+                                    double *dtau_dq, double *dtau_dqd, double *dtau_dydd, size_t B, int device);
 /* States whose joint-space inertia matrix H was not positive definite to working precision in the SPD solves behind
  * grbda_fd_dtau_* / grbda_fd_dq_* / grbda_fd_dqd_* / grbda_fd_derivatives_* (a pivot of the factorisation <= 0 or not finite: massless
  * chains, a singular pose of an implicit cluster) get NaN / Inf results; the reference's ColPivHouseholderQR would return some
