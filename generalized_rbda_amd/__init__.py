@@ -37,6 +37,8 @@ C_ABI_SYMBOLS = [
     "grbda_state_input_dims", "grbda_state_to_independent_f64", "grbda_state_to_independent_f32",
     "grbda_state_to_independent_host_f64", "grbda_spd_bad_pivots", "grbda_kernel_name", "grbda_project_positions_host_f64",
     "grbda_rnea_derivatives_f64", "grbda_rnea_derivatives_f32", "grbda_rnea_derivatives_host_f64",
+    "grbda_integrate_f64", "grbda_integrate_f32", "grbda_step_f64", "grbda_step_f32", "grbda_rollout_f64", "grbda_rollout_f32",
+    "grbda_integrate_host_f64", "grbda_step_host_f64",
 ]
 
 
@@ -134,6 +136,17 @@ def lib() -> ctypes.CDLL:
                                                                  c_double, c_int, c_void_p]
         getattr(L, "grbda_spanning_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                         c_size_t, c_int, c_void_p]
+    for sfx in ("f64", "f32"):
+        getattr(L, "grbda_integrate_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
+                                                         c_int, c_double, c_size_t, c_int, c_void_p]
+        getattr(L, "grbda_step_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        getattr(L, "grbda_rollout_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+    L.grbda_integrate_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_double, c_size_t, c_int]
+    L.grbda_step_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_int]
     L.grbda_state_input_dims.argtypes = [c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]
     for sfx in ("f64", "f32"):
         getattr(L, "grbda_state_to_independent_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -406,6 +419,98 @@ class Plan:
         _check(fn(self._h, q.data_ptr(), qd.data_ptr(), ydd.data_ptr(), v.data_ptr(), a.data_ptr(), B,
                   q.device.index or 0, c_void_p(s.cuda_stream)))
         return v, a
+
+    # ---- time stepping (include/grbda_hip.h "time stepping") ---------------------------------------------
+    def _state_args(self, q, qd, x, what: str):
+        """q[B,nq], qd[B,nv], x[B,nv]: contiguous device tensors of one floating dtype on one device; returns B"""
+        self._floating(q, qd, x)
+        B = q.shape[0]
+        if q.shape != (B, self.nq) or qd.shape != (B, self.nv) or x.shape != (B, self.nv):
+            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], {what}[B,{self.nv}]")
+        return B
+
+    def integrate(self, q, qd, ydd, dt: float, out=None, max_iter: int = 50, tol: float = 1e-8, stream=None):
+        """One semi-implicit Euler step on the configuration manifold (first order): yd' = yd + dt ydd, then the positions with yd'
+        -- y + dt yd' for explicit clusters, the quaternion base by ori::integrateQuatImplicit, implicit clusters by
+        q_span + dt G yd' and the Newton projection of project_positions.  Returns (q_next, qd_next, ok[B] bool).
+        out: (q_next, qd_next) to write to; they may be q and qd themselves."""
+        import torch
+
+        B = self._state_args(q, qd, ydd, "ydd")
+        q, qd, ydd = q.contiguous(), qd.contiguous(), ydd.contiguous()
+        if out is None:
+            qn = torch.empty((B, self.nq), dtype=q.dtype, device=q.device)
+            vn = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
+        else:
+            qn, vn = out
+            for t, ref in ((qn, q), (vn, qd)):
+                if t.shape != ref.shape or t.dtype != q.dtype or t.device != q.device or not t.is_contiguous():
+                    raise ValueError("out must be contiguous (q_next[B,nq], qd_next[B,nv]) tensors of the inputs' dtype on the inputs' device")
+        ok = torch.empty((B,), dtype=torch.int32, device=q.device)
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        if stream is not None:
+            for t in (q, qd, ydd, qn, vn, ok):
+                t.record_stream(s)
+        fn = getattr(lib(), f"grbda_integrate_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), ydd.data_ptr(), float(dt), qn.data_ptr(), vn.data_ptr(), ok.data_ptr(),
+                  int(max_iter), float(tol), B, q.device.index or 0, c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return qn, vn, ok.bool()
+
+    def step(self, q, qd, tau, dt: float, f_ext=None, stream=None):
+        """forward_dynamics followed by integrate on one stream (grbda_step_*): returns (q_next, qd_next, ydd, ok[B] bool)."""
+        import torch
+
+        B = self._state_args(q, qd, tau, "tau")
+        q, qd, tau = q.contiguous(), qd.contiguous(), tau.contiguous()
+        fe = None
+        if f_ext is not None:
+            if f_ext.shape != (B, self.n_bodies, 6) or f_ext.dtype != q.dtype or not f_ext.is_cuda:
+                raise ValueError(f"f_ext must be a device tensor [B,{self.n_bodies},6] of the same dtype")
+            f_ext = f_ext.contiguous()
+            fe = f_ext.data_ptr()
+        qn = torch.empty((B, self.nq), dtype=q.dtype, device=q.device)
+        vn = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
+        ydd = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
+        ok = torch.empty((B,), dtype=torch.int32, device=q.device)
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        if stream is not None:
+            for t in (q, qd, tau, qn, vn, ydd, ok) + (() if f_ext is None else (f_ext,)):
+                t.record_stream(s)
+        fn = getattr(lib(), f"grbda_step_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), fe, float(dt), ydd.data_ptr(), qn.data_ptr(), vn.data_ptr(),
+                  ok.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return qn, vn, ydd, ok.bool()
+
+    def rollout(self, q, qd, tau, dt: float, T: int, record: bool = False, stream=None):
+        """T steps from (q, qd), which are left untouched (grbda_rollout_* on copies).  tau: [B, nv], held for all steps, or [T, B, nv].
+        Returns (q_T, qd_T, ok[B] bool -- the AND over the steps), and with record=True also (q_traj[T,B,nq], qd_traj[T,B,nv]):
+        states 1 .. T."""
+        import torch
+
+        T = int(T)
+        per_step = tau.dim() == 3
+        if per_step and tau.shape[0] != T:
+            raise ValueError(f"expected tau[B,{self.nv}] or tau[{T},B,{self.nv}]")
+        B = self._state_args(q, qd, tau[0] if per_step and T > 0 else (tau if not per_step else qd), "tau")
+        tau = tau.contiguous()
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        with torch.cuda.stream(s):
+            qT, vT = q.clone(memory_format=torch.contiguous_format), qd.clone(memory_format=torch.contiguous_format)
+            work = torch.empty_like(vT)
+            ok = torch.ones((B,), dtype=torch.int32, device=q.device)
+            qt = torch.empty((T, B, self.nq), dtype=q.dtype, device=q.device) if record else None
+            vt = torch.empty((T, B, self.nv), dtype=q.dtype, device=q.device) if record else None
+        if stream is not None:
+            for t in (q, qd, tau):
+                t.record_stream(s)
+        fn = getattr(lib(), f"grbda_rollout_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        _check(fn(self._h, qT.data_ptr(), vT.data_ptr(), tau.data_ptr(), T if per_step else 1, float(dt), T, work.data_ptr(),
+                  None if qt is None else qt.data_ptr(), None if vt is None else vt.data_ptr(), ok.data_ptr(), B,
+                  q.device.index or 0, c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return (qT, vT, ok.bool(), qt, vt) if record else (qT, vT, ok.bool())
 
     # ---- contact side ---------------------------------------------------------------------------------
     def body_poses(self, q, stream=None):

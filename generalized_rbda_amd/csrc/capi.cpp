@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -950,6 +951,152 @@ int spanning(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *qd_s
     hipError_t e = launch_spanning<T>(d, p->host.n_clusters, span_count(p), q, qd, ydd, qd_span, qdd_span, B, scratch,
                                       grid, lds, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "spanning launch");
+}
+
+// ---- time stepping (kernels.hip, integrate_kernel; include/grbda_hip.h "Time stepping") ----------------------------------------------
+bool ranges_overlap(const void *a, size_t n, const void *b, size_t m);
+
+bool has_loop_clusters(const grbda_plan *p)
+{
+    for (const ClusterRec &c : p->host.lay64.clusters)
+        if (c.kind == CK_LOOP) return true;
+    return false;
+}
+// Everything grbda_integrate_* refuses, on the host and before any device call: the argument rules (device and host arrays alike), then
+// the two kinds of plan the integrator does not cover.  Outputs may BE their inputs (q_next == q, qd_next == qd); any other overlap of an
+// output with an input or with the other output is refused.
+template <class T>
+int integrate_args(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double dt, const T *q_next, const T *qd_next, int max_iter,
+                   double tol, size_t B)
+{
+    if (!q || !qd || !ydd || !q_next || !qd_next) return set_err(GRBDA_EINVAL, "null argument");
+    if (!std::isfinite(dt)) return set_err(GRBDA_EINVAL, "dt is not finite");
+    if (max_iter < 0 || std::isnan(tol)) return set_err(GRBDA_EINVAL, "bad projection arguments");
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const void *in[3] = {q, qd, ydd}, *out[2] = {q_next, qd_next};
+    const size_t in_bytes[3] = {bq, bv, bv}, out_bytes[2] = {bq, bv};
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 3; j++)
+            if (!(i == j && out[i] == in[j]) && ranges_overlap(out[i], out_bytes[i], in[j], in_bytes[j]))
+                return set_err(GRBDA_EINVAL, "an output array overlaps an input array (only q_next == q and qd_next == qd are allowed)");
+    if (ranges_overlap(q_next, bq, qd_next, bv)) return set_err(GRBDA_EINVAL, "q_next and qd_next overlap");
+    for (const ClusterRec &c : p->host.lay64.clusters)
+        if (c.kind == CK_FREE && p->host.ori_repr != 0)
+            return set_err(GRBDA_EUNSUPPORTED, "time stepping covers the quaternion floating base only: the rate map of a roll-pitch-yaw base is not built");
+    if (p->host.projection_only && has_loop_clusters(p))
+        return set_err(GRBDA_EUNSUPPORTED, "time stepping does not cover implicit clusters of plans on the spanning-tree route (their G is evaluated by the "
+                                           "spanning-tree kernels only)");
+    return GRBDA_OK;
+}
+
+// the launch itself (arguments checked, B > 0)
+template <class T>
+int integrate_launch(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double dt, T *q_next, T *qd_next, int32_t *ok, int max_iter,
+                     double tol, size_t B, int device, void *stream, bool ok_and = false)
+{
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
+    // The slot layout of the ABA of the same precision, like the other auxiliary kernels -- but only implicit clusters use slots, so an
+    // explicit plan asks for the staging area alone, and in fp32 (two wavefronts per SIMD by registers) runs eight wavefronts per CU.
+    const bool loops = has_loop_clusters(p);
+    const size_t store = loops ? static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T) : 0;
+    const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, loops || sizeof(T) == 8 ? 4 : 8, store, d.nq, d.nv, sizeof(T),
+                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[sizeof(T) == 8 ? 1 : 0]), true);
+    const size_t n_glb = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv) + kIntegrateLocalRows;
+    void *sp = nullptr;
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid_unclamped, n_glb, sizeof(T)), &sp)) return rc;
+    d.lds_bytes = static_cast<int>(s.lds_bytes);
+    hipError_t e = launch_integrate<T>(d, p->host.n_clusters, q, qd, ydd, static_cast<T>(dt), q_next, qd_next, ok, ok_and ? 1 : 0, B, max_iter, static_cast<T>(tol),
+                                       static_cast<T *>(sp), static_cast<int>(s.grid), s.lds_bytes, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate launch");
+}
+
+template <class T>
+int integrate(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double dt, T *q_next, T *qd_next, int32_t *ok, int max_iter, double tol,
+              size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = integrate_args<T>(p, q, qd, ydd, dt, q_next, qd_next, max_iter, tol, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    return integrate_launch<T>(p, q, qd, ydd, dt, q_next, qd_next, ok, max_iter, tol, B, device, stream);
+}
+
+// what grbda_step_* passes to the projection: the reference's nearZero, and the iteration count the Python layer passes to
+// grbda_project_positions_*
+constexpr int kStepMaxIter = 50;
+constexpr double kStepTol = 1e-8;
+
+// the argument rules of grbda_step_* beyond the integrator's: ydd is written by the forward dynamics and read by the integrator
+template <class T>
+int step_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *f_ext, double dt, const T *ydd, const T *q_next, const T *qd_next,
+              size_t B)
+{
+    if (!tau || !ydd) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = integrate_args<T>(p, q, qd, ydd, dt, q_next, qd_next, kStepMaxIter, kStepTol, B)) return rc;
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const size_t bf = B * static_cast<size_t>(p->host.n_bodies) * 6 * sizeof(T);
+    if (ranges_overlap(ydd, bv, q, bq) || ranges_overlap(ydd, bv, qd, bv) || ranges_overlap(ydd, bv, tau, bv) || ranges_overlap(ydd, bv, f_ext, bf))
+        return set_err(GRBDA_EINVAL, "ydd overlaps an input array");
+    if (ranges_overlap(q_next, bq, tau, bv) || ranges_overlap(qd_next, bv, tau, bv) || ranges_overlap(q_next, bq, f_ext, bf) ||
+        ranges_overlap(qd_next, bv, f_ext, bf))
+        return set_err(GRBDA_EINVAL, "an output array overlaps tau or f_ext");
+    return GRBDA_OK;
+}
+
+// grbda_aba_* followed by grbda_integrate_* on the same stream
+template <class T>
+int step(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *f_ext, double dt, T *ydd, T *q_next, T *qd_next, int32_t *ok, size_t B,
+         int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = step_args<T>(p, q, qd, tau, f_ext, dt, ydd, q_next, qd_next, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;  // (GRBDA_ENODEVICE whatever route the forward dynamics take)
+    if (int rc = run<T>(p, false, q, qd, tau, f_ext, ydd, B, device, stream)) return rc;
+    return integrate_launch<T>(p, q, qd, ydd, dt, q_next, qd_next, ok, kStepMaxIter, kStepTol, B, device, stream);
+}
+
+// T steps in place; every state copied to the trajectory arrays device-to-device on the same stream
+template <class T>
+int rollout(const grbda_plan *p, T *q, T *qd, const T *tau, int tau_steps, double dt, int n_steps, T *ydd_work, T *q_traj, T *qd_traj, int32_t *ok,
+            size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (n_steps < 0) return set_err(GRBDA_EINVAL, "T is negative");
+    if (tau_steps != 1 && tau_steps != n_steps) return set_err(GRBDA_EINVAL, "tau_steps must be 1 or T");
+    if (int rc = step_args<T>(p, q, qd, tau, static_cast<const T *>(nullptr), dt, ydd_work, q, qd, B)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, bq = B * nq * sizeof(T), bv = B * nv * sizeof(T);
+    const size_t steps = static_cast<size_t>(n_steps);
+    // (tau[T][B][nv]: every step's block, not only the first, stays clear of what the steps write)
+    if (tau_steps > 1 && (ranges_overlap(tau, steps * bv, q, bq) || ranges_overlap(tau, steps * bv, qd, bv) || ranges_overlap(tau, steps * bv, ydd_work, bv)))
+        return set_err(GRBDA_EINVAL, "tau overlaps an array the steps write");
+    const void *state[4] = {q, qd, tau, ydd_work};
+    const size_t state_bytes[4] = {bq, bv, (tau_steps > 1 ? steps : 1) * bv, bv};
+    for (int j = 0; j < 4; j++)
+        if (ranges_overlap(q_traj, steps * bq, state[j], state_bytes[j]) || ranges_overlap(qd_traj, steps * bv, state[j], state_bytes[j]))
+            return set_err(GRBDA_EINVAL, "a trajectory array overlaps a state array");
+    if (ranges_overlap(q_traj, steps * bq, qd_traj, steps * bv)) return set_err(GRBDA_EINVAL, "the trajectory arrays overlap");
+    if (B == 0 || n_steps == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    for (int k = 0; k < n_steps; k++) {
+        const T *tk = tau + (tau_steps > 1 ? static_cast<size_t>(k) * B * nv : 0);
+        if (int rc = run<T>(p, false, q, qd, tk, static_cast<const T *>(nullptr), ydd_work, B, device, stream)) return rc;
+        // (ok: the first step writes the flags, the later ones AND theirs into them)
+        if (int rc = integrate_launch<T>(p, q, qd, ydd_work, dt, q, qd, ok, kStepMaxIter, kStepTol, B, device, stream, k > 0)) return rc;
+        hipError_t e;
+        if (q_traj && (e = hipMemcpyAsync(q_traj + static_cast<size_t>(k) * B * nq, q, bq, hipMemcpyDeviceToDevice, hs)) != hipSuccess)
+            return hip_err(e, "hipMemcpyAsync");
+        if (qd_traj && (e = hipMemcpyAsync(qd_traj + static_cast<size_t>(k) * B * nv, qd, bv, hipMemcpyDeviceToDevice, hs)) != hipSuccess)
+            return hip_err(e, "hipMemcpyAsync");
+    }
+    return GRBDA_OK;
 }
 
 // ---- state input in the reference's conventions (kernels.hip, state_kernel) ----------------------------------
@@ -2982,6 +3129,70 @@ int grbda_spanning_f32(const grbda_plan *p, const float *q, const float *qd, con
                        float *qdd_span, size_t B, int device, void *stream)
 {
     return spanning<float>(p, q, qd, ydd, qd_span, qdd_span, B, device, stream);
+}
+
+int grbda_integrate_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double dt, double *q_next, double *qd_next,
+                        int32_t *ok, int max_iter, double tol, size_t B, int device, void *stream)
+{
+    return integrate<double>(p, q, qd, ydd, dt, q_next, qd_next, ok, max_iter, tol, B, device, stream);
+}
+int grbda_integrate_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, double dt, float *q_next, float *qd_next,
+                        int32_t *ok, int max_iter, double tol, size_t B, int device, void *stream)
+{
+    return integrate<float>(p, q, qd, ydd, dt, q_next, qd_next, ok, max_iter, tol, B, device, stream);
+}
+int grbda_step_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *f_ext, double dt, double *ydd,
+                   double *q_next, double *qd_next, int32_t *ok, size_t B, int device, void *stream)
+{
+    return step<double>(p, q, qd, tau, f_ext, dt, ydd, q_next, qd_next, ok, B, device, stream);
+}
+int grbda_step_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, const float *f_ext, double dt, float *ydd,
+                   float *q_next, float *qd_next, int32_t *ok, size_t B, int device, void *stream)
+{
+    return step<float>(p, q, qd, tau, f_ext, dt, ydd, q_next, qd_next, ok, B, device, stream);
+}
+int grbda_rollout_f64(const grbda_plan *p, double *q, double *qd, const double *tau, int tau_steps, double dt, int T, double *ydd_work,
+                      double *q_traj, double *qd_traj, int32_t *ok, size_t B, int device, void *stream)
+{
+    return rollout<double>(p, q, qd, tau, tau_steps, dt, T, ydd_work, q_traj, qd_traj, ok, B, device, stream);
+}
+int grbda_rollout_f32(const grbda_plan *p, float *q, float *qd, const float *tau, int tau_steps, double dt, int T, float *ydd_work,
+                      float *q_traj, float *qd_traj, int32_t *ok, size_t B, int device, void *stream)
+{
+    return rollout<float>(p, q, qd, tau, tau_steps, dt, T, ydd_work, q_traj, qd_traj, ok, B, device, stream);
+}
+int grbda_integrate_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double dt, double *q_next,
+                             double *qd_next, int32_t *ok, int max_iter, double tol, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = integrate_args<double>(p, q, qd, ydd, dt, q_next, qd_next, max_iter, tol, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dy = st.in(ydd, B * nv);
+    double *dqn = st.out(q_next, B * nq), *dvn = st.out(qd_next, B * nv);
+    int32_t *dok = st.out(ok, B);  // (a null `ok` only drops the copy)
+    return st.run([&] { return integrate<double>(p, dq, dqd, dy, dt, dqn, dvn, dok, max_iter, tol, B, device, nullptr); });
+}
+int grbda_step_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *f_ext, double dt, double *ydd,
+                        double *q_next, double *qd_next, int32_t *ok, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = step_args<double>(p, q, qd, tau, f_ext, dt, ydd, q_next, qd_next, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, nfe = static_cast<size_t>(p->host.n_bodies) * 6;
+    HostStage st;
+    const double *dfe = f_ext ? st.in(f_ext, B * nfe) : nullptr;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dt_ = st.in(tau, B * nv);
+    double *dy = st.out(ydd, B * nv), *dqn = st.out(q_next, B * nq), *dvn = st.out(qd_next, B * nv);
+    int32_t *dok = st.out(ok, B);
+    return st.run([&] { return step<double>(p, dq, dqd, dt_, dfe, dt, dy, dqn, dvn, dok, B, device, nullptr); });
 }
 
 int grbda_aba_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau,

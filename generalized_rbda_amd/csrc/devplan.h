@@ -62,6 +62,11 @@ template <class T>
 hipError_t launch_spanning(const DevPlan<T> &P, int n_clusters, int n_span, const T *q, const T *qd, const T *ydd,
                            T *qd_span, T *qdd_span, size_t B, T *scratch, int grid, size_t lds_bytes,
                            hipStream_t stream);
+// integrate_kernel: the wave's slab holds kIntegrateLocalRows rows behind the plan's global slots (per-lane cluster positions)
+constexpr int kIntegrateLocalRows = kMaxClusterBodies;
+template <class T>
+hipError_t launch_integrate(const DevPlan<T> &P, int n_clusters, const T *q, const T *qd, const T *ydd, T dt, T *q_next, T *qd_next,
+                            int32_t *ok, int ok_and, size_t B, int max_iter, T tol, T *scratch, int grid, size_t lds_bytes, hipStream_t stream);
 template <class T>
 hipError_t launch_poses(const DevPlan<T> &P, int n_clusters, const T *q, T *Xa, size_t B, int grid, hipStream_t stream);
 template <class T>

@@ -2374,6 +2374,113 @@ __global__ __launch_bounds__(kWave, 1) void spanning_kernel(DevPlan<T> DP, int n
 }
 
 // ---------------------------------------------------------------------------------------------
+// Time stepping: one semi-implicit (symplectic) Euler step on the configuration manifold, first order in dt:
+//     yd' = yd + dt ydd                                                   (all nv entries)
+//     explicit cluster         y'    = y + dt yd'                         (constant G: the independent coordinates ARE the state)
+//     free base, quaternion    p'    = p + dt R(quat)^T v'                (R of the OLD orientation; velocities [omega; v], body frame)
+//                              quat' = normalise(quat x [cos(|omega'| dt / 2), sin(|omega'| dt / 2) omega' / |omega'|])
+//                                      (ori::integrateQuatImplicit, OrientationTools.h:431-458; axis (1,0,0) when omega' = 0)
+//     implicit cluster         q_s'  = q_s + dt G(q_s) yd', then the Newton projection of the dependent entries back onto
+//                                      phi(q) = 0 with the independent ones fixed (project_cluster, GenericJoint.cpp:289-385)
+// The tile's q, qd and ydd are staged like every other kernel's inputs (coordinate-major rows of the wave's slab); the results
+// overwrite the q and qd rows and leave through write_outputs, so q_next / qd_next may be the input arrays themselves: nothing
+// of a tile is written before all of it is staged, and tiles do not share rows.  Lanes past the end of the batch read the rows
+// of the last state (same values, same result: they never lengthen the Newton loop) and write rows of their own that nobody
+// stores.  Per-lane positions of the cluster being projected: kMaxClusterBodies scalars per lane behind the wave's global slots.
+// ---------------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(kWave, 1) void integrate_kernel(DevPlan<T> DP, int n_clusters, const T *q, const T *qd, const T *ydd,
+                                                             T dt, T *q_next, T *qd_next, int32_t *ok, int ok_and, size_t B,
+                                                             int max_iter, T tol, T *scratch)
+{
+    const Tables<T> P = make_tables(DP);
+    const int lane = threadIdx.x;
+    Slots<T> S;
+    S.lane = lane;
+    const size_t in_rows = (size_t)(P.nq + 2 * P.nv);
+    T *slab = scratch + (size_t)blockIdx.x * ((size_t)DP.n_glb_slots + in_rows + kIntegrateLocalRows) * kWave;
+    S.glb = slab + in_rows * kWave;
+    T *qloc = S.glb + (size_t)DP.n_glb_slots * kWave + lane * kIntegrateLocalRows;
+    T *rows_q = slab, *rows_v = slab + (size_t)P.nq * kWave;
+    const size_t n_tiles = (B + kWave - 1) / kWave;
+    for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const size_t left = B - tile * kWave;
+        const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
+        stage_inputs(q, qd, ydd, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
+        const int src = lane < rows_valid ? lane : rows_valid - 1;
+        const bool ragged = rows_valid < kWave;  // (wave-uniform) some lanes read rows another lane stores: the stores land first
+        if (ragged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        Lane<T> L;
+        L.active = lane < rows_valid;
+        L.in_q = rows_q + src;
+        L.in_qd = rows_v + src;
+        L.in_x = slab + (size_t)(P.nq + P.nv) * kWave + src;
+        L.out_rows = nullptr;
+        L.fext = nullptr;
+        L.lane = lane;
+        T *oq = rows_q + lane, *ov = rows_v + lane;
+        for (int j = 0; j < P.nv; j++) ov[(size_t)j * kWave] = L.qd(j) + dt * L.x(j);
+        // (from here on L.qd is yd': a lane past the end reads what the last state's lane has just written)
+        if (ragged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        bool good = true;
+        for (int ci = 0; ci < n_clusters; ci++) {
+            const ClusterRec c = load_rec(P.clusters + ci);
+            if (c.kind == CK_FREE) {
+                T p[3], e[4], w[3], v[3];
+                for (int i = 0; i < 3; i++) {
+                    p[i] = L.q(c.q_index + i);
+                    w[i] = L.qd(c.v_index + i);
+                    v[i] = L.qd(c.v_index + 3 + i);
+                }
+                for (int i = 0; i < 4; i++) e[i] = L.q(c.q_index + 3 + i);
+                // R^T (quaternionToRotationMatrix returns R, OrientationTools.h:251-269): body-frame v into world axes
+                const T M[9] = {1 - 2 * (e[2] * e[2] + e[3] * e[3]), 2 * (e[1] * e[2] - e[0] * e[3]), 2 * (e[1] * e[3] + e[0] * e[2]),
+                                2 * (e[1] * e[2] + e[0] * e[3]), 1 - 2 * (e[1] * e[1] + e[3] * e[3]), 2 * (e[2] * e[3] - e[0] * e[1]),
+                                2 * (e[1] * e[3] - e[0] * e[2]), 2 * (e[2] * e[3] + e[0] * e[1]), 1 - 2 * (e[1] * e[1] + e[2] * e[2])};
+                for (int i = 0; i < 3; i++) oq[(size_t)(c.q_index + i) * kWave] = p[i] + dt * (M[3 * i] * v[0] + M[3 * i + 1] * v[1] + M[3 * i + 2] * v[2]);
+                const T ang = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+                T sn, cs;
+                sincos_cw(ang * dt * T(0.5), &sn, &cs);
+                const T k = ang > T(0) ? sn / ang : T(0);  // (omega' = 0: sin(0) (1,0,0) = 0)
+                const T d[3] = {k * w[0], k * w[1], k * w[2]};
+                T n[4] = {e[0] * cs - e[1] * d[0] - e[2] * d[1] - e[3] * d[2],
+                          e[0] * d[0] + e[1] * cs + e[2] * d[2] - e[3] * d[1],
+                          e[0] * d[1] + e[2] * cs + e[3] * d[0] - e[1] * d[2],
+                          e[0] * d[2] + e[3] * cs + e[1] * d[1] - e[2] * d[0]};
+                const T inv = T(1) / sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] + n[3] * n[3]);
+                for (int i = 0; i < 4; i++) oq[(size_t)(c.q_index + 3 + i) * kWave] = n[i] * inv;
+                continue;
+            }
+            if (c.kind == CK_LOOP) {
+                T yd3[3];
+                for (int a = 0; a < 3; a++) yd3[a] = a < c.n ? L.qd(c.v_index + a) : T(0);
+                // G at the OLD positions; qd_span = G yd' lands in the cluster's scratch block (ImpLayout::qds)
+                if (c.n == 1) { const T yd1[1] = {yd3[0]}; eval_loop_constraint<T, 1>(P, S, c, L, yd1, false); }
+                else if (c.n == 2) { const T yd2[2] = {yd3[0], yd3[1]}; eval_loop_constraint<T, 2>(P, S, c, L, yd2, false); }
+                else eval_loop_constraint<T, 3>(P, S, c, L, yd3, false);
+                const int qds = c.slot_imp_fwd + c.k * (c.n + 1);
+                for (int i = 0; i < c.k; i++) qloc[i] = L.q(c.q_index + i) + dt * S.ld1(qds + i);
+                T *qrow = qloc - c.q_index;  // project_cluster indexes a whole row of q
+                switch (c.n) {
+                    case 1: project_cluster<T, 1>(P, S, c, qrow, max_iter, tol, good); break;
+                    case 2: project_cluster<T, 2>(P, S, c, qrow, max_iter, tol, good); break;
+                    default: project_cluster<T, 3>(P, S, c, qrow, max_iter, tol, good); break;
+                }
+                for (int i = 0; i < c.k; i++) oq[(size_t)(c.q_index + i) * kWave] = qloc[i];
+                continue;
+            }
+            for (int a = 0; a < c.n; a++) oq[(size_t)(c.q_index + a) * kWave] = L.q(c.q_index + a) + dt * L.qd(c.v_index + a);
+        }
+        if (ok && L.active) {  // (ok_and: a rollout ANDs the flags of its steps)
+            int32_t *o = ok + tile * kWave + lane;
+            *o = (good && (!ok_and || *o != 0)) ? 1 : 0;
+        }
+        write_outputs(rows_q, q_next, tile, rows_valid, P.nq, lane);
+        write_outputs(rows_v, qd_next, tile, rows_valid, P.nv, lane);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host launchers (called by capi.cpp)
 // ---------------------------------------------------------------------------------------------
 template <class T>
@@ -2442,6 +2549,18 @@ hipError_t launch_spanning(const DevPlan<T> &P, int n_clusters, int n_span, cons
     return hipGetLastError();
 }
 template <class T>
+hipError_t launch_integrate(const DevPlan<T> &P, int n_clusters, const T *q, const T *qd, const T *ydd, T dt, T *q_next, T *qd_next,
+                            int32_t *ok, int ok_and, size_t B, int max_iter, T tol, T *scratch, int grid, size_t lds_bytes, hipStream_t stream)
+{
+    hipLaunchKernelGGL((integrate_kernel<T>), dim3(grid), dim3(kWave), lds_bytes, stream, P, n_clusters, q, qd, ydd, dt, q_next,
+                       qd_next, ok, ok_and, B, max_iter, tol, scratch);
+    return hipGetLastError();
+}
+template hipError_t launch_integrate<float>(const DevPlan<float> &, int, const float *, const float *, const float *, float, float *,
+                                            float *, int32_t *, int, size_t, int, float, float *, int, size_t, hipStream_t);
+template hipError_t launch_integrate<double>(const DevPlan<double> &, int, const double *, const double *, const double *, double,
+                                             double *, double *, int32_t *, int, size_t, int, double, double *, int, size_t, hipStream_t);
+template <class T>
 hipError_t launch_poses(const DevPlan<T> &P, int n_clusters, const T *q, T *Xa, size_t B, int grid, hipStream_t stream)
 {
     hipLaunchKernelGGL((poses_kernel<T>), dim3(grid), dim3(kWave), 0, stream, P, n_clusters, q, Xa, B);
@@ -2490,6 +2609,8 @@ hipError_t set_max_dynamic_lds()
                          reinterpret_cast<const void *>(&state_kernel<double>),
                          reinterpret_cast<const void *>(&spanning_kernel<float>),
                          reinterpret_cast<const void *>(&spanning_kernel<double>),
+                         reinterpret_cast<const void *>(&integrate_kernel<float>),
+                         reinterpret_cast<const void *>(&integrate_kernel<double>),
                          reinterpret_cast<const void *>(&aba_kernel<float, false, kAba32Waves>),
                          reinterpret_cast<const void *>(&aba_kernel<float, false, kAba32Waves, true>),
                          reinterpret_cast<const void *>(&rnea_kernel<float, false, true>),

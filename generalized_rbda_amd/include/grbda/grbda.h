@@ -221,6 +221,43 @@ Quat<T> rotationMatrixToQuaternion(const Mat3<T> &r1)
 }
 template <typename T>
 Quat<T> rpyToQuat(const Vec3<T> &rpy) { return rotationMatrixToQuaternion(rpyToRotMat(rpy)); }
+// Hamilton product of scalar-first quaternions (OrientationTools.h:364-377): (r1 r2 - v1 . v2, r1 v2 + r2 v1 + v1 x v2)
+template <typename T>
+Quat<T> quatProduct(const Quat<T> &a, const Quat<T> &b)
+{
+    return Quat<T>{a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
+                   a[0] * b[1] + b[0] * a[1] + a[2] * b[3] - a[3] * b[2],
+                   a[0] * b[2] + b[0] * a[2] + a[3] * b[1] - a[1] * b[3],
+                   a[0] * b[3] + b[0] * a[3] + a[1] * b[2] - a[2] * b[1]};
+}
+// the rotation by |omega| dt about omega as a quaternion; axis (1, 0, 0) when omega = 0, as the reference has it
+template <typename T>
+Quat<T> rotationIncrement(const Vec3<T> &omega, T dt)
+{
+    const T rate = std::sqrt(omega[0] * omega[0] + omega[1] * omega[1] + omega[2] * omega[2]);
+    const Vec3<T> axis = rate > T(0) ? Vec3<T>{omega[0] / rate, omega[1] / rate, omega[2] / rate} : Vec3<T>{T(1), T(0), T(0)};
+    const T half = rate * dt / T(2), s = std::sin(half);
+    return Quat<T>{std::cos(half), s * axis[0], s * axis[1], s * axis[2]};
+}
+template <typename T>
+Quat<T> normalised(const Quat<T> &q)
+{
+    const T n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    return Quat<T>{q[0] / n, q[1] / n, q[2] / n, q[3] / n};
+}
+// OrientationTools.h:386-413: omega in WORLD (inertial) coordinates -- the increment multiplies from the left
+template <typename T>
+Quat<T> integrateQuat(const Quat<T> &quat, const Vec3<T> &omega, T dt)
+{
+    return normalised(quatProduct(rotationIncrement(omega, dt), quat));
+}
+// OrientationTools.h:431-458: omega in BODY coordinates -- the increment multiplies from the right (what grbda_integrate_* applies to
+// the floating base)
+template <typename T>
+Quat<T> integrateQuatImplicit(const Quat<T> &quat, const Vec3<T> &omega, T dt)
+{
+    return normalised(quatProduct(quat, rotationIncrement(omega, dt)));
+}
 }  // namespace ori
 
 // OrientationRepresentation.h:11-49
@@ -1267,6 +1304,18 @@ public:
     }
 
     // batched entry points on HOST arrays (row-major q[B][nq], qd[B][nv], tau[B][nv] -> ydd[B][nv])
+    // One semi-implicit Euler step of B states on host arrays (include/grbda_hip.h "time stepping"; first order in dt): integrateBatch
+    // from given accelerations, stepBatch = forward dynamics + integrateBatch.  ok: null or B flags (every implicit cluster converged).
+    void integrateBatch(const double *q, const double *qd, const double *ydd, double dt, double *q_next, double *qd_next, int32_t *ok,
+                        size_t B, int device = 0, int max_iter = 50, double tol = 1e-8)
+    {
+        check(grbda_integrate_host_f64(plan(), q, qd, ydd, dt, q_next, qd_next, ok, max_iter, tol, B, device));
+    }
+    void stepBatch(const double *q, const double *qd, const double *tau, double dt, double *ydd, double *q_next, double *qd_next,
+                   int32_t *ok, size_t B, int device = 0, const double *f_ext = nullptr)
+    {
+        check(grbda_step_host_f64(plan(), q, qd, tau, f_ext, dt, ydd, q_next, qd_next, ok, B, device));
+    }
     void forwardDynamicsBatch(const double *q, const double *qd, const double *tau, double *ydd, size_t B, int device = 0)
     {
         check(grbda_aba_host_f64(plan(), q, qd, tau, nullptr, ydd, B, device));

@@ -314,6 +314,52 @@ int grbda_spanning_f64(const grbda_plan *plan, const double *q, const double *qd
 int grbda_spanning_f32(const grbda_plan *plan, const float *q, const float *qd, const float *ydd, float *qd_span,
                        float *qdd_span, size_t B, int device, void *stream);
 
+/* ---- time stepping ---------------------------------------------------------------------------------------- */
+/* One semi-implicit (symplectic) Euler step on the configuration manifold, in the engine's coordinates.  The step is FIRST ORDER in dt:
+ *
+ *     yd'   = yd + dt ydd                                              all nv entries
+ *     y'    = y + dt yd'                                               explicit clusters (Revolute, rotor, pair, triple, Generic: constant G)
+ *     p'    = p + dt R(quat)^T v'                                      free base: q = [p 3 | quat 4, scalar first], qd = [omega; v] in body
+ *     quat' = normalise(quat x [cos(a/2), sin(a/2) omega'/|omega'|])   coordinates, R of the OLD orientation, a = |omega'| dt; axis (1,0,0)
+ *                                                                      when omega' = 0 (ori::integrateQuatImplicit, OrientationTools.h:431-458)
+ *     q_s'  = q_s + dt G(q_s) yd', then the dependent entries          implicit clusters: G at the OLD positions, then the Newton projection
+ *             back onto phi(q) = 0, the independent ones fixed         of grbda_project_positions_* (GenericJoint.cpp:289-385)
+ *
+ * grbda_integrate_*: q [B][nq], qd, ydd [B][nv] in; q_next [B][nq], qd_next [B][nv] out, which may BE q and qd (equal pointers; any other
+ *   overlap of an output with an input is GRBDA_EINVAL).  ok: NULL or [B] int32, 1 when every implicit cluster of the state ended with
+ *   |phi| < tol (always 1 for models without implicit clusters); max_iter, tol: as for grbda_project_positions_*.
+ * grbda_step_*: exactly grbda_aba_* (tau, f_ext or NULL -> ydd) followed by grbda_integrate_* with max_iter = 50, tol = 1e-8 (the
+ *   reference's nearZero) on the same stream.  ydd [B][nv] is written: the accelerations of this step.  The caller owns it.
+ * grbda_rollout_*: exactly T calls of grbda_step_* in place on q, qd (in: state 0, out: state T), bit for bit.  tau_steps = 1: tau [B][nv]
+ *   held for all steps; tau_steps = T: tau [T][B][nv].  ydd_work [B][nv]: the caller's work array (the last step's accelerations on return).
+ *   q_traj [T][B][nq], qd_traj [T][B][nv] (each may be NULL): states 1 .. T, copied device-to-device after every step.  ok: NULL or [B],
+ *   the AND over the steps.
+ * All of them only enqueue (kernels and copies on `stream`, one after the other), never synchronise, and allocate nothing beyond the
+ * per-(device, stream) scratch slab: capturable after one eager call of the same B on the stream; dt and gravity are read at launch.
+ * Errors: GRBDA_EINVAL for NULL required pointers, a dt that is not finite, T < 0, tau_steps not in {1, T}, overlapping arrays;
+ * GRBDA_EUNSUPPORTED (text in grbda_last_error()) for a roll-pitch-yaw floating base -- its rate map is not built -- and for plans on the
+ * spanning-tree route that contain implicit clusters; explicit plans on that route are covered.  All of these are decided on the host
+ * before anything is enqueued.  B == 0 or T == 0: GRBDA_OK, nothing done.
+ * In fp32 |phi| < 1e-8 is out of reach: grbda_step_f32 / grbda_rollout_f32 report ok = 0 for states with implicit clusters (the positions
+ * are still projected, to fp32 accuracy); pass a tolerance that fits the precision to grbda_integrate_f32. */
+int grbda_integrate_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, double dt, double *q_next,
+                        double *qd_next, int32_t *ok, int max_iter, double tol, size_t B, int device, void *stream);
+int grbda_integrate_f32(const grbda_plan *plan, const float *q, const float *qd, const float *ydd, double dt, float *q_next,
+                        float *qd_next, int32_t *ok, int max_iter, double tol, size_t B, int device, void *stream);
+int grbda_step_f64(const grbda_plan *plan, const double *q, const double *qd, const double *tau, const double *f_ext, double dt,
+                   double *ydd, double *q_next, double *qd_next, int32_t *ok, size_t B, int device, void *stream);
+int grbda_step_f32(const grbda_plan *plan, const float *q, const float *qd, const float *tau, const float *f_ext, double dt, float *ydd,
+                   float *q_next, float *qd_next, int32_t *ok, size_t B, int device, void *stream);
+int grbda_rollout_f64(const grbda_plan *plan, double *q, double *qd, const double *tau, int tau_steps, double dt, int T, double *ydd_work,
+                      double *q_traj, double *qd_traj, int32_t *ok, size_t B, int device, void *stream);
+int grbda_rollout_f32(const grbda_plan *plan, float *q, float *qd, const float *tau, int tau_steps, double dt, int T, float *ydd_work,
+                      float *q_traj, float *qd_traj, int32_t *ok, size_t B, int device, void *stream);
+/* The same with HOST arrays (copied to the device and back; synchronise): the C++ facade's integrateBatch / stepBatch. */
+int grbda_integrate_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, double dt, double *q_next,
+                             double *qd_next, int32_t *ok, int max_iter, double tol, size_t B, int device);
+int grbda_step_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *tau, const double *f_ext, double dt,
+                        double *ydd, double *q_next, double *qd_next, int32_t *ok, size_t B, int device);
+
 /* ---- contact side --------------------------------------------------------------------- */
 /* Absolute transform world -> body of every body, TreeNode::Xa_ after TreeModel::forwardKinematics
  * (TreeModel.cpp:6-32): Xa[B][n_bodies][12] = rotation E (9, row-major: v_body = E v_world) then the position r
