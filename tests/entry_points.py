@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+import kinematics_ref as K
 import oracle_py as O
 import generalized_rbda_amd as G
 from generalized_rbda_amd.states import parse_clusters, random_states
@@ -169,9 +170,24 @@ def _chk_force(blob, s, o, tol):
     assert np.abs(lam.reshape(-1) - np.einsum("bi,bi->b", jtf, ds_ref)).max() / (1 + np.abs(lam).max()) < max(tol, 1e-8)
 
 
-def _chk_osim(blob, s, o, tol):
-    # Linv = J H^-1 J^T, H^-1 from the oracle's forward dynamics (columns of d ydd / d tau)
+def _chk_twists(blob, s, o, tol):
+    # v and a apart, every state on its own scale: a wrong state, or a term that is small next to the batch's largest |a|, cannot hide.
+    # The call feeds x["tau"] as ydd, so the reference does.
+    err = K.block_errors(o[0], K.body_twists(blob, s["q"], s["qd"], s["tau"], big=_big(blob)))
+    assert err.max() < tol, f"state {int(err.max(axis=1).argmax())}: v {err[:, 0].max():.2e}, a {err[:, 1].max():.2e} against {tol:.0e}"
+
+
+def _osim_frames(blob):
+    return [_body_index(blob, b) for b in OSIM_BODIES], [OFFSET, (0.0, 0.0, 0.0)]
+
+
+def _chk_osim(blob, s, o, tol, frames=None):
+    # frames: (bodies, offsets) of the call, the table's when None.  J against the numpy recursion's frame Jacobians: the identity below
+    # has the kernel's own J on both sides, and passes a frame on the wrong body or a dropped offset
     Linv, J = o
+    J_ref = K.frame_jacobians(blob, s["q"], *(frames or _osim_frames(blob)), big=_big(blob))
+    assert _rel(J, J_ref) < max(tol, 1e-9)
+    # Linv = J H^-1 J^T, H^-1 from the oracle's forward dynamics (columns of d ydd / d tau)
     Hinv = _fd_columns(blob, s["q"], np.zeros_like(s["qd"]), np.zeros_like(s["qd"]), "dtau")
     assert _rel(Linv, np.einsum("bij,bjk,blk->bil", J, Hinv, J)) < max(tol, 1e-8)
 
@@ -186,6 +202,10 @@ def _chk_project(blob, s, o, tol):
 
 def _chk_spanning(blob, s, o, tol):
     assert _rel(o[0], O.spanning_state(blob, s["q"], s["qd"])[1]) < max(tol, 1e-10)
+    # qdd_span = G ydd + g (the call feeds x["tau"] as ydd), at the bound test_spanning_recovery_matches_oracle holds the implicit bias to
+    ref = K.spanning_rates(blob, s["q"], s["qd"], s["tau"], big=_big(blob))[1]
+    g = ref - K.spanning_rates(blob, s["q"], np.zeros_like(s["qd"]), s["tau"], big=_big(blob))[1]
+    assert np.abs(o[1] - ref).max() < max(tol, 1e-8) * (1 + np.abs(g).max())
 
 
 def _chk_indep(blob, s, o, tol):
@@ -213,7 +233,7 @@ def _test_force(plan, x):
 
 
 def _inv_osim(plan, x):
-    return plan.inv_osim(x["q"], [_body_index(plan.blob, b) for b in OSIM_BODIES], [OFFSET, (0.0, 0.0, 0.0)], with_jacobian=True)
+    return plan.inv_osim(x["q"], *_osim_frames(plan.blob), with_jacobian=True)
 
 
 def _project(plan, x):
@@ -233,8 +253,8 @@ ENTRY = {
     "fd_dq": (lambda p, x: (p.fd_dq(x["q"], x["qd"], x["tau"]),), _chk_dq),
     "fd_derivatives": (lambda p, x: tuple(p.fd_derivatives(x["q"], x["qd"], x["tau"]).values()), _chk_derivs),
     "body_poses": (lambda p, x: (p.body_poses(x["q"]),), _chk_poses),
-    # (twists: no oracle entry point; test_gpu_parity.py holds them against the motion -- here (a), (b) and (d))
-    "body_twists": (lambda p, x: (p.body_twists(x["q"], x["qd"], x["tau"]),), None),
+    # (twists: no oracle entry point; the numpy recursion of kinematics_ref.py, pinned to the oracle's inverse dynamics on the CPU)
+    "body_twists": (lambda p, x: (p.body_twists(x["q"], x["qd"], x["tau"]),), _chk_twists),
     "apply_test_force": (_test_force, _chk_force),
     "inv_osim": (_inv_osim, _chk_osim),
     "project_positions": (lambda p, x: _project(p, x), _chk_project),
@@ -258,6 +278,9 @@ CASES += [("crba", "urdf_mini_cheetah", {}, B_CHAIN, "mass_matrix"), ("no_crba",
           ("no_efpa", "urdf_mini_cheetah", {"GRBDA_NO_EFPA": "1"}, 300, "inv_osim"),
           ("implicit", "urdf_four_bar", {}, 1000, "project_positions"), ("implicit", "urdf_four_bar", {}, 1000, "state_to_independent"),
           ("implicit", "urdf_four_bar", {}, 1000, "spanning"), ("spanning_tree", "parallel_chain_exp_d10_l16", {}, 300, "mass_matrix")]
+# twists on the routes the Mini Cheetah row does not reach: implicit differentials, a loop cluster, big clusters, a roll-pitch-yaw base
+CASES += [("implicit", "tello_with_arms", {}, 300, "body_twists"), ("implicit", "urdf_four_bar", {}, 300, "body_twists"),
+          ("spanning_tree", "parallel_chain_exp_d10_l16", {}, 300, "body_twists"), ("chain", "urdf_mini_cheetah_rpy", {}, 300, "body_twists")]
 IDS = [f"{ep}-{route}-{model}-B{B}" for route, model, env, B, ep in CASES]
 
 

@@ -13,7 +13,8 @@ The inputs of batch B are the first B rows of one draw of the ladder's largest b
 B - 1 lies a band of NaN, not the next valid state, and every output sits between canary bands (run_guarded asserts bounds, complete
 writes, untouched inputs and finite outputs).  Every state of every batch is held against the oracle with the table's checker at the
 table's tolerances; only the position derivatives, whose oracle is 2 nv single-state forward dynamics per state, are held on a sample
-above 65 states (first, last, both ends of the last tile and of the last group, a seeded few).  Body twists have no oracle checker.  The draws of
+above 65 states (first, last, both ends of the last tile and of the last group, a seeded few).  Body twists, spanning accelerations and the
+inverse OSIM's Jacobians are held to the numpy recursion of kinematics_ref.py, which the CPU suite pins to the oracle.  The draws of
 those derivative rows bound the conditioning of the implicit loops as the older derivative tests do (entry_points.py, draw_bound).
 
 Prefix invariance: where B and the ladder's largest batch launch the same kernels -- the same plan.kernel_name for forward / inverse

@@ -225,7 +225,9 @@ def _fixed_check(entry, blob, s, o, big):
         assert _rel(ds, ds_ref) < 1e-8
         assert np.abs(lam.reshape(-1) - np.einsum("bi,bi->b", jtf, ds_ref)).max() / (1 + np.abs(lam).max()) < 1e-8
     elif entry == "inv_osim":
-        _chk_osim(blob, s, o, TOL64)
+        from test_gpu_parity import _body_index
+
+        _chk_osim(blob, s, o, TOL64, frames=([_body_index(blob, FORCE_BODY)], [OFFSET]))  # (the one frame of _fixed_call)
     elif entry == "fd_dq":
         # (fp32 in and out, the differences in fp64: the tolerance of the fp64 differences and fp32 rounding of the result)
         assert _rel(o[0], _dq_oracle(blob, s["q"], s["qd"], s["tau"])) < 2e-5

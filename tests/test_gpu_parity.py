@@ -953,23 +953,13 @@ def test_inverse_operational_space_inertia(name, gpu):
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=gpu)
     Linv, J = plan.inv_osim(t(q), bodies, offsets, with_jacobian=True)
     Linv, J = Linv.cpu().numpy(), J.cpu().numpy()
-    # oracle: J rows from unit wrenches, H from unit accelerations
+    # oracle: J rows from unit wrenches (kinematics_ref.oracle_frame_jacobians), H from unit accelerations
+    from kinematics_ref import oracle_frame_jacobians
+
     Xa = O.body_poses(blob, q, nb)
     zero = np.zeros((B, nv))
     tau0 = O.inverse_dynamics(blob, q, zero, zero)
-    J_ref = np.zeros((B, 12, nv))
-    for c, (bd, off) in enumerate(zip(bodies, offsets)):
-        E, r = Xa[:, bd, :9].reshape(B, 3, 3), Xa[:, bd, 9:]
-        p = r + np.einsum("bji,j->bi", E, np.array(off))
-        for k in range(6):
-            e = E[:, k % 3, :]  # body axis in world coordinates
-            fext = np.zeros((B, nb, 6))
-            if k < 3:
-                fext[:, bd, :3] = e
-            else:
-                fext[:, bd, :3] = np.cross(p, e)
-                fext[:, bd, 3:] = e
-            J_ref[:, 6 * c + k] = tau0 - O.inverse_dynamics(blob, q, zero, zero, f_ext=fext)
+    J_ref = oracle_frame_jacobians(blob, q, bodies, offsets)
     H = np.zeros((B, nv, nv))
     for j in range(nv):
         ej = np.zeros((B, nv))
