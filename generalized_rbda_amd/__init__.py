@@ -30,6 +30,8 @@ C_ABI_SYMBOLS = [
     "grbda_body_poses_host_f64", "grbda_apply_test_force_host_f64",
     "grbda_inv_osim_host_f64", "grbda_fd_dq_f64", "grbda_fd_dq_f32", "grbda_body_poses_f64", "grbda_body_poses_f32",
     "grbda_apply_test_force_f64", "grbda_apply_test_force_f32", "grbda_inv_osim_f64", "grbda_inv_osim_f32",
+    "grbda_contact_points_f64", "grbda_contact_points_f32", "grbda_contact_dynamics_f64", "grbda_contact_dynamics_f32",
+    "grbda_contact_points_host_f64", "grbda_contact_dynamics_host_f64",
     "grbda_project_positions_f64", "grbda_project_positions_f32", "grbda_plan_span_dims",
     "grbda_spanning_f64", "grbda_spanning_f32", "grbda_fd_derivatives_f64", "grbda_fd_derivatives_f32",
     "grbda_mass_matrix_host_f64", "grbda_fd_derivatives_host_f64",
@@ -118,6 +120,11 @@ def lib() -> ctypes.CDLL:
         getattr(L, "grbda_body_twists_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
         getattr(L, "grbda_inv_osim_" + sfx).argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double),
                                                         c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        getattr(L, "grbda_contact_points_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double),
+                                                              c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        getattr(L, "grbda_contact_dynamics_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int),
+                                                                POINTER(c_double), c_void_p, c_double, c_void_p, c_void_p, c_void_p,
+                                                                c_size_t, c_int, c_void_p]
         getattr(L, "grbda_apply_test_force_" + sfx).argtypes = [c_void_p, c_void_p, c_int, POINTER(c_double), c_void_p,
                                                                 c_void_p, c_void_p, c_size_t, c_int, c_void_p]
     for sfx in ("f64", "f32"):
@@ -587,6 +594,73 @@ class Plan:
         _check(fn(self._h, q.data_ptr(), n, bod, off, Linv.data_ptr(), None if J is None else J.data_ptr(), B,
                   q.device.index or 0, c_void_p(s.cuda_stream)))
         return (Linv, J) if with_jacobian else Linv
+
+    def _contacts(self, bodies, offsets):
+        n = len(bodies)
+        if len(offsets) != n or any(len(o) != 3 for o in offsets):
+            raise ValueError("offsets must hold one (x, y, z) per body")
+        return n, (c_int * n)(*[int(b) for b in bodies]), (c_double * (3 * n))(*[float(x) for o in offsets for x in o])
+
+    def contact_points(self, q, bodies, offsets, qd=None, ydd=None, stream=None):
+        """World-frame position, velocity and classical acceleration of body-fixed points (grbda_contact_points_*): point offsets[c]
+        (body coordinates) of body bodies[c].  Returns (pos, vel, acc), [B, n, 3] each; vel is None without qd, acc is None without qd
+        and ydd."""
+        import torch
+
+        given = [t for t in (qd, ydd) if t is not None]
+        self._floating(q, *given)
+        B = q.shape[0]
+        if not q.is_cuda or q.shape != (B, self.nq) or any(t.shape != (B, self.nv) or t.dtype != q.dtype or t.device != q.device for t in given):
+            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}] of one dtype")
+        n, bod, off = self._contacts(bodies, offsets)
+        q = q.contiguous()
+        qd = None if qd is None else qd.contiguous()
+        ydd = None if ydd is None else ydd.contiguous()
+        new = lambda: torch.empty((B, n, 3), dtype=q.dtype, device=q.device)
+        pos, vel, acc = new(), (None if qd is None else new()), (None if qd is None or ydd is None else new())
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        if stream is not None:
+            for t in (q, qd, ydd, pos, vel, acc):
+                if t is not None:
+                    t.record_stream(s)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        fn = getattr(lib(), f"grbda_contact_points_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        _check(fn(self._h, q.data_ptr(), ptr(qd), ptr(ydd), n, bod, off, ptr(pos), ptr(vel), ptr(acc), B, q.device.index or 0,
+                  c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return pos, vel, acc
+
+    def contact_dynamics(self, q, qd, tau, bodies, offsets, a_des=None, damping: float = 0.0, f_ext=None, stream=None):
+        """Forward dynamics with the points offsets[c] of bodies[c] held to the world-frame accelerations a_des[B, n, 3] (None: zero)
+        (grbda_contact_dynamics_*): (J_w H^-1 J_w^T + damping I) lambda = a_des - p_ddot(ydd_free).  Returns (ydd[B, nv], lambda[B, n, 3]
+        -- world-frame forces on the bodies at the points --, ydd_free[B, nv]).  Redundant contacts need damping > 0; a state whose
+        matrix is not positive definite gets NaN and is counted by spd_bad_pivots()."""
+        import torch
+
+        B = self._state_args(q, qd, tau, "tau")
+        n, bod, off = self._contacts(bodies, offsets)
+        q, qd, tau = q.contiguous(), qd.contiguous(), tau.contiguous()
+        if f_ext is not None:
+            if f_ext.shape != (B, self.n_bodies, 6) or f_ext.dtype != q.dtype or not f_ext.is_cuda:
+                raise ValueError(f"f_ext must be a device tensor [B,{self.n_bodies},6] of the same dtype")
+            f_ext = f_ext.contiguous()
+        if a_des is not None:
+            if a_des.shape != (B, n, 3) or a_des.dtype != q.dtype or not a_des.is_cuda:
+                raise ValueError(f"a_des must be a device tensor [B,{n},3] of the same dtype")
+            a_des = a_des.contiguous()
+        ydd = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
+        free = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
+        lam = torch.empty((B, n, 3), dtype=q.dtype, device=q.device)
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        if stream is not None:
+            for t in (q, qd, tau, ydd, free, lam) + tuple(t for t in (f_ext, a_des) if t is not None):
+                t.record_stream(s)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        fn = getattr(lib(), f"grbda_contact_dynamics_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), ptr(f_ext), n, bod, off, ptr(a_des), float(damping), ydd.data_ptr(),
+                  lam.data_ptr(), free.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return ydd, lam, free
 
     def fd_derivatives(self, q, qd, tau, want=("dq", "dqd", "dtau"), stream=None):
         """d ydd / d q, d ydd / d qd, d ydd / d tau of the forward dynamics in one pass (grbda_fd_derivatives_*): a dict

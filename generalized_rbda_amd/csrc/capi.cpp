@@ -273,6 +273,7 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
     if ((e = set_max_dynamic_lds()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     if ((e = set_max_dynamic_lds_deriv()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     if ((e = set_max_dynamic_lds_minv()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
+    if ((e = set_max_dynamic_lds_contact()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     t.bad_count = spd_bad_count_address();
     auto ins = p->dev.emplace(device, t);
     *out = &ins.first->second;
@@ -1171,6 +1172,20 @@ int poses(const grbda_plan *p, const T *q, T *Xa, size_t B, int device, void *st
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "poses launch");
 }
 
+// the two launches of twists() on work arrays of the caller's: vs, as [B][span_count] (arguments checked, B > 0)
+template <class T>
+int twists_core(const grbda_plan *p, const DeviceTables &t, const T *q, const T *qd, const T *ydd, T *V, T *vs, T *as, size_t B, int device,
+                void *stream)
+{
+    const size_t ns = static_cast<size_t>(span_count(p));
+    if (int rc = spanning<T>(p, q, qd, ydd, vs, as, B, device, stream)) return rc;
+    DevPlan<T> d = make_dev_plan<T>(p, t, false, false);
+    const size_t g = tile_grid(t.n_cu, 8, B);
+    hipError_t e = launch_twists<T>(d, p->host.n_clusters, static_cast<int>(ns), q, vs, as, V, B, static_cast<int>(g),
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "twists launch");
+}
+
 // spatial velocity / acceleration of every body: the spanning rates (spanning_kernel) into the plan's per-(device, stream)
 // workspace, then the tree walk (twists_kernel)
 template <class T>
@@ -1187,12 +1202,7 @@ int twists(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *V, siz
     if (int rc = ensure_work(p, p->work, device, stream, 2 * B * ns * sizeof(T) + 256, &wptr)) return rc;
     Carver<T> w(wptr, 2 * B * ns);
     T *vs = w.take(B * ns), *as = w.take(B * ns);
-    if (int rc = spanning<T>(p, q, qd, ydd, vs, as, B, device, stream)) return rc;
-    DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
-    const size_t g = tile_grid(t->n_cu, 8, B);
-    hipError_t e = launch_twists<T>(d, p->host.n_clusters, static_cast<int>(ns), q, vs, as, V, B, static_cast<int>(g),
-                                    static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? GRBDA_OK : hip_err(e, "twists launch");
+    return twists_core<T>(p, *t, q, qd, ydd, V, vs, as, B, device, stream);
 }
 
 // world wrench (about the world origin) of a Cartesian force at a point fixed in body `body`
@@ -1288,14 +1298,7 @@ int test_force(const grbda_plan *p, const T *q, int body, const double *offset, 
 }
 
 // ---- inverse operational-space inertia of a set of contact frames (include/grbda_hip.h) -----------------------
-constexpr int kMaxContacts = 8;
-template <class T>
-struct ContactSet {
-    int n;
-    int body[kMaxContacts];
-    T off[kMaxContacts][3];
-};
-
+// (ContactSet<T>, kMaxContacts: devplan.h)
 // rows (b, j), j < 6 n: unit spatial force e_{j % 6} in contact frame j / 6 (body axes, origin at the contact
 // point) as a world wrench on that body; row 6 n: no force
 template <class T>
@@ -1351,25 +1354,25 @@ __global__ void osim_combine_kernel(const T *__restrict__ acc, const T *__restri
 
 // Inverse OSIM by force propagation (chain_kernels.hip, osim_chain_kernel) for models the chain program covers and contact
 // frames on link / base bodies.  Returns 1 when the fast path does not apply (the caller then takes the unit-wrench path).
+// The host half: the argument block of the force-propagation kernel for these contacts; false when the fast path does not apply.
 template <class T>
-int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *bodies, const double *offsets, T *Linv, T *J,
-                   size_t B, int device, void *stream, const T *tf_force, T *tf_lambda, T *tf_dstate)
+bool osim_chain_args(const grbda_plan *p, int n_contacts, const int *bodies, const double *offsets, bool want_J, const T *tf_force, T *tf_lambda,
+                     T *tf_dstate, OsimArgs<T> &A)
 {
     const HostPlan &h = p->host;
     const ChainSlot slot = chain_slot(sizeof(T) == 8);
     const ChainProgram &cp = h.chain[slot];
     // (programs with generic clusters -- plan.h, ChainGen -- have no walk steps in the force-propagation kernel: unit-wrench path)
-    if (p->opt.no_chain || p->opt.no_efpa || !cp.ok || !cp.gens.empty() || n_contacts > kOsimMaxContacts) return 1;
+    if (p->opt.no_chain || p->opt.no_efpa || !cp.ok || !cp.gens.empty() || n_contacts > kOsimMaxContacts) return false;
     const Layout &L = h.lay64;
-    OsimArgs<T> A;
     std::memset(&A, 0, sizeof A);
     A.n_contacts = n_contacts;
-    A.want_J = J ? 1 : 0;
+    A.want_J = want_J ? 1 : 0;
     A.test_force = tf_force ? 1 : 0;
     A.force = tf_force;
     A.lambda_inv = tf_lambda;
     A.dstate = tf_dstate;
-    if (tf_force && n_contacts != 1) return 1;
+    if (tf_force && n_contacts != 1) return false;
     std::vector<std::vector<int>> path_clusters(n_contacts);
     int max_rows = 0;
     for (int e = 0; e < n_contacts; e++) {
@@ -1378,7 +1381,7 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
         int rows = 0, len = 0;
         bool first = true;
         while (c >= 0) {
-            if (len >= kOsimMaxPath) return 1;
+            if (len >= kOsimMaxPath) return false;
             const ClusterRec &cr = L.clusters[c];
             OsimStep st;
             st.v_index = static_cast<int16_t>(cr.v_index);
@@ -1390,7 +1393,7 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
                 st.kind = OSIM_FREE;
                 rows += 6;
             } else if (cr.shape != SHAPE_GENERIC) {
-                if (first && b != cr.link_body) return 1;  // a contact on a rotor
+                if (first && b != cr.link_body) return false;  // a contact on a rotor
                 for (size_t i = 0; i < cp.links.size(); i++)
                     if (cp.links[i].v_index == cr.v_index) found = static_cast<int>(i);
                 st.kind = OSIM_LINK;
@@ -1404,22 +1407,22 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
                 // contact on it) or at link2 (a contact on it or below)
                 for (size_t i = 0; i < cp.diffs.size(); i++)
                     if (cp.diffs[i].v_index == cr.v_index) found = static_cast<int>(i);
-                if (found < 0) return 1;
+                if (found < 0) return false;
                 if (!first || L.bodies[b].cofs == cp.diffs[found].cofs[1]) st.kind = OSIM_DIFF_LINK2;
                 else if (L.bodies[b].cofs == cp.diffs[found].cofs[0]) st.kind = OSIM_DIFF_LINK1;
-                else return 1;  // a contact on a rotor
+                else return false;  // a contact on a rotor
                 rows += 2;
             } else {
-                if (!first) return 1;  // pair clusters are leaves of the chain program
+                if (!first) return false;  // pair clusters are leaves of the chain program
                 for (size_t i = 0; i < cp.pairs.size(); i++)
                     if (cp.pairs[i].v_index == cr.v_index) found = static_cast<int>(i);
-                if (found < 0) return 1;
+                if (found < 0) return false;
                 if (L.bodies[b].cofs == cp.pairs[found].cofs[0]) st.kind = OSIM_PAIR_LINK1;
                 else if (L.bodies[b].cofs == cp.pairs[found].cofs[1]) st.kind = OSIM_PAIR_LINK2;
-                else return 1;
+                else return false;
                 rows += 2;
             }
-            if (found < 0) return 1;
+            if (found < 0) return false;
             st.rec = static_cast<int16_t>(found);
             A.path[e][len++] = st;
             path_clusters[e].push_back(c);
@@ -1464,10 +1467,22 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
             }
             A.common[e1][e2] = rows;
         }
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
     A.w_base = cp.n_glb;
     A.w_stride = 6 * max_rows;
+    return true;
+}
+// The device half: one launch of osim_chain_kernel.  zeros: B * nv scalars of the caller's work space (cleared here), which stand in for
+// the velocities and torques of every tile.
+template <class T>
+int osim_chain_launch(const grbda_plan *p, const OsimArgs<T> &A, const T *q, T *Linv, T *J, size_t B, int device, void *stream, T *zeros)
+{
+    const HostPlan &h = p->host;
+    const ChainSlot slot = chain_slot(sizeof(T) == 8);
+    const ChainProgram &cp = h.chain[slot];
+    const int n_contacts = A.n_contacts;
+    const bool tf_force = A.test_force != 0;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
     ChainDev<T> d = chain_dev<T>(p, *t, slot);
     no_gens(d);
     d.n_glb_slots = cp.n_glb + n_contacts * A.w_stride;
@@ -1482,16 +1497,59 @@ int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *b
     const size_t n_rows = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(h.nq + 2 * h.nv);
     void *scratch = nullptr;
     if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, n_rows, sizeof(T)), &scratch)) return rc;
-    // a block of zeros stands in for the velocities and torques of every tile (grown under ensure_work's capture rule)
-    const size_t zneed = B * static_cast<size_t>(h.nv) * sizeof(T) + 256;
-    void *zeros = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, zneed, &zeros)) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     hipError_t e;
-    if ((e = hipMemsetAsync(zeros, 0, zneed, hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    if ((e = hipMemsetAsync(zeros, 0, B * static_cast<size_t>(h.nv) * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
     e = launch_osim_chain<T>(d, A, q, static_cast<const T *>(zeros), Linv, J, B, static_cast<T *>(scratch), static_cast<int>(s.grid),
                              s.lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "osim chain launch");
+}
+template <class T>
+int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *bodies, const double *offsets, T *Linv, T *J,
+                   size_t B, int device, void *stream, const T *tf_force, T *tf_lambda, T *tf_dstate)
+{
+    OsimArgs<T> A;
+    if (!osim_chain_args<T>(p, n_contacts, bodies, offsets, J != nullptr, tf_force, tf_lambda, tf_dstate, A)) return 1;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    // the block of zeros (grown under ensure_work's capture rule)
+    void *zeros = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, B * static_cast<size_t>(p->host.nv) * sizeof(T) + 256, &zeros)) return rc;
+    return osim_chain_launch<T>(p, A, q, Linv, J, B, device, stream, static_cast<T *>(zeros));
+}
+
+// The unit-wrench route: 6 n + 1 rows per state through the forward and the inverse dynamics.  Scalars of work space per state: the poses;
+// per row q, wrenches, zeros and the two results.
+size_t osim_unit_per_state(const grbda_plan *p, int n_contacts)
+{
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, R = 6 * static_cast<size_t>(n_contacts) + 1;
+    return nbod * 12 + R * (nq + nbod * 6 + 3 * nv);
+}
+// nb states of that route on the caller's work space: takes nb * osim_unit_per_state scalars from w
+template <class T>
+int inv_osim_unit(const grbda_plan *p, const ContactSet<T> &cs, const T *q, T *Linv, T *J, size_t nb, int device, void *stream, Carver<T> &w)
+{
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies;
+    const size_t m = 6 * static_cast<size_t>(cs.n), R = m + 1, nrows = nb * R;
+    const size_t before = w.taken;
+    T *Xa = w.take(nb * nbod * 12), *qx = w.take(nrows * nq), *fext = w.take(nrows * nbod * 6), *zero = w.take(nrows * nv);
+    T *acc = w.take(nrows * nv), *tau = w.take(nrows * nv);
+    assert(w.taken - before == nb * osim_unit_per_state(p, cs.n));
+    (void)before;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(zero, 0, nrows * nv * sizeof(T), hs);
+    if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    if (int rc = poses<T>(p, q, Xa, nb, device, stream)) return rc;
+    hipLaunchKernelGGL((osim_expand_kernel<T>), dim3(blocks_for(nrows)), dim3(256), 0, hs, cs, q, Xa, static_cast<int>(nq), static_cast<int>(nbod), nb,
+                       qx, fext);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "expand launch");
+    int rc;
+    if ((rc = run<T>(p, false, qx, zero, zero, fext, acc, nrows, device, stream)) || (rc = run<T>(p, true, qx, zero, zero, fext, tau, nrows, device, stream)))
+        return rc;
+    hipLaunchKernelGGL((osim_combine_kernel<T>), dim3(blocks_for(nb * m * m)), dim3(256), 0, hs, acc, tau, static_cast<int>(nv), static_cast<int>(m), nb,
+                       Linv, J);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "combine launch");
+    return GRBDA_OK;
 }
 
 template <class T>
@@ -1516,33 +1574,157 @@ int inv_osim(const grbda_plan *p, const T *q, int n_contacts, const int *bodies,
     }
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
-    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies;
-    const size_t m = 6 * static_cast<size_t>(n_contacts), R = m + 1;
-    const size_t per_state = nbod * 12 + R * (nq + nbod * 6 + 3 * nv);  // poses; per row q, wrenches, zeros, 2 results
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    const size_t m = 6 * static_cast<size_t>(n_contacts);
+    const size_t per_state = osim_unit_per_state(p, n_contacts);
     const Chunk c = fixed_chunk(256u << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
-    const size_t rows = c.chunk * R;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        if (int rc = inv_osim_unit<T>(p, cs, q + b0 * nq, Linv + b0 * m * m, J ? J + b0 * m * nv : nullptr, nb, device, stream, w)) return rc;
+    }
+    return GRBDA_OK;
+}
+
+// ---- contact points and contact-constrained forward dynamics (contact_kernels.hip; include/grbda_hip.h) -----------------------------
+// the contact description of grbda_inv_osim_*, checked on the host
+template <class T>
+int contact_set(const grbda_plan *p, int n_contacts, const int *bodies, const double *offsets, ContactSet<T> &cs)
+{
+    if (!bodies || !offsets) return set_err(GRBDA_EINVAL, "null argument");
+    if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact points per call");
+    cs.n = n_contacts;
+    for (int c = 0; c < n_contacts; c++) {
+        if (bodies[c] < 0 || bodies[c] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+        cs.body[c] = bodies[c];
+        for (int i = 0; i < 3; i++) cs.off[c][i] = static_cast<T>(offsets[3 * c + i]);
+    }
+    return GRBDA_OK;
+}
+// no output array may share a byte with an input array or with another output (null entries are skipped)
+template <size_t NI, size_t NO>
+int no_overlap(const void *const (&in)[NI], const size_t (&in_bytes)[NI], const void *const (&out)[NO], const size_t (&out_bytes)[NO])
+{
+    for (size_t i = 0; i < NO; i++) {
+        for (size_t j = 0; j < NI; j++)
+            if (ranges_overlap(out[i], out_bytes[i], in[j], in_bytes[j])) return set_err(GRBDA_EINVAL, "an output array overlaps an input array");
+        for (size_t j = i + 1; j < NO; j++)
+            if (ranges_overlap(out[i], out_bytes[i], out[j], out_bytes[j])) return set_err(GRBDA_EINVAL, "two output arrays overlap");
+    }
+    return GRBDA_OK;
+}
+template <class T>
+int contact_points_args(const grbda_plan *p, const T *q, const T *qd, const T *ydd, int n_contacts, const int *bodies, const double *offsets,
+                        const T *pos, const T *vel, const T *acc, size_t B, ContactSet<T> &cs)
+{
+    if (!q) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, cs)) return rc;
+    if (!pos && !vel && !acc) return set_err(GRBDA_EINVAL, "no output asked for");
+    if ((vel || acc) && !qd) return set_err(GRBDA_EINVAL, "vel and acc need qd");
+    if (acc && !ydd) return set_err(GRBDA_EINVAL, "acc needs ydd");
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const size_t bo = B * static_cast<size_t>(n_contacts) * 3 * sizeof(T);
+    const void *const in[3] = {q, qd, ydd}, *const out[3] = {pos, vel, acc};
+    const size_t in_bytes[3] = {bq, bv, bv}, out_bytes[3] = {bo, bo, bo};
+    return no_overlap(in, in_bytes, out, out_bytes);
+}
+// Per chunk: poses, and for vel / acc the twists (at ydd, or at zeros when only vel is asked for), then contact_points_kernel.  One slab of
+// p->work for the whole pipeline (twists_core takes its spanning rates from it).
+template <class T>
+int contact_points(const grbda_plan *p, const T *q, const T *qd, const T *ydd, int n_contacts, const int *bodies, const double *offsets, T *pos,
+                   T *vel, T *acc, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<T> cs;
+    if (int rc = contact_points_args<T>(p, q, qd, ydd, n_contacts, bodies, offsets, pos, vel, acc, B, cs)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n = static_cast<size_t>(n_contacts);
+    const bool rates = vel || acc, zero_ydd = rates && !acc;  // (vel alone: the twists' velocity half does not depend on ydd)
+    const size_t per_state = nbod * 12 + (rates ? nbod * 12 + 2 * ns + (zero_ydd ? nv : 0) : 0);
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
     Carver<T> w(wptr, c.chunk * per_state);
-    T *Xa = w.take(c.chunk * nbod * 12), *qx = w.take(rows * nq), *fext = w.take(rows * nbod * 6), *zero = w.take(rows * nv);
-    T *acc = w.take(rows * nv), *tau = w.take(rows * nv);
+    T *Xa = w.take(c.chunk * nbod * 12), *V = rates ? w.take(c.chunk * nbod * 12) : nullptr;
+    T *vs = rates ? w.take(c.chunk * ns) : nullptr, *as = rates ? w.take(c.chunk * ns) : nullptr, *zeros = zero_ydd ? w.take(c.chunk * nv) : nullptr;
     assert(w.taken == w.cap);
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(zero, 0, rows * nv * sizeof(T), hs);
-    if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    hipError_t e;
+    if (zeros && (e = hipMemsetAsync(zeros, 0, c.chunk * nv * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    const T g[3] = {static_cast<T>(p->host.gravity[3]), static_cast<T>(p->host.gravity[4]), static_cast<T>(p->host.gravity[5])};
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
-        const size_t nrows = nb * R;
         if (int rc = poses<T>(p, q + b0 * nq, Xa, nb, device, stream)) return rc;
-        hipLaunchKernelGGL((osim_expand_kernel<T>), dim3(blocks_for(nrows)), dim3(256), 0, hs, cs, q + b0 * nq, Xa, static_cast<int>(nq),
-                           static_cast<int>(nbod), nb, qx, fext);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "expand launch");
+        if (rates)
+            if (int rc = twists_core<T>(p, *t, q + b0 * nq, qd + b0 * nv, zeros ? zeros : ydd + b0 * nv, V, vs, as, nb, device, stream)) return rc;
+        e = launch_contact_points<T>(cs, Xa, V, static_cast<int>(nbod), g, nb, pos ? pos + b0 * n * 3 : nullptr, vel ? vel + b0 * n * 3 : nullptr,
+                                     acc ? acc + b0 * n * 3 : nullptr, hs);
+        if (e != hipSuccess) return hip_err(e, "contact points launch");
+    }
+    return GRBDA_OK;
+}
+
+template <class T>
+int contact_dynamics_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *f_ext, int n_contacts, const int *bodies,
+                          const double *offsets, const T *a_des, double damping, const T *ydd, const T *lambda, const T *ydd_free, size_t B,
+                          ContactSet<T> &cs)
+{
+    if (!q || !qd || !tau || !ydd || !lambda) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, cs)) return rc;
+    if (!std::isfinite(damping) || damping < 0) return set_err(GRBDA_EINVAL, "damping must be finite and not negative");
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const size_t bf = B * static_cast<size_t>(p->host.n_bodies) * 6 * sizeof(T), bc = B * static_cast<size_t>(n_contacts) * 3 * sizeof(T);
+    const void *const in[5] = {q, qd, tau, f_ext, a_des}, *const out[3] = {ydd, lambda, ydd_free};
+    const size_t in_bytes[5] = {bq, bv, bv, bf, bc}, out_bytes[3] = {bv, bc, bv};
+    return no_overlap(in, in_bytes, out, out_bytes);
+}
+// Forward dynamics subject to "these points have this acceleration".  Per chunk, on one slab of p->work carved here for the whole pipeline
+// (the inverse OSIM and the twists take their work arrays from it; the forward dynamics use the scratch slab and work_proj only):
+//   1 ydd_free = FD(q, qd, tau, f_ext)          2 poses          3 twists at ydd_free          4 Linv = J H^-1 J^T of the contact frames
+//   5 contact_solve_kernel: lambda and the wrench rows          6 ydd = FD(q, qd, tau, wrench rows)
+template <class T>
+int contact_dynamics(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *f_ext, int n_contacts, const int *bodies,
+                     const double *offsets, const T *a_des, double damping, T *ydd, T *lambda, T *ydd_free, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<T> cs;
+    if (int rc = contact_dynamics_args<T>(p, q, qd, tau, f_ext, n_contacts, bodies, offsets, a_des, damping, ydd, lambda, ydd_free, B, cs)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    OsimArgs<T> A;
+    const bool chain = osim_chain_args<T>(p, n_contacts, bodies, offsets, false, nullptr, nullptr, nullptr, A);
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n = static_cast<size_t>(n_contacts);
+    const size_t m6 = 6 * n;
+    // ydd_free (when the caller does not keep it), poses, twists and their spanning rates, Linv, wrench rows, and the inverse OSIM's own
+    const size_t osim_ws = chain ? nv : osim_unit_per_state(p, n_contacts);
+    const size_t per_state = (ydd_free ? 0 : nv) + nbod * 24 + 2 * ns + m6 * m6 + nbod * 6 + osim_ws;
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    const T g[3] = {static_cast<T>(p->host.gravity[3]), static_cast<T>(p->host.gravity[4]), static_cast<T>(p->host.gravity[5])};
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        T *yf = ydd_free ? ydd_free + b0 * nv : w.take(nb * nv);
+        T *Xa = w.take(nb * nbod * 12), *V = w.take(nb * nbod * 12), *vs = w.take(nb * ns), *as = w.take(nb * ns);
+        T *Linv = w.take(nb * m6 * m6), *wrench = w.take(nb * nbod * 6);
+        const T *qc = q + b0 * nq, *qdc = qd + b0 * nv, *tc = tau + b0 * nv, *fc = f_ext ? f_ext + b0 * nbod * 6 : nullptr;
         int rc;
-        if ((rc = run<T>(p, false, qx, zero, zero, fext, acc, nrows, device, stream)) ||
-            (rc = run<T>(p, true, qx, zero, zero, fext, tau, nrows, device, stream)))
+        if ((rc = run<T>(p, false, qc, qdc, tc, fc, yf, nb, device, stream)) || (rc = poses<T>(p, qc, Xa, nb, device, stream)) ||
+            (rc = twists_core<T>(p, *t, qc, qdc, yf, V, vs, as, nb, device, stream)))
             return rc;
-        hipLaunchKernelGGL((osim_combine_kernel<T>), dim3(blocks_for(nb * m * m)), dim3(256), 0, hs, acc, tau, static_cast<int>(nv),
-                           static_cast<int>(m), nb, Linv + b0 * m * m, J ? J + b0 * m * nv : nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "combine launch");
+        if (chain) rc = osim_chain_launch<T>(p, A, qc, Linv, nullptr, nb, device, stream, w.take(nb * nv));
+        else rc = inv_osim_unit<T>(p, cs, qc, Linv, nullptr, nb, device, stream, w);
+        if (rc) return rc;
+        hipError_t e = launch_contact_solve<T>(cs, Linv, Xa, V, a_des ? a_des + b0 * n * 3 : nullptr, fc, static_cast<int>(nbod), static_cast<T>(damping), g, nb,
+                                               lambda + b0 * n * 3, wrench, t->bad_count, t->n_cu, hs);
+        if (e != hipSuccess) return hip_err(e, "contact solve launch");
+        if ((rc = run<T>(p, false, qc, qdc, tc, wrench, ydd + b0 * nv, nb, device, stream))) return rc;
     }
     return GRBDA_OK;
 }
@@ -2905,6 +3087,65 @@ int grbda_inv_osim_f32(const grbda_plan *p, const float *q, int n_contacts, cons
                        float *Linv, float *J, size_t B, int device, void *stream)
 {
     return inv_osim<float>(p, q, n_contacts, bodies, offsets, Linv, J, B, device, stream);
+}
+int grbda_contact_points_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, int n_contacts, const int *bodies,
+                             const double *offsets, double *pos, double *vel, double *acc, size_t B, int device, void *stream)
+{
+    return contact_points<double>(p, q, qd, ydd, n_contacts, bodies, offsets, pos, vel, acc, B, device, stream);
+}
+int grbda_contact_points_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, int n_contacts, const int *bodies,
+                             const double *offsets, float *pos, float *vel, float *acc, size_t B, int device, void *stream)
+{
+    return contact_points<float>(p, q, qd, ydd, n_contacts, bodies, offsets, pos, vel, acc, B, device, stream);
+}
+int grbda_contact_dynamics_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *f_ext, int n_contacts,
+                               const int *bodies, const double *offsets, const double *a_des, double damping, double *ydd, double *lambda,
+                               double *ydd_free, size_t B, int device, void *stream)
+{
+    return contact_dynamics<double>(p, q, qd, tau, f_ext, n_contacts, bodies, offsets, a_des, damping, ydd, lambda, ydd_free, B, device, stream);
+}
+int grbda_contact_dynamics_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, const float *f_ext, int n_contacts,
+                               const int *bodies, const double *offsets, const float *a_des, double damping, float *ydd, float *lambda,
+                               float *ydd_free, size_t B, int device, void *stream)
+{
+    return contact_dynamics<float>(p, q, qd, tau, f_ext, n_contacts, bodies, offsets, a_des, damping, ydd, lambda, ydd_free, B, device, stream);
+}
+int grbda_contact_points_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, int n_contacts, const int *bodies,
+                                  const double *offsets, double *pos, double *vel, double *acc, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<double> cs;
+    if (int rc = contact_points_args<double>(p, q, qd, ydd, n_contacts, bodies, offsets, pos, vel, acc, B, cs)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, no = B * static_cast<size_t>(n_contacts) * 3;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = qd ? st.in(qd, B * nv) : nullptr, *dy = ydd ? st.in(ydd, B * nv) : nullptr;
+    double *dp = pos ? st.out(pos, no) : nullptr, *dv = vel ? st.out(vel, no) : nullptr, *da = acc ? st.out(acc, no) : nullptr;
+    return st.run([&] { return contact_points<double>(p, dq, dqd, dy, n_contacts, bodies, offsets, dp, dv, da, B, device, nullptr); });
+}
+int grbda_contact_dynamics_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *f_ext, int n_contacts,
+                                    const int *bodies, const double *offsets, const double *a_des, double damping, double *ydd, double *lambda,
+                                    double *ydd_free, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<double> cs;
+    if (int rc = contact_dynamics_args<double>(p, q, qd, tau, f_ext, n_contacts, bodies, offsets, a_des, damping, ydd, lambda, ydd_free, B, cs))
+        return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, nfe = static_cast<size_t>(p->host.n_bodies) * 6, no = B * static_cast<size_t>(n_contacts) * 3;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dt = st.in(tau, B * nv);
+    const double *dfe = f_ext ? st.in(f_ext, B * nfe) : nullptr, *dad = a_des ? st.in(a_des, no) : nullptr;
+    double *dy = st.out(ydd, B * nv), *dl = st.out(lambda, no), *dyf = ydd_free ? st.out(ydd_free, B * nv) : nullptr;
+    return st.run([&] {
+        return contact_dynamics<double>(p, dq, dqd, dt, dfe, n_contacts, bodies, offsets, dad, damping, dy, dl, dyf, B, device, nullptr);
+    });
 }
 int grbda_aba_sharded_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, float *ydd, size_t B,
                           int n_gpus)

@@ -192,6 +192,30 @@ template <class T>
 hipError_t launch_osim_chain(const ChainDev<T> &P, const OsimArgs<T> &A, const T *q, const T *zeros, T *Linv, T *J, size_t B,
                              T *scratch, int grid, size_t lds_bytes, hipStream_t stream);
 
+// contact points of one call (capi.cpp builds it from the caller's host arrays; passed to the kernels by value): point off[c], body
+// coordinates, fixed in body body[c]
+constexpr int kMaxContacts = 8;
+template <class T>
+struct ContactSet {
+    int n;
+    int body[kMaxContacts];
+    T off[kMaxContacts][3];
+};
+// contact-point kinematics and the per-state contact solve (contact_kernels.hip).  Xa: body poses, V: body twists, g: the plan's gravity
+// (linear part).  launch_contact_points: pos / vel / acc [nb][n][3], any of them null (V may be null when only pos is asked for).
+// launch_contact_solve: Linv [nb][6 n][6 n], V the twists at the unconstrained accelerations, a_des [nb][n][3] or null, fext_in
+// [nb][n_bodies][6] or null; writes lambda [nb][n][3] and the wrench rows fext_out [nb][n_bodies][6].
+template <class T>
+hipError_t launch_contact_points(const ContactSet<T> &cs, const T *Xa, const T *V, int n_bodies, const T g[3], size_t nb, T *pos, T *vel, T *acc,
+                                 hipStream_t stream);
+template <class T>
+hipError_t launch_contact_solve(const ContactSet<T> &cs, const T *Linv, const T *Xa, const T *V, const T *a_des, const T *fext_in, int n_bodies,
+                                T mu, const T g[3], size_t nb, T *lambda, T *fext_out, unsigned long long *bad_count, int n_cu,
+                                hipStream_t stream);
+size_t contact_solve_lds_bytes(int n_contacts, size_t elem, int lanes);
+int contact_solve_lanes(int n_contacts, size_t elem);
+hipError_t set_max_dynamic_lds_contact();
+
 // composite-rigid-body algorithm (crba_kernels.hip)
 template <class T>
 hipError_t launch_crba(const DevPlan<T> &P, const CrbaBody *cb, int n_clusters, int n_rows, const T *q, T *H, size_t B, T *scratch,

@@ -239,7 +239,9 @@ int grbda_rnea_derivatives_host_f64(const grbda_plan *plan, const double *q, con
  * grbda_fd_dtau_* / grbda_fd_dq_* / grbda_fd_dqd_* / grbda_fd_derivatives_* (a pivot of the factorisation <= 0 or not finite: massless
  * chains, a singular pose of an implicit cluster) get NaN / Inf results; the reference's ColPivHouseholderQR would return some
  * least-squares answer there (src/Dynamics/ClusterTreeNode.cpp:33-37).  The solve kernels COUNT such states per device: this call
- * synchronises the device, returns the count since the last reset and (reset != 0) clears it. */
+ * synchronises the device, returns the count since the last reset and (reset != 0) clears it.  The contact solve of
+ * grbda_contact_dynamics_* counts into the same word: a state whose J_w H^-1 J_w^T + damping I had such a pivot (redundant contacts
+ * with damping = 0) has NaN in its lambda and ydd. */
 int grbda_spd_bad_pivots(int device, unsigned long long *count, int reset);
 /* The name of the kernel grbda_aba_* (kind 0) / grbda_rnea_* (kind 1) launches for a batch of B states in this precision (32 | 64) on
  * this device, without external forces -- as rocprofv3 prints it (template arguments included; the chain kernels' inverse dynamics
@@ -403,6 +405,60 @@ int grbda_inv_osim_f64(const grbda_plan *plan, const double *q, int n_contacts, 
                        const double *offsets, double *Linv, double *J, size_t B, int device, void *stream);
 int grbda_inv_osim_f32(const grbda_plan *plan, const float *q, int n_contacts, const int *bodies,
                        const double *offsets, float *Linv, float *J, size_t B, int device, void *stream);
+
+/* ---- contact points and contact-constrained forward dynamics ------------------------------------------------------------------
+ * Contacts are described as for grbda_inv_osim_*: n_contacts in 1 .. 8, host arrays bodies[n] and offsets[n][3] (a point fixed in the
+ * body, body coordinates).  Every other array is a device array, row-major; the calls only enqueue on `stream`.
+ *
+ * grbda_contact_points_*: world-frame position, velocity and classical acceleration of the points -- cp.position_ / velocity_ /
+ * acceleration_ after TreeModel::contactPointForwardKinematics / contactPointForwardAccelerationKinematics (TreeModel.cpp:59-100), what
+ * getPosition / getLinearVelocity / getLinearAcceleration return for a body with an offset.  pos, vel, acc: [B][n][3] each, world axes;
+ * any may be NULL, not all three.  vel needs qd, acc needs qd and ydd; otherwise those inputs may be NULL.  With E, r of
+ * grbda_body_poses_* and [omega; v | alpha; a] of grbda_body_twists_* (body axes, a carrying -gravity), o the offset and g the plan's
+ * gravity:
+ *     p      = r + E^T o
+ *     p_dot  = E^T (v + omega x o)
+ *     p_ddot = E^T (a + alpha x o + omega x (v + omega x o)) + g          (a point of a body at rest: 0)
+ *
+ * grbda_contact_dynamics_*: the forward dynamics subject to "these points have this acceleration" (Pinocchio:
+ * forwardDynamics(q, v, tau, J, gamma, inv_damping)); the reference leaves this solve to the simulator that calls
+ * inverseOperationalSpaceInertiaMatrix and the contact-point kinematics.  With J_w [3 n][nv] the world-frame Jacobian of the points
+ * (E^T times the force rows of the frame Jacobians of grbda_inv_osim_*):
+ *     ydd_free = FD(q, qd, tau, f_ext)
+ *     (J_w H^-1 J_w^T + damping I) lambda = a_des - p_ddot(q, qd, ydd_free)
+ *     ydd      = FD(q, qd, tau, f_ext + world wrenches [p x lambda_c ; lambda_c] on bodies[c])
+ *   a_des     NULL (zero) or [B][n][3]: the world-frame acceleration each point shall have (the caller puts a Baumgarte term here)
+ *   damping   mu >= 0, finite
+ *   ydd [B][nv], lambda [B][n][3]   outputs; lambda: world-frame forces ON the bodies at the points
+ *   ydd_free  NULL or [B][nv]: the unconstrained accelerations
+ * The result satisfies p_ddot(ydd) = a_des - mu lambda: the rigid constraint for mu = 0 and independent contacts.  Redundant contacts
+ * (several points on one foot) make the matrix singular and need mu > 0.  The matrix is factored per state by Cholesky
+ * (contact_kernels.hip): a pivot that is not positive or not finite gives NaN in that state's lambda and ydd (ydd_free is not
+ * affected), the call still returns GRBDA_OK, and the state is counted in the counter behind grbda_spd_bad_pivots.
+ * Per chunk of the batch: forward dynamics, poses, twists, inverse OSIM, one solve kernel, forward dynamics -- on every plan that
+ * grbda_inv_osim_*, grbda_body_twists_* and grbda_aba_* with f_ext accept.
+ *
+ * Errors, all decided on the host before anything is enqueued: GRBDA_EINVAL for NULL required pointers, n_contacts outside 1 .. 8, a
+ * body index out of range, a damping that is negative or not finite, no output asked for, outputs that overlap inputs or each other.
+ * B == 0: GRBDA_OK.  No synchronisation, no allocation beyond the scratch slab and the work slab (chunked like the other pipelines,
+ * GRBDA_WORK_MAX_MB): capturable after one eager call of the same B and n_contacts on the stream; gravity is read at launch.
+ * The _host_ variants take host arrays (allocate, copy and synchronise per call). */
+int grbda_contact_points_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, int n_contacts,
+                             const int *bodies, const double *offsets, double *pos, double *vel, double *acc, size_t B, int device,
+                             void *stream);
+int grbda_contact_points_f32(const grbda_plan *plan, const float *q, const float *qd, const float *ydd, int n_contacts, const int *bodies,
+                             const double *offsets, float *pos, float *vel, float *acc, size_t B, int device, void *stream);
+int grbda_contact_dynamics_f64(const grbda_plan *plan, const double *q, const double *qd, const double *tau, const double *f_ext,
+                               int n_contacts, const int *bodies, const double *offsets, const double *a_des, double damping, double *ydd,
+                               double *lambda, double *ydd_free, size_t B, int device, void *stream);
+int grbda_contact_dynamics_f32(const grbda_plan *plan, const float *q, const float *qd, const float *tau, const float *f_ext,
+                               int n_contacts, const int *bodies, const double *offsets, const float *a_des, double damping, float *ydd,
+                               float *lambda, float *ydd_free, size_t B, int device, void *stream);
+int grbda_contact_points_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, int n_contacts,
+                                  const int *bodies, const double *offsets, double *pos, double *vel, double *acc, size_t B, int device);
+int grbda_contact_dynamics_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *tau, const double *f_ext,
+                                    int n_contacts, const int *bodies, const double *offsets, const double *a_des, double damping,
+                                    double *ydd, double *lambda, double *ydd_free, size_t B, int device);
 
 /* ---- convenience: host pointers (single-state facade calls, small batches) ------------------ */
 /* allocate, copy in, run on `device`, copy out, synchronise.  Still the HIP path. */
