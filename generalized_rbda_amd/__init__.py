@@ -37,7 +37,7 @@ C_ABI_SYMBOLS = [
     "grbda_mass_matrix_host_f64", "grbda_fd_derivatives_host_f64",
     "grbda_body_twists_f64", "grbda_body_twists_f32", "grbda_body_twists_host_f64",
     "grbda_state_input_dims", "grbda_state_to_independent_f64", "grbda_state_to_independent_f32",
-    "grbda_state_to_independent_host_f64", "grbda_spd_bad_pivots", "grbda_kernel_name", "grbda_project_positions_host_f64",
+    "grbda_state_to_independent_host_f64", "grbda_spd_bad_pivots", "grbda_kernel_name", "grbda_contact_solve_launch", "grbda_project_positions_host_f64",
     "grbda_rnea_derivatives_f64", "grbda_rnea_derivatives_f32", "grbda_rnea_derivatives_host_f64",
     "grbda_integrate_f64", "grbda_integrate_f32", "grbda_step_f64", "grbda_step_f32", "grbda_rollout_f64", "grbda_rollout_f32",
     "grbda_integrate_host_f64", "grbda_step_host_f64",
@@ -105,6 +105,7 @@ def lib() -> ctypes.CDLL:
     L.grbda_time_kernel.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
                                     c_void_p, c_int, POINTER(c_float)]
     L.grbda_device_count.restype = c_int
+    L.grbda_contact_solve_launch.argtypes = [c_int, c_int, c_int, POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]
     for sfx in ("f64", "f32"):
         getattr(L, "grbda_bias_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
                                                     c_void_p]
@@ -819,3 +820,11 @@ def spd_bad_pivots(device: int = 0, reset: bool = True) -> int:
     n = ctypes.c_ulonglong(0)
     _check(lib().grbda_spd_bad_pivots(int(device), ctypes.byref(n), 1 if reset else 0))
     return int(n.value)
+
+
+def contact_solve_launch(n_contacts: int, dtype: str, device: int = -1):
+    """(lanes, lds_bytes, grid_cap) of the solve kernel contact_dynamics launches for n_contacts in "f32" / "f64" on `device`
+    (grbda_contact_solve_launch); device < 0 touches no device and gives grid_cap for a single CU."""
+    lanes, lds, cap = c_int(0), c_size_t(0), c_size_t(0)
+    _check(lib().grbda_contact_solve_launch(int(n_contacts), 32 if dtype == "f32" else 64, int(device), byref(lanes), byref(lds), byref(cap)))
+    return lanes.value, lds.value, cap.value

@@ -178,6 +178,15 @@ void free_chain_tables(Tables &ct)
         (void)hipFree(ptr);
 }
 
+// the CU count every persistent grid is sized by
+hipError_t device_cu_count(int device, int *n_cu)
+{
+    hipDeviceProp_t prop;
+    if (hipError_t e = hipGetDeviceProperties(&prop, device); e != hipSuccess) return e;
+    *n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    return hipSuccess;
+}
+
 int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
 {
     int count = 0;
@@ -267,9 +276,7 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
             (e = up(p->crow.data(), p->crow.size() * sizeof(int32_t), (void **)&t.crow)) != hipSuccess)
             return hip_err(e, "plan upload");
     }
-    hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_err(e, "hipGetDeviceProperties");
-    t.n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if ((e = device_cu_count(device, &t.n_cu)) != hipSuccess) return hip_err(e, "hipGetDeviceProperties");
     if ((e = set_max_dynamic_lds()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     if ((e = set_max_dynamic_lds_deriv()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     if ((e = set_max_dynamic_lds_minv()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
@@ -3109,6 +3116,24 @@ int grbda_contact_dynamics_f32(const grbda_plan *p, const float *q, const float 
                                float *ydd_free, size_t B, int device, void *stream)
 {
     return contact_dynamics<float>(p, q, qd, tau, f_ext, n_contacts, bodies, offsets, a_des, damping, ydd, lambda, ydd_free, B, device, stream);
+}
+int grbda_contact_solve_launch(int n_contacts, int precision, int device, int *lanes, size_t *lds_bytes, size_t *grid_cap)
+{
+    if (!lanes || !lds_bytes || !grid_cap || (precision != 32 && precision != 64)) return set_err(GRBDA_EINVAL, "bad argument");
+    if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact points per call");
+    const ContactSolveLaunch L = contact_solve_launch(n_contacts, precision == 32 ? sizeof(float) : sizeof(double));
+    if (L.lanes == 0) return set_err(GRBDA_EINVAL, "the contact solve does not fit the LDS");
+    int n_cu = 1;
+    if (device >= 0) {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_err(GRBDA_ENODEVICE, "no HIP device available");
+        if (device >= n) return set_err(GRBDA_EINVAL, "device index out of range");
+        if (hipError_t e = device_cu_count(device, &n_cu); e != hipSuccess) return hip_err(e, "hipGetDeviceProperties");
+    }
+    *lanes = L.lanes;
+    *lds_bytes = L.lds_bytes;
+    *grid_cap = static_cast<size_t>(n_cu) * L.per_cu;
+    return GRBDA_OK;
 }
 int grbda_contact_points_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, int n_contacts, const int *bodies,
                                   const double *offsets, double *pos, double *vel, double *acc, size_t B, int device)

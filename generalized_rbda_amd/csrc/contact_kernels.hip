@@ -241,18 +241,27 @@ hipError_t launch_contact_points(const ContactSet<T> &cs, const T *Xa, const T *
     hipLaunchKernelGGL((contact_points_kernel<T>), dim3(blocks), dim3(256), 0, stream, cs, Xa, V, n_bodies, g[0], g[1], g[2], nb, pos, vel, acc);
     return hipGetLastError();
 }
+// what one launch of the solve is made of: the width, its dynamic LDS and the workgroups a CU holds (the grid cap is n_cu times that);
+// lanes == 0 when no width fits the 160 KiB.  launch_contact_solve and grbda_contact_solve_launch both read it from here.
+ContactSolveLaunch contact_solve_launch(int n_contacts, size_t elem)
+{
+    ContactSolveLaunch L;
+    L.lanes = contact_solve_lanes(n_contacts, elem);
+    L.lds_bytes = contact_solve_lds_bytes(n_contacts, elem, L.lanes);
+    if (L.lds_bytes > 160u * 1024u) L.lanes = 0;
+    L.per_cu = std::max<size_t>(1, std::min<size_t>(32, lds_workgroups_per_cu(L.lds_bytes)));
+    return L;
+}
 template <class T>
 hipError_t launch_contact_solve(const ContactSet<T> &cs, const T *Linv, const T *Xa, const T *V, const T *a_des, const T *fext_in, int n_bodies,
                                 T mu, const T g[3], size_t nb, T *lambda, T *fext_out, unsigned long long *bad_count, int n_cu,
                                 hipStream_t stream)
 {
-    const int lanes = contact_solve_lanes(cs.n, sizeof(T));
-    const size_t lds = contact_solve_lds_bytes(cs.n, sizeof(T), lanes);
-    if (lds > 160u * 1024u) return hipErrorInvalidValue;
-    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(32, lds_workgroups_per_cu(lds)));
-    const size_t grid = std::min(static_cast<size_t>(n_cu) * per_cu, (nb + lanes - 1) / lanes);
-    hipLaunchKernelGGL((contact_solve_kernel<T>), dim3(static_cast<unsigned>(grid)), dim3(lanes), lds, stream, cs, Linv, Xa, V, a_des, fext_in,
-                       n_bodies, mu, g[0], g[1], g[2], nb, lambda, fext_out, bad_count);
+    const ContactSolveLaunch L = contact_solve_launch(cs.n, sizeof(T));
+    if (L.lanes == 0) return hipErrorInvalidValue;
+    const size_t grid = std::min(static_cast<size_t>(n_cu) * L.per_cu, (nb + L.lanes - 1) / L.lanes);
+    hipLaunchKernelGGL((contact_solve_kernel<T>), dim3(static_cast<unsigned>(grid)), dim3(L.lanes), L.lds_bytes, stream, cs, Linv, Xa, V, a_des,
+                       fext_in, n_bodies, mu, g[0], g[1], g[2], nb, lambda, fext_out, bad_count);
     return hipGetLastError();
 }
 template hipError_t launch_contact_points<float>(const ContactSet<float> &, const float *, const float *, int, const float[3], size_t, float *,

@@ -214,6 +214,12 @@ hipError_t launch_contact_solve(const ContactSet<T> &cs, const T *Linv, const T 
                                 hipStream_t stream);
 size_t contact_solve_lds_bytes(int n_contacts, size_t elem, int lanes);
 int contact_solve_lanes(int n_contacts, size_t elem);
+struct ContactSolveLaunch {
+    int lanes;         // states per workgroup (0: nothing fits)
+    size_t lds_bytes;  // dynamic LDS per workgroup
+    size_t per_cu;     // workgroups per CU the grid is capped at
+};
+ContactSolveLaunch contact_solve_launch(int n_contacts, size_t elem);
 hipError_t set_max_dynamic_lds_contact();
 
 // composite-rigid-body algorithm (crba_kernels.hip)

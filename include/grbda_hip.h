@@ -454,6 +454,11 @@ int grbda_contact_dynamics_f64(const grbda_plan *plan, const double *q, const do
 int grbda_contact_dynamics_f32(const grbda_plan *plan, const float *q, const float *qd, const float *tau, const float *f_ext,
                                int n_contacts, const int *bodies, const double *offsets, const float *a_des, double damping, float *ydd,
                                float *lambda, float *ydd_free, size_t B, int device, void *stream);
+/* What grbda_contact_dynamics_* launches its solve kernel with for n_contacts (1 .. 8) in this precision (32 | 64): the states per
+ * workgroup (64, 32 or 16), the dynamic LDS of a workgroup in bytes, and the most workgroups one launch has -- the CUs of `device` times
+ * the workgroups a CU holds; batches beyond grid_cap * lanes states take further trips of the grid.  device < 0 touches no device and
+ * reports grid_cap for a single CU.  The launch reads the same record (contact_kernels.hip, contact_solve_launch). */
+int grbda_contact_solve_launch(int n_contacts, int precision, int device, int *lanes, size_t *lds_bytes, size_t *grid_cap);
 int grbda_contact_points_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, int n_contacts,
                                   const int *bodies, const double *offsets, double *pos, double *vel, double *acc, size_t B, int device);
 int grbda_contact_dynamics_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *tau, const double *f_ext,

@@ -98,6 +98,14 @@ SETS = {
     # four corners of each sole of the MIT Humanoid: 8 contacts, rank 12 of 24 -- singular without damping
     "humanoid_soles": ("urdf_mit_humanoid", ["left_ankle_link"] * 4 + ["right_ankle_link"] * 4, _CORNERS * 2),
 }
+# the Mini Cheetah sets of test_contact_solve_gpu.py, one per contact count: up to four feet; four feet and a point of the floating-base
+# body; four feet and 2, 3, 4 further points along shanks that already carry a foot (several contacts on one body: singular without damping)
+_KNEES = SETS["cheetah_feet"][1]
+_SHANK = [(0.03, 0.01, -0.1), (-0.02, 0.015, -0.05), (0.01, -0.02, -0.15), (0.02, 0.02, -0.12)]
+for _n in range(1, 9):
+    _names = _KNEES[:_n] if _n <= 4 else _KNEES + (["Floating Base"] if _n == 5 else _KNEES[: _n - 4])
+    _offs = [(0.0, 0.0, -0.2)] * min(_n, 4) + ([(0.15, -0.04, 0.03)] if _n == 5 else _SHANK[: max(_n - 4, 0)])
+    SETS[f"cheetah_n{_n}"] = ("urdf_mini_cheetah", _names, _offs)
 
 
 def contact_set(key):
@@ -105,6 +113,61 @@ def contact_set(key):
     model, names, offsets = SETS[key]
     blob = EP._model(model)
     return model, [body_index(blob, nm) for nm in names], offsets
+
+
+# ---- the solve alone: what contact_solve_kernel reads, and how well its lambda solves it (test_contact_solve_gpu.py) -----------------
+def solve_inputs(Linv, Xa, V, bodies, offsets, a_des, mu, g):
+    """(A [B, 3 n, 3 n], rhs [B, 3 n]) of the contact solve in float64 from the arrays the kernel reads -- the header comment of
+    contact_kernels.hip restated: Linv [B, 6 n, 6 n] (inv_osim), Xa [B, n_bodies, 12] (body_poses), V [B, n_bodies, 12] (body_twists at
+    ydd_free), g the gravity's linear part:
+        A   = R Linv_ff R^T + mu I,  R = blockdiag E_c^T, Linv_ff the force-force 3 x 3 blocks
+        rhs = a_des - p_ddot,        p_ddot = E^T (a + alpha x o + omega x (v + omega x o)) + g
+    The kernel factors the lower triangle (blocks c2 <= c1 of Linv_ff and, of a diagonal block's product, the entries j <= i): A is the
+    symmetric matrix of that triangle, so what Linv lacks in symmetry is not charged to the solve."""
+    Linv, Xa, V = (np.asarray(a, dtype=np.float64) for a in (Linv, Xa, V))
+    B, n = Linv.shape[0], len(bodies)
+    o = np.asarray(offsets, dtype=np.float64)[None]
+    E = Xa[:, list(bodies), :9].reshape(B, n, 3, 3)
+    Lff = Linv.reshape(B, n, 6, n, 6)[:, :, 3:, :, 3:]  # [B, c1, 3, c2, 3]
+    A = np.einsum("bcki,bckdl,bdlj->bcidj", E, Lff, E).reshape(B, 3 * n, 3 * n)
+    A = np.tril(A) + np.swapaxes(np.tril(A, -1), 1, 2) + mu * np.eye(3 * n)[None]
+    W = V[:, list(bodies)]
+    w, v, al, a = W[:, :, 0:3], W[:, :, 3:6], W[:, :, 6:9], W[:, :, 9:12]
+    acc = _to_world(E, a + np.cross(al, o) + np.cross(w, v + np.cross(w, o))) + np.asarray(g, dtype=np.float64)[None, None]
+    rhs = (np.zeros((B, n, 3)) if a_des is None else np.asarray(a_des, dtype=np.float64)) - acc
+    return A, rhs.reshape(B, 3 * n)
+
+
+def backward_error(A, lam, rhs):
+    """|A lam - rhs|_inf / (|A|_inf |lam|_inf + |rhs|_inf) per state: small for every solve that is stable, whatever cond(A).  The
+    residual is evaluated in extended precision: in float64 its own rounding is as large as the residual of a good fp64 solve."""
+    A, rhs = np.asarray(A, dtype=np.longdouble), np.asarray(rhs, dtype=np.longdouble)
+    lam = np.asarray(lam, dtype=np.longdouble).reshape(rhs.shape)
+    res = np.abs((A * lam[:, None, :]).sum(axis=2) - rhs).max(axis=1)
+    return (res / (np.abs(A).sum(axis=2).max(axis=1) * np.abs(lam).max(axis=1) + np.abs(rhs).max(axis=1))).astype(np.float64)
+
+
+def cholesky_solve(A, rhs, dtype):
+    """lambda [B, m] of a plain Cholesky solve carried out in `dtype` on A and rhs rounded to it (the yardstick of the kernel's solve)"""
+    A, y = np.array(A, dtype=dtype), np.array(rhs, dtype=dtype)
+    m = A.shape[1]
+    L = np.zeros_like(A)
+    for j in range(m):
+        L[:, j, j] = np.sqrt(A[:, j, j] - (L[:, j, :j] * L[:, j, :j]).sum(axis=1, dtype=dtype))
+        for i in range(j + 1, m):
+            L[:, i, j] = (A[:, i, j] - (L[:, i, :j] * L[:, j, :j]).sum(axis=1, dtype=dtype)) / L[:, j, j]
+    for i in range(m):
+        y[:, i] = (y[:, i] - (L[:, i, :i] * y[:, :i]).sum(axis=1, dtype=dtype)) / L[:, i, i]
+    for i in range(m - 1, -1, -1):
+        y[:, i] = (y[:, i] - (L[:, i + 1:, i] * y[:, i + 1:]).sum(axis=1, dtype=dtype)) / L[:, i, i]
+    assert y.dtype == np.dtype(dtype)
+    return y
+
+
+def cholesky_bound(m, dtype):
+    """m (3 m + 1) u: the backward error a Cholesky solve of order m in `dtype` is bounded by (Higham, Accuracy and Stability of
+    Numerical Algorithms, theorem 10.4, gamma_{3 m + 1} to first order and summed over a row for the infinity norm)"""
+    return m * (3 * m + 1) * float(np.finfo(dtype).eps) / 2
 
 
 def rel_per_state(got, ref):

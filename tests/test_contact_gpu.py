@@ -7,7 +7,7 @@ two spanning-tree models; contact_dynamics (ydd, lambda, ydd_free) on the force-
 OSIM, implicit clusters, one and eight contacts (the latter redundant: damping 1e-3, with external forces), the spanning-tree route --
 and on the device outputs alone p_ddot(ydd) + mu lambda = a_des at 1e-8.
 fp32 at TOL32 on float32-rounded inputs against the fp64 reference (the two sets with cond(A) <= 2.4e2); the measured worst is printed.
-Then: the singular solve is counted or finite, a chunked call equals the one-chunk call bit for bit, a captured call replays the eager
+Then: the singular solve is counted or finite (and counts exactly the states whose lambda is NaN, ydd_free finite), a chunked call equals the one-chunk call bit for bit, a captured call replays the eager
 bits, and the host-array variant equals the device call bit for bit."""
 import ctypes
 import functools
@@ -183,6 +183,10 @@ def test_singular_solve_is_counted_or_finite(gpu):
     finite = all(np.isfinite(_np(o)).all() for o in outs)
     print(f"rank-deficient contacts without damping: {bad} states counted, outputs finite: {finite}")
     assert bad > 0 or finite
+    # the contract state by state: a counted state is a state whose lambda is NaN, and ydd_free is untouched by the solve
+    nan_states = int(np.isnan(_np(outs[1])).reshape(B, -1).any(axis=1).sum())
+    assert bad == nan_states, f"{bad} states counted, {nan_states} states with NaN in lambda"
+    assert np.isfinite(_np(outs[2])).all(), "ydd_free is not finite"
 
 
 def test_chunked_call_equals_the_one_chunk_call(gpu, monkeypatch):
