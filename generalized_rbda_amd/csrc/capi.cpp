@@ -1829,16 +1829,146 @@ __global__ void combine_kernel(int mode, const T *__restrict__ r, int nv, int R,
     }
 }
 
+// ---- derivative routes: which stage computes each output of the derivative entry points -- ONE definition (choose_derivs), asked once per
+// call, as choose_aba / Route.  The analytic recursion covers explicit clusters up to nv = 64, the manifold route models with implicit
+// clusters through the spanning tree (manifold_kernels.hip); everything else is a difference batch of derived().
+inline bool analytic_covers(const grbda_plan *p)
+{
+    return p->host.deriv.ok && p->host.crba.ok && !p->opt.no_analytic && !p->opt.no_crba && p->host.nv <= kWave;
+}
+inline bool manifold_covers(const grbda_plan *p)
+{
+    return p->span && !p->opt.no_manifold && !p->opt.no_analytic && p->host.nv <= kWave && p->span->host.nv <= kWave &&
+           p->host.deriv.related.size() == static_cast<size_t>(p->host.nv);
+}
+// BY_MINV: H^-1 = W^T W from the articulated-body quantities (minv_kernels.hip); BY_FACTOR: dense factorisation of H (deriv_kernels.hip);
+// BY_MANIFOLD: the projected spanning-tree matrices and the same factorisation; BY_DIFFERENCES: a batch of derived()
+enum DerivPath { NOT_WANTED, BY_MINV, BY_FACTOR, BY_MANIFOLD, BY_DIFFERENCES };
+enum MassPath { MASS_MANIFOLD, MASS_CRBA, MASS_UNIT_BATCH };
+struct DerivRoute {
+    DerivPath dq, dqd, dtau;
+    bool solve_f64;  // BY_FACTOR: fp32 matrices factorised in fp64 (GRBDA_SOLVE_F64)
+    MassPath mass;   // (whatever else is wanted)
+};
+// `minv_tables`: DeviceTables::minv_bodies and minv_coltab are both on the device
+DerivRoute choose_derivs(const grbda_plan *p, bool minv_tables, size_t elem, bool dq, bool dqd, bool dtau)
+{
+    const bool manifold = manifold_covers(p);
+    // (H = G^T H_s G through the spanning tree is asked first, then one CRBA launch, instead of nv + 1 inverse dynamics)
+    const MassPath mass = p->opt.no_crba ? MASS_UNIT_BATCH : (manifold ? MASS_MANIFOLD : (p->host.crba.ok ? MASS_CRBA : MASS_UNIT_BATCH));
+    DerivPath state = BY_DIFFERENCES, tau = BY_DIFFERENCES;  // d/dq and d/dqd share a path
+    bool wide = false;
+    if (analytic_covers(p)) {
+        const MinvProgram &mv = p->host.deriv.minv;
+        wide = elem == 4 && p->opt.solve_f64;
+        // (GRBDA_NO_MINV=1 keeps the factorisation route: A/B runs)
+        const bool minv = mv.ok && minv_tables && !wide && !p->opt.no_minv && minv_solve_lds_bytes(p->host.nv, (dq ? 1 : 0) + (dqd ? 1 : 0), mv.n_entries, elem) <= 160u * 1024u;
+        state = tau = minv ? BY_MINV : BY_FACTOR;
+    } else if (manifold) {
+        // plans with big clusters (beyond the structured limits): d/dtau by the manifold route, d/dq and d/dqd by difference batches
+        tau = BY_MANIFOLD;
+        state = p->host.big_clusters ? BY_DIFFERENCES : BY_MANIFOLD;
+    }
+    return {dq ? state : NOT_WANTED, dqd ? state : NOT_WANTED, dtau ? tau : NOT_WANTED, wide, mass};
+}
+
+// ---- launch sites shared by the derivative pipelines -----------------------------------------------------------------------------------
+// a persistent grid: no more workgroups than the LDS of a CU holds at once (JVRC-1's unpack: 12 of its 12.4 KB blocks, not 16) or than units of work
+inline size_t persistent_grid(int n_cu, size_t cap, size_t lds_bytes, size_t units)
+{
+    return std::min(static_cast<size_t>(n_cu) * std::min(cap, lds_workgroups_per_cu(lds_bytes + 512)), units);
+}
+// whole groups of `il` states in one call of fn(b0, nb, il) (interleaved layouts), the tail of the batch in a second, state-major
+template <class Fn>
+int for_groups_then_tail(size_t B, int il, Fn fn)
+{
+    const size_t Bg = il > 1 ? B / il * il : 0;
+    if (int rc = Bg ? fn(static_cast<size_t>(0), Bg, il) : GRBDA_OK) return rc;
+    return B > Bg ? fn(Bg, B - Bg, 1) : GRBDA_OK;
+}
+// The batched SPD solve on H in packed rows: H^-1 and up to two solved right-hand sides.  One wavefront per state, as many as the LDS of a CU holds;
+// `mfma`: the matrix-core kernel, workgroups of four wavefronts on groups of kDerivGroup states.  `wide`: fp32 in fp64.  `il`: the plain fp32 solve only.
+template <class T>
+hipError_t spd_solve_stage(const DeviceTables &t, const T *H, const T *r1, const T *r2, T *Hinv, T *x1, T *x2, int nv, int n_rhs, size_t nb,
+                           bool wide, bool mfma, int il, hipStream_t hs)
+{
+    const size_t lds = spd_solve_lds_bytes(nv, wide ? 8 : sizeof(T), n_rhs);
+    const size_t cap = mfma ? static_cast<size_t>(spd_mfma_workgroups_per_cu(nv)) : 16;
+    const size_t per_cu = std::max<size_t>(1, std::min(lds ? lds_workgroups_per_cu(lds) : 16, cap));
+    const size_t units = mfma ? (nb + kDerivGroup - 1) / kDerivGroup : nb;
+    const int grid = static_cast<int>(std::min(static_cast<size_t>(t.n_cu) * per_cu, units));
+    if constexpr (sizeof(T) == 8) return launch_spd_solve<double, double>(H, 1, r1, r2, Hinv, x1, x2, t.deriv_related, nv, nb, grid, hs, 1);
+    else if (wide) return launch_spd_solve<float, double>(H, 1, r1, r2, Hinv, x1, x2, t.deriv_related, nv, nb, grid, hs, 1);
+    else return launch_spd_solve<float, float>(H, 1, r1, r2, Hinv, x1, x2, t.deriv_related, nv, nb, grid, hs, il);
+}
+// The spanning-tree stage of a chunk: the spanning state and the coupling rows of the constraint (q_s, qd_s, qdd_s, cpl), the spanning
+// tree's inverse dynamics into x_s, and its derivative recursion into (Aq, Av, Hs) where Hs is given.  Without x_s (H only) the
+// recursion runs at zero velocity and acceleration -- its H does not depend on them -- and nothing but q_s comes from the constraint.
+template <class T>
+int spanning_stage(const grbda_plan *p, const DeviceTables &t, const DeviceTables &ts, const DevPlan<T> &d, const DevPlan<T> &ds, int want_d, const T *q, const T *qd,
+                   const T *ydd, const T *f_ext, T *q_s, T *qd_s, T *qdd_s, T *cpl, T *x_s, T *Aq, T *Av, T *Hs, size_t nb, size_t chunk, int device, void *stream)
+{
+    const grbda_plan *sp = p->span;
+    const size_t nv_s = sp->host.nv;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    hipError_t e;
+    if (!x_s && (e = hipMemsetAsync(qd_s, 0, 2 * chunk * nv_s * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    e = launch_manifold_constraint<T>(d, p->host.n_clusters, t.span_q, t.span_v, t.crow, sp->host.nq, static_cast<int>(nv_s), p->n_cpl_rows, want_d, q, qd, ydd,
+                                      q_s, qd_s, x_s ? qdd_s : nullptr, cpl, nb, static_cast<int>(tile_grid(t.n_cu, 4, nb)), hs, p->constraint_shape, p->has_trig);
+    if (e != hipSuccess) return hip_err(e, "manifold constraint launch");
+    if (!x_s && (e = hipMemsetAsync(qd_s, 0, chunk * nv_s * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    if (int rc = x_s ? run<T>(sp, true, q_s, qd_s, qdd_s, f_ext, x_s, nb, device, stream) : GRBDA_OK) return rc;
+    if (!Hs) return GRBDA_OK;
+    const size_t g2 = tile_grid(ts.n_cu, 4, nb);
+    void *scratch = nullptr;
+    if (int rc = ensure_scratch(sp, device, stream, scratch_bytes(g2, sp->host.deriv.n_rows, sizeof(T)), &scratch)) return rc;
+    e = launch_rnea_deriv<T>(ds, ts.deriv_bodies, sp->host.n_clusters, sp->host.deriv.n_rows, sp->host.deriv.n_max, q_s, qd_s, qdd_s, Aq, Av, Hs, nb,
+                             static_cast<T *>(scratch), static_cast<int>(g2), hs, kWave);
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "spanning derivative launch");
+}
+
+// the mass matrix by the composite-rigid-body kernel (crba_kernels.hip): one launch instead of nv + 1 inverse-dynamics evaluations
+template <class T>
+int crba_mass(const grbda_plan *p, const T *q, T *out, size_t B, int device, void *stream)
+{
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const int nq = p->host.nq, nv = p->host.nv;
+    const size_t nn = static_cast<size_t>(nv) * nv;
+    DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
+    const size_t crba_waves = static_cast<size_t>(sizeof(T) == 4 ? p->opt.crba_waves : std::min(p->opt.crba_waves, 8));  // (fp64: 256 registers, two per SIMD)
+    const size_t grid = tile_grid(t->n_cu, crba_waves, B);
+    void *scratch = nullptr;
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(grid, p->host.crba.n_rows, sizeof(T)), &scratch)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (!t->deriv_related) {
+        hipError_t e = hipMemsetAsync(out, 0, B * nn * sizeof(T), hs);
+        if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+        e = launch_crba<T>(d, t->crba_bodies, p->host.n_clusters, p->host.crba.n_rows, q, out, B, static_cast<T *>(scratch), static_cast<int>(grid), hs, false, 1);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "crba launch");
+    }
+    // the lower triangle in packed rows (row-local stores), then unpacked in place, one wavefront per state (JVRC-1, 131 072 states, f32: 1.10 against
+    // 1.65 ms for the plain layout; f64 about even); whole groups of kDerivGroup states interleaved (a quarter of the open cache lines per store)
+    const int il = unpack_symmetric_lds_bytes(nv, sizeof(T), kDerivGroup) <= 60 * 1024 ? kDerivGroup : 1;
+    return for_groups_then_tail(B, il, [&](size_t b0, size_t nb, int ilp) {
+        hipError_t e = launch_crba<T>(d, t->crba_bodies, p->host.n_clusters, p->host.crba.n_rows, q + b0 * nq, out + b0 * nn, nb, static_cast<T *>(scratch),
+                                      static_cast<int>(tile_grid(t->n_cu, crba_waves, nb)), hs, true, ilp);
+        if (e != hipSuccess) return hip_err(e, "crba launch");
+        const size_t g2 = persistent_grid(t->n_cu, 16, unpack_symmetric_lds_bytes(nv, sizeof(T), ilp), nb / ilp);
+        e = launch_unpack_symmetric<T>(out + b0 * nn, t->deriv_related, nv, nb, static_cast<int>(g2), hs, ilp);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "unpack launch");
+    });
+}
+
+// the expanded batches: expand / run / combine, in chunks of at most 256 MB of rows
 template <class T>
 int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau, const T *f_ext, T *out, size_t B,
             int device, void *stream, double step = 1.0)
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!q || !out) return set_err(GRBDA_EINVAL, "null argument");
     const bool differences = dm_steps_qd(mode) || dm_steps_q(mode);
-    if ((mode == DM_BIAS || differences) && !qd) return set_err(GRBDA_EINVAL, "null argument");
-    if (differences && !tau) return set_err(GRBDA_EINVAL, "null argument");
+    if (!q || !out || ((mode == DM_BIAS || differences) && !qd) || (differences && !tau)) return set_err(GRBDA_EINVAL, "null argument");
     bool reproject = false;
     if (dm_steps_q(mode)) {
         if (!(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
@@ -1848,44 +1978,6 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const int nq = p->host.nq, nv = p->host.nv;
-    if (mode == DM_MASS && p->host.crba.ok && !p->opt.no_crba) {
-        // composite-rigid-body kernel (crba_kernels.hip): one launch instead of nv + 1 inverse-dynamics evaluations
-        DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
-        const size_t crba_waves = static_cast<size_t>(sizeof(T) == 4 ? p->opt.crba_waves : std::min(p->opt.crba_waves, 8));  // (fp64: 256 registers, two per SIMD)
-        const size_t grid = tile_grid(t->n_cu, crba_waves, B);
-        void *scratch = nullptr;
-        if (int rc = ensure_scratch(p, device, stream, scratch_bytes(grid, p->host.crba.n_rows, sizeof(T)), &scratch)) return rc;
-        hipStream_t hs = static_cast<hipStream_t>(stream);
-        hipError_t e;
-        if (t->deriv_related) {
-            // the lower triangle in packed rows (row-local stores), then unpacked in place, one wavefront per state
-            // (JVRC-1, 131 072 states, f32: 1.10 against 1.65 ms for the plain layout; f64 about even)
-            // whole groups of kDerivGroup states interleaved (crba_kernels.hip: a quarter of the open cache lines per store), the tail
-            // of the batch state-major
-            const int il = unpack_symmetric_lds_bytes(nv, sizeof(T), kDerivGroup) <= 60 * 1024 ? kDerivGroup : 1;
-            const size_t Bg = il > 1 ? B / il * il : 0;
-            for (int part = 0; part < 2; part++) {
-                const size_t b0 = part == 0 ? 0 : Bg, nbp = part == 0 ? Bg : B - Bg;
-                if (nbp == 0) continue;
-                const int ilp = part == 0 ? il : 1;
-                const size_t gp = tile_grid(t->n_cu, crba_waves, nbp);
-                e = launch_crba<T>(d, t->crba_bodies, p->host.n_clusters, p->host.crba.n_rows, q + b0 * nq, out + b0 * static_cast<size_t>(nv) * nv, nbp,
-                                   static_cast<T *>(scratch), static_cast<int>(gp), hs, true, ilp);
-                if (e != hipSuccess) return hip_err(e, "crba launch");
-                // (a persistent grid: no more workgroups than the LDS of a CU holds at once -- 12 of JVRC-1's 12.4 KB blocks, not 16)
-                size_t g2 = static_cast<size_t>(t->n_cu) * std::min<size_t>(16, lds_workgroups_per_cu(unpack_symmetric_lds_bytes(nv, sizeof(T), ilp) + 512));
-                if (g2 > nbp / ilp) g2 = nbp / ilp;
-                e = launch_unpack_symmetric<T>(out + b0 * static_cast<size_t>(nv) * nv, t->deriv_related, nv, nbp, static_cast<int>(g2), hs, ilp);
-                if (e != hipSuccess) return hip_err(e, "unpack launch");
-            }
-            return GRBDA_OK;
-        }
-        e = hipMemsetAsync(out, 0, B * static_cast<size_t>(nv) * nv * sizeof(T), hs);
-        if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-        e = launch_crba<T>(d, t->crba_bodies, p->host.n_clusters, p->host.crba.n_rows, q, out, B, static_cast<T *>(scratch),
-                           static_cast<int>(grid), hs, false, 1);
-        return e == hipSuccess ? GRBDA_OK : hip_err(e, "crba launch");
-    }
     const int R = mode == DM_BIAS ? 1 : (differences ? 2 * nv : nv + 1);
     const size_t row_scalars = static_cast<size_t>(nq) + 3 * static_cast<size_t>(nv);  // q, qd, x, result
     const Chunk c = fixed_chunk(256u << 20, row_scalars * sizeof(T) * static_cast<size_t>(R), B);
@@ -1921,15 +2013,6 @@ int derived(const grbda_plan *p, int mode, const T *q, const T *qd, const T *tau
     return GRBDA_OK;
 }
 
-// ---- analytic first-order derivatives of the forward dynamics (deriv_kernels.hip) ---------------------------------
-// d ydd / d tau = H^-1, d ydd / d q = -H^-1 dID/dq, d ydd / d qd = -H^-1 dID/dqd at ydd = FD(q, qd, tau); any of the three
-// outputs may be null.  Returns 1 when the model is not covered (implicit loops, nv > 64): the
-// callers then fall back to the unit-vector / central-difference batches of derived().
-template <class T>
-bool analytic_covers(const grbda_plan *p)
-{
-    return p->host.deriv.ok && p->host.crba.ok && !p->opt.no_analytic && !p->opt.no_crba && p->host.nv <= kWave;
-}
 // Forward / inverse dynamics through the spanning tree (HostPlan::projection_only; the reference's Projection-method cross-check,
 // RigidBodyTreeDynamics.cpp:86-97):  tau = G^T ID_s(q_s, G yd, G ydd + g);  ydd = (G^T H_s G)^-1 (tau - G^T ID_s(q_s, G yd, g)).
 template <class T>
@@ -1953,7 +2036,7 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
     Carver<T> w(wptr, c.chunk * per_state);
     auto take = [&](size_t per) { return w.take(c.chunk * per); };
     T *q_s = take(nq_s), *qd_s = take(nv_s), *qdd_s = take(nv_s), *x_s = take(nv_s), *cpl = take(p->n_cpl_rows);
-    T *Aq = nullptr, *Av = nullptr, *Hs = rnea ? nullptr : take(nn_s);
+    T *Hs = rnea ? nullptr : take(nn_s);
     // (more than 64 velocities: related-coordinate TABLES instead of one-word masks, and the workgroup-per-state solve on the one right-hand
     // side instead of H^-1 -- manifold_kernels.hip, kernels 2w and 4)
     const bool wide_nv = nv > static_cast<size_t>(kWave) || nv_s > static_cast<size_t>(kWave);
@@ -1964,25 +2047,16 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
     hipError_t e;
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         const size_t grid = tile_grid(t->n_cu, 4, nb);
-        // inverse dynamics: qdd_s = G ydd + g; forward dynamics: qdd_s = g (the bias of the spanning tree with the constraint's own acceleration)
-        e = launch_manifold_constraint<T>(d, p->host.n_clusters, t->span_q, t->span_v, t->crow, static_cast<int>(nq_s), static_cast<int>(nv_s),
-                                          p->n_cpl_rows, 0, q + b0 * nq, qd + b0 * nv, rnea ? x + b0 * nv : nullptr, q_s, qd_s, qdd_s, cpl, nb,
-                                          static_cast<int>(grid), hs, p->constraint_shape, p->has_trig);
-        if (e != hipSuccess) return hip_err(e, "manifold constraint launch");
-        if (int rc = run<T>(sp, true, q_s, qd_s, qdd_s, f_ext ? f_ext + b0 * static_cast<size_t>(p->host.n_bodies) * 6 : nullptr, x_s, nb, device, stream))
-            return rc;
+        // inverse dynamics: qdd_s = G ydd + g; forward dynamics: qdd_s = g (the bias of the spanning tree with the constraint's own acceleration),
+        // and H_s from the spanning recursion
+        const T *fe = f_ext ? f_ext + b0 * static_cast<size_t>(p->host.n_bodies) * 6 : nullptr;
+        if (int rc = spanning_stage<T>(p, *t, *ts, d, ds, 0, q + b0 * nq, qd + b0 * nv, rnea ? x + b0 * nv : nullptr, fe, q_s, qd_s, qdd_s, cpl, x_s, nullptr, nullptr, Hs, nb, c.chunk, device, stream)) return rc;
         if (rnea) {
             e = launch_manifold_apply<T>(d, p->host.n_clusters, t->span_v, t->crow, static_cast<int>(nv_s), p->n_cpl_rows, 0, x_s, nullptr, nullptr,
                                          cpl, out + b0 * nv, nb, static_cast<int>(grid), hs, big);
             if (e != hipSuccess) return hip_err(e, "manifold apply launch");
             continue;
         }
-        const size_t g2 = tile_grid(ts->n_cu, 4, nb);
-        void *scratch = nullptr;
-        if (int rc = ensure_scratch(sp, device, stream, scratch_bytes(g2, sp->host.deriv.n_rows, sizeof(T)), &scratch)) return rc;
-        e = launch_rnea_deriv<T>(ds, ts->deriv_bodies, sp->host.n_clusters, sp->host.deriv.n_rows, sp->host.deriv.n_max, q_s, qd_s, qdd_s, Aq, Av, Hs,
-                                 nb, static_cast<T *>(scratch), static_cast<int>(g2), hs, kWave);
-        if (e != hipSuccess) return hip_err(e, "spanning derivative launch");
         if (wide_nv) {
             if (!t->related_table || !ts->related_table) return set_err(GRBDA_EUNSUPPORTED, "more than 64 velocities on a plan without big clusters");
             e = launch_manifold_project_wide<T>(d, p->host.n_clusters, t->span_v, t->crow, nullptr, nullptr, t->related_table, ts->related_table,
@@ -1998,18 +2072,8 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
         e = launch_manifold_project<T>(d, p->host.n_clusters, t->span_v, t->crow, t->deriv_related, ts->deriv_related, static_cast<int>(nv_s),
                                        p->n_cpl_rows, 1, nullptr, nullptr, Hs, nullptr, cpl, nullptr, nullptr, Hw, nb, static_cast<int>(grid), hs, 1, big);
         if (e != hipSuccess) return hip_err(e, "manifold projection launch");
-        const size_t lds = spd_solve_lds_bytes(static_cast<int>(nv), sizeof(T), 0);
-        size_t per_cu = lds ? lds_workgroups_per_cu(lds) : 16;
-        if (per_cu > 16) per_cu = 16;
-        if (per_cu < 1) per_cu = 1;
-        size_t g3 = static_cast<size_t>(t->n_cu) * per_cu;
-        if (g3 > nb) g3 = nb;
-        if constexpr (sizeof(T) == 4)
-            e = launch_spd_solve<float, float>(Hw, 1, nullptr, nullptr, Hinv, nullptr, nullptr, t->deriv_related, static_cast<int>(nv), nb,
-                                               static_cast<int>(g3), hs, 1);
-        else
-            e = launch_spd_solve<double, double>(Hw, 1, nullptr, nullptr, Hinv, nullptr, nullptr, t->deriv_related, static_cast<int>(nv), nb,
-                                                 static_cast<int>(g3), hs, 1);
+        // (H^-1 alone, never on the matrix cores)
+        e = spd_solve_stage<T>(*t, Hw, nullptr, nullptr, Hinv, nullptr, nullptr, static_cast<int>(nv), 0, nb, false, false, 1, hs);
         if (e != hipSuccess) return hip_err(e, "spd solve launch");
         e = launch_manifold_apply<T>(d, p->host.n_clusters, t->span_v, t->crow, static_cast<int>(nv_s), p->n_cpl_rows, 1, x_s, x + b0 * nv, Hinv, cpl,
                                      out + b0 * nv, nb, static_cast<int>(grid), hs, big);
@@ -2063,22 +2127,26 @@ int projection_run_f32_through_f64(const grbda_plan *p, bool rnea, const float *
         return projection_run<double>(p, rnea, a[0], a[1], a[2], a[4], a[3], nb, device, stream);
     });
 }
-
-// Models with implicit clusters (manifold_kernels.hip): ydd = FD; spanning state and the first-order parts of G, g per state;
-// tau_s and (A_q, A_v, H_s) of the spanning tree from its own plan; projection with the per-state G; the same SPD solve.
-// H only (dq == dqd == nullptr): qd and tau may be null.
-template <class T>
-bool manifold_covers(const grbda_plan *p)
+// The central difference d/dq (DM_DQ, DM_ID_DQ) for fp32 callers.  A central difference in fp32 has no usable step (eps / h + h^2 bottoms
+// out near 1e-2 relative): the differences are taken in fp64 on the converted inputs and the matrices converted back.
+int dq_through_f64(const grbda_plan *p, int mode, const float *q, const float *qd, const float *x, double step, float *J, size_t B, int device,
+                   void *stream)
 {
-    return p->span && !p->opt.no_manifold && !p->opt.no_analytic && p->host.nv <= kWave && p->span->host.nv <= kWave &&
-           p->host.deriv.related.size() == static_cast<size_t>(p->host.nv);
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    const CvtArray arrays[] = {{q, nullptr, nq}, {qd, nullptr, nv}, {x, nullptr, nv}, {nullptr, J, nv * nv}};
+    return through_f64(p, 64u << 20, arrays, B, device, stream, [&](double *const *a, size_t nb) {
+        return derived<double>(p, mode, a[0], a[1], a[2], nullptr, a[3], nb, device, stream, step);
+    });
 }
+
+// BY_MANIFOLD, MASS_MANIFOLD.  Models with implicit clusters (manifold_kernels.hip): ydd = FD; spanning state and the first-order parts of G, g
+// per state; tau_s and (A_q, A_v, H_s) of the spanning tree from its own plan; projection with the per-state G; the same SPD solve.
+// H only (dq == dqd == nullptr): qd and tau may be null.  Plans with big clusters have no analytic d/dq, d/dqd (choose_derivs): forward dynamics
+// differences for explicit clusters; implicit ones would need the Newton re-projection, which refuses such plans.
 template <class T>
 int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, T *dq, T *dqd, T *dtau, T *Hout, size_t B, int device,
                     void *stream)
 {
-    if (!q || ((dq || dqd) && (!qd || !tau))) return set_err(GRBDA_EINVAL, "null argument");
-    if (B == 0 || (!dq && !dqd && !dtau && !Hout)) return GRBDA_OK;
     DeviceTables *t = nullptr, *ts = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const grbda_plan *sp = p->span;
@@ -2087,12 +2155,12 @@ int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     const size_t nq_s = sp->host.nq, nv_s = sp->host.nv, nn_s = nv_s * nv_s;
     const bool need_d = dq || dqd;
     const bool big = p->host.big_clusters;
-    // (clusters beyond the structured limits: no analytic d/dq, d/dqd -- the callers' difference batches take over: forward dynamics
-    // differences for explicit clusters; implicit ones would need the Newton re-projection, which refuses such plans)
-    if (big && need_d) return 1;
+    assert(!(big && need_d));
     const int n_rhs = (dq ? 1 : 0) + (dqd ? 1 : 0);
     const bool solve = need_d || dtau;
-    const int il = (need_d && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs)) ? kDerivGroup : 1;
+    // (H^-1 alone stays off the matrix cores here)
+    const bool mfma = need_d && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs);
+    const int il = mfma ? kDerivGroup : 1;
     // workspace per state: spanning state (q_s, qd_s, qdd_s, tau_s), zeros for a missing qd, coupling rows, the three spanning
     // matrices, the three projected matrices, ydd
     const size_t per_state = nq_s + 3 * nv_s + nv + static_cast<size_t>(p->n_cpl_rows) + 3 * nn_s + 3 * nn + nv;
@@ -2101,9 +2169,9 @@ int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     // (up to 16 GiB -- but no more than the batch itself needs: a small batch does not pin a large slab)
     const size_t want = std::min<size_t>(16384ull << 20, ((B + kWave - 1) / kWave * kWave) * per_state * sizeof(T) + (1u << 20));
     const Chunk c = budgeted_chunk(p, p->work, device, stream, want, per_state * sizeof(T), B);
-    const size_t chunk = c.chunk;
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    const size_t chunk = c.chunk;
     Carver<T> w(wptr, chunk * per_state);
     auto take = [&](size_t per) { return w.take(chunk * per); };
     T *q_s = take(nq_s), *qd_s = take(nv_s), *qdd_s = take(nv_s), *tau_s = take(nv_s), *zeros = take(nv), *cpl = take(p->n_cpl_rows);
@@ -2114,31 +2182,14 @@ int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
     DevPlan<T> ds = make_dev_plan<T>(sp, *ts, false, false);
     hipError_t e;
     for (const auto [b0, nb] : ChunkWalk{B, chunk}) {
-        const T *qc = q + b0 * nq, *qdc = qd ? qd + b0 * nv : zeros, *yddc = nullptr;
-        if (!qd && (e = hipMemsetAsync(zeros, 0, nb * nv * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
-        if (need_d) {
-            if (int rc = run<T>(p, false, qc, qdc, tau + b0 * nv, nullptr, ydd, nb, device, stream)) return rc;
-            yddc = ydd;
-        } else {
-            // H only: the recursion runs at zero velocity and acceleration (its H does not depend on them)
-            if ((e = hipMemsetAsync(qd_s, 0, 2 * chunk * nv_s * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
-        }
-        const size_t grid = tile_grid(t->n_cu, 4, nb);
-        e = launch_manifold_constraint<T>(d, p->host.n_clusters, t->span_q, t->span_v, t->crow, static_cast<int>(nq_s), static_cast<int>(nv_s),
-                                          p->n_cpl_rows, need_d ? 1 : 0, qc, qdc, yddc, q_s, qd_s, need_d ? qdd_s : nullptr, cpl, nb,
-                                          static_cast<int>(grid), hs, p->constraint_shape, p->has_trig);
-        if (e != hipSuccess) return hip_err(e, "manifold constraint launch");
-        if (!need_d && (e = hipMemsetAsync(qd_s, 0, chunk * nv_s * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
+        const T *qc = q + b0 * nq, *qdc = need_d ? qd + b0 * nv : zeros;  // (H only: zero velocities, whatever the caller gave)
+        if (!need_d && (e = hipMemsetAsync(zeros, 0, nb * nv * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
         if (need_d)
-            if (int rc = run<T>(sp, true, q_s, qd_s, qdd_s, nullptr, tau_s, nb, device, stream)) return rc;
-        {
-            const size_t g2 = tile_grid(ts->n_cu, 4, nb);
-            void *scratch = nullptr;
-            if (int rc = ensure_scratch(sp, device, stream, scratch_bytes(g2, sp->host.deriv.n_rows, sizeof(T)), &scratch)) return rc;
-            e = launch_rnea_deriv<T>(ds, ts->deriv_bodies, sp->host.n_clusters, sp->host.deriv.n_rows, sp->host.deriv.n_max, q_s, qd_s, qdd_s,
-                                     need_d ? Aq : nullptr, need_d ? Av : nullptr, Hs, nb, static_cast<T *>(scratch), static_cast<int>(g2), hs, kWave);
-            if (e != hipSuccess) return hip_err(e, "spanning derivative launch");
-        }
+            if (int rc = run<T>(p, false, qc, qdc, tau + b0 * nv, nullptr, ydd, nb, device, stream)) return rc;
+        if (int rc = spanning_stage<T>(p, *t, *ts, d, ds, need_d ? 1 : 0, qc, qdc, need_d ? ydd : nullptr, nullptr, q_s, qd_s, qdd_s, cpl,
+                                       need_d ? tau_s : nullptr, need_d ? Aq : nullptr, need_d ? Av : nullptr, Hs, nb, chunk, device, stream))
+            return rc;
+        const size_t grid = tile_grid(t->n_cu, 4, nb);
         // the projected H goes to the caller's array when no solve follows, or (state-major layouts, whole groups) to d/dtau
         T *H = !solve ? Hout + b0 * nn : ((dtau && !(il > 1 && (B % kDerivGroup) != 0)) ? dtau + b0 * nn : Hw);
         e = launch_manifold_project<T>(d, p->host.n_clusters, t->span_v, t->crow, t->deriv_related, ts->deriv_related, static_cast<int>(nv_s),
@@ -2147,125 +2198,99 @@ int manifold_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
         if (e != hipSuccess) return hip_err(e, "manifold projection launch");
         if (!solve) {
             // packed lower rows -> the full symmetric matrix, in place
-            size_t g4 = static_cast<size_t>(t->n_cu) * std::min<size_t>(16, lds_workgroups_per_cu(unpack_symmetric_lds_bytes(static_cast<int>(nv), sizeof(T), 1) + 512));
-            if (g4 > nb) g4 = nb;
+            const size_t g4 = persistent_grid(t->n_cu, 16, unpack_symmetric_lds_bytes(static_cast<int>(nv), sizeof(T), 1), nb);
             e = launch_unpack_symmetric<T>(H, t->deriv_related, static_cast<int>(nv), nb, static_cast<int>(g4), hs, 1);
             if (e != hipSuccess) return hip_err(e, "unpack launch");
             continue;
         }
-        const size_t lds = spd_solve_lds_bytes(static_cast<int>(nv), sizeof(T), n_rhs);
-        size_t per_cu = lds ? lds_workgroups_per_cu(lds) : 16;
-        const bool mfma = need_d && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs);
-        if (per_cu > (mfma ? static_cast<size_t>(spd_mfma_workgroups_per_cu(static_cast<int>(nv))) : 16u)) per_cu = mfma ? spd_mfma_workgroups_per_cu(static_cast<int>(nv)) : 16;
-        if (per_cu < 1) per_cu = 1;
-        size_t g3 = static_cast<size_t>(t->n_cu) * per_cu;
-        const size_t units = mfma ? (nb + kDerivGroup - 1) / kDerivGroup : nb;
-        if (g3 > units) g3 = units;
-        T *o1 = dq ? dq + b0 * nn : nullptr, *o2 = dqd ? dqd + b0 * nn : nullptr, *o3 = dtau ? dtau + b0 * nn : nullptr;
-        const T *r1 = dq ? Dq : nullptr, *r2 = dqd ? Dqd : nullptr;
-        if constexpr (sizeof(T) == 4)
-            e = launch_spd_solve<float, float>(H, 1, r1, r2, o3, o1, o2, t->deriv_related, static_cast<int>(nv), nb, static_cast<int>(g3), hs, il);
-        else
-            e = launch_spd_solve<double, double>(H, 1, r1, r2, o3, o1, o2, t->deriv_related, static_cast<int>(nv), nb, static_cast<int>(g3), hs, 1);
+        e = spd_solve_stage<T>(*t, H, dq ? Dq : nullptr, dqd ? Dqd : nullptr, dtau ? dtau + b0 * nn : nullptr, dq ? dq + b0 * nn : nullptr,
+                               dqd ? dqd + b0 * nn : nullptr, static_cast<int>(nv), n_rhs, nb, false, mfma, il, hs);
         if (e != hipSuccess) return hip_err(e, "spd solve launch");
     }
     return GRBDA_OK;
 }
 
-template <class T>
-int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, T *dq, T *dqd, T *dtau, size_t B, int device,
-                    void *stream)
+// Chunk size of analytic_derivs.  The slab holds chunk * per_state scalars, plus B nv of them (`ydd_bytes`) when the forward dynamics of the
+// WHOLE batch runs in one launch up front (160 MB for a million JVRC-1 states in fp32) instead of one launch per chunk -- a
+// quarter-million-state launch runs at 0.35 ms, a quarter of the million-state launch at 0.29.  Every branch keeps the slab within the
+// budget, or at one tile of states when the budget is smaller than that.  A stream that captures replays the decision of the eager call it
+// captures after (same B, same layout; grbda_plan::deriv_chunk): the held slab may have grown since, and a chunk derived from it again would
+// record another launch sequence.
+grbda_plan::DerivChunk deriv_chunk_decision(const grbda_plan *p, int n_cu, size_t ps_bytes, bool need_d, size_t ydd_bytes, size_t B, int device,
+                                            void *stream)
 {
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    if (!analytic_covers<T>(p)) {
-        if (manifold_covers<T>(p)) return manifold_derivs<T>(p, q, qd, tau, dq, dqd, dtau, nullptr, B, device, stream);
-        return 1;
+    const bool capturing = is_capturing(stream);
+    const auto it = p->deriv_chunk.find({device, stream});
+    if (capturing && it != p->deriv_chunk.end() && it->second.B == B && it->second.per_state_bytes == ps_bytes && it->second.need_d == need_d && it->second.chunk)
+        return it->second;
+    const size_t B_groups = (B + kDerivGroup - 1) / kDerivGroup * kDerivGroup;  // (the last group of the workspace is allocated whole)
+    grbda_plan::DerivChunk dc = {B, ps_bytes, B_groups, need_d, false};            // one chunk: no whole-batch ydd
+    const size_t budget = work_budget(p, p->work, device, stream, (4096ull << 20) + ydd_bytes);
+    if (B_groups * ps_bytes > budget) {
+        // (room for the whole batch's ydd and a tile of states besides; otherwise the forward dynamics runs per chunk)
+        dc.ydd_all = need_d && budget >= ydd_bytes + static_cast<size_t>(kWave) * ps_bytes;
+        dc.chunk = whole_tiles((budget - (dc.ydd_all ? ydd_bytes : 0)) / (ps_bytes ? ps_bytes : 1));  // (and with them whole groups of the interleaved workspace)
+        // whole ROUNDS of the one-state-per-lane kernels: a chunk of 2.4 rounds of wavefront slots takes as long as 3 (measured: 159 488-state
+        // chunks of JVRC-1, 2 492 tiles on 1 024 slots of the recursion and 2 048 of the factor kernel / the ABA: 19 % and 40 % of the
+        // slots idle in the last round).  n_cu * 8 wavefronts = one round at two per SIMD, two rounds of the recursion's four per CU.
+        const size_t round = static_cast<size_t>(n_cu) * 8 * kWave;
+        if (dc.chunk >= round) dc.chunk = dc.chunk / round * round;
+        if (dc.chunk >= B) {  // (only when the budget is below one tile: a single chunk, then without the whole-batch ydd)
+            dc.chunk = B_groups;
+            dc.ydd_all = false;
+        }
     }
-    if (!q || ((dq || dqd) && (!qd || !tau))) return set_err(GRBDA_EINVAL, "null argument");
-    if (B == 0 || (!dq && !dqd && !dtau)) return GRBDA_OK;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
+    if (!capturing) p->deriv_chunk[{device, stream}] = dc;
+    return dc;
+}
+// d ydd / d tau = H^-1, d ydd / d q = -H^-1 dID/dq, d ydd / d qd = -H^-1 dID/dqd at ydd = FD(q, qd, tau); any of the three outputs may be
+// null, one at least is not.  `minv`, `wide`: choose_derivs (BY_MINV; DerivRoute::solve_f64).
+template <class T>
+int analytic_derivs(const grbda_plan *p, const DeviceTables *t, bool minv, bool wide, const T *q, const T *qd, const T *tau, T *dq, T *dqd, T *dtau,
+                    size_t B, int device, void *stream)
+{
     const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
     const bool need_d = dq || dqd;
     // H is built in the caller's d/dtau array when that is wanted (the factor is out of it before H^-1 goes in); dID/dq and
     // dID/dqd in rnea_deriv_kernel's packed layout, the H nobody asked for, and ydd take workspace
-    const bool wide0 = sizeof(T) == 4 && p->opt.solve_f64;
     const int n_rhs = (dq ? 1 : 0) + (dqd ? 1 : 0);
     // (d / d tau alone: the CRBA kernel writes the same interleaved H and the matrix-core solve inverts it)
     // (fp64 stays state-major: its interleaved workspace was built and measured in round 4 -- MIT Humanoid 8 % faster, JVRC-1 36 % slower, the
     // row-per-lane fp64 solve reads an interleaved block strided; profiles/r4_derivative_recursion_experiments.txt -- and removed again)
     // H^-1 = W^T W from the articulated-body quantities (minv_kernels.hip): no H, no dense factorisation; f32 and f64 alike on the
-    // matrix cores, both workspaces interleaved by groups of kDerivGroup states.  GRBDA_NO_MINV=1 keeps the factorisation route (A/B runs)
+    // matrix cores, both workspaces interleaved by groups of kDerivGroup states.
     const MinvProgram &mv = p->host.deriv.minv;
-    const bool minv = mv.ok && t->minv_bodies && t->minv_coltab && !wide0 && !p->opt.no_minv &&
-                      minv_solve_lds_bytes(static_cast<int>(nv), n_rhs, mv.n_entries, sizeof(T)) <= 160u * 1024u;
-    const int il = minv ? kDerivGroup : ((!wide0 && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs)) ? kDerivGroup : 1);
+    // f32 with the matrix-core solve: the recursion writes H, dID/dq, dID/dqd interleaved by groups of kDerivGroup states
+    // (deriv_kernels.hip); every other combination of the factorisation route keeps the state-major layout
+    const bool mfma = !minv && !wide && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs);
+    const int il = (minv || mfma) ? kDerivGroup : 1;
     // (only an INTERLEAVED H block can reach past the caller's array: the state-major layouts always build H in place)
     const bool h_in_place = !minv && dtau && (il == 1 || (B % kDerivGroup) == 0);
     const size_t per_state = minv ? static_cast<size_t>(mv.n_entries) + (need_d ? 2 * nn + nv : 0)
                                   : (h_in_place ? 0 : nn) + (need_d ? 2 * nn + nv : 0);
-    // Chunk size.  The slab holds chunk * per_state scalars, plus B nv of them when the forward dynamics of the WHOLE batch runs in one
-    // launch up front (160 MB for a million JVRC-1 states in fp32) instead of one launch per chunk -- a quarter-million-state launch runs at
-    // 0.35 ms, a quarter of the million-state launch at 0.29.  Every branch keeps the slab within the budget, or at one tile of states when
-    // the budget is smaller than that.  A stream that captures replays the decision of the eager call it captures after (same B, same
-    // layout): the held slab may have grown since, and a chunk derived from it again would record another launch sequence.
-    const size_t ps_bytes = per_state * sizeof(T), ydd_bytes = need_d ? B * nv * sizeof(T) : 0;
-    const size_t B_groups = (B + kDerivGroup - 1) / kDerivGroup * kDerivGroup;  // (the last group of the workspace is allocated whole)
-    size_t chunk = 0;
-    bool ydd_all = false;
-    const bool capturing = is_capturing(stream);
-    {
-        const auto it = p->deriv_chunk.find({device, stream});
-        if (capturing && it != p->deriv_chunk.end() && it->second.B == B && it->second.per_state_bytes == ps_bytes && it->second.need_d == need_d) {
-            chunk = it->second.chunk;
-            ydd_all = it->second.ydd_all;
-        }
-    }
-    if (!chunk) {
-        const size_t budget = work_budget(p, p->work, device, stream, (4096ull << 20) + ydd_bytes);
-        const size_t tile = static_cast<size_t>(kWave) * ps_bytes;
-        if (B_groups * ps_bytes <= budget) {
-            chunk = B_groups;  // one chunk: no whole-batch ydd
-        } else {
-            // (room for the whole batch's ydd and a tile of states besides; otherwise the forward dynamics runs per chunk)
-            ydd_all = need_d && budget >= ydd_bytes + tile;
-            chunk = whole_tiles((budget - (ydd_all ? ydd_bytes : 0)) / (ps_bytes ? ps_bytes : 1));  // (and with them whole groups of the interleaved workspace)
-            // whole ROUNDS of the one-state-per-lane kernels: a chunk of 2.4 rounds of wavefront slots takes as long as 3 (measured: 159 488-state
-            // chunks of JVRC-1, 2 492 tiles on 1 024 slots of the recursion and 2 048 of the factor kernel / the ABA: 19 % and 40 % of the
-            // slots idle in the last round).  n_cu * 8 wavefronts = one round at two per SIMD, two rounds of the recursion's four per CU.
-            const size_t round = static_cast<size_t>(t->n_cu) * 8 * kWave;
-            if (chunk >= round) chunk = chunk / round * round;
-            if (chunk >= B) {  // (only when the budget is below one tile: a single chunk, then without the whole-batch ydd)
-                chunk = B_groups;
-                ydd_all = false;
-            }
-        }
-        if (!capturing) p->deriv_chunk[{device, stream}] = {B, ps_bytes, chunk, need_d, ydd_all};
-    }
-    // f32 with the matrix-core solve: the recursion writes H, dID/dq, dID/dqd interleaved by groups of kDerivGroup states
-    // (deriv_kernels.hip); every other combination keeps the state-major layout (il, above)
+    const grbda_plan::DerivChunk dc = deriv_chunk_decision(p, t->n_cu, per_state * sizeof(T), need_d, need_d ? B * nv * sizeof(T) : 0, B, device, stream);
+    const size_t chunk = dc.chunk;
     void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, (chunk * per_state + (ydd_all ? B * nv : 0)) * sizeof(T) + 256, &wptr)) return rc;
-    Carver<T> w(wptr, chunk * per_state + (ydd_all ? B * nv : 0));
+    if (int rc = ensure_work(p, p->work, device, stream, (chunk * per_state + (dc.ydd_all ? B * nv : 0)) * sizeof(T) + 256, &wptr)) return rc;
+    Carver<T> w(wptr, chunk * per_state + (dc.ydd_all ? B * nv : 0));
     T *wH = (!minv && !h_in_place) ? w.take(chunk * nn) : nullptr, *Dq = need_d ? w.take(chunk * nn) : nullptr, *Dqd = need_d ? w.take(chunk * nn) : nullptr;
     T *ydd_chunk = w.take(need_d ? chunk * nv : 0);
     T *recs = minv ? w.take(chunk * mv.n_entries) : nullptr;
     assert(w.taken == chunk * per_state);
-    T *ydd_whole = ydd_all ? w.take(B * nv) : nullptr;
+    T *ydd_whole = dc.ydd_all ? w.take(B * nv) : nullptr;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
-    if (ydd_all)
+    if (dc.ydd_all)
         if (int rc = run<T>(p, false, q, qd, tau, nullptr, ydd_whole, B, device, stream)) return rc;
     for (const auto [b0, nb] : ChunkWalk{B, chunk}) {
-        T *ydd = ydd_all ? ydd_whole + b0 * nv : ydd_chunk;
+        T *ydd = dc.ydd_all ? ydd_whole + b0 * nv : ydd_chunk;
         // (an interleaved H block spans the slots of a whole group: when the batch does not end on a group boundary the last
         // group would reach past the caller's d/dtau array, so that H goes to the workspace)
         T *H = h_in_place ? dtau + b0 * nn : wH;
         hipError_t e = hipSuccess;
         // (both kernels write H as packed rows of its lower triangle; the solve reads it through DerivProgram::related, so
         // nothing is cleared)
-        if (need_d && !ydd_all)
+        if (need_d && !dc.ydd_all)
             if (int rc = run<T>(p, false, q + b0 * nq, qd + b0 * nv, tau + b0 * nv, nullptr, ydd, nb, device, stream)) return rc;
         const size_t grid = tile_grid(t->n_cu, 8, nb);
         const size_t rows = std::max(p->host.crba.n_rows, (need_d || minv) ? p->host.deriv.n_rows : 0);  // (the factor kernel of the minv route uses the recursion's rows)
@@ -2287,58 +2312,77 @@ int analytic_derivs(const grbda_plan *p, const T *q, const T *qd, const T *tau, 
         }
         T *o1 = dq ? dq + b0 * nn : nullptr, *o2 = dqd ? dqd + b0 * nn : nullptr, *o3 = dtau ? dtau + b0 * nn : nullptr;
         const T *r1 = dq ? Dq : nullptr, *r2 = dqd ? Dqd : nullptr;
-        if (minv) {
-            // articulated-inertia recursion -> record blocks (one state per lane, two wavefronts per SIMD), then the walk and the two
-            // products on the matrix cores (one state per wavefront)
-            e = launch_abi_factor<T>(d, t->deriv_bodies, t->minv_bodies, p->host.n_clusters, p->host.deriv.n_rows, p->host.deriv.n_max,
-                                     mv.n_entries, q + b0 * nq, recs, nb, static_cast<T *>(scratch), static_cast<int>(grid), hs, kDerivGroup,
-                                     t->bad_count);
-            if (e != hipSuccess) return hip_err(e, "articulated-inertia factor launch");
-            size_t per_cu = static_cast<size_t>(minv_workgroups_per_cu<T>(static_cast<int>(nv), p->host.deriv.n_max, n_rhs, mv.n_entries));
-            if (p->opt.minv_wpc > 0 && per_cu > static_cast<size_t>(p->opt.minv_wpc)) per_cu = static_cast<size_t>(p->opt.minv_wpc);
-            size_t g3 = static_cast<size_t>(t->n_cu) * per_cu;
-            const size_t units = (nb + kDerivGroup - 1) / kDerivGroup;
-            if (g3 > units) g3 = units;
-            e = launch_minv_solve<T>(recs, mv.n_entries, kDerivGroup, t->minv_coltab, mv.max_depth, mv.base_off, p->host.deriv.n_max, r1, r2,
-                                     kDerivGroup, o3, o1, o2, t->deriv_related, static_cast<int>(nv), nb, static_cast<int>(g3), hs);
-            if (e != hipSuccess) return hip_err(e, "minv solve launch");
+        if (!minv) {
+            e = spd_solve_stage<T>(*t, H, r1, r2, o3, o1, o2, static_cast<int>(nv), n_rhs, nb, wide, mfma, il, hs);
+            if (e != hipSuccess) return hip_err(e, "spd solve launch");
             continue;
         }
-        // one wavefront per state; as many as the LDS of a CU holds
-        const bool wide = sizeof(T) == 4 && p->opt.solve_f64;
-        const size_t lds = spd_solve_lds_bytes(static_cast<int>(nv), wide ? 8 : sizeof(T), (dq ? 1 : 0) + (dqd ? 1 : 0));
-        size_t per_cu = lds ? lds_workgroups_per_cu(lds) : 16;
-        const bool mfma = !wide && spd_solve_on_mfma(sizeof(T), static_cast<int>(nv), n_rhs);
-        if (per_cu > (mfma ? static_cast<size_t>(spd_mfma_workgroups_per_cu(static_cast<int>(nv))) : 16u)) per_cu = mfma ? spd_mfma_workgroups_per_cu(static_cast<int>(nv)) : 16;  // (matrix-core kernel: workgroups of four wavefronts)
-        if (per_cu < 1) per_cu = 1;
-        size_t g3 = static_cast<size_t>(t->n_cu) * per_cu;
-        const size_t units = mfma ? (nb + kDerivGroup - 1) / kDerivGroup : nb;
-        if (g3 > units) g3 = units;
-        const uint64_t *rel = t->deriv_related;
-        const int nvi = static_cast<int>(nv), g3i = static_cast<int>(g3), hp = 1;
-        const int sil = il;
-        if constexpr (sizeof(T) == 4) {
-            if (wide) e = launch_spd_solve<float, double>(H, hp, r1, r2, o3, o1, o2, rel, nvi, nb, g3i, hs, 1);
-            else e = launch_spd_solve<float, float>(H, hp, r1, r2, o3, o1, o2, rel, nvi, nb, g3i, hs, sil);
-        } else {
-            e = launch_spd_solve<double, double>(H, hp, r1, r2, o3, o1, o2, rel, nvi, nb, g3i, hs, 1);
-        }
-        if (e != hipSuccess) return hip_err(e, "spd solve launch");
+        // articulated-inertia recursion -> record blocks (one state per lane, two wavefronts per SIMD), then the walk and the two
+        // products on the matrix cores (one state per wavefront)
+        e = launch_abi_factor<T>(d, t->deriv_bodies, t->minv_bodies, p->host.n_clusters, p->host.deriv.n_rows, p->host.deriv.n_max,
+                                 mv.n_entries, q + b0 * nq, recs, nb, static_cast<T *>(scratch), static_cast<int>(grid), hs, kDerivGroup,
+                                 t->bad_count);
+        if (e != hipSuccess) return hip_err(e, "articulated-inertia factor launch");
+        size_t per_cu = static_cast<size_t>(minv_workgroups_per_cu<T>(static_cast<int>(nv), p->host.deriv.n_max, n_rhs, mv.n_entries));
+        if (p->opt.minv_wpc > 0 && per_cu > static_cast<size_t>(p->opt.minv_wpc)) per_cu = static_cast<size_t>(p->opt.minv_wpc);
+        const size_t g3 = std::min(static_cast<size_t>(t->n_cu) * per_cu, (nb + kDerivGroup - 1) / kDerivGroup);
+        e = launch_minv_solve<T>(recs, mv.n_entries, kDerivGroup, t->minv_coltab, mv.max_depth, mv.base_off, p->host.deriv.n_max, r1, r2,
+                                 kDerivGroup, o3, o1, o2, t->deriv_related, static_cast<int>(nv), nb, static_cast<int>(g3), hs);
+        if (e != hipSuccess) return hip_err(e, "minv solve launch");
     }
     return GRBDA_OK;
 }
 
+// ---- grbda_fd_dtau_* / _dqd_* / _dq_* / _derivatives_* ----------------------------------------------------------------------------------
+// Their one body; `args`: the entry point was given every array it needs.  The route record once, its one analytic or manifold stage for the
+// outputs that stage covers, a difference batch for each of the others (d/dtau, d/dqd, d/dq, in that order).
 template <class T>
-int manifold_mass(const grbda_plan *p, const T *q, T *H, size_t B, int device, void *stream)
+int fd_by_route(const grbda_plan *p, bool args, const T *q, const T *qd, const T *tau, double step, T *dq, T *dqd, T *dtau, size_t B, int device, void *stream)
 {
-    // models with implicit clusters: H = G^T H_s G through the spanning tree (manifold_kernels.hip) instead of nv + 1 inverse dynamics
-    if (!p || !q || !H || p->opt.no_crba) return 1;
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!manifold_covers<T>(p)) return 1;
-    return manifold_derivs<T>(p, q, nullptr, nullptr, nullptr, nullptr, nullptr, H, B, device, stream);
+    if (!args) return set_err(GRBDA_EINVAL, "null argument");
+    // (fp64 looks at the step first; fp32, whose differences are taken in fp64, after an empty batch and a missing device -- as the entry points always did)
+    if (sizeof(T) == 8 && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+    if (B == 0 || (!dq && !dqd && !dtau)) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    if (!(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+    const DerivRoute r = choose_derivs(p, t->minv_bodies && t->minv_coltab, sizeof(T), dq, dqd, dtau);
+    const DerivPath stage = dtau && r.dtau != BY_DIFFERENCES ? r.dtau : (dq ? r.dq : r.dqd);
+    const auto staged = [](T *out, DerivPath path) { return path == BY_DIFFERENCES ? nullptr : out; };
+    int rc = GRBDA_OK;
+    if (stage == BY_MANIFOLD) rc = manifold_derivs<T>(p, q, qd, tau, staged(dq, r.dq), staged(dqd, r.dqd), dtau, nullptr, B, device, stream);
+    else if (stage == BY_MINV || stage == BY_FACTOR) rc = analytic_derivs<T>(p, t, stage == BY_MINV, r.solve_f64, q, qd, tau, dq, dqd, dtau, B, device, stream);
+    if (!rc && r.dtau == BY_DIFFERENCES) rc = derived<T>(p, DM_DTAU, q, nullptr, nullptr, nullptr, dtau, B, device, stream);
+    if (!rc && r.dqd == BY_DIFFERENCES) rc = derived<T>(p, DM_DQD, q, qd, tau, nullptr, dqd, B, device, stream);
+    if (rc || r.dq != BY_DIFFERENCES) return rc;
+    if constexpr (sizeof(T) == 4) return dq_through_f64(p, DM_DQ, q, qd, tau, step, dq, B, device, stream);
+    else return derived<T>(p, DM_DQ, q, qd, tau, nullptr, dq, B, device, stream, step);
+}
+template <class T>
+int fd_dtau(const grbda_plan *p, const T *q, T *Hinv, size_t B, int device, void *stream)
+{
+    return fd_by_route<T>(p, q && Hinv, q, nullptr, nullptr, 1.0, nullptr, nullptr, Hinv, B, device, stream);
+}
+template <class T>
+int fd_dqd(const grbda_plan *p, const T *q, const T *qd, const T *tau, T *J, size_t B, int device, void *stream)
+{
+    return fd_by_route<T>(p, q && qd && tau && J, q, qd, tau, 1.0, nullptr, J, nullptr, B, device, stream);
+}
+template <class T>
+int fd_dq(const grbda_plan *p, const T *q, const T *qd, const T *tau, double step, T *J, size_t B, int device, void *stream)
+{
+    if (sizeof(T) == 4 && !p) return set_err(GRBDA_EINVAL, "null argument");  // (the fp32 entry point's word for a null plan)
+    return fd_by_route<T>(p, q && qd && tau && J, q, qd, tau, step, J, nullptr, nullptr, B, device, stream);
+}
+template <class T>
+int fd_derivatives(const grbda_plan *p, const T *q, const T *qd, const T *tau, T *dq, T *dqd, T *dtau, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null argument");  // (as for a null array)
+    return fd_by_route<T>(p, q && qd && tau, q, qd, tau, 1e-6, dq, dqd, dtau, B, device, stream);
 }
 
-// the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
 // ---- first-order derivatives of the INVERSE dynamics (grbda_rnea_derivatives_*, include/grbda_hip.h) ------------------------------------
 // [a, a + n) and [b, b + m) share a byte
 bool ranges_overlap(const void *a, size_t n, const void *b, size_t m)
@@ -2348,35 +2392,25 @@ bool ranges_overlap(const void *a, size_t n, const void *b, size_t m)
 }
 // d tau / d q and d tau / d qd at (q, qd, ydd).  Plans the analytic recursion covers: rnea_deriv_kernel on the caller's ydd (no forward
 // dynamics, no solve) writes its run layout STRAIGHT INTO dq / dqd -- whole groups of kDerivGroup states interleaved where
-// unpack_runs_interleave allows, the tail of the batch state-major, as the CRBA path of derived() lays out H -- and unpack_runs_kernel turns
+// unpack_runs_interleave allows, the tail of the batch state-major, as crba_mass() lays out H -- and unpack_runs_kernel turns
 // every block into row-major in place: the scratch slab, no work slab, the same launches for the same B (capturable).  Every other plan:
 // the difference batches of derived() over the inverse dynamics.
 template <class T>
 int id_derivs(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double step, T *dq, T *dqd, size_t B, int device, void *stream)
 {
-    if (!analytic_covers<T>(p)) {
+    if (!analytic_covers(p)) {
         if (dqd)
             if (int rc = derived<T>(p, DM_ID_DQD, q, qd, ydd, nullptr, dqd, B, device, stream)) return rc;
         if (!dq) return GRBDA_OK;
-        if constexpr (sizeof(T) == 8) {
-            return derived<T>(p, DM_ID_DQ, q, qd, ydd, nullptr, dq, B, device, stream, step);
-        } else {
-            // (a central difference has no usable step in fp32 -- grbda_fd_dq_f32: taken in fp64 on the converted inputs)
-            if (!(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
-            const size_t nq = p->host.nq, nv = p->host.nv;
-            const CvtArray arrays[] = {{q, nullptr, nq}, {qd, nullptr, nv}, {ydd, nullptr, nv}, {nullptr, dq, nv * nv}};
-            return through_f64(p, 64u << 20, arrays, B, device, stream, [&](double *const *a, size_t nb) {
-                return derived<double>(p, DM_ID_DQ, a[0], a[1], a[2], nullptr, a[3], nb, device, stream, step);
-            });
-        }
+        if constexpr (sizeof(T) == 8) return derived<T>(p, DM_ID_DQ, q, qd, ydd, nullptr, dq, B, device, stream, step);
+        else if (!(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+        else return dq_through_f64(p, DM_ID_DQ, q, qd, ydd, step, dq, B, device, stream);
     }
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     if (!t->deriv_related) return set_err(GRBDA_EUNSUPPORTED, "the plan has no related-coordinate masks on the device");
     const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
     const int nvi = static_cast<int>(nv);
-    const int il = unpack_runs_interleave(nvi, sizeof(T));
-    const size_t Bg = il > 1 ? B / il * il : 0;
     // (interleaved results: one wavefront per SIMD; state-major: three per CU -- analytic_derivs)
     const size_t waves_il = p->opt.deriv_waves ? static_cast<size_t>(p->opt.deriv_waves) : 4, waves_sm = p->opt.deriv_waves ? waves_il : 3;
     void *scratch = nullptr;
@@ -2385,28 +2419,28 @@ int id_derivs(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double
     hipStream_t hs = static_cast<hipStream_t>(stream);
     DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
     T *o0 = dq ? dq : dqd, *o1 = dq ? dqd : nullptr;  // (the unpack's first matrix is never null)
-    for (int part = 0; part < 2; part++) {
-        const size_t b0 = part == 0 ? 0 : Bg, nbp = part == 0 ? Bg : B - Bg;
-        if (nbp == 0) continue;
-        const int ilp = part == 0 ? il : 1;
-        const size_t g = tile_grid(t->n_cu, ilp > 1 ? waves_il : waves_sm, nbp);
+    return for_groups_then_tail(B, unpack_runs_interleave(nvi, sizeof(T)), [&](size_t b0, size_t nb, int ilp) {
+        const size_t g = tile_grid(t->n_cu, ilp > 1 ? waves_il : waves_sm, nb);
         hipError_t e = launch_rnea_deriv<T>(d, t->deriv_bodies, p->host.n_clusters, p->host.deriv.n_rows, p->host.deriv.n_max, q + b0 * nq, qd + b0 * nv,
-                                            ydd + b0 * nv, dq ? dq + b0 * nn : nullptr, dqd ? dqd + b0 * nn : nullptr, nullptr, nbp, static_cast<T *>(scratch),
+                                            ydd + b0 * nv, dq ? dq + b0 * nn : nullptr, dqd ? dqd + b0 * nn : nullptr, nullptr, nb, static_cast<T *>(scratch),
                                             static_cast<int>(g), hs, ilp);
         if (e != hipSuccess) return hip_err(e, "rnea derivative launch");
-        // (a persistent grid: as many workgroups of 256 threads as a CU holds, eight at the most)
-        const size_t units = nbp / ilp;
-        size_t g2 = static_cast<size_t>(t->n_cu) * std::min<size_t>(8, lds_workgroups_per_cu(unpack_runs_lds_bytes(nvi, sizeof(T), ilp) + 512));
-        if (g2 > units) g2 = units;
-        e = launch_unpack_runs<T>(o0 + b0 * nn, o1 ? o1 + b0 * nn : nullptr, t->deriv_related, nvi, nbp, static_cast<int>(g2), hs, ilp);
-        if (e != hipSuccess) return hip_err(e, "run unpack launch");
-    }
-    return GRBDA_OK;
+        // (workgroups of 256 threads, eight per CU at the most)
+        const size_t g2 = persistent_grid(t->n_cu, 8, unpack_runs_lds_bytes(nvi, sizeof(T), ilp), nb / ilp);
+        e = launch_unpack_runs<T>(o0 + b0 * nn, o1 ? o1 + b0 * nn : nullptr, t->deriv_related, nvi, nb, static_cast<int>(g2), hs, ilp);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "run unpack launch");
+    });
 }
 template <class T>
 int mass_matrix(const grbda_plan *p, const T *q, T *H, size_t B, int device, void *stream)
 {
-    if (const int rc = manifold_mass<T>(p, q, H, B, device, stream); rc != 1) return rc;
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (!q || !H) return set_err(GRBDA_EINVAL, "null argument");
+    if (B == 0) return GRBDA_OK;
+    const MassPath m = choose_derivs(p, false, sizeof(T), false, false, false).mass;
+    if (m == MASS_MANIFOLD) return manifold_derivs<T>(p, q, nullptr, nullptr, nullptr, nullptr, nullptr, H, B, device, stream);
+    if (m == MASS_CRBA) return crba_mass<T>(p, q, H, B, device, stream);
     return derived<T>(p, DM_MASS, q, nullptr, nullptr, nullptr, H, B, device, stream);
 }
 // the argument rules of grbda_rnea_derivatives_* (device and host arrays alike)
@@ -2441,6 +2475,7 @@ int rnea_derivatives(const grbda_plan *p, const T *q, const T *qd, const T *ydd,
     return id_derivs<T>(p, q, qd, ydd, step, dq, dqd, B, device, stream);
 }
 
+// the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
 template <class T>
 static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B)
 {
@@ -2902,7 +2937,7 @@ int grbda_plan_info(const grbda_plan *p, grbda_plan_info_t *info)
     info->chain_aba_f64 = p->host.chain[SLOT_F64].ok && !p->opt.no_chain;
     info->chain_rnea_f32 = p->host.rchain[SLOT_F32].ok && !p->opt.no_chain;
     info->chain_rnea_f64 = p->host.rchain[SLOT_F64].ok && !p->opt.no_chain;
-    info->analytic_derivatives = (analytic_covers<double>(p) || manifold_covers<double>(p)) ? 1 : 0;
+    info->analytic_derivatives = (analytic_covers(p) || manifold_covers(p)) ? 1 : 0;
     info->n_chain_differentials = p->opt.no_chain ? 0 : static_cast<int>(p->host.chain[SLOT_F32].diffs.size());
     info->latency_mode_f32 = p->host.chain[SLOT_LM2_F32].ok && !p->opt.no_chain && !p->opt.no_latency_mode;
     info->latency_mode_f64 = p->host.chain[SLOT_LM2_F64].ok && !p->opt.no_chain && !p->opt.no_latency_mode;
@@ -2932,99 +2967,53 @@ int grbda_rnea_f32(const grbda_plan *p, const float *q, const float *qd, const f
     return run<float>(p, true, q, qd, ydd, f_ext, tau, B, device, stream);
 }
 
-int grbda_bias_f64(const grbda_plan *p, const double *q, const double *qd, const double *f_ext, double *out, size_t B,
-                   int device, void *stream)
+int grbda_bias_f64(const grbda_plan *p, const double *q, const double *qd, const double *f_ext, double *out, size_t B, int device, void *stream)
 {
     return derived<double>(p, DM_BIAS, q, qd, nullptr, f_ext, out, B, device, stream);
 }
-int grbda_bias_f32(const grbda_plan *p, const float *q, const float *qd, const float *f_ext, float *out, size_t B,
-                   int device, void *stream)
+int grbda_bias_f32(const grbda_plan *p, const float *q, const float *qd, const float *f_ext, float *out, size_t B, int device, void *stream)
 {
     return derived<float>(p, DM_BIAS, q, qd, nullptr, f_ext, out, B, device, stream);
 }
 int grbda_mass_matrix_f64(const grbda_plan *p, const double *q, double *H, size_t B, int device, void *stream)
 {
-    if (const int rc = manifold_mass<double>(p, q, H, B, device, stream); rc != 1) return rc;
-    return derived<double>(p, DM_MASS, q, nullptr, nullptr, nullptr, H, B, device, stream);
+    return mass_matrix<double>(p, q, H, B, device, stream);
 }
 int grbda_mass_matrix_f32(const grbda_plan *p, const float *q, float *H, size_t B, int device, void *stream)
 {
-    if (const int rc = manifold_mass<float>(p, q, H, B, device, stream); rc != 1) return rc;
-    return derived<float>(p, DM_MASS, q, nullptr, nullptr, nullptr, H, B, device, stream);
+    return mass_matrix<float>(p, q, H, B, device, stream);
 }
 int grbda_fd_dtau_f64(const grbda_plan *p, const double *q, double *Hinv, size_t B, int device, void *stream)
 {
-    if (p && q && Hinv)
-        if (const int rc = analytic_derivs<double>(p, q, nullptr, nullptr, nullptr, nullptr, Hinv, B, device, stream); rc != 1) return rc;
-    return derived<double>(p, DM_DTAU, q, nullptr, nullptr, nullptr, Hinv, B, device, stream);
+    return fd_dtau<double>(p, q, Hinv, B, device, stream);
 }
 int grbda_fd_dtau_f32(const grbda_plan *p, const float *q, float *Hinv, size_t B, int device, void *stream)
 {
-    if (p && q && Hinv)
-        if (const int rc = analytic_derivs<float>(p, q, nullptr, nullptr, nullptr, nullptr, Hinv, B, device, stream); rc != 1) return rc;
-    return derived<float>(p, DM_DTAU, q, nullptr, nullptr, nullptr, Hinv, B, device, stream);
+    return fd_dtau<float>(p, q, Hinv, B, device, stream);
 }
-int grbda_fd_dqd_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double *J, size_t B,
-                     int device, void *stream)
+int grbda_fd_dqd_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double *J, size_t B, int device, void *stream)
 {
-    if (p && q && qd && tau && J)
-        if (const int rc = analytic_derivs<double>(p, q, qd, tau, nullptr, J, nullptr, B, device, stream); rc != 1) return rc;
-    return derived<double>(p, DM_DQD, q, qd, tau, nullptr, J, B, device, stream);
+    return fd_dqd<double>(p, q, qd, tau, J, B, device, stream);
 }
-int grbda_fd_dqd_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, float *J, size_t B,
-                     int device, void *stream)
+int grbda_fd_dqd_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, float *J, size_t B, int device, void *stream)
 {
-    if (p && q && qd && tau && J)
-        if (const int rc = analytic_derivs<float>(p, q, qd, tau, nullptr, J, nullptr, B, device, stream); rc != 1) return rc;
-    return derived<float>(p, DM_DQD, q, qd, tau, nullptr, J, B, device, stream);
+    return fd_dqd<float>(p, q, qd, tau, J, B, device, stream);
 }
-
-int grbda_fd_dq_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double step, double *J,
-                    size_t B, int device, void *stream)
+int grbda_fd_dq_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double step, double *J, size_t B, int device, void *stream)
 {
-    if (p && q && qd && tau && J && step > 0)
-        if (const int rc = analytic_derivs<double>(p, q, qd, tau, J, nullptr, nullptr, B, device, stream); rc != 1) return rc;
-    return derived<double>(p, DM_DQ, q, qd, tau, nullptr, J, B, device, stream, step);
+    return fd_dq<double>(p, q, qd, tau, step, J, B, device, stream);
 }
-int grbda_fd_dq_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, double step, float *J,
-                    size_t B, int device, void *stream)
+int grbda_fd_dq_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, double step, float *J, size_t B, int device, void *stream)
 {
-    // A central difference in fp32 has no usable step (eps / h + h^2 bottoms out near 1e-2 relative): the differences
-    // are taken in fp64 on the converted inputs and the matrices converted back.
-    if (!p || !q || !qd || !tau || !J) return set_err(GRBDA_EINVAL, "null argument");
-    if (B == 0) return GRBDA_OK;
-    if (step > 0)
-        if (const int rc = analytic_derivs<float>(p, q, qd, tau, J, nullptr, nullptr, B, device, stream); rc != 1) return rc;
-    GRBDA_CALL_SCOPE(p);
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    const CvtArray arrays[] = {{q, nullptr, nq}, {qd, nullptr, nv}, {tau, nullptr, nv}, {nullptr, J, nv * nv}};
-    return through_f64(p, 64u << 20, arrays, B, device, stream, [&](double *const *a, size_t nb) {
-        return derived<double>(p, DM_DQ, a[0], a[1], a[2], nullptr, a[3], nb, device, stream, step);
-    });
+    return fd_dq<float>(p, q, qd, tau, step, J, B, device, stream);
 }
-int grbda_fd_derivatives_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double *dq, double *dqd,
-                             double *dtau, size_t B, int device, void *stream)
+int grbda_fd_derivatives_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, double *dq, double *dqd, double *dtau, size_t B, int device, void *stream)
 {
-    if (!p || !q || !qd || !tau) return set_err(GRBDA_EINVAL, "null argument");
-    const int rc = analytic_derivs<double>(p, q, qd, tau, dq, dqd, dtau, B, device, stream);
-    if (rc != 1) return rc;
-    if (dtau) if (const int r2 = grbda_fd_dtau_f64(p, q, dtau, B, device, stream)) return r2;
-    if (dqd) if (const int r2 = grbda_fd_dqd_f64(p, q, qd, tau, dqd, B, device, stream)) return r2;
-    if (dq) if (const int r2 = grbda_fd_dq_f64(p, q, qd, tau, 1e-6, dq, B, device, stream)) return r2;
-    return GRBDA_OK;
+    return fd_derivatives<double>(p, q, qd, tau, dq, dqd, dtau, B, device, stream);
 }
-int grbda_fd_derivatives_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, float *dq, float *dqd, float *dtau,
-                             size_t B, int device, void *stream)
+int grbda_fd_derivatives_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, float *dq, float *dqd, float *dtau, size_t B, int device, void *stream)
 {
-    if (!p || !q || !qd || !tau) return set_err(GRBDA_EINVAL, "null argument");
-    const int rc = analytic_derivs<float>(p, q, qd, tau, dq, dqd, dtau, B, device, stream);
-    if (rc != 1) return rc;
-    if (dtau) if (const int r2 = grbda_fd_dtau_f32(p, q, dtau, B, device, stream)) return r2;
-    if (dqd) if (const int r2 = grbda_fd_dqd_f32(p, q, qd, tau, dqd, B, device, stream)) return r2;
-    if (dq) if (const int r2 = grbda_fd_dq_f32(p, q, qd, tau, 1e-6, dq, B, device, stream)) return r2;
-    return GRBDA_OK;
+    return fd_derivatives<float>(p, q, qd, tau, dq, dqd, dtau, B, device, stream);
 }
 int grbda_rnea_derivatives_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double step, double *dtau_dq,
                                double *dtau_dqd, double *dtau_dydd, size_t B, int device, void *stream)
