@@ -1,6 +1,7 @@
 // capi.cpp -- implementation of include/grbda_hip.h on top of plan.cpp and kernels.hip.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cassert>
 #include <cmath>
 #include <cstdio>
@@ -867,7 +868,23 @@ int span_count(const grbda_plan *p)
     return n;
 }
 
-// launch shape of the ABA kernel of the same precision: the auxiliary kernels use its slot layout
+// Launch shape and scratch slab of an auxiliary kernel -- one that works on a slot layout of the forward dynamics of the same precision:
+// waves_per_cu one-wavefront workgroups per CU over the tiles of B states, `store_bytes` of slot store each, and a slab of `slab_rows` rows
+// besides the nq + 2 nv staged input rows.  The slab is sized by the grid before the LDS-fit clamp, where that is asked for (inherited).
+template <class T>
+int aux_launch(const grbda_plan *p, const DeviceTables &t, size_t B, size_t waves_per_cu, size_t store_bytes, bool clamp_to_lds_fit, size_t slab_rows,
+               int device, void *stream, LaunchShape &s, T *&scratch)
+{
+    const HostPlan &h = p->host;
+    s = launch_shape(t.n_cu, (B + kWave - 1) / kWave, waves_per_cu, store_bytes, h.nq, h.nv, sizeof(T),
+                     static_cast<size_t>(p->opt.lds_bytes_per_wave[sizeof(T) == 8 ? 1 : 0]), clamp_to_lds_fit);
+    void *sp = nullptr;
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid_unclamped, slab_rows + static_cast<size_t>(h.nq + 2 * h.nv), sizeof(T)), &sp)) return rc;
+    scratch = static_cast<T *>(sp);
+    return GRBDA_OK;
+}
+// the auxiliary kernels of kernels.hip: the ABA's own slot layout, one wavefront per SIMD (they are not register-tuned), no LDS-fit clamp
+// (inherited, not chosen)
 template <class T>
 int aux_setup(const grbda_plan *p, size_t B, int device, void *stream, DevPlan<T> &d, T **scratch, int *grid,
               size_t *lds_bytes)
@@ -878,14 +895,9 @@ int aux_setup(const grbda_plan *p, size_t B, int device, void *stream, DevPlan<T
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     d = make_dev_plan<T>(p, *t, false, false);
-    // one wavefront per SIMD: these kernels are not register-tuned (no LDS-fit clamp: inherited, not chosen)
-    const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, 4, static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T), d.nq, d.nv, sizeof(T),
-                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[sizeof(T) == 8 ? 1 : 0]), false);
-    const size_t n_glb = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv);
-    void *sp = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, n_glb, sizeof(T)), &sp)) return rc;
+    LaunchShape s;
+    if (int rc = aux_launch<T>(p, *t, B, 4, static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T), false, d.n_glb_slots, device, stream, s, *scratch)) return rc;
     d.lds_bytes = static_cast<int>(s.lds_bytes);
-    *scratch = static_cast<T *>(sp);
     *grid = static_cast<int>(s.grid);
     *lds_bytes = s.lds_bytes;
     return GRBDA_OK;
@@ -1009,14 +1021,14 @@ int integrate_launch(const grbda_plan *p, const T *q, const T *qd, const T *ydd,
     // explicit plan asks for the staging area alone, and in fp32 (two wavefronts per SIMD by registers) runs eight wavefronts per CU.
     const bool loops = has_loop_clusters(p);
     const size_t store = loops ? static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T) : 0;
-    const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, loops || sizeof(T) == 8 ? 4 : 8, store, d.nq, d.nv, sizeof(T),
-                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[sizeof(T) == 8 ? 1 : 0]), true);
-    const size_t n_glb = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(d.nq + 2 * d.nv) + kIntegrateLocalRows;
-    void *sp = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid_unclamped, n_glb, sizeof(T)), &sp)) return rc;
+    LaunchShape s;
+    T *scratch = nullptr;
+    if (int rc = aux_launch<T>(p, *t, B, loops || sizeof(T) == 8 ? 4 : 8, store, true, static_cast<size_t>(d.n_glb_slots) + kIntegrateLocalRows, device, stream, s,
+                               scratch))
+        return rc;
     d.lds_bytes = static_cast<int>(s.lds_bytes);
     hipError_t e = launch_integrate<T>(d, p->host.n_clusters, q, qd, ydd, static_cast<T>(dt), q_next, qd_next, ok, ok_and ? 1 : 0, B, max_iter, static_cast<T>(tol),
-                                       static_cast<T *>(sp), static_cast<int>(s.grid), s.lds_bytes, static_cast<hipStream_t>(stream));
+                                       scratch, static_cast<int>(s.grid), s.lds_bytes, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate launch");
 }
 
@@ -1164,6 +1176,64 @@ int state_convert(const grbda_plan *p, const uint8_t *pos_sp, const uint8_t *vel
 }
 
 // ---- contact side: body poses, test force (include/grbda_hip.h) ---------------------------------------------
+// ("1..8": kMaxContacts, devplan.h; `noun`: what the entry point calls its contacts)
+int contact_count(int n_contacts, const char *noun)
+{
+    if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, std::string("1..8 contact ") + noun + " per call");
+    return GRBDA_OK;
+}
+// the contact description of an entry point, checked on the host: the arrays, the count, then every body index
+template <class T>
+int contact_set(const grbda_plan *p, int n_contacts, const int *bodies, const double *offsets, const char *noun, ContactSet<T> &cs)
+{
+    if (!bodies || !offsets) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = contact_count(n_contacts, noun)) return rc;
+    cs.n = n_contacts;
+    for (int c = 0; c < n_contacts; c++) {
+        if (bodies[c] < 0 || bodies[c] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+        cs.body[c] = bodies[c];
+        for (int i = 0; i < 3; i++) cs.off[c][i] = static_cast<T>(offsets[3 * c + i]);
+    }
+    return GRBDA_OK;
+}
+// no output array may share a byte with an input array or with another output (null entries are skipped)
+template <size_t NI, size_t NO>
+int no_overlap(const void *const (&in)[NI], const size_t (&in_bytes)[NI], const void *const (&out)[NO], const size_t (&out_bytes)[NO])
+{
+    for (size_t i = 0; i < NO; i++) {
+        for (size_t j = 0; j < NI; j++)
+            if (ranges_overlap(out[i], out_bytes[i], in[j], in_bytes[j])) return set_err(GRBDA_EINVAL, "an output array overlaps an input array");
+        for (size_t j = i + 1; j < NO; j++)
+            if (ranges_overlap(out[i], out_bytes[i], out[j], out_bytes[j])) return set_err(GRBDA_EINVAL, "two output arrays overlap");
+    }
+    return GRBDA_OK;
+}
+template <class T>
+std::array<T, 3> gravity3(const grbda_plan *p)  // the plan's gravity, linear part (world axes)
+{
+    return {static_cast<T>(p->host.gravity[3]), static_cast<T>(p->host.gravity[4]), static_cast<T>(p->host.gravity[5])};
+}
+
+// The stages of the kinematics (arguments checked, nb > 0, device found): poses_kernel; the spanning rates into the caller's work arrays
+// vs, as [nb][span_count], then twists_kernel.
+template <class T>
+int poses_stage(const grbda_plan *p, const DeviceTables &t, const T *q, T *Xa, size_t nb, void *stream)
+{
+    const DevPlan<T> d = make_dev_plan<T>(p, t, false, false);
+    hipError_t e = launch_poses<T>(d, p->host.n_clusters, q, Xa, nb, static_cast<int>(tile_grid(t.n_cu, 8, nb)), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "poses launch");
+}
+template <class T>
+int twists_stage(const grbda_plan *p, const DeviceTables &t, const T *q, const T *qd, const T *ydd, T *V, T *vs, T *as, size_t nb, int device,
+                 void *stream)
+{
+    if (int rc = spanning<T>(p, q, qd, ydd, vs, as, nb, device, stream)) return rc;
+    const DevPlan<T> d = make_dev_plan<T>(p, t, false, false);
+    hipError_t e = launch_twists<T>(d, p->host.n_clusters, span_count(p), q, vs, as, V, nb, static_cast<int>(tile_grid(t.n_cu, 8, nb)),
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "twists launch");
+}
+
 template <class T>
 int poses(const grbda_plan *p, const T *q, T *Xa, size_t B, int device, void *stream)
 {
@@ -1173,24 +1243,7 @@ int poses(const grbda_plan *p, const T *q, T *Xa, size_t B, int device, void *st
     if (B == 0) return GRBDA_OK;
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
-    DevPlan<T> d = make_dev_plan<T>(p, *t, false, false);
-    const size_t g = tile_grid(t->n_cu, 8, B);
-    hipError_t e = launch_poses<T>(d, p->host.n_clusters, q, Xa, B, static_cast<int>(g), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? GRBDA_OK : hip_err(e, "poses launch");
-}
-
-// the two launches of twists() on work arrays of the caller's: vs, as [B][span_count] (arguments checked, B > 0)
-template <class T>
-int twists_core(const grbda_plan *p, const DeviceTables &t, const T *q, const T *qd, const T *ydd, T *V, T *vs, T *as, size_t B, int device,
-                void *stream)
-{
-    const size_t ns = static_cast<size_t>(span_count(p));
-    if (int rc = spanning<T>(p, q, qd, ydd, vs, as, B, device, stream)) return rc;
-    DevPlan<T> d = make_dev_plan<T>(p, t, false, false);
-    const size_t g = tile_grid(t.n_cu, 8, B);
-    hipError_t e = launch_twists<T>(d, p->host.n_clusters, static_cast<int>(ns), q, vs, as, V, B, static_cast<int>(g),
-                                    static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? GRBDA_OK : hip_err(e, "twists launch");
+    return poses_stage<T>(p, *t, q, Xa, B, stream);
 }
 
 // spatial velocity / acceleration of every body: the spanning rates (spanning_kernel) into the plan's per-(device, stream)
@@ -1209,9 +1262,11 @@ int twists(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *V, siz
     if (int rc = ensure_work(p, p->work, device, stream, 2 * B * ns * sizeof(T) + 256, &wptr)) return rc;
     Carver<T> w(wptr, 2 * B * ns);
     T *vs = w.take(B * ns), *as = w.take(B * ns);
-    return twists_core<T>(p, *t, q, qd, ydd, V, vs, as, B, device, stream);
+    return twists_stage<T>(p, *t, q, qd, ydd, V, vs, as, B, device, stream);
 }
 
+// ---- inverse operational-space inertia of a set of contact frames (include/grbda_hip.h) -----------------------
+// (ContactSet<T>, kMaxContacts: devplan.h)
 // world wrench (about the world origin) of a Cartesian force at a point fixed in body `body`
 template <class T>
 __global__ void wrench_kernel(const T *__restrict__ Xa, const T *__restrict__ force, int n_bodies, int body, T ox, T oy,
@@ -1252,60 +1307,6 @@ __global__ void test_force_finish(const T *__restrict__ a1, const T *__restrict_
     }
 }
 
-template <class T>
-int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *bodies, const double *offsets, T *Linv, T *J,
-                   size_t B, int device, void *stream, const T *tf_force, T *tf_lambda, T *tf_dstate);
-
-template <class T>
-int test_force(const grbda_plan *p, const T *q, int body, const double *offset, const T *force, T *lambda_inv, T *dstate,
-               size_t B, int device, void *stream)
-{
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    if (!q || !offset || !force || !lambda_inv || !dstate) return set_err(GRBDA_EINVAL, "null argument");
-    if (body < 0 || body >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
-    if (B == 0) return GRBDA_OK;
-    {   // models the chain program covers: one launch of the force-propagation kernel (osim_chain_kernel, applyTestForce mode)
-        const int rc = inv_osim_chain<T>(p, q, 1, &body, offset, nullptr, nullptr, B, device, stream, force, lambda_inv, dstate);
-        if (rc != 1) return rc;
-    }
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies;
-    const size_t per_state = nbod * 18 + 5 * nv;  // poses, wrenches, zeros, four results
-    const Chunk c = fixed_chunk(256u << 20, per_state * sizeof(T), B);
-    const size_t chunk = c.chunk;
-    void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
-    Carver<T> w(wptr, chunk * per_state);
-    T *Xa = w.take(chunk * nbod * 12), *fext = w.take(chunk * nbod * 6), *zero = w.take(chunk * nv);
-    T *a1 = w.take(chunk * nv), *a0 = w.take(chunk * nv), *t1 = w.take(chunk * nv), *t0 = w.take(chunk * nv);
-    assert(w.taken == w.cap);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(zero, 0, chunk * nv * sizeof(T), hs);
-    if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    for (const auto [b0, nb] : ChunkWalk{B, chunk}) {
-        const T *qc = q + b0 * nq;
-        if (int rc = poses<T>(p, qc, Xa, nb, device, stream)) return rc;
-        const int blocks = blocks_for(nb);
-        hipLaunchKernelGGL((wrench_kernel<T>), dim3(blocks), dim3(256), 0, hs, Xa, force + 3 * b0, static_cast<int>(nbod),
-                           body, static_cast<T>(offset[0]), static_cast<T>(offset[1]), static_cast<T>(offset[2]), nb, fext);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "wrench launch");
-        int rc;
-        if ((rc = run<T>(p, false, qc, zero, zero, fext, a1, nb, device, stream)) ||
-            (rc = run<T>(p, false, qc, zero, zero, nullptr, a0, nb, device, stream)) ||
-            (rc = run<T>(p, true, qc, zero, zero, fext, t1, nb, device, stream)) ||
-            (rc = run<T>(p, true, qc, zero, zero, nullptr, t0, nb, device, stream)))
-            return rc;
-        hipLaunchKernelGGL((test_force_finish<T>), dim3(blocks), dim3(256), 0, hs, a1, a0, t1, t0, static_cast<int>(nv), nb,
-                           dstate + b0 * nv, lambda_inv + b0);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "finish launch");
-    }
-    return GRBDA_OK;
-}
-
-// ---- inverse operational-space inertia of a set of contact frames (include/grbda_hip.h) -----------------------
-// (ContactSet<T>, kMaxContacts: devplan.h)
 // rows (b, j), j < 6 n: unit spatial force e_{j % 6} in contact frame j / 6 (body axes, origin at the contact
 // point) as a world wrench on that body; row 6 n: no force
 template <class T>
@@ -1359,27 +1360,43 @@ __global__ void osim_combine_kernel(const T *__restrict__ acc, const T *__restri
     }
 }
 
-// Inverse OSIM by force propagation (chain_kernels.hip, osim_chain_kernel) for models the chain program covers and contact
-// frames on link / base bodies.  Returns 1 when the fast path does not apply (the caller then takes the unit-wrench path).
-// The host half: the argument block of the force-propagation kernel for these contacts; false when the fast path does not apply.
+// The unit-wrench route: 6 n + 1 rows per state through the forward and the inverse dynamics.  Scalars of work space per state: the poses;
+// per row q, wrenches, zeros and the two results.
+size_t osim_unit_per_state(const grbda_plan *p, int n_contacts)
+{
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, R = 6 * static_cast<size_t>(n_contacts) + 1;
+    return nbod * 12 + R * (nq + nbod * 6 + 3 * nv);
+}
+// Which way one call takes the inverse OSIM (grbda_inv_osim_*, grbda_apply_test_force_*, grbda_contact_dynamics_*; table in DESIGN.md):
+// force propagation along the contacts' ancestor paths (chain_kernels.hip, osim_chain_kernel) for models the chain program covers and
+// contact frames on link / base bodies, else unit wrenches.  Asked once per call, after the argument checks.
 template <class T>
-bool osim_chain_args(const grbda_plan *p, int n_contacts, const int *bodies, const double *offsets, bool want_J, const T *tf_force, T *tf_lambda,
-                     T *tf_dstate, OsimArgs<T> &A)
+struct OsimRoute {
+    bool chain;           // force propagation; else the unit-wrench route
+    OsimArgs<T> args;     // chain: the argument block of the force-propagation kernel for these contacts
+    size_t ws_per_state;  // scalars of work space per state: nv zeros (chain), osim_unit_per_state (unit wrenches)
+};
+// (tf_*: applyTestForce mode, one contact)
+template <class T>
+OsimRoute<T> choose_osim(const grbda_plan *p, int n_contacts, const int *bodies, const double *offsets, bool want_J, const T *tf_force, T *tf_lambda,
+                         T *tf_dstate)
 {
     const HostPlan &h = p->host;
     const ChainSlot slot = chain_slot(sizeof(T) == 8);
     const ChainProgram &cp = h.chain[slot];
-    // (programs with generic clusters -- plan.h, ChainGen -- have no walk steps in the force-propagation kernel: unit-wrench path)
-    if (p->opt.no_chain || p->opt.no_efpa || !cp.ok || !cp.gens.empty() || n_contacts > kOsimMaxContacts) return false;
+    OsimRoute<T> r{};  // (every early return below: the unit-wrench route)
+    r.ws_per_state = osim_unit_per_state(p, n_contacts);
+    // (programs with generic clusters -- plan.h, ChainGen -- have no walk steps in the force-propagation kernel)
+    if (p->opt.no_chain || p->opt.no_efpa || !cp.ok || !cp.gens.empty() || n_contacts > kOsimMaxContacts) return r;
     const Layout &L = h.lay64;
-    std::memset(&A, 0, sizeof A);
+    OsimArgs<T> &A = r.args;
     A.n_contacts = n_contacts;
     A.want_J = want_J ? 1 : 0;
     A.test_force = tf_force ? 1 : 0;
     A.force = tf_force;
     A.lambda_inv = tf_lambda;
     A.dstate = tf_dstate;
-    if (tf_force && n_contacts != 1) return false;
+    if (tf_force && n_contacts != 1) return r;
     std::vector<std::vector<int>> path_clusters(n_contacts);
     int max_rows = 0;
     for (int e = 0; e < n_contacts; e++) {
@@ -1388,7 +1405,7 @@ bool osim_chain_args(const grbda_plan *p, int n_contacts, const int *bodies, con
         int rows = 0, len = 0;
         bool first = true;
         while (c >= 0) {
-            if (len >= kOsimMaxPath) return false;
+            if (len >= kOsimMaxPath) return r;
             const ClusterRec &cr = L.clusters[c];
             OsimStep st;
             st.v_index = static_cast<int16_t>(cr.v_index);
@@ -1400,7 +1417,7 @@ bool osim_chain_args(const grbda_plan *p, int n_contacts, const int *bodies, con
                 st.kind = OSIM_FREE;
                 rows += 6;
             } else if (cr.shape != SHAPE_GENERIC) {
-                if (first && b != cr.link_body) return false;  // a contact on a rotor
+                if (first && b != cr.link_body) return r;  // a contact on a rotor
                 for (size_t i = 0; i < cp.links.size(); i++)
                     if (cp.links[i].v_index == cr.v_index) found = static_cast<int>(i);
                 st.kind = OSIM_LINK;
@@ -1414,22 +1431,22 @@ bool osim_chain_args(const grbda_plan *p, int n_contacts, const int *bodies, con
                 // contact on it) or at link2 (a contact on it or below)
                 for (size_t i = 0; i < cp.diffs.size(); i++)
                     if (cp.diffs[i].v_index == cr.v_index) found = static_cast<int>(i);
-                if (found < 0) return false;
+                if (found < 0) return r;
                 if (!first || L.bodies[b].cofs == cp.diffs[found].cofs[1]) st.kind = OSIM_DIFF_LINK2;
                 else if (L.bodies[b].cofs == cp.diffs[found].cofs[0]) st.kind = OSIM_DIFF_LINK1;
-                else return false;  // a contact on a rotor
+                else return r;  // a contact on a rotor
                 rows += 2;
             } else {
-                if (!first) return false;  // pair clusters are leaves of the chain program
+                if (!first) return r;  // pair clusters are leaves of the chain program
                 for (size_t i = 0; i < cp.pairs.size(); i++)
                     if (cp.pairs[i].v_index == cr.v_index) found = static_cast<int>(i);
-                if (found < 0) return false;
+                if (found < 0) return r;
                 if (L.bodies[b].cofs == cp.pairs[found].cofs[0]) st.kind = OSIM_PAIR_LINK1;
                 else if (L.bodies[b].cofs == cp.pairs[found].cofs[1]) st.kind = OSIM_PAIR_LINK2;
-                else return false;
+                else return r;
                 rows += 2;
             }
-            if (found < 0) return false;
+            if (found < 0) return r;
             st.rec = static_cast<int16_t>(found);
             A.path[e][len++] = st;
             path_clusters[e].push_back(c);
@@ -1476,65 +1493,41 @@ bool osim_chain_args(const grbda_plan *p, int n_contacts, const int *bodies, con
         }
     A.w_base = cp.n_glb;
     A.w_stride = 6 * max_rows;
-    return true;
+    r.chain = true;
+    r.ws_per_state = static_cast<size_t>(h.nv);
+    return r;
 }
-// The device half: one launch of osim_chain_kernel.  zeros: B * nv scalars of the caller's work space (cleared here), which stand in for
-// the velocities and torques of every tile.
+// The force-propagation route: one launch of osim_chain_kernel.  zeros: B * nv scalars of the caller's work space (cleared here), which
+// stand in for the velocities and torques of every tile.
 template <class T>
-int osim_chain_launch(const grbda_plan *p, const OsimArgs<T> &A, const T *q, T *Linv, T *J, size_t B, int device, void *stream, T *zeros)
+int osim_chain_launch(const grbda_plan *p, const DeviceTables &t, const OsimArgs<T> &A, const T *q, T *Linv, T *J, size_t B, int device, void *stream,
+                      T *zeros)
 {
     const HostPlan &h = p->host;
     const ChainSlot slot = chain_slot(sizeof(T) == 8);
     const ChainProgram &cp = h.chain[slot];
-    const int n_contacts = A.n_contacts;
-    const bool tf_force = A.test_force != 0;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    ChainDev<T> d = chain_dev<T>(p, *t, slot);
+    ChainDev<T> d = chain_dev<T>(p, t, slot);
     no_gens(d);
-    d.n_glb_slots = cp.n_glb + n_contacts * A.w_stride;
+    d.n_glb_slots = cp.n_glb + A.n_contacts * A.w_stride;
     d.out_lds = -1;  // (the force-propagation kernel keeps its result rows in the slab)
     // (gravity enters the acceleration sweep only, which runs in applyTestForce mode alone -- there without it)
-    if (tf_force)
+    if (A.test_force)
         for (int i = 0; i < 6; i++) d.a_root[i] = T(0);
     // one wavefront per SIMD: the walk kernel is not register-tuned (no LDS-fit clamp: inherited, not chosen)
-    const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, 4, static_cast<size_t>(cp.n_lds) * kWave * sizeof(T), h.nq, h.nv, sizeof(T),
-                                       static_cast<size_t>(p->opt.lds_bytes_per_wave[sizeof(T) == 8 ? 1 : 0]), false);
+    LaunchShape s;
+    T *scratch = nullptr;
+    if (int rc = aux_launch<T>(p, t, B, 4, static_cast<size_t>(cp.n_lds) * kWave * sizeof(T), false, d.n_glb_slots, device, stream, s, scratch)) return rc;
     d.lds_bytes = static_cast<int>(s.lds_bytes);
-    const size_t n_rows = static_cast<size_t>(d.n_glb_slots) + static_cast<size_t>(h.nq + 2 * h.nv);
-    void *scratch = nullptr;
-    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, n_rows, sizeof(T)), &scratch)) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     hipError_t e;
     if ((e = hipMemsetAsync(zeros, 0, B * static_cast<size_t>(h.nv) * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    e = launch_osim_chain<T>(d, A, q, static_cast<const T *>(zeros), Linv, J, B, static_cast<T *>(scratch), static_cast<int>(s.grid),
-                             s.lds_bytes, hs);
+    e = launch_osim_chain<T>(d, A, q, static_cast<const T *>(zeros), Linv, J, B, scratch, static_cast<int>(s.grid), s.lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "osim chain launch");
 }
+// nb states of the unit-wrench route on the caller's work space: takes nb * osim_unit_per_state scalars from w
 template <class T>
-int inv_osim_chain(const grbda_plan *p, const T *q, int n_contacts, const int *bodies, const double *offsets, T *Linv, T *J,
-                   size_t B, int device, void *stream, const T *tf_force, T *tf_lambda, T *tf_dstate)
-{
-    OsimArgs<T> A;
-    if (!osim_chain_args<T>(p, n_contacts, bodies, offsets, J != nullptr, tf_force, tf_lambda, tf_dstate, A)) return 1;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    // the block of zeros (grown under ensure_work's capture rule)
-    void *zeros = nullptr;
-    if (int rc = ensure_work(p, p->work, device, stream, B * static_cast<size_t>(p->host.nv) * sizeof(T) + 256, &zeros)) return rc;
-    return osim_chain_launch<T>(p, A, q, Linv, J, B, device, stream, static_cast<T *>(zeros));
-}
-
-// The unit-wrench route: 6 n + 1 rows per state through the forward and the inverse dynamics.  Scalars of work space per state: the poses;
-// per row q, wrenches, zeros and the two results.
-size_t osim_unit_per_state(const grbda_plan *p, int n_contacts)
-{
-    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, R = 6 * static_cast<size_t>(n_contacts) + 1;
-    return nbod * 12 + R * (nq + nbod * 6 + 3 * nv);
-}
-// nb states of that route on the caller's work space: takes nb * osim_unit_per_state scalars from w
-template <class T>
-int inv_osim_unit(const grbda_plan *p, const ContactSet<T> &cs, const T *q, T *Linv, T *J, size_t nb, int device, void *stream, Carver<T> &w)
+int inv_osim_unit(const grbda_plan *p, const DeviceTables &t, const ContactSet<T> &cs, const T *q, T *Linv, T *J, size_t nb, int device, void *stream,
+                  Carver<T> &w)
 {
     const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies;
     const size_t m = 6 * static_cast<size_t>(cs.n), R = m + 1, nrows = nb * R;
@@ -1546,7 +1539,7 @@ int inv_osim_unit(const grbda_plan *p, const ContactSet<T> &cs, const T *q, T *L
     hipStream_t hs = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(zero, 0, nrows * nv * sizeof(T), hs);
     if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    if (int rc = poses<T>(p, q, Xa, nb, device, stream)) return rc;
+    if (int rc = poses_stage<T>(p, t, q, Xa, nb, stream)) return rc;
     hipLaunchKernelGGL((osim_expand_kernel<T>), dim3(blocks_for(nrows)), dim3(256), 0, hs, cs, q, Xa, static_cast<int>(nq), static_cast<int>(nbod), nb,
                        qx, fext);
     if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "expand launch");
@@ -1555,78 +1548,100 @@ int inv_osim_unit(const grbda_plan *p, const ContactSet<T> &cs, const T *q, T *L
         return rc;
     hipLaunchKernelGGL((osim_combine_kernel<T>), dim3(blocks_for(nb * m * m)), dim3(256), 0, hs, acc, tau, static_cast<int>(nv), static_cast<int>(m), nb,
                        Linv, J);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "combine launch");
+    return (e = hipGetLastError()) == hipSuccess ? GRBDA_OK : hip_err(e, "combine launch");
+}
+// nb states of the inverse OSIM on the route chosen: takes nb * r.ws_per_state scalars from w
+template <class T>
+int osim_stage(const grbda_plan *p, const DeviceTables &t, const OsimRoute<T> &r, const ContactSet<T> &cs, const T *q, T *Linv, T *J, size_t nb, int device,
+               void *stream, Carver<T> &w)
+{
+    if (r.chain) return osim_chain_launch<T>(p, t, r.args, q, Linv, J, nb, device, stream, w.take(nb * r.ws_per_state));
+    return inv_osim_unit<T>(p, t, cs, q, Linv, J, nb, device, stream, w);
+}
+
+// grbda_apply_test_force_*: the force-propagation kernel in applyTestForce mode, one unchunked launch; else four runs of the dynamics per
+// chunk, with and without the point's wrench
+template <class T>
+int test_force(const grbda_plan *p, const T *q, int body, const double *offset, const T *force, T *lambda_inv, T *dstate,
+               size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (!q || !offset || !force || !lambda_inv || !dstate) return set_err(GRBDA_EINVAL, "null argument");
+    if (body < 0 || body >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    if (B == 0) return GRBDA_OK;
+    const OsimRoute<T> r = choose_osim<T>(p, 1, &body, offset, false, force, lambda_inv, dstate);
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    void *wptr = nullptr;
+    if (r.chain) {  // (the block of zeros: grown under ensure_work's capture rule)
+        if (int rc = ensure_work(p, p->work, device, stream, B * r.ws_per_state * sizeof(T) + 256, &wptr)) return rc;
+        return osim_chain_launch<T>(p, *t, r.args, q, nullptr, nullptr, B, device, stream, static_cast<T *>(wptr));
+    }
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies;
+    const size_t per_state = nbod * 18 + 5 * nv;  // poses, wrenches, zeros, four results
+    const Chunk c = fixed_chunk(256u << 20, per_state * sizeof(T), B);
+    const size_t chunk = c.chunk;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, chunk * per_state);
+    T *Xa = w.take(chunk * nbod * 12), *fext = w.take(chunk * nbod * 6), *zero = w.take(chunk * nv);
+    T *a1 = w.take(chunk * nv), *a0 = w.take(chunk * nv), *t1 = w.take(chunk * nv), *t0 = w.take(chunk * nv);
+    assert(w.taken == w.cap);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(zero, 0, chunk * nv * sizeof(T), hs);
+    if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    for (const auto [b0, nb] : ChunkWalk{B, chunk}) {
+        const T *qc = q + b0 * nq;
+        if (int rc = poses_stage<T>(p, *t, qc, Xa, nb, stream)) return rc;
+        const int blocks = blocks_for(nb);
+        hipLaunchKernelGGL((wrench_kernel<T>), dim3(blocks), dim3(256), 0, hs, Xa, force + 3 * b0, static_cast<int>(nbod),
+                           body, static_cast<T>(offset[0]), static_cast<T>(offset[1]), static_cast<T>(offset[2]), nb, fext);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "wrench launch");
+        int rc;
+        if ((rc = run<T>(p, false, qc, zero, zero, fext, a1, nb, device, stream)) ||
+            (rc = run<T>(p, false, qc, zero, zero, nullptr, a0, nb, device, stream)) ||
+            (rc = run<T>(p, true, qc, zero, zero, fext, t1, nb, device, stream)) ||
+            (rc = run<T>(p, true, qc, zero, zero, nullptr, t0, nb, device, stream)))
+            return rc;
+        hipLaunchKernelGGL((test_force_finish<T>), dim3(blocks), dim3(256), 0, hs, a1, a0, t1, t0, static_cast<int>(nv), nb,
+                           dstate + b0 * nv, lambda_inv + b0);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "finish launch");
+    }
     return GRBDA_OK;
 }
 
+// grbda_inv_osim_*: force propagation in one unchunked launch over the batch, unit wrenches in chunks of 256 MiB
 template <class T>
 int inv_osim(const grbda_plan *p, const T *q, int n_contacts, const int *bodies, const double *offsets, T *Linv, T *J,
              size_t B, int device, void *stream)
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (!q || !bodies || !offsets || !Linv) return set_err(GRBDA_EINVAL, "null argument");
-    if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact frames per call");
+    if (!q || !Linv) return set_err(GRBDA_EINVAL, "null argument");
     ContactSet<T> cs;
-    cs.n = n_contacts;
-    for (int c = 0; c < n_contacts; c++) {
-        if (bodies[c] < 0 || bodies[c] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
-        cs.body[c] = bodies[c];
-        for (int i = 0; i < 3; i++) cs.off[c][i] = static_cast<T>(offsets[3 * c + i]);
-    }
+    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, "frames", cs)) return rc;
     if (B == 0) return GRBDA_OK;
-    {
-        const int rc = inv_osim_chain<T>(p, q, n_contacts, bodies, offsets, Linv, J, B, device, stream, nullptr, nullptr, nullptr);
-        if (rc != 1) return rc;
-    }
+    const OsimRoute<T> r = choose_osim<T>(p, n_contacts, bodies, offsets, J != nullptr, nullptr, nullptr, nullptr);
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    const size_t m = 6 * static_cast<size_t>(n_contacts);
-    const size_t per_state = osim_unit_per_state(p, n_contacts);
-    const Chunk c = fixed_chunk(256u << 20, per_state * sizeof(T), B);
+    const size_t nq = p->host.nq, nv = p->host.nv, m = 6 * static_cast<size_t>(n_contacts), per_state = r.ws_per_state;
+    const Chunk c = r.chain ? Chunk{B, B * per_state * sizeof(T) + 256} : fixed_chunk(256u << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         Carver<T> w(wptr, c.chunk * per_state);
-        if (int rc = inv_osim_unit<T>(p, cs, q + b0 * nq, Linv + b0 * m * m, J ? J + b0 * m * nv : nullptr, nb, device, stream, w)) return rc;
+        if (int rc = osim_stage<T>(p, *t, r, cs, q + b0 * nq, Linv + b0 * m * m, J ? J + b0 * m * nv : nullptr, nb, device, stream, w)) return rc;
     }
     return GRBDA_OK;
 }
 
 // ---- contact points and contact-constrained forward dynamics (contact_kernels.hip; include/grbda_hip.h) -----------------------------
-// the contact description of grbda_inv_osim_*, checked on the host
-template <class T>
-int contact_set(const grbda_plan *p, int n_contacts, const int *bodies, const double *offsets, ContactSet<T> &cs)
-{
-    if (!bodies || !offsets) return set_err(GRBDA_EINVAL, "null argument");
-    if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact points per call");
-    cs.n = n_contacts;
-    for (int c = 0; c < n_contacts; c++) {
-        if (bodies[c] < 0 || bodies[c] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
-        cs.body[c] = bodies[c];
-        for (int i = 0; i < 3; i++) cs.off[c][i] = static_cast<T>(offsets[3 * c + i]);
-    }
-    return GRBDA_OK;
-}
-// no output array may share a byte with an input array or with another output (null entries are skipped)
-template <size_t NI, size_t NO>
-int no_overlap(const void *const (&in)[NI], const size_t (&in_bytes)[NI], const void *const (&out)[NO], const size_t (&out_bytes)[NO])
-{
-    for (size_t i = 0; i < NO; i++) {
-        for (size_t j = 0; j < NI; j++)
-            if (ranges_overlap(out[i], out_bytes[i], in[j], in_bytes[j])) return set_err(GRBDA_EINVAL, "an output array overlaps an input array");
-        for (size_t j = i + 1; j < NO; j++)
-            if (ranges_overlap(out[i], out_bytes[i], out[j], out_bytes[j])) return set_err(GRBDA_EINVAL, "two output arrays overlap");
-    }
-    return GRBDA_OK;
-}
 template <class T>
 int contact_points_args(const grbda_plan *p, const T *q, const T *qd, const T *ydd, int n_contacts, const int *bodies, const double *offsets,
                         const T *pos, const T *vel, const T *acc, size_t B, ContactSet<T> &cs)
 {
     if (!q) return set_err(GRBDA_EINVAL, "null argument");
-    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, cs)) return rc;
+    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, "points", cs)) return rc;
     if (!pos && !vel && !acc) return set_err(GRBDA_EINVAL, "no output asked for");
     if ((vel || acc) && !qd) return set_err(GRBDA_EINVAL, "vel and acc need qd");
     if (acc && !ydd) return set_err(GRBDA_EINVAL, "acc needs ydd");
@@ -1637,7 +1652,7 @@ int contact_points_args(const grbda_plan *p, const T *q, const T *qd, const T *y
     return no_overlap(in, in_bytes, out, out_bytes);
 }
 // Per chunk: poses, and for vel / acc the twists (at ydd, or at zeros when only vel is asked for), then contact_points_kernel.  One slab of
-// p->work for the whole pipeline (twists_core takes its spanning rates from it).
+// p->work for the whole pipeline (twists_stage takes its spanning rates from it).
 template <class T>
 int contact_points(const grbda_plan *p, const T *q, const T *qd, const T *ydd, int n_contacts, const int *bodies, const double *offsets, T *pos,
                    T *vel, T *acc, size_t B, int device, void *stream)
@@ -1662,12 +1677,12 @@ int contact_points(const grbda_plan *p, const T *q, const T *qd, const T *ydd, i
     hipStream_t hs = static_cast<hipStream_t>(stream);
     hipError_t e;
     if (zeros && (e = hipMemsetAsync(zeros, 0, c.chunk * nv * sizeof(T), hs)) != hipSuccess) return hip_err(e, "hipMemsetAsync");
-    const T g[3] = {static_cast<T>(p->host.gravity[3]), static_cast<T>(p->host.gravity[4]), static_cast<T>(p->host.gravity[5])};
+    const std::array<T, 3> g = gravity3<T>(p);
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
-        if (int rc = poses<T>(p, q + b0 * nq, Xa, nb, device, stream)) return rc;
+        if (int rc = poses_stage<T>(p, *t, q + b0 * nq, Xa, nb, stream)) return rc;
         if (rates)
-            if (int rc = twists_core<T>(p, *t, q + b0 * nq, qd + b0 * nv, zeros ? zeros : ydd + b0 * nv, V, vs, as, nb, device, stream)) return rc;
-        e = launch_contact_points<T>(cs, Xa, V, static_cast<int>(nbod), g, nb, pos ? pos + b0 * n * 3 : nullptr, vel ? vel + b0 * n * 3 : nullptr,
+            if (int rc = twists_stage<T>(p, *t, q + b0 * nq, qd + b0 * nv, zeros ? zeros : ydd + b0 * nv, V, vs, as, nb, device, stream)) return rc;
+        e = launch_contact_points<T>(cs, Xa, V, static_cast<int>(nbod), g.data(), nb, pos ? pos + b0 * n * 3 : nullptr, vel ? vel + b0 * n * 3 : nullptr,
                                      acc ? acc + b0 * n * 3 : nullptr, hs);
         if (e != hipSuccess) return hip_err(e, "contact points launch");
     }
@@ -1680,7 +1695,7 @@ int contact_dynamics_args(const grbda_plan *p, const T *q, const T *qd, const T 
                           ContactSet<T> &cs)
 {
     if (!q || !qd || !tau || !ydd || !lambda) return set_err(GRBDA_EINVAL, "null argument");
-    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, cs)) return rc;
+    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, "points", cs)) return rc;
     if (!std::isfinite(damping) || damping < 0) return set_err(GRBDA_EINVAL, "damping must be finite and not negative");
     const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
     const size_t bf = B * static_cast<size_t>(p->host.n_bodies) * 6 * sizeof(T), bc = B * static_cast<size_t>(n_contacts) * 3 * sizeof(T);
@@ -1703,17 +1718,15 @@ int contact_dynamics(const grbda_plan *p, const T *q, const T *qd, const T *tau,
     if (B == 0) return GRBDA_OK;
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
-    OsimArgs<T> A;
-    const bool chain = osim_chain_args<T>(p, n_contacts, bodies, offsets, false, nullptr, nullptr, nullptr, A);
+    const OsimRoute<T> r = choose_osim<T>(p, n_contacts, bodies, offsets, false, nullptr, nullptr, nullptr);
     const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n = static_cast<size_t>(n_contacts);
     const size_t m6 = 6 * n;
     // ydd_free (when the caller does not keep it), poses, twists and their spanning rates, Linv, wrench rows, and the inverse OSIM's own
-    const size_t osim_ws = chain ? nv : osim_unit_per_state(p, n_contacts);
-    const size_t per_state = (ydd_free ? 0 : nv) + nbod * 24 + 2 * ns + m6 * m6 + nbod * 6 + osim_ws;
+    const size_t per_state = (ydd_free ? 0 : nv) + nbod * 24 + 2 * ns + m6 * m6 + nbod * 6 + r.ws_per_state;
     const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
-    const T g[3] = {static_cast<T>(p->host.gravity[3]), static_cast<T>(p->host.gravity[4]), static_cast<T>(p->host.gravity[5])};
+    const std::array<T, 3> g = gravity3<T>(p);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         Carver<T> w(wptr, c.chunk * per_state);
@@ -1722,13 +1735,11 @@ int contact_dynamics(const grbda_plan *p, const T *q, const T *qd, const T *tau,
         T *Linv = w.take(nb * m6 * m6), *wrench = w.take(nb * nbod * 6);
         const T *qc = q + b0 * nq, *qdc = qd + b0 * nv, *tc = tau + b0 * nv, *fc = f_ext ? f_ext + b0 * nbod * 6 : nullptr;
         int rc;
-        if ((rc = run<T>(p, false, qc, qdc, tc, fc, yf, nb, device, stream)) || (rc = poses<T>(p, qc, Xa, nb, device, stream)) ||
-            (rc = twists_core<T>(p, *t, qc, qdc, yf, V, vs, as, nb, device, stream)))
+        if ((rc = run<T>(p, false, qc, qdc, tc, fc, yf, nb, device, stream)) || (rc = poses_stage<T>(p, *t, qc, Xa, nb, stream)) ||
+            (rc = twists_stage<T>(p, *t, qc, qdc, yf, V, vs, as, nb, device, stream)) ||
+            (rc = osim_stage<T>(p, *t, r, cs, qc, Linv, nullptr, nb, device, stream, w)))
             return rc;
-        if (chain) rc = osim_chain_launch<T>(p, A, qc, Linv, nullptr, nb, device, stream, w.take(nb * nv));
-        else rc = inv_osim_unit<T>(p, cs, qc, Linv, nullptr, nb, device, stream, w);
-        if (rc) return rc;
-        hipError_t e = launch_contact_solve<T>(cs, Linv, Xa, V, a_des ? a_des + b0 * n * 3 : nullptr, fc, static_cast<int>(nbod), static_cast<T>(damping), g, nb,
+        hipError_t e = launch_contact_solve<T>(cs, Linv, Xa, V, a_des ? a_des + b0 * n * 3 : nullptr, fc, static_cast<int>(nbod), static_cast<T>(damping), g.data(), nb,
                                                lambda + b0 * n * 3, wrench, t->bad_count, t->n_cu, hs);
         if (e != hipSuccess) return hip_err(e, "contact solve launch");
         if ((rc = run<T>(p, false, qc, qdc, tc, wrench, ydd + b0 * nv, nb, device, stream))) return rc;
@@ -2449,16 +2460,10 @@ int rnea_derivatives_args(const grbda_plan *p, const T *q, const T *qd, const T 
 {
     if (!q || !qd || !ydd) return set_err(GRBDA_EINVAL, "null argument");
     if (!dq && !dqd && !dydd) return set_err(GRBDA_EINVAL, "no output asked for");
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    const void *in[3] = {q, qd, ydd}, *out[3] = {dq, dqd, dydd};
-    const size_t in_bytes[3] = {B * nq * sizeof(T), B * nv * sizeof(T), B * nv * sizeof(T)}, out_bytes = B * nv * nv * sizeof(T);
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++)
-            if (ranges_overlap(out[i], out_bytes, in[j], in_bytes[j])) return set_err(GRBDA_EINVAL, "an output array overlaps an input array");
-        for (int j = i + 1; j < 3; j++)
-            if (ranges_overlap(out[i], out_bytes, out[j], out_bytes)) return set_err(GRBDA_EINVAL, "two output arrays overlap");
-    }
-    return GRBDA_OK;
+    const size_t nq = p->host.nq, nv = p->host.nv, bo = B * nv * nv * sizeof(T);
+    const void *const in[3] = {q, qd, ydd}, *const out[3] = {dq, dqd, dydd};
+    const size_t in_bytes[3] = {B * nq * sizeof(T), B * nv * sizeof(T), B * nv * sizeof(T)}, out_bytes[3] = {bo, bo, bo};
+    return no_overlap(in, in_bytes, out, out_bytes);
 }
 template <class T>
 int rnea_derivatives(const grbda_plan *p, const T *q, const T *qd, const T *ydd, double step, T *dq, T *dqd, T *dydd, size_t B, int device,
@@ -3109,7 +3114,7 @@ int grbda_contact_dynamics_f32(const grbda_plan *p, const float *q, const float 
 int grbda_contact_solve_launch(int n_contacts, int precision, int device, int *lanes, size_t *lds_bytes, size_t *grid_cap)
 {
     if (!lanes || !lds_bytes || !grid_cap || (precision != 32 && precision != 64)) return set_err(GRBDA_EINVAL, "bad argument");
-    if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact points per call");
+    if (int rc = contact_count(n_contacts, "points")) return rc;
     const ContactSolveLaunch L = contact_solve_launch(n_contacts, precision == 32 ? sizeof(float) : sizeof(double));
     if (L.lanes == 0) return set_err(GRBDA_EINVAL, "the contact solve does not fit the LDS");
     int n_cu = 1;
@@ -3247,7 +3252,7 @@ int grbda_inv_osim_host_f64(const grbda_plan *p, const double *q, int n_contacts
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
     if (!q || !Linv) return set_err(GRBDA_EINVAL, "null argument");
-    if (n_contacts < 1 || n_contacts > kMaxContacts) return set_err(GRBDA_EINVAL, "1..8 contact frames per call");
+    if (int rc = contact_count(n_contacts, "frames")) return rc;  // (the arrays and the body indices: the inner call's, once the device is found)
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const size_t nq = p->host.nq, nv = p->host.nv, m = 6 * static_cast<size_t>(n_contacts);

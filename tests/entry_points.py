@@ -217,7 +217,7 @@ def _chk_indep(blob, s, o, tol):
 
 OFFSET = (0.05, -0.02, 0.1)
 # contact frames on links, not rotors: a frame on a rotor sends the inverse OSIM and applyTestForce from the force-propagation kernel
-# (inv_osim_chain) to the unit-wrench route (Mini Cheetah)
+# (capi.cpp, choose_osim) to the unit-wrench route (Mini Cheetah)
 FORCE_BODY = "FL_knee_link"
 OSIM_BODIES = ("FR_knee_link", "FL_knee_link")
 
