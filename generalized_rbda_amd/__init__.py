@@ -41,6 +41,8 @@ C_ABI_SYMBOLS = [
     "grbda_rnea_derivatives_f64", "grbda_rnea_derivatives_f32", "grbda_rnea_derivatives_host_f64",
     "grbda_integrate_f64", "grbda_integrate_f32", "grbda_step_f64", "grbda_step_f32", "grbda_rollout_f64", "grbda_rollout_f32",
     "grbda_integrate_host_f64", "grbda_step_host_f64",
+    "grbda_plan_total_mass", "grbda_energy_f64", "grbda_energy_f32", "grbda_centroidal_f64", "grbda_centroidal_f32",
+    "grbda_centroidal_matrix_f64", "grbda_centroidal_matrix_f32", "grbda_energy_host_f64", "grbda_centroidal_host_f64",
 ]
 
 
@@ -155,6 +157,14 @@ def lib() -> ctypes.CDLL:
                                            c_double, c_size_t, c_int]
     L.grbda_step_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_int]
+    L.grbda_plan_total_mass.argtypes = [c_void_p, POINTER(c_double)]
+    for sfx in ("f64", "f32"):
+        getattr(L, "grbda_energy_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        getattr(L, "grbda_centroidal_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_size_t, c_int, c_void_p]
+        getattr(L, "grbda_centroidal_matrix_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+    L.grbda_energy_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
+    L.grbda_centroidal_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
     L.grbda_state_input_dims.argtypes = [c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]
     for sfx in ("f64", "f32"):
         getattr(L, "grbda_state_to_independent_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -662,6 +672,78 @@ class Plan:
                   lam.data_ptr(), free.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
         with torch.cuda.stream(s):
             return ydd, lam, free
+
+    # ---- energy and centroidal quantities -----------------------------------------------------------
+    def total_mass(self) -> float:
+        """The sum of the body masses (grbda_plan_total_mass); no device."""
+        m = c_double(0.0)
+        _check(lib().grbda_plan_total_mass(self._h, byref(m)))
+        return m.value
+
+    def _centroidal_call(self, name: str, q, qd, ydd, shapes, stream):
+        """one call of grbda_energy_* / grbda_centroidal_*: `shapes` maps every output to its per-state shape, or to None when it is
+        not asked for; returns the outputs in that order (None where not asked for)"""
+        import torch
+
+        given = [t for t in (qd, ydd) if t is not None]
+        self._floating(q, *given)
+        B = q.shape[0]
+        if not q.is_cuda or q.shape != (B, self.nq) or any(t.shape != (B, self.nv) or t.dtype != q.dtype or t.device != q.device for t in given):
+            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}] of one dtype")
+        q = q.contiguous()
+        qd = None if qd is None else qd.contiguous()
+        ydd = None if ydd is None else ydd.contiguous()
+        outs = [None if shp is None else torch.empty((B,) + shp, dtype=q.dtype, device=q.device) for shp in shapes]
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        if stream is not None:
+            for t in [q, qd, ydd] + outs:
+                if t is not None:
+                    t.record_stream(s)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        fn = getattr(lib(), f"grbda_{name}_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        ins = (ptr(qd),) if name == "energy" else (ptr(qd), ptr(ydd))
+        _check(fn(self._h, q.data_ptr(), *ins, *[ptr(o) for o in outs], B, q.device.index or 0, c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return outs
+
+    def energy(self, q, qd=None, stream=None):
+        """(kinetic[B], potential[B]) (grbda_energy_*): 1/2 yd^T H yd, None without qd; -g . sum m_i c_i, zero at the world origin."""
+        kinetic, potential = self._centroidal_call("energy", q, qd, None, [None if qd is None else (), ()], stream)
+        return kinetic, potential
+
+    def centroidal(self, q, qd=None, ydd=None, want=("com", "com_vel", "h", "hdot"), stream=None):
+        """Centre of mass, its velocity, the centroidal momentum and its rate (grbda_centroidal_*): a dict of the names in `want` --
+        com[B, 3], com_vel[B, 3], h[B, 6], hdot[B, 6], world axes, h and hdot [angular about the centre of mass; linear].  com_vel and h
+        need qd, hdot needs qd and ydd (the true generalized acceleration); with the default `want`, what the given inputs do not
+        allow is left out."""
+        names = ("com", "com_vel", "h", "hdot")
+        if any(w not in names for w in want):
+            raise ValueError(f"want holds names out of {names}")
+        default = tuple(want) == names
+        need = {"com": (), "com_vel": (qd,), "h": (qd,), "hdot": (qd, ydd)}
+        shape = {"com": (3,), "com_vel": (3,), "h": (6,), "hdot": (6,)}
+        ask = [n in want and not (default and any(t is None for t in need[n])) for n in names]
+        outs = self._centroidal_call("centroidal", q, qd, ydd, [shape[n] if a else None for n, a in zip(names, ask)], stream)
+        return {n: o for n, o, a in zip(names, outs, ask) if a}
+
+    def centroidal_matrix(self, q, stream=None):
+        """The centroidal momentum matrix A[B, 6, nv], h = A(q) yd (grbda_centroidal_matrix_*)."""
+        import torch
+
+        self._floating(q)
+        B = q.shape[0]
+        if not q.is_cuda or q.shape != (B, self.nq):
+            raise ValueError(f"expected a device tensor q[B,{self.nq}]")
+        q = q.contiguous()
+        A = torch.empty((B, 6, self.nv), dtype=q.dtype, device=q.device)
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        if stream is not None:
+            q.record_stream(s)
+            A.record_stream(s)
+        fn = getattr(lib(), f"grbda_centroidal_matrix_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        _check(fn(self._h, q.data_ptr(), A.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return A
 
     def fd_derivatives(self, q, qd, tau, want=("dq", "dqd", "dtau"), stream=None):
         """d ydd / d q, d ydd / d qd, d ydd / d tau of the forward dynamics in one pass (grbda_fd_derivatives_*): a dict

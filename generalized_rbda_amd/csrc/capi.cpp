@@ -82,6 +82,7 @@ struct DeviceTables {
     int32_t *minv_coltab = nullptr;     // ... and the column programs of minv_mfma_kernel
     int32_t *related_table = nullptr;   // HostPlan::related_table (plans of the wide route with more than 64 velocities)
     int32_t *span_q = nullptr, *span_v = nullptr, *crow = nullptr;  // grbda_plan::span_q / span_v / crow
+    int32_t *centroidal_rows = nullptr;  // per body (own first scratch row or -1, parent's first row or -1): centroidal_kernels.hip
     int n_cu = 0;
     unsigned long long *bad_count = nullptr;  // this device's counter of states with a pivot that is not positive (deriv_kernels.hip)
 };
@@ -188,6 +189,23 @@ hipError_t device_cu_count(int device, int *n_cu)
     return hipSuccess;
 }
 
+// Scratch rows of centroidal_kernel (devplan.h): bodies with children get kCentroidalBodyRows rows each, in body order; leaves none.
+struct CentroidalRows {
+    std::vector<int32_t> rows;  // per body: own first row or -1, the tree parent's first row or -1
+    int n_parent_bodies = 0;
+};
+CentroidalRows centroidal_rows(const HostPlan &h)
+{
+    CentroidalRows r;
+    const std::vector<BodyRec> &bodies = h.lay64.bodies;
+    r.rows.assign(2 * bodies.size(), -1);
+    for (size_t b = 0; b < bodies.size(); b++)
+        if (bodies[b].has_child) r.rows[2 * b] = kCentroidalBodyRows * r.n_parent_bodies++;
+    for (size_t b = 0; b < bodies.size(); b++)
+        if (bodies[b].parent >= 0) r.rows[2 * b + 1] = r.rows[2 * static_cast<size_t>(bodies[b].parent)];
+    return r;
+}
+
 int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
 {
     int count = 0;
@@ -277,6 +295,7 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
             (e = up(p->crow.data(), p->crow.size() * sizeof(int32_t), (void **)&t.crow)) != hipSuccess)
             return hip_err(e, "plan upload");
     }
+    if ((e = up(centroidal_rows(h).rows, &t.centroidal_rows)) != hipSuccess) return hip_err(e, "plan upload");
     if ((e = device_cu_count(device, &t.n_cu)) != hipSuccess) return hip_err(e, "hipGetDeviceProperties");
     if ((e = set_max_dynamic_lds()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     if ((e = set_max_dynamic_lds_deriv()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
@@ -1263,6 +1282,141 @@ int twists(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *V, siz
     Carver<T> w(wptr, 2 * B * ns);
     T *vs = w.take(B * ns), *as = w.take(B * ns);
     return twists_stage<T>(p, *t, q, qd, ydd, V, vs, as, B, device, stream);
+}
+
+// ---- energy, centre of mass, centroidal momentum (centroidal_kernels.hip; include/grbda_hip.h) -----------------------------------
+// sum of the body masses: entry (3, 3) of the 21 packed inertia constants behind BodyRec::cofs + 12 (devmath.h, sidx(3, 3) = 15)
+double plan_total_mass(const grbda_plan *p)
+{
+    double m = 0;
+    for (const BodyRec &b : p->host.lay64.bodies) m += p->host.consts[static_cast<size_t>(b.cofs) + 12 + 15];
+    return m;
+}
+// what the outputs of a call need: the velocities (kinetic, com_vel, h) and the accelerations (hdot)
+template <class T>
+bool centroidal_velocities(const CentroidalOut<T> &o) { return o.kinetic || o.com_vel || o.h || o.hdot; }
+// Everything the entry points refuse, on the host and before any device call.  `sizes`: elements per state of the six outputs.
+template <class T>
+int centroidal_args(const grbda_plan *p, const T *q, const T *qd, const T *ydd, const CentroidalOut<T> &o, size_t B)
+{
+    if (!q) return set_err(GRBDA_EINVAL, "null argument");
+    if (!o.kinetic && !o.potential && !o.com && !o.com_vel && !o.h && !o.hdot) return set_err(GRBDA_EINVAL, "no output asked for");
+    if (centroidal_velocities(o) && !qd) return set_err(GRBDA_EINVAL, "kinetic, com_vel, h and hdot need qd");
+    if (o.hdot && !ydd) return set_err(GRBDA_EINVAL, "hdot needs ydd");
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T), b1 = B * sizeof(T);
+    const void *const in[3] = {q, qd, ydd}, *const out[6] = {o.kinetic, o.potential, o.com, o.com_vel, o.h, o.hdot};
+    const size_t in_bytes[3] = {bq, bv, bv}, out_bytes[6] = {b1, b1, 3 * b1, 3 * b1, 6 * b1, 6 * b1};
+    if (int rc = no_overlap(in, in_bytes, out, out_bytes)) return rc;
+    if ((o.com || o.com_vel || o.h || o.hdot) && !(plan_total_mass(p) > 0))
+        return set_err(GRBDA_EUNSUPPORTED, "the total mass of the model is not positive: the centre of mass and the centroidal momentum are not defined");
+    return GRBDA_OK;
+}
+// One launch of centroidal_kernel over nb rows (arguments checked, nb > 0, device found): the spanning rates into the caller's work arrays
+// vs, as [nb][span_count] when an output needs them (spanning<T>, as twists_stage; velocities alone: the acceleration half is computed at
+// ydd = qd and not read), the scratch slab sized by the launch record, then the one launch site.
+template <class T>
+int centroidal_stage(const grbda_plan *p, const DeviceTables &t, const T *q, const T *qd, const T *ydd, const CentroidalOut<T> &o, T *vs, T *as,
+                     size_t nb, int device, void *stream)
+{
+    const bool velocities = centroidal_velocities(o), rates = o.hdot != nullptr;
+    if (velocities)
+        if (int rc = spanning<T>(p, q, qd, rates ? ydd : qd, vs, as, nb, device, stream)) return rc;
+    const CentroidalLaunch L = centroidal_launch(velocities, rates, centroidal_rows(p->host).n_parent_bodies, t.n_cu, nb);
+    void *scratch = nullptr;
+    if (int rc = ensure_scratch(p, device, stream, scratch_bytes(L.grid, L.slab_rows, sizeof(T)), &scratch)) return rc;
+    const DevPlan<T> d = make_dev_plan<T>(p, t, false, false);
+    const std::array<T, 3> g = gravity3<T>(p);
+    hipError_t e = launch_centroidal<T>(d, p->host.n_clusters, span_count(p), t.centroidal_rows, L, q, velocities ? vs : nullptr, rates ? as : nullptr,
+                                        g.data(), static_cast<T>(plan_total_mass(p)), o, nb, static_cast<T *>(scratch), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "centroidal launch");
+}
+// grbda_energy_* and grbda_centroidal_*: the batch in chunks of the work slab (the spanning rates are all it holds; none without velocities)
+template <class T>
+int centroidal(const grbda_plan *p, const T *q, const T *qd, const T *ydd, const CentroidalOut<T> &o, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = centroidal_args<T>(p, q, qd, ydd, o, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, ns = static_cast<size_t>(span_count(p));
+    Chunk c{B, 0};
+    T *vs = nullptr, *as = nullptr;
+    if (centroidal_velocities(o)) {
+        c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, 2 * ns * sizeof(T), B);
+        void *wptr = nullptr;
+        if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+        Carver<T> w(wptr, c.chunk * 2 * ns);
+        vs = w.take(c.chunk * ns);
+        as = w.take(c.chunk * ns);
+        assert(w.taken == w.cap);
+    }
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        CentroidalOut<T> oc{};
+        oc.kinetic = o.kinetic ? o.kinetic + b0 : nullptr;
+        oc.potential = o.potential ? o.potential + b0 : nullptr;
+        oc.com = o.com ? o.com + b0 * 3 : nullptr;
+        oc.com_vel = o.com_vel ? o.com_vel + b0 * 3 : nullptr;
+        oc.h = o.h ? o.h + b0 * 6 : nullptr;
+        oc.hdot = o.hdot ? o.hdot + b0 * 6 : nullptr;
+        if (int rc = centroidal_stage<T>(p, *t, q + b0 * nq, qd ? qd + b0 * nv : nullptr, ydd ? ydd + b0 * nv : nullptr, oc, vs, as, nb, device, stream))
+            return rc;
+    }
+    return GRBDA_OK;
+}
+// row (b, j) of the expanded batch of the momentum matrix: state b at the unit velocity e_j
+template <class T>
+__global__ void unit_velocity_rows_kernel(const T *__restrict__ q, int nq, int nv, size_t nb, T *__restrict__ q_x, T *__restrict__ qd_x)
+{
+    const size_t width = (size_t)(nq + nv), total = nb * (size_t)nv * width;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t row = t / width;
+        const int col = (int)(t % width);
+        if (col < nq) q_x[row * nq + col] = q[(row / nv) * nq + col];
+        else qd_x[row * nv + (col - nq)] = (size_t)(col - nq) == row % nv ? T(1) : T(0);
+    }
+}
+template <class T>
+int centroidal_matrix_args(const grbda_plan *p, const T *q, const T *A, size_t B)
+{
+    if (!q || !A) return set_err(GRBDA_EINVAL, "null argument");
+    const void *const in[1] = {q}, *const out[1] = {A};
+    const size_t in_bytes[1] = {B * static_cast<size_t>(p->host.nq) * sizeof(T)}, out_bytes[1] = {B * 6 * static_cast<size_t>(p->host.nv) * sizeof(T)};
+    if (int rc = no_overlap(in, in_bytes, out, out_bytes)) return rc;
+    if (!(plan_total_mass(p) > 0))
+        return set_err(GRBDA_EUNSUPPORTED, "the total mass of the model is not positive: the centre of mass and the centroidal momentum are not defined");
+    return GRBDA_OK;
+}
+// A[B][6][nv], h = A(q) yd: momentum is linear in yd, so column j is the h of (q, e_j) -- the expanded batch of nv rows per state through the
+// same two stages, as many states per pass as the work slab holds (per state nv rows of q, qd, and the two spanning rates)
+template <class T>
+int centroidal_matrix(const grbda_plan *p, const T *q, T *A, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = centroidal_matrix_args<T>(p, q, A, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, ns = static_cast<size_t>(span_count(p));
+    const size_t per_state = nv * (nq + nv + 2 * ns);
+    const Chunk c = fixed_chunk(work_budget(p, p->work, device, stream, 1024ull << 20), per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, c.chunk * per_state);
+    T *q_x = w.take(c.chunk * nv * nq), *qd_x = w.take(c.chunk * nv * nv), *vs = w.take(c.chunk * nv * ns), *as = w.take(c.chunk * nv * ns);
+    assert(w.taken == w.cap);
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        hipLaunchKernelGGL((unit_velocity_rows_kernel<T>), dim3(blocks_for(nb * nv * (nq + nv))), dim3(256), 0, static_cast<hipStream_t>(stream), q + b0 * nq,
+                           static_cast<int>(nq), static_cast<int>(nv), nb, q_x, qd_x);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_err(e, "unit velocity rows launch");
+        CentroidalOut<T> o{};
+        o.h = A + b0 * 6 * nv;
+        o.h_cols = static_cast<int>(nv);
+        if (int rc = centroidal_stage<T>(p, *t, q_x, qd_x, static_cast<const T *>(nullptr), o, vs, as, nb * nv, device, stream)) return rc;
+    }
+    return GRBDA_OK;
 }
 
 // ---- inverse operational-space inertia of a set of contact frames (include/grbda_hip.h) -----------------------
@@ -2832,6 +2986,7 @@ void grbda_plan_free(grbda_plan *p)
         (void)hipFree(t.aba_steps); (void)hipFree(t.rnea_steps); (void)hipFree(t.consts64); (void)hipFree(t.consts32);
         (void)hipFree(t.cints); (void)hipFree(t.dq_map); (void)hipFree(t.crba_bodies); (void)hipFree(t.deriv_bodies); (void)hipFree(t.deriv_related); (void)hipFree(t.related_table); (void)hipFree(t.minv_bodies); (void)hipFree(t.minv_coltab);
         (void)hipFree(t.span_q); (void)hipFree(t.span_v); (void)hipFree(t.crow);
+        (void)hipFree(t.centroidal_rows);
         for (int w = 0; w < kChainSlots; w++) {
             free_chain_tables(t.rchain[w]);
             free_chain_tables(t.chain[w]);
@@ -3453,6 +3608,94 @@ int grbda_step_host_f64(const grbda_plan *p, const double *q, const double *qd, 
     double *dy = st.out(ydd, B * nv), *dqn = st.out(q_next, B * nq), *dvn = st.out(qd_next, B * nv);
     int32_t *dok = st.out(ok, B);
     return st.run([&] { return step<double>(p, dq, dqd, dt_, dfe, dt, dy, dqn, dvn, dok, B, device, nullptr); });
+}
+
+int grbda_plan_total_mass(const grbda_plan *p, double *mass)
+{
+    if (!p || !mass) return set_err(GRBDA_EINVAL, "null argument");
+    *mass = plan_total_mass(p);
+    return GRBDA_OK;
+}
+int grbda_energy_f64(const grbda_plan *p, const double *q, const double *qd, double *kinetic, double *potential, size_t B, int device, void *stream)
+{
+    CentroidalOut<double> o{};
+    o.kinetic = kinetic;
+    o.potential = potential;
+    return centroidal<double>(p, q, qd, nullptr, o, B, device, stream);
+}
+int grbda_energy_f32(const grbda_plan *p, const float *q, const float *qd, float *kinetic, float *potential, size_t B, int device, void *stream)
+{
+    CentroidalOut<float> o{};
+    o.kinetic = kinetic;
+    o.potential = potential;
+    return centroidal<float>(p, q, qd, nullptr, o, B, device, stream);
+}
+int grbda_centroidal_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double *com, double *com_vel, double *h,
+                         double *hdot, size_t B, int device, void *stream)
+{
+    CentroidalOut<double> o{};
+    o.com = com;
+    o.com_vel = com_vel;
+    o.h = h;
+    o.hdot = hdot;
+    return centroidal<double>(p, q, qd, ydd, o, B, device, stream);
+}
+int grbda_centroidal_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, float *com, float *com_vel, float *h, float *hdot,
+                         size_t B, int device, void *stream)
+{
+    CentroidalOut<float> o{};
+    o.com = com;
+    o.com_vel = com_vel;
+    o.h = h;
+    o.hdot = hdot;
+    return centroidal<float>(p, q, qd, ydd, o, B, device, stream);
+}
+int grbda_centroidal_matrix_f64(const grbda_plan *p, const double *q, double *A, size_t B, int device, void *stream)
+{
+    return centroidal_matrix<double>(p, q, A, B, device, stream);
+}
+int grbda_centroidal_matrix_f32(const grbda_plan *p, const float *q, float *A, size_t B, int device, void *stream)
+{
+    return centroidal_matrix<float>(p, q, A, B, device, stream);
+}
+// host arrays: the checks of the device entry points first, then the device, then the staging
+static int centroidal_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, const CentroidalOut<double> &o, size_t B,
+                               int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = centroidal_args<double>(p, q, qd, ydd, o, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = qd ? st.in(qd, B * nv) : nullptr, *dy = ydd ? st.in(ydd, B * nv) : nullptr;
+    CentroidalOut<double> d{};
+    d.kinetic = o.kinetic ? st.out(o.kinetic, B) : nullptr;
+    d.potential = o.potential ? st.out(o.potential, B) : nullptr;
+    d.com = o.com ? st.out(o.com, B * 3) : nullptr;
+    d.com_vel = o.com_vel ? st.out(o.com_vel, B * 3) : nullptr;
+    d.h = o.h ? st.out(o.h, B * 6) : nullptr;
+    d.hdot = o.hdot ? st.out(o.hdot, B * 6) : nullptr;
+    return st.run([&] { return centroidal<double>(p, dq, dqd, dy, d, B, device, nullptr); });
+}
+int grbda_energy_host_f64(const grbda_plan *p, const double *q, const double *qd, double *kinetic, double *potential, size_t B, int device)
+{
+    CentroidalOut<double> o{};
+    o.kinetic = kinetic;
+    o.potential = potential;
+    return centroidal_host_f64(p, q, qd, nullptr, o, B, device);
+}
+int grbda_centroidal_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, double *com, double *com_vel, double *h,
+                              double *hdot, size_t B, int device)
+{
+    CentroidalOut<double> o{};
+    o.com = com;
+    o.com_vel = com_vel;
+    o.h = h;
+    o.hdot = hdot;
+    return centroidal_host_f64(p, q, qd, ydd, o, B, device);
 }
 
 int grbda_aba_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau,

@@ -222,6 +222,32 @@ struct ContactSolveLaunch {
 ContactSolveLaunch contact_solve_launch(int n_contacts, size_t elem);
 hipError_t set_max_dynamic_lds_contact();
 
+// energy, centre of mass and centroidal momentum (centroidal_kernels.hip).  A body with children keeps its pose (12), velocity (6) and
+// acceleration (6) in kCentroidalBodyRows rows [value][kWave] of the wavefront's scratch; `rows` holds per body (its first row or -1 for
+// a leaf, its tree parent's first row or -1), built on the host (capi.cpp, ensure_device).
+constexpr int kCentroidalBodyRows = 24;
+// Outputs of one launch, device arrays over the nb rows of the launch, any of them null: kinetic[nb], potential[nb], com[nb][3],
+// com_vel[nb][3], h[nb][6], hdot[nb][6] ([angular 3 about the centre of mass; linear 3], world axes).  The momentum matrix runs the
+// expanded batch (nv rows per state, row (b, j) = state b at unit velocity j): h_cols = nv sends the h of row r to column r % nv of
+// A[r / nv][6][nv] (h_cols = 0: h[r][6]).
+template <class T>
+struct CentroidalOut {
+    T *kinetic, *potential, *com, *com_vel, *h, *hdot;
+    int h_cols;
+};
+// what one launch is made of: the kernel variant (0 positions, 1 + velocities, 2 + accelerations), the grid, the scratch rows per wavefront
+struct CentroidalLaunch {
+    int level;
+    size_t grid;
+    size_t slab_rows;
+};
+CentroidalLaunch centroidal_launch(bool velocities, bool rates, int n_parent_bodies, int n_cu, size_t nb);
+// qd_span / qdd_span: the spanning rates of spanning_kernel (null below the level that reads them); g: the plan's gravity (linear part)
+template <class T>
+hipError_t launch_centroidal(const DevPlan<T> &P, int n_clusters, int n_span, const int32_t *rows, const CentroidalLaunch &L, const T *q,
+                             const T *qd_span, const T *qdd_span, const T g[3], T mass, const CentroidalOut<T> &out, size_t nb, T *scratch,
+                             hipStream_t stream);
+
 // composite-rigid-body algorithm (crba_kernels.hip)
 template <class T>
 hipError_t launch_crba(const DevPlan<T> &P, const CrbaBody *cb, int n_clusters, int n_rows, const T *q, T *H, size_t B, T *scratch,

@@ -1311,6 +1311,24 @@ public:
     {
         check(grbda_integrate_host_f64(plan(), q, qd, ydd, dt, q_next, qd_next, ok, max_iter, tol, B, device));
     }
+    // Energy and centroidal quantities of B states on host arrays (include/grbda_hip.h "energy and centroidal quantities"; Pinocchio:
+    // computeKineticEnergy / computePotentialEnergy, centerOfMass, computeCentroidalMomentumTimeVariation).  Any output may be null, not
+    // all; kinetic, com_vel and h need qd, hdot needs qd and ydd.  World axes; h, hdot: [angular 3 about the centre of mass; linear 3].
+    double totalMass()
+    {
+        double m = 0;
+        check(grbda_plan_total_mass(plan(), &m));
+        return m;
+    }
+    void energyBatch(const double *q, const double *qd, double *kinetic, double *potential, size_t B, int device = 0)
+    {
+        check(grbda_energy_host_f64(plan(), q, qd, kinetic, potential, B, device));
+    }
+    void centroidalBatch(const double *q, const double *qd, const double *ydd, double *com, double *com_vel, double *h, double *hdot, size_t B,
+                         int device = 0)
+    {
+        check(grbda_centroidal_host_f64(plan(), q, qd, ydd, com, com_vel, h, hdot, B, device));
+    }
     void stepBatch(const double *q, const double *qd, const double *tau, double dt, double *ydd, double *q_next, double *qd_next,
                    int32_t *ok, size_t B, int device = 0, const double *f_ext = nullptr)
     {

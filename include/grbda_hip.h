@@ -465,6 +465,46 @@ int grbda_contact_dynamics_host_f64(const grbda_plan *plan, const double *q, con
                                     int n_contacts, const int *bodies, const double *offsets, const double *a_des, double damping,
                                     double *ydd, double *lambda, double *ydd_free, size_t B, int device);
 
+/* ---- energy and centroidal quantities ------------------------------------------------------------------------------------------
+ * What a trajectory is judged and controlled by (Pinocchio: computeKineticEnergy, computePotentialEnergy, centerOfMass,
+ * computeCentroidalMomentumTimeVariation, ccrba), from ONE kernel per chunk (centroidal_kernels.hip) instead of grbda_body_poses_* +
+ * grbda_body_twists_* and a reduction of 24 values per body outside the library.  Device arrays, row-major; all outputs in world axes.
+ *
+ * grbda_plan_total_mass: M = the sum of the body masses (rotors included).  Host only, no device.
+ * grbda_energy_*:        kinetic[B] = 1/2 yd^T H(q) yd;  potential[B] = -g . sum_i m_i c_i, zero at the world origin, g the plan's gravity.
+ * grbda_centroidal_*:    com[B][3], com_vel[B][3];  h[B][6] = [angular 3 about the centre of mass; linear 3], the centroidal momentum;
+ *                        hdot[B][6], its rate at the generalized acceleration ydd (the true one, as for grbda_body_twists_*).  Without
+ *                        external forces and with ydd = FD(q, qd, tau), a floating-base model has hdot = [0; M g]; external forces add
+ *                        their wrenches about the centre of mass.  There is no f_ext argument: they enter through ydd.
+ * grbda_centroidal_matrix_*: A[B][6][nv] with h = A(q) yd (the centroidal momentum matrix).  Momentum is linear in yd, so column j is
+ *                        the h of the state (q, e_j): evaluated over the expanded batch (nv rows per state) with the same kernel -- the
+ *                        exact difference form of grbda_mass_matrix_* above (no step size enters), chunked so that the work slab
+ *                        (nv (nq + nv + 2 span_vel) scalars per state) stays within GRBDA_WORK_MAX_MB.
+ *
+ * Any output may be NULL, not all of them.  kinetic, com_vel and h need qd; hdot needs qd and ydd; inputs no requested output needs may
+ * be NULL (positions alone never touch qd).  q, qd, ydd as for the inverse dynamics (implicit clusters: spanning positions on the
+ * manifold).  Accepted on every plan that grbda_body_twists_* accepts (roll-pitch-yaw base, implicit clusters, the spanning-tree route).
+ * Errors, all decided on the host before anything is enqueued: GRBDA_EINVAL for a NULL plan, a missing required pointer, no output asked
+ * for, outputs that overlap inputs or each other; GRBDA_EUNSUPPORTED (text in grbda_last_error()) for com, com_vel, h, hdot or A when the
+ * total mass is not positive.  B == 0: GRBDA_OK.  The calls only enqueue: no synchronisation, no allocation beyond the scratch slab and
+ * the work slab (the spanning rates; chunked like the other pipelines) -- capturable after one eager call of the same B on the stream;
+ * gravity is read at launch.  The _host_ variants take host arrays (allocate, copy and synchronise per call). */
+int grbda_plan_total_mass(const grbda_plan *plan, double *mass);
+int grbda_energy_f64(const grbda_plan *plan, const double *q, const double *qd, double *kinetic, double *potential, size_t B, int device,
+                     void *stream);
+int grbda_energy_f32(const grbda_plan *plan, const float *q, const float *qd, float *kinetic, float *potential, size_t B, int device,
+                     void *stream);
+int grbda_centroidal_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, double *com, double *com_vel,
+                         double *h, double *hdot, size_t B, int device, void *stream);
+int grbda_centroidal_f32(const grbda_plan *plan, const float *q, const float *qd, const float *ydd, float *com, float *com_vel, float *h,
+                         float *hdot, size_t B, int device, void *stream);
+int grbda_centroidal_matrix_f64(const grbda_plan *plan, const double *q, double *A, size_t B, int device, void *stream);
+int grbda_centroidal_matrix_f32(const grbda_plan *plan, const float *q, float *A, size_t B, int device, void *stream);
+int grbda_energy_host_f64(const grbda_plan *plan, const double *q, const double *qd, double *kinetic, double *potential, size_t B,
+                          int device);
+int grbda_centroidal_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, double *com, double *com_vel,
+                              double *h, double *hdot, size_t B, int device);
+
 /* ---- convenience: host pointers (single-state facade calls, small batches) ------------------ */
 /* allocate, copy in, run on `device`, copy out, synchronise.  Still the HIP path. */
 int grbda_aba_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *tau,
