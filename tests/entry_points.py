@@ -1,10 +1,16 @@
 """The table of device entry points the GPU tests share: ENTRY (name -> (call, oracle checker)), CASES (route x model x plan-time switches
 x batch x entry point), and what makes their models, states and inputs.  A plain module, not a test file: test_graph_capture_gpu.py,
-test_buffer_edges_gpu.py and test_batch_ladder_gpu.py all go through it, so an entry point added to the library is covered by every one
-of them with one more row here.
+test_buffer_edges_gpu.py, test_batch_ladder_gpu.py and test_concurrent_streams_gpu.py all go through it, so an entry point added to the
+library is covered by every one of them with one more row here.  Covered: forward / inverse dynamics (with and without f_ext), bias force,
+mass matrix, the forward-dynamics derivatives, body poses and twists, applyTestForce, the inverse OSIM, the projection, the state
+conversion, the spanning rates, the inverse-dynamics derivatives, integrate / step / rollout, contact points and contact dynamics, energy,
+the centroidal quantities and the momentum matrix.
 
-call(plan, x) returns a tuple of output tensors, x holding the device tensors "q", "qd", "tau", "fext", "force", "q_start", "q_proj";
-check(blob, s, outs, tol) compares the numpy outputs `outs` of the states `s` (a dict of numpy inputs) with the oracle."""
+call(plan, x) returns a tuple of output tensors whose leading dimension is the batch, x holding the device tensors "q", "qd", "tau",
+"fext", "force", "q_start", "q_proj", "a_des", "tau_T"; check(blob, s, outs, tol) compares the numpy outputs `outs` of the states `s` (a
+dict of numpy inputs) with the oracle, or with a numpy reference the CPU suite pins to the oracle.  The checkers of the later rows print
+what they measured (HELD model type what: error of bound).  TYPED is the table by number type: the rows of CASES in fp64 and fp32 less
+NOT_RUN, and what every one of the four files is parametrised over."""
 import functools
 import os
 
@@ -29,6 +35,7 @@ def _big(blob):
 
 
 _zoo = functools.lru_cache(maxsize=None)(zoo)  # (the descriptions are immutable bytes: built once per process)
+_NAMES = {}  # blob -> the name _model() made it under (a checker is handed the blob: its contact set and time step go by the name)
 
 
 @functools.lru_cache(maxsize=None)
@@ -36,12 +43,18 @@ def _model(name):
     if name == "two_parent":
         from test_capi_cpu import two_parent_model
 
-        return two_parent_model().serialize()
-    if name.startswith("parallel_chain"):
+        blob = two_parent_model().serialize()
+    elif name.startswith("parallel_chain"):
         blob = G.urdf_to_blob(os.path.join(ROBOT_MODELS, name + ".urdf"))
         _BIG.add(blob)
-        return blob
-    return _zoo()[name]
+    else:
+        blob = _zoo()[name]
+    _NAMES.setdefault(blob, name)
+    return blob
+
+
+def _name(blob):
+    return _NAMES.get(bytes(blob), "?")
 
 
 def _states(blob, B, seed, max_cond=None):
@@ -241,6 +254,214 @@ def _project(plan, x):
     x["q_proj"].copy_(x["q_start"])
     return x["q_proj"], plan.project_positions(x["q_proj"])
 
+
+# ---- the entry points added after the table: inverse-dynamics derivatives, time stepping, contacts, centroidal quantities -------------
+# Their checkers reuse references the CPU suite pins to the oracle (id_derivative_refs, integrate_ref, contact_ref, centroidal_ref); those
+# modules import this one, so they are imported where they are used.
+T_ROLL = 3  # steps of the rollout row
+# the contact set of a model's contact rows (contact_ref.SETS); every other model: one point, OFFSET, on its last link
+CONTACT_SETS = {"urdf_mini_cheetah": "cheetah_feet", "tello_with_arms": "tello_feet", "urdf_mit_humanoid": "humanoid_soles"}
+DAMPING = 1e-3  # of the redundant eight-contact set, as test_contact_gpu.py runs it
+# time steps of the integrate / step / rollout rows where integrate_ref.dt_of(model) fails the 95 % condition on a draw of the table
+# (test_entry_draws_cpu.py asserts the condition for every draw): none does -- the four-bar's reference accepts every state of every
+# draw at integrate_ref.DT's 0.05 (measured shares: 100 % for seeds 1, 2, 3, 4, 11, 21, 100 .. 103, fp64 and fp32-rounded inputs)
+DT_HALVED = {}
+# (No fp32 row needs an allowance against the float32 run of the reference: every new row holds TOL32 on the MI355X on every draw of the
+# four files, tello_with_arms' kinetic energy included -- worst 2.5e-6 on the scale 1 + |ref| of centroidal_ref.scale_error.)
+
+
+def _held(blob, tol, what, err, bound):
+    err = float(err)
+    print(f"HELD {_name(blob)} {'f64' if tol < 1e-6 else 'f32'} {what}: {err:.2e} of {bound:.1e}")
+    assert err < bound, f"{what}: {err:.2e} against {bound:.1e}"
+
+
+@functools.lru_cache(maxsize=None)
+def _contacts(blob):
+    """(bodies, offsets) of the contact rows of the model `blob`"""
+    import contact_ref
+
+    key = CONTACT_SETS.get(_name(blob))
+    if key is not None:
+        return tuple(contact_ref.contact_set(key)[1:])
+    from test_contact_gpu import _last_link
+
+    return [_last_link(blob)], [OFFSET]
+
+
+def _dt(blob):
+    import integrate_ref
+
+    return DT_HALVED.get(_name(blob), integrate_ref.dt_of(_name(blob)))
+
+
+def _is64(t):
+    return t.dtype.itemsize == 8
+
+
+def _id_derivs(plan, x):
+    return tuple(plan.id_derivatives(x["q"], x["qd"], x["tau"]).values())  # (dq, dqd, dydd; the table feeds tau as ydd)
+
+
+def _chk_id_derivs(blob, s, o, tol):
+    from id_derivative_refs import oracle_refs
+
+    ref = oracle_refs(blob, {"q": s["q"], "qd": s["qd"], "ydd": s["tau"]})
+    for k, got, floor in (("dydd", o[2], 1e-9), ("dqd", o[1], 1e-8), ("dq", o[0], 2e-5)):  # the bounds of test_id_derivatives_gpu.py
+        _held(blob, tol, "id_derivatives " + k, _rel(got, ref[k]), max(tol, floor))
+
+
+def _integrate(plan, x):
+    import integrate_ref
+    import test_integrate_gpu
+
+    # (the table feeds tau as ydd; the projection's tolerance per type as test_integrate_gpu.py passes it)
+    return plan.integrate(x["q"], x["qd"], x["tau"], _dt(plan.blob), tol=integrate_ref.TOL if _is64(x["q"]) else test_integrate_gpu.TOL32)
+
+
+def _hold_step(blob, tol, what, q, qd, ydd, got, flags=True):
+    """(q', qd', ok) of one step from (q, qd) with the acceleration ydd against integrate_ref.reference_step on the states the reference
+    accepts, by the rules and bounds of test_integrate_gpu.py: fp64 at 1e-9, quaternion up to sign; fp32 qd', explicit and independent
+    coordinates at 16 eps32 max(1, |ref|), quaternion at 32 eps32, dependent coordinates at 1e-3 on the gated states; ok equals the
+    reference's flag except within a factor 10 of either tolerance (flags=False: the caller cannot hold ok -- step in fp32)."""
+    import integrate_ref as R
+    import test_integrate_gpu as TI
+
+    qn, vn, ok = got
+    rq, rv, rok, phi = R.reference_step(blob, q, qd, ydd, _dt(blob), big=_big(blob))
+    assert rok.any(), f"{what}: the reference accepts none of the {len(rok)} states: nothing was compared"
+    kinds = R.column_kinds(blob)
+    qn = TI.quat_sign_aligned(qn, rq, kinds)
+    assert np.isfinite(qn[rok]).all() and np.isfinite(vn[rok]).all()
+    if tol < 1e-6:
+        _held(blob, tol, what + " q'", np.abs(qn - rq)[rok].max(), 1e-9)
+        _held(blob, tol, what + " qd'", np.abs(vn - rv)[rok].max(), 1e-9)
+        if flags:
+            TI.check_flags(ok, rok, phi, R.TOL, what)
+        return
+    eps = TI.EPS32
+    _held(blob, tol, what + " qd' / (16 eps max(1, |ref|))", (np.abs(vn - rv) / (16 * eps * np.maximum(1.0, np.abs(rv))))[rok].max(), 1.0 + 1e-12)
+    plain, quat, dep = (kinds == "pos") | (kinds == "ind"), kinds == "quat", kinds == "dep"
+    if plain.any():
+        _held(blob, tol, what + " plain q' / (16 eps max(1, |ref|))",
+              (np.abs(qn - rq) / (16 * eps * np.maximum(1.0, np.abs(rq))))[np.ix_(rok, plain)].max(), 1.0 + 1e-12)
+    if quat.any():
+        _held(blob, tol, what + " quaternion / eps", np.abs(qn - rq)[np.ix_(rok, quat)].max() / eps, 32.0 + 1e-9)
+    if dep.any():
+        gated = rok & R.gate(blob, q, qd) & R.gate(blob, rq, rv)
+        assert gated.any(), f"{what}: no state passes the conditioning gate before and after the step"
+        _held(blob, tol, what + " dependent q'", np.abs(qn - rq)[np.ix_(gated, dep)].max(), TI.TOL32 * (1 + 1e-12))
+        if flags:
+            unsure = ((phi > R.TOL / 10) & (phi < R.TOL * 10)) | ((phi > TI.TOL32 / 10) & (phi < TI.TOL32 * 10))
+            bad = (ok.astype(bool) != rok) & ~unsure & gated
+            assert not bad.any(), f"{what}: ok differs from the reference on gated states {np.nonzero(bad)[0][:8]}"
+    elif flags:
+        assert ok.all()
+
+
+def _chk_integrate(blob, s, o, tol):
+    _hold_step(blob, tol, "integrate", s["q"], s["qd"], s["tau"], o)
+
+
+def _hold_dynamics_step(blob, tol, what, q, qd, ydd_ref, got, flags=True):
+    """(q', qd', ok) of a step whose acceleration the DEVICE computed, against reference_step fed the oracle's ydd_ref.  qd' = qd + dt ydd
+    carries dt times the error of ydd, which the table bounds by tol (1 + max |ydd|); q' moves by dt qd' through maps of gain about one
+    (a rotation, unit rows of G, rows of G inside the conditioning gate).  So both are held at tol on the scale 1 + max |ref| + dt max |ydd|,
+    on the states the reference accepts; ok in fp64 by the rule of test_integrate_gpu.py, in fp32 on models without implicit clusters
+    (all true) -- grbda_step_* passes the reference's 1e-8 to the projection, which fp32 cannot reach, so its fp32 flag says nothing."""
+    import integrate_ref as R
+    import test_integrate_gpu as TI
+
+    qn, vn, ok = got
+    rq, rv, rok, phi = R.reference_step(blob, q, qd, ydd_ref, _dt(blob), big=_big(blob))
+    assert rok.any(), f"{what}: the reference accepts none of the {len(rok)} states: nothing was compared"
+    kinds = R.column_kinds(blob)
+    qn = TI.quat_sign_aligned(qn, rq, kinds)
+    assert np.isfinite(qn[rok]).all() and np.isfinite(vn[rok]).all()
+    scale = 1.0 + max(np.abs(rq[rok]).max(), np.abs(rv[rok]).max()) + _dt(blob) * np.abs(ydd_ref[rok]).max()
+    _held(blob, tol, what + " q'", np.abs(qn - rq)[rok].max() / scale, tol)
+    _held(blob, tol, what + " qd'", np.abs(vn - rv)[rok].max() / scale, tol)
+    if flags and tol < 1e-6:
+        TI.check_flags(ok, rok, phi, R.TOL, what)
+    elif flags and not ((kinds == "ind") | (kinds == "dep")).any():
+        assert ok.all()
+    return rq, rv, rok
+
+
+def _chk_step(blob, s, o, tol, fext=False):
+    qn, vn, ydd, ok = o
+    ref = O.forward_dynamics(blob, s["q"], s["qd"], s["tau"], s["fext"] if fext else None, big=_big(blob))
+    _held(blob, tol, "step ydd", _rel(ydd, ref), tol)
+    _hold_dynamics_step(blob, tol, "step", s["q"], s["qd"], ref, (qn, vn, ok))
+
+
+def _rollout(plan, x):
+    # (per-step torques [T, B, nv] from the table's [B, T, nv]; the recorded trajectories come back with the batch in front)
+    qT, vT, ok, qt, vt = plan.rollout(x["q"], x["qd"], x["tau_T"].transpose(0, 1).contiguous(), _dt(plan.blob), T_ROLL, record=True)
+    return qt.transpose(0, 1), vt.transpose(0, 1), ok
+
+
+def _chk_rollout(blob, s, o, tol):
+    """T_ROLL reference steps of the oracle's forward dynamics, every recorded state held.  fp64: the chain of reference steps from the
+    inputs.  fp32: each recorded state against ONE reference step from the device's own previous recorded state (exact in float64) --
+    a chain would charge the kernel with the growth of a 1e-3 difference through d ydd / d q over dt = 0.25, which is the dynamics'."""
+    qt, vt, ok = o
+    q, qd = s["q"], s["qd"]
+    for k in range(T_ROLL):
+        ydd = O.forward_dynamics(blob, q, qd, s["tau_T"][:, k], big=_big(blob))
+        q, qd, _ = _hold_dynamics_step(blob, tol, f"rollout state {k + 1}", q, qd, ydd, (qt[:, k], vt[:, k], ok), flags=False)
+        if tol > 1e-6:
+            q, qd = qt[:, k], vt[:, k]
+    assert ok.all()  # (the AND over the steps; the row's model has no implicit cluster, so the reference accepts every state)
+
+
+def _contact_points(plan, x):
+    return plan.contact_points(x["q"], *_contacts(plan.blob), qd=x["qd"], ydd=x["tau"])  # (the table feeds tau as ydd)
+
+
+def _chk_contact_points(blob, s, o, tol):
+    import contact_ref as C
+
+    ref = C.contact_points(blob, s["q"], *_contacts(blob), s["qd"], s["tau"])
+    for what, got, r in zip(("pos", "vel", "acc"), o, ref):
+        _held(blob, tol, "contact_points " + what, C.rel_per_state(got, r).max(), tol)
+
+
+def _contact_dynamics(plan, x, damped=False):
+    return plan.contact_dynamics(x["q"], x["qd"], x["tau"], *_contacts(plan.blob), a_des=x["a_des"], damping=DAMPING if damped else 0.0,
+                                 f_ext=x["fext"] if damped else None)
+
+
+def _chk_contact_dynamics(blob, s, o, tol, damped=False):
+    import contact_ref as C
+
+    ref = C.contact_dynamics(blob, s["q"], s["qd"], s["tau"], *_contacts(blob), s["a_des"], DAMPING if damped else 0.0, s["fext"] if damped else None)
+    for what, got, key in (("ydd", o[0], "ydd"), ("lambda", o[1], "lam"), ("ydd_free", o[2], "ydd_free")):
+        _held(blob, tol, "contact_dynamics " + what, C.rel_per_state(got, ref[key]).max(), tol)
+
+
+def _hold_centroidal(blob, s, tol, entry, names, outs, ydd):
+    import centroidal_ref as C
+
+    ref = C.centroidal(blob, s["q"], s["qd"], ydd, big=_big(blob))
+    for k, got in zip(names, outs):
+        _held(blob, tol, f"{entry} {k}", C.scale_error(got, ref[k]).max(), tol)
+
+
+def _chk_energy(blob, s, o, tol):
+    _hold_centroidal(blob, s, tol, "energy", ("kinetic", "potential"), o, None)
+
+
+def _chk_centroidal(blob, s, o, tol):
+    _hold_centroidal(blob, s, tol, "centroidal", ("com", "com_vel", "h", "hdot"), o, s["tau"])  # (the call feeds tau as ydd)
+
+
+def _chk_centroidal_matrix(blob, s, o, tol):
+    import centroidal_ref as C
+
+    _held(blob, tol, "centroidal_matrix A", C.scale_error(o[0], C.momentum_matrix(blob, s["q"], big=_big(blob))).max(), tol)
+
+
 ENTRY = {
     "aba": (_aba, _chk_aba),
     "aba_fext": (_aba_fext, lambda b, s, o, t: _chk_aba(b, s, o, t, True)),
@@ -261,6 +482,17 @@ ENTRY = {
     # (fp32 states sit within rounding of the manifold, not within 1e-8)
     "state_to_independent": (lambda p, x: p.state_to_independent(x["q"], x["qd"], tol=1e-8 if x["q"].dtype.itemsize == 8 else 1e-3), _chk_indep),
     "spanning": (lambda p, x: p.spanning(x["q"], x["qd"], x["tau"]), _chk_spanning),
+    "id_derivatives": (_id_derivs, _chk_id_derivs),
+    "integrate": (_integrate, _chk_integrate),
+    "step": (lambda p, x: p.step(x["q"], x["qd"], x["tau"], _dt(p.blob)), _chk_step),
+    "step_fext": (lambda p, x: p.step(x["q"], x["qd"], x["tau"], _dt(p.blob), f_ext=x["fext"]), lambda b, s, o, t: _chk_step(b, s, o, t, True)),
+    "rollout": (_rollout, _chk_rollout),
+    "contact_points": (_contact_points, _chk_contact_points),
+    "contact_dynamics": (_contact_dynamics, _chk_contact_dynamics),
+    "contact_dynamics_damped_fext": (lambda p, x: _contact_dynamics(p, x, True), lambda b, s, o, t: _chk_contact_dynamics(b, s, o, t, True)),
+    "energy": (lambda p, x: p.energy(x["q"], x["qd"]), _chk_energy),
+    "centroidal": (lambda p, x: tuple(p.centroidal(x["q"], x["qd"], x["tau"]).values()), _chk_centroidal),
+    "centroidal_matrix": (lambda p, x: (p.centroidal_matrix(x["q"]),), _chk_centroidal_matrix),
 }
 
 CASES = []
@@ -281,7 +513,29 @@ CASES += [("crba", "urdf_mini_cheetah", {}, B_CHAIN, "mass_matrix"), ("no_crba",
 # twists on the routes the Mini Cheetah row does not reach: implicit differentials, a loop cluster, big clusters, a roll-pitch-yaw base
 CASES += [("implicit", "tello_with_arms", {}, 300, "body_twists"), ("implicit", "urdf_four_bar", {}, 300, "body_twists"),
           ("spanning_tree", "parallel_chain_exp_d10_l16", {}, 300, "body_twists"), ("chain", "urdf_mini_cheetah_rpy", {}, 300, "body_twists")]
+# the entry points added after the table, B = 300: small, ragged, more than four tiles and below every route threshold
+CASES += [("analytic", "urdf_mini_cheetah", {}, 300, "id_derivatives"), ("manifold", "urdf_four_bar", {}, 300, "id_derivatives"),
+          ("quaternion", "urdf_mini_cheetah", {}, 300, "integrate"), ("newton", "urdf_four_bar", {}, 300, "integrate"),
+          ("explicit", "urdf_mini_cheetah", {}, 300, "step"), ("interpreter", "urdf_mini_cheetah", {}, 300, "step_fext"),
+          ("newton", "urdf_four_bar", {}, 300, "step"), ("explicit", "urdf_mini_cheetah", {}, 300, "rollout"),
+          ("feet", "urdf_mini_cheetah", {}, 300, "contact_points"), ("feet", "tello_with_arms", {}, 300, "contact_points"),
+          ("spanning_tree", "parallel_chain_exp_d10_l16", {}, 300, "contact_points"),
+          ("efpa", "urdf_mini_cheetah", {}, 300, "contact_dynamics"), ("no_efpa", "urdf_mini_cheetah", {"GRBDA_NO_EFPA": "1"}, 300, "contact_dynamics"),
+          ("feet", "tello_with_arms", {}, 300, "contact_dynamics"), ("soles", "urdf_mit_humanoid", {}, 300, "contact_dynamics_damped_fext")]
+for _ep in ("energy", "centroidal"):
+    CASES += [("explicit", "urdf_mit_humanoid", {}, 300, _ep), ("implicit", "tello_with_arms", {}, 300, _ep),
+              ("spanning_tree", "parallel_chain_exp_d10_l16", {}, 300, _ep)]
+CASES += [("explicit", "urdf_mit_humanoid", {}, 300, "centroidal_matrix"), ("implicit", "tello_with_arms", {}, 300, "centroidal_matrix")]
 IDS = [f"{ep}-{route}-{model}-B{B}" for route, model, env, B, ep in CASES]
+assert len(set(IDS)) == len(IDS)
+# (entry point, model, type) that no file runs, with the reason
+NOT_RUN = {
+    ("contact_dynamics_damped_fext", "urdf_mit_humanoid", "f32"): "test_contact_gpu.py bounds cond(A) for fp32 on the Mini Cheetah's and Tello's feet only: "
+                                                                  "the eight-contact set is rank 12 of 24 and stands on its damping",
+}
+# the table by number type: what the four files are parametrised over
+TYPED = [(c, dt) for c in CASES for dt in ("f64", "f32") if (c[4], c[1], dt) not in NOT_RUN]
+TYPED_IDS = [f"{ep}-{route}-{model}-B{B}-{dt}" for (route, model, env, B, ep), dt in TYPED]
 
 
 @functools.lru_cache(maxsize=8)
@@ -294,6 +548,12 @@ def _host_inputs(blob, n_bodies, B, seed, dtype, max_cond=None):
     s = {"q": q, "qd": qd, "tau": tau, "fext": rng.uniform(-1, 1, (B, n_bodies, 6)), "force": rng.uniform(-1, 1, (B, 3))}
     # projection input: the states moved off the manifold by a little (Newton has something to do)
     s["q_start"] = q + rng.uniform(-0.05, 0.05, q.shape)
+    # what the later entry points need, drawn after every key above and from a generator of their own: q, qd, tau, fext, force and q_start
+    # keep their bits for every row that was here before.  a_des: one acceleration per contact of the model's contact set; tau_T: the
+    # rollout's per-step torques, batch in front like every key (the ladder takes the first B rows of each)
+    rng2 = np.random.default_rng([seed, 20250])
+    s["a_des"] = rng2.uniform(-1, 1, (B, len(_contacts(blob)[0]), 3))
+    s["tau_T"] = tau[:, None, :] * rng2.uniform(0.4, 1.0, (B, T_ROLL, 1))
     s = {k: np.asarray(torch.as_tensor(v, dtype=dtype).double()) for k, v in s.items()}
     return s
 
@@ -316,8 +576,8 @@ def _host(outs):
 # reference's 2e-5, the draw bounds cond(K_d) of the implicit loops as the derivative tests of test_gpu_parity.py do (models.py,
 # valid_states: a state that satisfies phi to 1e-12 sits 1e-12 / sigma_min off the manifold, and the difference quotient along the
 # manifold then differs from the exact derivative at the state; measured on the four-bar, fp64: 1.2e-4 at cond 422, 8e-6 at 325,
-# 1.5e-6 at 150 and below).  Explicit models are not affected by the bound.
-DIFFERENTIATES = ("fd_dq", "fd_derivatives")
+# 1.5e-6 at 150 and below).  Explicit models are not affected by the bound.  id_derivatives differentiates the inverse dynamics the same way.
+DIFFERENTIATES = ("fd_dq", "fd_derivatives", "id_derivatives")
 
 
 def draw_bound(entry):

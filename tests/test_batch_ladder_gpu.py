@@ -5,14 +5,16 @@ Tile ladder: B in 1, 2, 63, 64, 65, 127, 128, 129, 257 (a tile is 64 states), fo
 dynamics in fp32, and in both types with f_ext (which sends forward dynamics to the interpreter), on the chain kernels and latency mode
 (Mini Cheetah, MIT humanoid), differential segments (TelloWithArms), the single-cluster kernel (four-bar), the interpreter (MIT humanoid,
 GRBDA_NO_CHAIN=1) and the spanning-tree route (parallel chain); and every other row of the entry-point table (entry_points.py) on that
-row's own model.  Group ladder: the derivative pipeline packs four states into one workgroup's MFMA tiles and pads H with the identity, so
-fd_derivatives, fd_dtau and mass_matrix also run B in 1, 2, 3, 4, 5, 7, 8, 9, 63, 64, 65 on the minv route, the dense route
-(GRBDA_NO_MINV=1), the fp64 solve of fp32 batches (GRBDA_SOLVE_F64=1) and the manifold route (Tello).
+row's own model -- the inverse-dynamics derivatives, integrate / step / rollout, contact points and contact dynamics, energy, the
+centroidal quantities and the momentum matrix among them.  Group ladder: the derivative pipeline packs four states into one workgroup's
+MFMA tiles and pads H with the identity, so fd_derivatives, fd_dtau and mass_matrix also run B in 1, 2, 3, 4, 5, 7, 8, 9, 63, 64, 65 on
+the minv route, the dense route (GRBDA_NO_MINV=1), the fp64 solve of fp32 batches (GRBDA_SOLVE_F64=1) and the manifold route (Tello), and
+id_derivatives on its analytic route (Mini Cheetah).
 
 The inputs of batch B are the first B rows of one draw of the ladder's largest batch, placed in guarded buffers (guarded.py): behind row
 B - 1 lies a band of NaN, not the next valid state, and every output sits between canary bands (run_guarded asserts bounds, complete
 writes, untouched inputs and finite outputs).  Every state of every batch is held against the oracle with the table's checker at the
-table's tolerances; only the position derivatives, whose oracle is 2 nv single-state forward dynamics per state, are held on a sample
+table's tolerances; only the position derivatives (of the forward and of the inverse dynamics), whose oracle is taken state by state, are held on a sample
 above 65 states (first, last, both ends of the last tile and of the last group, a seeded few).  Body twists, spanning accelerations and the
 inverse OSIM's Jacobians are held to the numpy recursion of kinematics_ref.py, which the CPU suite pins to the oracle.  The draws of
 those derivative rows bound the conditioning of the implicit loops as the older derivative tests do (entry_points.py, draw_bound).
@@ -29,7 +31,7 @@ import functools
 import numpy as np
 import pytest
 
-from entry_points import CASES, DIFFERENTIATES, ENTRY, TILE, TOL32, TOL64, _host, _host_inputs, _model, draw_bound, edge_states, plan_for, run_guarded, same_bits_np
+from entry_points import CASES, DIFFERENTIATES, ENTRY, TILE, TOL32, TOL64, TYPED, _host, _host_inputs, _model, draw_bound, edge_states, plan_for, run_guarded, same_bits_np
 from generalized_rbda_amd.states import parse_clusters
 from graph_capture import capture
 
@@ -46,10 +48,12 @@ DYNAMICS_MODELS = [("urdf_mini_cheetah", {}), ("urdf_mit_humanoid", {}), ("tello
 # (fp64 forward / inverse dynamics without f_ext: test_gpu_parity.py runs 1, 63, 64, 200 on the whole zoo)
 DYNAMICS = [(m, e, ep, dt) for m, e in DYNAMICS_MODELS for ep, dts in (("aba", ("f32",)), ("rnea", ("f32",)), ("aba_fext", ("f32", "f64")),
                                                                        ("rnea_fext", ("f32", "f64"))) for dt in dts]
-OTHERS = [(model, env, ep, dt) for route, model, env, B, ep in CASES if ep not in ("aba", "rnea", "aba_fext", "rnea_fext") for dt in ("f32", "f64")]
+OTHERS = [(c[1], c[2], c[4], dt) for c in CASES if c[4] not in ("aba", "rnea", "aba_fext", "rnea_fext") for dt in ("f32", "f64") if (c, dt) in TYPED]
 DERIV_ROUTES = [("minv", "urdf_mini_cheetah", {}, ("f32", "f64")), ("dense", "urdf_mini_cheetah", {"GRBDA_NO_MINV": "1"}, ("f32", "f64")),
                 ("solve_f64", "urdf_mini_cheetah", {"GRBDA_SOLVE_F64": "1"}, ("f32",)), ("manifold", "tello", {}, ("f32", "f64"))]
 DERIVS = [(model, env, ep, dt) for route, model, env, dts in DERIV_ROUTES for ep in ("fd_derivatives", "fd_dtau", "mass_matrix") for dt in dts]
+# the inverse-dynamics derivatives pack groups of four on their analytic route (Mini Cheetah)
+DERIVS += [("urdf_mini_cheetah", {}, "id_derivatives", dt) for dt in ("f32", "f64")]
 
 
 def _id(case):

@@ -1,6 +1,8 @@
 """Writes outside an output, output elements never written, inputs written to, and results that depend on the pointer's alignment.
 
-Every row of the entry-point table (entry_points.py: entry point x route x model x switches), fp32 and fp64, with every input and every
+Every row of the entry-point table (entry_points.py: entry point x route x model x switches -- the inverse-dynamics derivatives,
+integrate / step / rollout, the contact entry points, energy, the centroidal quantities and the momentum matrix included), fp32 and fp64
+(less entry_points.NOT_RUN), with every input and every
 output inside a guarded buffer of guarded.py -- a view between two 4 KiB bands of a canary bit pattern, the view itself pre-filled with
 it -- at the row's own batch size and at a ragged small one (B = 65: one full tile and one state; the chain rows' B_CHAIN is ragged as
 it is, and needed for their route).  lead = 0 keeps the allocator's alignment, lead = 1 moves every pointer by one element (4 / 8 bytes),
@@ -15,7 +17,7 @@ import numpy as np
 import pytest
 
 import guarded  # noqa: F401  (the helper the runner uses)
-from entry_points import B_CHAIN, CASES, ENTRY, IDS, TOL32, TOL64, _body_index, _host_inputs, _model, _rel, OFFSET, OSIM_BODIES, draw_bound, edge_states, plan_for, run_guarded, same_bits_np
+from entry_points import B_CHAIN, CASES, ENTRY, IDS, TOL32, TOL64, TYPED, _body_index, _contacts, _host_inputs, _model, _rel, OFFSET, OSIM_BODIES, draw_bound, edge_states, plan_for, run_guarded, same_bits_np
 
 pytestmark = pytest.mark.gpu
 B_RAGGED = 65
@@ -24,6 +26,9 @@ B_RAGGED = 65
 SIZED = [(c, b) for c in CASES for b in ((c[3],) if c[3] == B_CHAIN else (c[3], B_RAGGED))]
 SIZED_IDS = [f"{ep}-{route}-{model}-B{b}" for (route, model, env, B, ep), b in SIZED]
 assert {i.rsplit("-B", 1)[0] for i in SIZED_IDS} == {i.rsplit("-B", 1)[0] for i in IDS}  # every row of the table
+# ... in both types, less what the table itself leaves out (entry_points.NOT_RUN)
+SIZED_TYPED = [(c, b, dt) for c, b in SIZED for dt in ("f64", "f32") if (c, dt) in TYPED]
+SIZED_TYPED_IDS = [f"{ep}-{route}-{model}-B{b}-{dt}" for (route, model, env, B, ep), b, dt in SIZED_TYPED]
 
 
 def _dtype(name):
@@ -33,8 +38,7 @@ def _dtype(name):
 
 
 @pytest.mark.parametrize("lead", [0, 1])
-@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
-@pytest.mark.parametrize("case,B", SIZED, ids=SIZED_IDS)
+@pytest.mark.parametrize("case,B,dtype_name", SIZED_TYPED, ids=SIZED_TYPED_IDS)
 def test_entry_point_keeps_to_its_buffers(case, B, dtype_name, lead, gpu):
     route, model, env, _, entry = case
     dtype, tol = _dtype(dtype_name), TOL64 if dtype_name == "f64" else TOL32
@@ -66,6 +70,12 @@ OPTIONAL = {  # name -> (model, switches, call, full entry point of the table, i
                                      "fd_derivatives", (2,)),
     "state_positions_only": ("urdf_four_bar", {}, lambda p, x: tuple(o for o in p.state_to_independent(x["q"], tol=1e-8 if x["q"].dtype.itemsize == 8 else 1e-3)
                                                                      if o is not None), "state_to_independent", (0, 2)),
+    # (an output that is not asked for is not allocated: an arena made and left unwritten would fail run_guarded)
+    "contact_points_positions_only": ("urdf_mini_cheetah", {}, lambda p, x: tuple(o for o in p.contact_points(x["q"], *_contacts(p.blob)) if o is not None),
+                                      "contact_points", (0,)),
+    "centroidal_hdot_only": ("urdf_mit_humanoid", {}, lambda p, x: tuple(p.centroidal(x["q"], x["qd"], x["tau"], want=("hdot",)).values()),
+                             "centroidal", (3,)),
+    "energy_without_qd": ("urdf_mit_humanoid", {}, lambda p, x: tuple(o for o in p.energy(x["q"]) if o is not None), "energy", (1,)),
 }
 
 

@@ -3,7 +3,8 @@ by threads and streams"): a call's result must be BIT-identical whether or not o
 result it is compared with -- the same call made alone -- is itself held against the oracle.  concurrency.py gives the gate, the
 round-robin enqueue, the per-repetition events and the overlap count.
 
-1. Every row of the entry-point table (entry_points.py), fp32 and fp64, on N_STREAMS = 4 streams.  Stream i has its own inputs (seed
+1. Every row of the entry-point table (entry_points.py: the inverse-dynamics derivatives, integrate / step / rollout, the contact entry
+   points, energy, the centroidal quantities and the momentum matrix included), fp32 and fp64, on N_STREAMS = 4 streams.  Stream i has its own inputs (seed
    100 + i) and its own batch B - i, so the streams are ragged differently and hold slabs of different sizes on the row's route.
    Serial pass: one call per stream, alone, against the oracle on edge_states(B - i).  Concurrent pass: behind a gate (a spin kernel all
    worker streams wait for) the host queues R repetitions round-robin over the streams, every repetition into fresh outputs.  Asserted:
@@ -28,7 +29,7 @@ import pytest
 
 import concurrency as C
 import generalized_rbda_amd as G
-from entry_points import CASES, ENTRY, IDS, TOL32, TOL64, _host, _inputs, _model, draw_bound, edge_states, plan_for, same_bits_np
+from entry_points import CASES, ENTRY, IDS, NOT_RUN, TOL32, TOL64, TYPED, TYPED_IDS, _host, _inputs, _model, draw_bound, edge_states, plan_for, same_bits_np
 
 pytestmark = pytest.mark.gpu
 
@@ -189,9 +190,9 @@ def _where(got, want):
 
 
 # ---- 1. streams sharing a plan give the serial bits ------------------------------------------------------------------------------------
-SHARED = [(c, dt) for c in CASES for dt in ("f64", "f32")]
-SHARED_IDS = [f"{i}-{dt}" for i in IDS for dt in ("f64", "f32")]
-assert {i.rsplit("-", 1)[0] for i in SHARED_IDS} == set(IDS) and len(SHARED) == 2 * len(CASES)  # every row of the table, both types
+SHARED, SHARED_IDS = TYPED, TYPED_IDS
+# every row of the table, both types, less what the table itself leaves out
+assert {i.rsplit("-", 1)[0] for i in SHARED_IDS} == set(IDS) and len(SHARED) == 2 * len(CASES) - len(NOT_RUN)
 
 
 def shared_plan_case(case, dtype_name, gpu, sizes=None):
@@ -231,6 +232,10 @@ STATE_ROWS = [
     ("work_proj (forward dynamics)", _row("spanning_tree", "parallel_chain_exp_d10_l16", "aba"), ("f64", "f32")),
     ("work_proj (mass matrix)", _row("spanning_tree", "parallel_chain_exp_d10_l16", "mass_matrix"), ("f64", "f32")),
     ("scratch slab of the auxiliary kernels", _row("implicit", "urdf_four_bar", "project_positions"), ("f64", "f32")),
+    ("parents' pose, velocity and acceleration rows of centroidal_kernel in the scratch slab", _row("explicit", "urdf_mit_humanoid", "centroidal"), ("f64", "f32")),
+    ("work slab of the contact pipeline", _row("efpa", "urdf_mini_cheetah", "contact_dynamics"), ("f64", "f32")),
+    ("work slab of the momentum matrix", _row("explicit", "urdf_mit_humanoid", "centroidal_matrix"), ("f64", "f32")),
+    ("forward dynamics and projection chained on one stream", _row("explicit", "urdf_mini_cheetah", "rollout"), ("f64", "f32")),
 ]
 # the minv derivatives under GRBDA_WORK_MAX_MB=1 at the batch test_graph_capture_gpu.py captures: many chunks per call
 CAPPED = ("chunked: 1 MiB of work slab", ("minv", "urdf_mini_cheetah", {}, 20000, "fd_derivatives"), ("f32",))

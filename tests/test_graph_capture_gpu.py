@@ -1,4 +1,6 @@
-"""Graph capture of every stream-taking device entry point ("Graph capture"), fp32 and fp64, on each route a plan can take.
+"""Graph capture of every stream-taking device entry point ("Graph capture"), fp32 and fp64, on each route a plan can take:
+the rows of the entry-point table by number type (entry_points.TYPED), from forward dynamics to rollout (whose recorded trajectories
+are allocated inside the captured call), the contact pipeline and the centroidal quantities.
 
 For every case: (a) capture succeeds after one eager call of the same batch on the capturing stream; (b) two replays with fresh inputs
 (written in place) equal, bit for bit, eager calls on those inputs; (c) a seeded sample agrees with the oracle at the tolerances of
@@ -10,7 +12,7 @@ import numpy as np
 import pytest
 
 import generalized_rbda_amd as G
-from entry_points import B_CHAIN, CASES, ENTRY, IDS, TOL32, TOL64, _host, _inputs, _model  # noqa: F401
+from entry_points import B_CHAIN, CASES, ENTRY, IDS, TOL32, TOL64, TYPED, TYPED_IDS, _host, _inputs, _model  # noqa: F401
 from graph_capture import capture
 from models import zoo
 
@@ -18,8 +20,7 @@ pytestmark = pytest.mark.gpu
 N_ORACLE = 6         # states of each replay checked against the oracle
 
 
-@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
-@pytest.mark.parametrize("route,model,env,B,entry", CASES, ids=IDS)
+@pytest.mark.parametrize("route,model,env,B,entry,dtype_name", [c + (dt,) for c, dt in TYPED], ids=TYPED_IDS)
 def test_capture_replay_matches_eager_and_oracle(route, model, env, B, entry, dtype_name, gpu, monkeypatch):
     import torch
 
