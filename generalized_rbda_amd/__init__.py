@@ -32,6 +32,7 @@ C_ABI_SYMBOLS = [
     "grbda_apply_test_force_f64", "grbda_apply_test_force_f32", "grbda_inv_osim_f64", "grbda_inv_osim_f32",
     "grbda_contact_points_f64", "grbda_contact_points_f32", "grbda_contact_dynamics_f64", "grbda_contact_dynamics_f32",
     "grbda_contact_points_host_f64", "grbda_contact_dynamics_host_f64",
+    "grbda_contact_impulse_f64", "grbda_contact_impulse_f32", "grbda_contact_impulse_host_f64",
     "grbda_project_positions_f64", "grbda_project_positions_f32", "grbda_plan_span_dims",
     "grbda_spanning_f64", "grbda_spanning_f32", "grbda_fd_derivatives_f64", "grbda_fd_derivatives_f32",
     "grbda_mass_matrix_host_f64", "grbda_fd_derivatives_host_f64",
@@ -128,6 +129,8 @@ def lib() -> ctypes.CDLL:
         getattr(L, "grbda_contact_dynamics_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int),
                                                                 POINTER(c_double), c_void_p, c_double, c_void_p, c_void_p, c_void_p,
                                                                 c_size_t, c_int, c_void_p]
+        getattr(L, "grbda_contact_impulse_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double), c_void_p,
+                                                               c_double, c_double, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
         getattr(L, "grbda_apply_test_force_" + sfx).argtypes = [c_void_p, c_void_p, c_int, POINTER(c_double), c_void_p,
                                                                 c_void_p, c_void_p, c_size_t, c_int, c_void_p]
     for sfx in ("f64", "f32"):
@@ -672,6 +675,33 @@ class Plan:
                   lam.data_ptr(), free.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
         with torch.cuda.stream(s):
             return ydd, lam, free
+
+    def contact_impulse(self, q, qd, bodies, offsets, v_des=None, restitution: float = 0.0, damping: float = 0.0, stream=None):
+        """The instant the points offsets[c] of bodies[c] close (grbda_contact_impulse_*): (J_w H^-1 J_w^T + damping I) Lambda =
+        v_des - (1 + restitution) J_w qd, qd_next = qd + H^-1 J_w^T Lambda, with v_des[B, n, 3] (None: zero) in world axes.  Returns
+        (qd_next[B, nv], impulse[B, n, 3] -- world-frame impulses on the bodies at the points); the points then move at
+        v_des - restitution J_w qd - damping impulse.  q does not change; gravity and tau do not enter.  Redundant contacts need
+        damping > 0; a state whose matrix is not positive definite gets NaN and is counted by spd_bad_pivots()."""
+        import torch
+
+        B = self._state_args(q, qd, qd, "qd")
+        n, bod, off = self._contacts(bodies, offsets)
+        q, qd = q.contiguous(), qd.contiguous()
+        if v_des is not None:
+            if v_des.shape != (B, n, 3) or v_des.dtype != q.dtype or not v_des.is_cuda:
+                raise ValueError(f"v_des must be a device tensor [B,{n},3] of the same dtype")
+            v_des = v_des.contiguous()
+        qd_next = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
+        impulse = torch.empty((B, n, 3), dtype=q.dtype, device=q.device)
+        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        if stream is not None:
+            for t in (q, qd, qd_next, impulse) + (() if v_des is None else (v_des,)):
+                t.record_stream(s)
+        fn = getattr(lib(), f"grbda_contact_impulse_{'f32' if q.dtype == torch.float32 else 'f64'}")
+        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), n, bod, off, None if v_des is None else v_des.data_ptr(), float(restitution),
+                  float(damping), qd_next.data_ptr(), impulse.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
+        with torch.cuda.stream(s):
+            return qd_next, impulse
 
     # ---- energy and centroidal quantities -----------------------------------------------------------
     def total_mass(self) -> float:

@@ -1901,6 +1901,71 @@ int contact_dynamics(const grbda_plan *p, const T *q, const T *qd, const T *tau,
     return GRBDA_OK;
 }
 
+// Everything grbda_contact_impulse_* refuses, on the host and before any device call.  qd_next may BE qd (equal pointers, as for
+// grbda_integrate_*); any other overlap of an output with an input or with the other output is refused.
+template <class T>
+int contact_impulse_args(const grbda_plan *p, const T *q, const T *qd, int n_contacts, const int *bodies, const double *offsets, const T *v_des,
+                         double restitution, double damping, const T *qd_next, const T *impulse, size_t B, ContactSet<T> &cs)
+{
+    if (!q || !qd || !qd_next || !impulse) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, "points", cs)) return rc;
+    if (!std::isfinite(damping) || damping < 0) return set_err(GRBDA_EINVAL, "damping must be finite and not negative");
+    if (!std::isfinite(restitution) || restitution < 0 || restitution > 1) return set_err(GRBDA_EINVAL, "restitution must lie in [0, 1]");
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const size_t bc = B * static_cast<size_t>(n_contacts) * 3 * sizeof(T);
+    const void *const in[3] = {q, qd_next == qd ? nullptr : qd, v_des}, *const out[2] = {qd_next, impulse};  // (null entries are skipped)
+    const size_t in_bytes[3] = {bq, bv, bc}, out_bytes[2] = {bv, bc};
+    return no_overlap(in, in_bytes, out, out_bytes);
+}
+// The instant a contact closes: (J_w H^-1 J_w^T + mu I) Lambda = v_des - (1 + e) J_w qd, qd_next = qd + H^-1 J_w^T Lambda.  Per chunk, on one
+// slab of p->work carved here for the whole pipeline (as contact_dynamics):
+//   1 poses          2 twists at qd (the acceleration halves, computed at zeros, are not read)          3 Linv of the contact frames
+//   4 impulse_solve_kernel: the impulses and the wrench rows          5 y1 = FD(q, 0, 0, wrench rows), y0 = FD(q, 0, 0, none): the forward
+//   dynamics are affine in the wrenches, so y1 - y0 = H^-1 J_w^T Lambda with gravity cancelled          6 qd_next = qd + (y1 - y0)
+// A chunk reads its rows of qd (stage 2) before stage 6 writes them, so qd_next == qd is safe.
+template <class T>
+int contact_impulse(const grbda_plan *p, const T *q, const T *qd, int n_contacts, const int *bodies, const double *offsets, const T *v_des,
+                    double restitution, double damping, T *qd_next, T *impulse, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<T> cs;
+    if (int rc = contact_impulse_args<T>(p, q, qd, n_contacts, bodies, offsets, v_des, restitution, damping, qd_next, impulse, B, cs)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const OsimRoute<T> r = choose_osim<T>(p, n_contacts, bodies, offsets, false, nullptr, nullptr, nullptr);
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n = static_cast<size_t>(n_contacts);
+    const size_t m6 = 6 * n;
+    // zeros, y1, y0, poses, twists and their spanning rates, Linv, wrench rows, and the inverse OSIM's own
+    const size_t per_state = 3 * nv + nbod * 24 + 2 * ns + m6 * m6 + nbod * 6 + r.ws_per_state;
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // (the zeros lead the slab at the chunk's full size: every pass finds them where this call cleared them)
+    if (hipError_t e = hipMemsetAsync(wptr, 0, c.chunk * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        const T *zero = w.take(c.chunk * nv);
+        T *y1 = w.take(nb * nv), *y0 = w.take(nb * nv);
+        T *Xa = w.take(nb * nbod * 12), *V = w.take(nb * nbod * 12), *vs = w.take(nb * ns), *as = w.take(nb * ns);
+        T *Linv = w.take(nb * m6 * m6), *wrench = w.take(nb * nbod * 6);
+        const T *qc = q + b0 * nq, *qdc = qd + b0 * nv;
+        int rc;
+        if ((rc = poses_stage<T>(p, *t, qc, Xa, nb, stream)) || (rc = twists_stage<T>(p, *t, qc, qdc, zero, V, vs, as, nb, device, stream)) ||
+            (rc = osim_stage<T>(p, *t, r, cs, qc, Linv, nullptr, nb, device, stream, w)))
+            return rc;
+        hipError_t e = launch_impulse_solve<T>(cs, Linv, Xa, V, v_des ? v_des + b0 * n * 3 : nullptr, static_cast<int>(nbod), static_cast<T>(damping),
+                                               static_cast<T>(restitution), nb, impulse + b0 * n * 3, wrench, t->bad_count, t->n_cu, hs);
+        if (e != hipSuccess) return hip_err(e, "impulse solve launch");
+        if ((rc = run<T>(p, false, qc, zero, zero, wrench, y1, nb, device, stream)) || (rc = run<T>(p, false, qc, zero, zero, nullptr, y0, nb, device, stream)))
+            return rc;
+        if ((e = launch_impulse_finish<T>(qdc, y1, y0, nb * nv, qd_next + b0 * nv, hs)) != hipSuccess) return hip_err(e, "impulse finish launch");
+    }
+    return GRBDA_OK;
+}
+
 // ---- derived quantities: expanded batches over the two kernels (include/grbda_hip.h) ---------------------
 // (DM_ID_DQD, DM_ID_DQ: the same difference batches as DM_DQD, DM_DQ over the INVERSE dynamics, `tau` holding ydd -- grbda_rnea_derivatives_*)
 enum DerivedMode { DM_BIAS = 0, DM_MASS = 1, DM_DTAU = 2, DM_DQD = 3, DM_DQ = 4, DM_ID_DQD = 5, DM_ID_DQ = 6 };
@@ -3319,6 +3384,36 @@ int grbda_contact_dynamics_host_f64(const grbda_plan *p, const double *q, const 
     double *dy = st.out(ydd, B * nv), *dl = st.out(lambda, no), *dyf = ydd_free ? st.out(ydd_free, B * nv) : nullptr;
     return st.run([&] {
         return contact_dynamics<double>(p, dq, dqd, dt, dfe, n_contacts, bodies, offsets, dad, damping, dy, dl, dyf, B, device, nullptr);
+    });
+}
+int grbda_contact_impulse_f64(const grbda_plan *p, const double *q, const double *qd, int n_contacts, const int *bodies, const double *offsets,
+                              const double *v_des, double restitution, double damping, double *qd_next, double *impulse, size_t B, int device,
+                              void *stream)
+{
+    return contact_impulse<double>(p, q, qd, n_contacts, bodies, offsets, v_des, restitution, damping, qd_next, impulse, B, device, stream);
+}
+int grbda_contact_impulse_f32(const grbda_plan *p, const float *q, const float *qd, int n_contacts, const int *bodies, const double *offsets,
+                              const float *v_des, double restitution, double damping, float *qd_next, float *impulse, size_t B, int device,
+                              void *stream)
+{
+    return contact_impulse<float>(p, q, qd, n_contacts, bodies, offsets, v_des, restitution, damping, qd_next, impulse, B, device, stream);
+}
+int grbda_contact_impulse_host_f64(const grbda_plan *p, const double *q, const double *qd, int n_contacts, const int *bodies, const double *offsets,
+                                   const double *v_des, double restitution, double damping, double *qd_next, double *impulse, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<double> cs;
+    if (int rc = contact_impulse_args<double>(p, q, qd, n_contacts, bodies, offsets, v_des, restitution, damping, qd_next, impulse, B, cs)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, no = B * static_cast<size_t>(n_contacts) * 3;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dvd = v_des ? st.in(v_des, no) : nullptr;
+    double *dqn = st.out(qd_next, B * nv), *di = st.out(impulse, no);  // (qd_next == qd on the host: two device arrays, the input copied first)
+    return st.run([&] {
+        return contact_impulse<double>(p, dq, dqd, n_contacts, bodies, offsets, dvd, restitution, damping, dqn, di, B, device, nullptr);
     });
 }
 int grbda_aba_sharded_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, float *ydd, size_t B,

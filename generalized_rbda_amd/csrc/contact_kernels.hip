@@ -20,6 +20,9 @@
 // triangle is indexed through LDS addresses, never through a per-lane array, so nothing goes to the private segment.  A workgroup is one
 // (possibly partial) wavefront of `lanes` states: contact_solve_lanes() picks 64, 32 or 16 so that the most states are resident per CU
 // within its 160 KiB of LDS (fp64 with 8 contacts does not fit 64 lanes at all).
+//
+// impulse_solve_kernel (grbda_contact_impulse_*): the same mapping, matrix and factorisation with the velocity-level right-hand side
+// v_des - (1 + e) p_dot; impulse_finish_kernel adds the velocity change to qd.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -210,6 +213,128 @@ __global__ __launch_bounds__(kWave) void contact_solve_kernel(ContactSet<T> cs, 
     }
 }
 
+// The velocity-level twin of contact_solve_kernel (grbda_contact_impulse_*): the same mapping, the same A and the same factorisation, with
+//     rhs = v_des - (1 + e) p_dot,   p_dot = E^T (v + omega x o)
+// from the velocity halves of the twist rows alone (the acceleration halves are never read; gravity does not enter).  Writes the impulses
+// [nb][n][3] and the wrench row [nb][n_bodies][6] = zeros + [p x Lambda_c ; Lambda_c] on body[c], contacts on one body accumulating.
+// The assembly of A and the factor / solve are a COPY of contact_solve_kernel's text: moving them into device functions both kernels call
+// changed the instruction stream of the two existing instantiations (DESIGN.md 7g'), so that kernel's text stays as it was measured.
+template <class T>
+__global__ __launch_bounds__(kWave) void impulse_solve_kernel(ContactSet<T> cs, const T *__restrict__ Linv, const T *__restrict__ Xa,
+                                                              const T *__restrict__ V, const T *__restrict__ v_des, int n_bodies, T mu,
+                                                              T one_plus_e, size_t nb, T *__restrict__ impulse, T *__restrict__ wrench,
+                                                              unsigned long long *bad_count)
+{
+    const int W = (int)blockDim.x, lane = (int)threadIdx.x;
+    const int n = cs.n, m = 3 * n, m6 = 6 * n, tri = m * (m + 1) / 2;
+    T *A = reinterpret_cast<T *>(contact_smem) + lane;  // packed lower triangle: entry (i, j <= i) at A[(i (i + 1) / 2 + j) W]
+    T *y = A + (size_t)tri * W;                         // right-hand side, then the impulses: y[i W]
+    for (size_t b = blockIdx.x * (size_t)W + lane; b < nb; b += (size_t)gridDim.x * W) {
+        const T *Lb = Linv + b * (size_t)m6 * m6;
+        const T *Xb = Xa + b * (size_t)n_bodies * 12, *Vb = V + b * (size_t)n_bodies * 12;
+        // A = R Linv_ff R^T + mu I, block by block of the lower triangle
+        for (int c1 = 0; c1 < n; c1++) {
+            T E1[9];
+            {
+                const T *X1 = Xb + (size_t)cs.body[c1] * 12;
+                for (int i = 0; i < 9; i++) E1[i] = X1[i];
+            }
+            for (int c2 = 0; c2 <= c1; c2++) {
+                const T *X2 = Xb + (size_t)cs.body[c2] * 12;
+                const T *Lc = Lb + (size_t)(6 * c1 + 3) * m6 + 6 * c2 + 3;
+                T tmp[3][3];  // Linv block times E2
+                for (int k = 0; k < 3; k++)
+                    for (int j = 0; j < 3; j++) tmp[k][j] = Lc[k * m6] * X2[j] + Lc[k * m6 + 1] * X2[3 + j] + Lc[k * m6 + 2] * X2[6 + j];
+                for (int i = 0; i < 3; i++) {
+                    const int ri = 3 * c1 + i, row = ri * (ri + 1) / 2 + 3 * c2;
+                    for (int j = 0; j < 3; j++) {
+                        T v = E1[i] * tmp[0][j] + E1[3 + i] * tmp[1][j] + E1[6 + i] * tmp[2][j];
+                        if (c1 == c2) {
+                            if (j > i) continue;
+                            if (j == i) v += mu;
+                        }
+                        A[(size_t)(row + j) * W] = v;
+                    }
+                }
+            }
+        }
+        // rhs = v_des - (1 + e) p_dot
+        for (int c = 0; c < n; c++) {
+            const size_t row = (size_t)cs.body[c] * 12;
+            const T o[3] = {cs.off[c][0], cs.off[c][1], cs.off[c][2]};
+            T u[3], vel[3];
+            point_velocity(Vb + row, o, u);
+            rot_t(Xb + row, u, vel);
+            for (int i = 0; i < 3; i++) y[(size_t)(3 * c + i) * W] = (v_des ? v_des[(b * n + c) * 3 + i] : T(0)) - one_plus_e * vel[i];
+        }
+        // A = L L^T in place
+        bool bad = false;
+        for (int j = 0; j < m; j++) {
+            const int rj = j * (j + 1) / 2;
+            T d = A[(size_t)(rj + j) * W];
+            for (int k = 0; k < j; k++) {
+                const T l = A[(size_t)(rj + k) * W];
+                d -= l * l;
+            }
+            if (!(d > T(0)) || !(d < T(INFINITY))) bad = true;
+            const T ljj = sqrt(d), inv = T(1) / ljj;
+            A[(size_t)(rj + j) * W] = ljj;
+            for (int i = j + 1; i < m; i++) {
+                const int ri = i * (i + 1) / 2;
+                T s = A[(size_t)(ri + j) * W];
+                for (int k = 0; k < j; k++) s -= A[(size_t)(ri + k) * W] * A[(size_t)(rj + k) * W];
+                A[(size_t)(ri + j) * W] = s * inv;
+            }
+        }
+        // L z = rhs, L^T Lambda = z
+        for (int i = 0; i < m; i++) {
+            const int ri = i * (i + 1) / 2;
+            T s = y[(size_t)i * W];
+            for (int k = 0; k < i; k++) s -= A[(size_t)(ri + k) * W] * y[(size_t)k * W];
+            y[(size_t)i * W] = s / A[(size_t)(ri + i) * W];
+        }
+        for (int i = m - 1; i >= 0; i--) {
+            T s = y[(size_t)i * W];
+            for (int k = i + 1; k < m; k++) s -= A[(size_t)(k * (k + 1) / 2 + i) * W] * y[(size_t)k * W];
+            y[(size_t)i * W] = s / A[(size_t)(i * (i + 1) / 2 + i) * W];
+        }
+        if (bad) {
+            // a pivot that is not positive or not finite: the state gets NaN, and is counted (grbda_spd_bad_pivots)
+            for (int i = 0; i < m; i++) y[(size_t)i * W] = T(NAN);
+            if (bad_count) atomicAdd(bad_count, 1ull);
+        }
+        // the impulses, and the wrench row of the forward-dynamics call that turns them into a velocity change
+        T *w = wrench + b * (size_t)n_bodies * 6;
+        for (int i = 0; i < n_bodies * 6; i++) w[i] = T(0);
+        for (int c = 0; c < n; c++) {
+            const T *X = Xb + (size_t)cs.body[c] * 12;
+            const T o[3] = {cs.off[c][0], cs.off[c][1], cs.off[c][2]};
+            T p[3], f[3], mo[3];
+            rot_t(X, o, p);
+            for (int i = 0; i < 3; i++) {
+                p[i] += X[9 + i];
+                f[i] = y[(size_t)(3 * c + i) * W];
+                impulse[(b * n + c) * 3 + i] = f[i];
+            }
+            cross3(p, f, mo);
+            T *wb = w + (size_t)cs.body[c] * 6;
+            for (int i = 0; i < 3; i++) {
+                wb[i] += mo[i];
+                wb[3 + i] += f[i];
+            }
+        }
+    }
+}
+
+// qd_next = qd + (y1 - y0), element by element: y1, y0 the forward dynamics at rest with and without the impulses' wrenches.  qd_next may
+// be qd (an element is read before it is written, by the same thread).
+template <class T>
+__global__ void impulse_finish_kernel(const T *qd, const T *__restrict__ y1, const T *__restrict__ y0, size_t total, T *qd_next)
+{
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        qd_next[t] = qd[t] + (y1[t] - y0[t]);
+}
+
 size_t contact_solve_lds_bytes(int n_contacts, size_t elem, int lanes)
 {
     const size_t m = 3 * static_cast<size_t>(n_contacts);
@@ -264,6 +389,31 @@ hipError_t launch_contact_solve(const ContactSet<T> &cs, const T *Linv, const T 
                        fext_in, n_bodies, mu, g[0], g[1], g[2], nb, lambda, fext_out, bad_count);
     return hipGetLastError();
 }
+// the impulse solve launches from the same record: the same triangle and one right-hand side in LDS
+template <class T>
+hipError_t launch_impulse_solve(const ContactSet<T> &cs, const T *Linv, const T *Xa, const T *V, const T *v_des, int n_bodies, T mu, T restitution,
+                                size_t nb, T *impulse, T *wrench, unsigned long long *bad_count, int n_cu, hipStream_t stream)
+{
+    const ContactSolveLaunch L = contact_solve_launch(cs.n, sizeof(T));
+    if (L.lanes == 0) return hipErrorInvalidValue;
+    const size_t grid = std::min(static_cast<size_t>(n_cu) * L.per_cu, (nb + L.lanes - 1) / L.lanes);
+    hipLaunchKernelGGL((impulse_solve_kernel<T>), dim3(static_cast<unsigned>(grid)), dim3(L.lanes), L.lds_bytes, stream, cs, Linv, Xa, V, v_des,
+                       n_bodies, mu, T(1) + restitution, nb, impulse, wrench, bad_count);
+    return hipGetLastError();
+}
+template <class T>
+hipError_t launch_impulse_finish(const T *qd, const T *y1, const T *y0, size_t total, T *qd_next, hipStream_t stream)
+{
+    const int blocks = static_cast<int>((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+    hipLaunchKernelGGL((impulse_finish_kernel<T>), dim3(blocks), dim3(256), 0, stream, qd, y1, y0, total, qd_next);
+    return hipGetLastError();
+}
+template hipError_t launch_impulse_solve<float>(const ContactSet<float> &, const float *, const float *, const float *, const float *, int, float,
+                                                float, size_t, float *, float *, unsigned long long *, int, hipStream_t);
+template hipError_t launch_impulse_solve<double>(const ContactSet<double> &, const double *, const double *, const double *, const double *, int,
+                                                 double, double, size_t, double *, double *, unsigned long long *, int, hipStream_t);
+template hipError_t launch_impulse_finish<float>(const float *, const float *, const float *, size_t, float *, hipStream_t);
+template hipError_t launch_impulse_finish<double>(const double *, const double *, const double *, size_t, double *, hipStream_t);
 template hipError_t launch_contact_points<float>(const ContactSet<float> &, const float *, const float *, int, const float[3], size_t, float *,
                                                  float *, float *, hipStream_t);
 template hipError_t launch_contact_points<double>(const ContactSet<double> &, const double *, const double *, int, const double[3], size_t,
@@ -275,10 +425,11 @@ template hipError_t launch_contact_solve<double>(const ContactSet<double> &, con
                                                  const double *, int, double, const double[3], size_t, double *, double *, unsigned long long *,
                                                  int, hipStream_t);
 
-// the solve asks for more dynamic LDS than the 64 KiB default (per device, as for the other kernel families)
+// the solves ask for more dynamic LDS than the 64 KiB default (per device, as for the other kernel families)
 hipError_t set_max_dynamic_lds_contact()
 {
-    for (const void *f : {reinterpret_cast<const void *>(&contact_solve_kernel<float>), reinterpret_cast<const void *>(&contact_solve_kernel<double>)}) {
+    for (const void *f : {reinterpret_cast<const void *>(&contact_solve_kernel<float>), reinterpret_cast<const void *>(&contact_solve_kernel<double>),
+                          reinterpret_cast<const void *>(&impulse_solve_kernel<float>), reinterpret_cast<const void *>(&impulse_solve_kernel<double>)}) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }

@@ -220,6 +220,14 @@ struct ContactSolveLaunch {
     size_t per_cu;     // workgroups per CU the grid is capped at
 };
 ContactSolveLaunch contact_solve_launch(int n_contacts, size_t elem);
+// launch_impulse_solve: the velocity-level solve on the same launch record -- V the twists at qd (velocity halves only), v_des [nb][n][3]
+// or null; writes impulse [nb][n][3] and the wrench rows [nb][n_bodies][6].  launch_impulse_finish: qd_next = qd + (y1 - y0) over `total`
+// elements (qd_next may be qd).
+template <class T>
+hipError_t launch_impulse_solve(const ContactSet<T> &cs, const T *Linv, const T *Xa, const T *V, const T *v_des, int n_bodies, T mu, T restitution,
+                                size_t nb, T *impulse, T *wrench, unsigned long long *bad_count, int n_cu, hipStream_t stream);
+template <class T>
+hipError_t launch_impulse_finish(const T *qd, const T *y1, const T *y0, size_t total, T *qd_next, hipStream_t stream);
 hipError_t set_max_dynamic_lds_contact();
 
 // energy, centre of mass and centroidal momentum (centroidal_kernels.hip).  A body with children keeps its pose (12), velocity (6) and

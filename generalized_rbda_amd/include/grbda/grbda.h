@@ -1329,6 +1329,15 @@ public:
     {
         check(grbda_centroidal_host_f64(plan(), q, qd, ydd, com, com_vel, h, hdot, B, device));
     }
+    // The instant contacts close, for B states on host arrays (include/grbda_hip.h "contact impulses"; Pinocchio: impulseDynamics):
+    // (J_w H^-1 J_w^T + damping I) Lambda = v_des - (1 + restitution) J_w qd, qd_next = qd + H^-1 J_w^T Lambda.  Point c is offsets[3 c ..]
+    // (body coordinates) of body bodies[c], 1 .. 8 of them; v_des: null (zero) or [B][n][3], world axes.  qd_next[B][nv] (may be qd),
+    // impulse[B][n][3]: world-frame impulses on the bodies at the points.  Gravity and tau do not enter.
+    void contactImpulseBatch(const double *q, const double *qd, int n_contacts, const int *bodies, const double *offsets, const double *v_des,
+                             double restitution, double damping, double *qd_next, double *impulse, size_t B, int device = 0)
+    {
+        check(grbda_contact_impulse_host_f64(plan(), q, qd, n_contacts, bodies, offsets, v_des, restitution, damping, qd_next, impulse, B, device));
+    }
     void stepBatch(const double *q, const double *qd, const double *tau, double dt, double *ydd, double *q_next, double *qd_next,
                    int32_t *ok, size_t B, int device = 0, const double *f_ext = nullptr)
     {

@@ -241,7 +241,7 @@ int grbda_rnea_derivatives_host_f64(const grbda_plan *plan, const double *q, con
  * least-squares answer there (src/Dynamics/ClusterTreeNode.cpp:33-37).  The solve kernels COUNT such states per device: this call
  * synchronises the device, returns the count since the last reset and (reset != 0) clears it.  The contact solve of
  * grbda_contact_dynamics_* counts into the same word: a state whose J_w H^-1 J_w^T + damping I had such a pivot (redundant contacts
- * with damping = 0) has NaN in its lambda and ydd. */
+ * with damping = 0) has NaN in its lambda and ydd.  So does the solve of grbda_contact_impulse_* (NaN in impulse and qd_next). */
 int grbda_spd_bad_pivots(int device, unsigned long long *count, int reset);
 /* The name of the kernel grbda_aba_* (kind 0) / grbda_rnea_* (kind 1) launches for a batch of B states in this precision (32 | 64) on
  * this device, without external forces -- as rocprofv3 prints it (template arguments included; the chain kernels' inverse dynamics
@@ -457,13 +457,48 @@ int grbda_contact_dynamics_f32(const grbda_plan *plan, const float *q, const flo
 /* What grbda_contact_dynamics_* launches its solve kernel with for n_contacts (1 .. 8) in this precision (32 | 64): the states per
  * workgroup (64, 32 or 16), the dynamic LDS of a workgroup in bytes, and the most workgroups one launch has -- the CUs of `device` times
  * the workgroups a CU holds; batches beyond grid_cap * lanes states take further trips of the grid.  device < 0 touches no device and
- * reports grid_cap for a single CU.  The launch reads the same record (contact_kernels.hip, contact_solve_launch). */
+ * reports grid_cap for a single CU.  The launch reads the same record (contact_kernels.hip, contact_solve_launch).  The solve of
+ * grbda_contact_impulse_* (below) launches from that record too: its LDS footprint is the same triangle plus one right-hand side. */
 int grbda_contact_solve_launch(int n_contacts, int precision, int device, int *lanes, size_t *lds_bytes, size_t *grid_cap);
 int grbda_contact_points_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *ydd, int n_contacts,
                                   const int *bodies, const double *offsets, double *pos, double *vel, double *acc, size_t B, int device);
 int grbda_contact_dynamics_host_f64(const grbda_plan *plan, const double *q, const double *qd, const double *tau, const double *f_ext,
                                     int n_contacts, const int *bodies, const double *offsets, const double *a_des, double damping,
                                     double *ydd, double *lambda, double *ydd_free, size_t B, int device);
+
+/* ---- contact impulses: the instant a contact closes -----------------------------------------------------------------------------
+ * A point that touches down with a velocity loses it in one instant: the velocity-level twin of the solve above (Pinocchio:
+ * impulseDynamics; Crocoddyl's impulse models).  Contacts are described as for grbda_contact_dynamics_*: n_contacts in 1 .. 8, host
+ * arrays bodies[n] and offsets[n][3]; every other array is a device array, row-major.  With J_w [3 n][nv] the world-frame Jacobian of
+ * the points, v- = J_w qd their velocities before the impact (the vel of grbda_contact_points_*), e = restitution and mu = damping:
+ *     (J_w H^-1 J_w^T + mu I) Lambda = v_des - (1 + e) v-
+ *     qd_next = qd + H^-1 J_w^T Lambda
+ *   v_des        NULL (zero) or [B][n][3]: world-frame velocity the points shall have after the impact (before restitution)
+ *   restitution  e in [0, 1], finite;  damping  mu >= 0, finite
+ *   qd_next [B][nv], impulse [B][n][3]   outputs; impulse: world-frame impulses ON the bodies at the points
+ * The result satisfies J_w qd_next = v_des - e v- - mu Lambda: for e = 0, mu = 0 and independent contacts the plastic impact (the points
+ * stop); e = 1, mu = 0, v_des = 0 conserves the kinetic energy.  q is not changed by an impact.  Gravity and tau do not enter: finite
+ * forces give no impulse over an instant.  Redundant contacts need mu > 0.  The matrix is the one of the solve above, factored per state
+ * by the same Cholesky: a pivot that is not positive or not finite gives NaN in that state's impulse and qd_next, the call still returns
+ * GRBDA_OK, and the state is counted in the counter behind grbda_spd_bad_pivots.
+ * Per chunk of the batch: poses, twists, inverse OSIM, one solve kernel, two forward dynamics at rest (with and without the impulses'
+ * wrenches: their difference is H^-1 J_w^T Lambda) and one element-wise kernel -- on every plan grbda_contact_dynamics_* accepts.
+ *
+ * Errors, all decided on the host before anything is enqueued: GRBDA_EINVAL for a NULL plan, q, qd, qd_next or impulse, n_contacts
+ * outside 1 .. 8, a body index out of range, a damping that is negative or not finite, a restitution that is not finite or outside
+ * [0, 1], outputs that overlap inputs or each other -- except qd_next == qd (equal pointers), which is allowed as in grbda_integrate_*:
+ * a chunk reads its rows of qd before it writes them.  B == 0: GRBDA_OK.  No synchronisation, no allocation beyond the scratch slab and
+ * the work slab (chunked like the other pipelines, GRBDA_WORK_MAX_MB): capturable after one eager call of the same B and n_contacts on
+ * the stream.  The _host_ variant takes host arrays (allocates, copies and synchronises per call). */
+int grbda_contact_impulse_f64(const grbda_plan *plan, const double *q, const double *qd, int n_contacts, const int *bodies,
+                              const double *offsets, const double *v_des, double restitution, double damping, double *qd_next,
+                              double *impulse, size_t B, int device, void *stream);
+int grbda_contact_impulse_f32(const grbda_plan *plan, const float *q, const float *qd, int n_contacts, const int *bodies,
+                              const double *offsets, const float *v_des, double restitution, double damping, float *qd_next, float *impulse,
+                              size_t B, int device, void *stream);
+int grbda_contact_impulse_host_f64(const grbda_plan *plan, const double *q, const double *qd, int n_contacts, const int *bodies,
+                                   const double *offsets, const double *v_des, double restitution, double damping, double *qd_next,
+                                   double *impulse, size_t B, int device);
 
 /* ---- energy and centroidal quantities ------------------------------------------------------------------------------------------
  * What a trajectory is judged and controlled by (Pinocchio: computeKineticEnergy, computePotentialEnergy, centerOfMass,
