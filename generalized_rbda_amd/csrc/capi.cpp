@@ -661,7 +661,7 @@ Route choose_rnea(const grbda_plan *p, int n_cu, size_t B, bool f_ext)
 
 template <class T>
 int run_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const T *q, const T *qd, const T *tau, T *ydd, size_t B, int device,
-              void *stream)
+              void *stream, bool gravity = true)
 {
     const HostPlan &h = p->host;
     const ChainProgram &cp = h.chain[r.slot];
@@ -669,6 +669,8 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const 
     const size_t in_rows = static_cast<size_t>(h.nq + 2 * h.nv);
     const hipStream_t hs = static_cast<hipStream_t>(stream);
     ChainDev<T> d = chain_dev<T>(p, t, r.slot);
+    if (!gravity)
+        for (int i = 0; i < 6; i++) d.a_root[i] = T(0);
     void *scratch = nullptr;
     if (r.path == ROUTE_GEN1) {  // single-cluster programs: the fused, slab-free kernel (chain_kernels.hip, aba_gen1_kernel)
         gen1_only(d);
@@ -718,7 +720,7 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const 
 
 template <class T>
 int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const T *q, const T *qd, const T *ydd, T *tau, size_t B, int device,
-                   void *stream)
+                   void *stream, bool gravity = true)
 {
     const HostPlan &h = p->host;
     const RneaChainProgram &rp = h.rchain[r.slot];
@@ -726,6 +728,8 @@ int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, c
     const size_t in_rows = static_cast<size_t>(h.nq + 2 * h.nv);
     const hipStream_t hs = static_cast<hipStream_t>(stream);
     RneaChainDev<T> d = rnea_chain_dev<T>(p, t, r.slot);
+    if (!gravity)
+        for (int i = 0; i < 6; i++) d.a_root[i] = T(0);
     void *scratch = nullptr;
     if (r.path == ROUTE_LM) {  // (chain_kernels.hip, rnea_chain_lm_kernel)
         if (rp.diffs.empty()) d.diffs = nullptr;  // (fp32 programs only)
@@ -763,9 +767,11 @@ int projection_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, cons
 int projection_run_f32_through_f64(const grbda_plan *p, bool rnea, const float *q, const float *qd, const float *x, const float *f_ext, float *out,
                                    size_t B, int device, void *stream);
 
+// gravity = false: the same dynamics with a_root = 0, for callers that difference two runs and want no gravity in either (the unit-wrench
+// route of the inverse OSIM).  The spanning-tree route keeps the plan's gravity: its sub-plan's launches are not reached from here.
 template <class T>
 int run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, const T *f_ext, T *out, size_t B,
-        int device, void *stream)
+        int device, void *stream, bool gravity = true)
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
@@ -785,9 +791,12 @@ int run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, con
     // chain-structured fast path (chain_kernels.hip) of models the chain programs cover
     const Route r = rnea ? choose_rnea<T>(p, t->n_cu, B, f_ext != nullptr) : choose_aba<T>(p, t->n_cu, B, f_ext != nullptr);
     if (r.path != ROUTE_INTERPRETER)
-        return rnea ? run_rnea_chain<T>(p, *t, r, q, qd, x, out, B, device, stream) : run_chain<T>(p, *t, r, q, qd, x, out, B, device, stream);
+        return rnea ? run_rnea_chain<T>(p, *t, r, q, qd, x, out, B, device, stream, gravity)
+                    : run_chain<T>(p, *t, r, q, qd, x, out, B, device, stream, gravity);
     DevPlan<T> d = make_dev_plan<T>(p, *t, rnea, f_ext != nullptr);
     d.fext = f_ext;
+    if (!gravity)
+        for (int i = 0; i < 6; i++) d.a_root[i] = T(0);
     const int kid = (rnea ? 2 : 0) + (sizeof(T) == 8 ? 1 : 0);
     const LaunchShape s = launch_shape(t->n_cu, (B + kWave - 1) / kWave, static_cast<size_t>(kid == 1 ? p->opt.waves_per_cu_f64_wide_regs : p->opt.waves_per_cu[kid]),
                                        static_cast<size_t>(d.n_lds_slots) * kWave * sizeof(T), d.nq, d.nv, sizeof(T),
@@ -1697,8 +1706,11 @@ int inv_osim_unit(const grbda_plan *p, const DeviceTables &t, const ContactSet<T
     hipLaunchKernelGGL((osim_expand_kernel<T>), dim3(blocks_for(nrows)), dim3(256), 0, hs, cs, q, Xa, static_cast<int>(nq), static_cast<int>(nbod), nb,
                        qx, fext);
     if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "expand launch");
+    // (without gravity: the rows are differenced against the row that has no wrench, and gravity in both would cancel only up to rounding
+    // -- the inverse OSIM, and the contact impulse built on it, then differ between two gravities, 8.5e-5 of 10 in fp32)
     int rc;
-    if ((rc = run<T>(p, false, qx, zero, zero, fext, acc, nrows, device, stream)) || (rc = run<T>(p, true, qx, zero, zero, fext, tau, nrows, device, stream)))
+    if ((rc = run<T>(p, false, qx, zero, zero, fext, acc, nrows, device, stream, false)) ||
+        (rc = run<T>(p, true, qx, zero, zero, fext, tau, nrows, device, stream, false)))
         return rc;
     hipLaunchKernelGGL((osim_combine_kernel<T>), dim3(blocks_for(nb * m * m)), dim3(256), 0, hs, acc, tau, static_cast<int>(nv), static_cast<int>(m), nb,
                        Linv, J);

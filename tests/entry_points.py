@@ -3,11 +3,11 @@ x batch x entry point), and what makes their models, states and inputs.  A plain
 test_buffer_edges_gpu.py, test_batch_ladder_gpu.py and test_concurrent_streams_gpu.py all go through it, so an entry point added to the
 library is covered by every one of them with one more row here.  Covered: forward / inverse dynamics (with and without f_ext), bias force,
 mass matrix, the forward-dynamics derivatives, body poses and twists, applyTestForce, the inverse OSIM, the projection, the state
-conversion, the spanning rates, the inverse-dynamics derivatives, integrate / step / rollout, contact points and contact dynamics, energy,
-the centroidal quantities and the momentum matrix.
+conversion, the spanning rates, the inverse-dynamics derivatives, integrate / step / rollout, contact points, contact dynamics and contact
+impulses, energy, the centroidal quantities and the momentum matrix.
 
 call(plan, x) returns a tuple of output tensors whose leading dimension is the batch, x holding the device tensors "q", "qd", "tau",
-"fext", "force", "q_start", "q_proj", "a_des", "tau_T"; check(blob, s, outs, tol) compares the numpy outputs `outs` of the states `s` (a
+"fext", "force", "q_start", "q_proj", "a_des", "tau_T", "v_des"; check(blob, s, outs, tol) compares the numpy outputs `outs` of the states `s` (a
 dict of numpy inputs) with the oracle, or with a numpy reference the CPU suite pins to the oracle.  The checkers of the later rows print
 what they measured (HELD model type what: error of bound).  TYPED is the table by number type: the rows of CASES in fp64 and fp32 less
 NOT_RUN, and what every one of the four files is parametrised over."""
@@ -256,7 +256,7 @@ def _project(plan, x):
 
 
 # ---- the entry points added after the table: inverse-dynamics derivatives, time stepping, contacts, centroidal quantities -------------
-# Their checkers reuse references the CPU suite pins to the oracle (id_derivative_refs, integrate_ref, contact_ref, centroidal_ref); those
+# Their checkers reuse references the CPU suite pins to the oracle (id_derivative_refs, integrate_ref, contact_ref, impulse_ref, centroidal_ref); those
 # modules import this one, so they are imported where they are used.
 T_ROLL = 3  # steps of the rollout row
 # the contact set of a model's contact rows (contact_ref.SETS); every other model: one point, OFFSET, on its last link
@@ -303,10 +303,12 @@ def _id_derivs(plan, x):
     return tuple(plan.id_derivatives(x["q"], x["qd"], x["tau"]).values())  # (dq, dqd, dydd; the table feeds tau as ydd)
 
 
-def _chk_id_derivs(blob, s, o, tol):
+def _chk_id_derivs(blob, s, o, tol, ref=None):
+    """ref: id_derivative_refs.oracle_refs of the states, where the caller has them already (test_gravity_gpu.py: one evaluation for
+    both precisions)"""
     from id_derivative_refs import oracle_refs
 
-    ref = oracle_refs(blob, {"q": s["q"], "qd": s["qd"], "ydd": s["tau"]})
+    ref = ref or oracle_refs(blob, {"q": s["q"], "qd": s["qd"], "ydd": s["tau"]})
     for k, got, floor in (("dydd", o[2], 1e-9), ("dqd", o[1], 1e-8), ("dq", o[0], 2e-5)):  # the bounds of test_id_derivatives_gpu.py
         _held(blob, tol, "id_derivatives " + k, _rel(got, ref[k]), max(tol, floor))
 
@@ -440,6 +442,33 @@ def _chk_contact_dynamics(blob, s, o, tol, damped=False):
         _held(blob, tol, "contact_dynamics " + what, C.rel_per_state(got, ref[key]).max(), tol)
 
 
+RESTITUTION = 0.25  # of the contact_impulse rows
+
+
+def _contact_impulse(plan, x):
+    return plan.contact_impulse(x["q"], x["qd"], *_contacts(plan.blob), v_des=x["v_des"], restitution=RESTITUTION)
+
+
+def _chk_contact_impulse(blob, s, o, tol):
+    """qd_next and impulse against impulse_ref, every state on its own scale: fp64 at TOL64; fp32 by the rule of
+    test_impulse_gpu.py::test_contact_impulse_fp32 -- TOL32, or that file's MARGINS32 for the contact set where it lists one -- with the
+    closed form carried out in float32 (that file's yardstick) printed beside each figure"""
+    import contact_ref as C
+    import impulse_ref as I
+
+    ref = I.contact_impulse(blob, s["q"], s["qd"], *_contacts(blob), s["v_des"], RESTITUTION, 0.0)
+    bound, yard = tol, None
+    if tol > 1e-6:
+        from test_impulse_gpu import MARGINS32
+
+        bound = MARGINS32.get(CONTACT_SETS.get(_name(blob)), (tol,))[0]
+        yard = I.contact_impulse_in(np.float32, ref, s["qd"], s["v_des"], RESTITUTION, 0.0)
+    for i, (what, key) in enumerate((("qd_next", "qd_next"), ("impulse", "impulse"))):
+        assert np.isfinite(o[i]).all(), f"contact_impulse {what}: not finite"
+        note = "" if yard is None else f" (the closed form in float32: {C.rel_per_state(yard[i].astype(np.float64), ref[key]).max():.2e})"
+        _held(blob, tol, f"contact_impulse {what}{note}", C.rel_per_state(o[i], ref[key]).max(), bound)
+
+
 def _hold_centroidal(blob, s, tol, entry, names, outs, ydd):
     import centroidal_ref as C
 
@@ -490,6 +519,7 @@ ENTRY = {
     "contact_points": (_contact_points, _chk_contact_points),
     "contact_dynamics": (_contact_dynamics, _chk_contact_dynamics),
     "contact_dynamics_damped_fext": (lambda p, x: _contact_dynamics(p, x, True), lambda b, s, o, t: _chk_contact_dynamics(b, s, o, t, True)),
+    "contact_impulse": (_contact_impulse, _chk_contact_impulse),
     "energy": (lambda p, x: p.energy(x["q"], x["qd"]), _chk_energy),
     "centroidal": (lambda p, x: tuple(p.centroidal(x["q"], x["qd"], x["tau"]).values()), _chk_centroidal),
     "centroidal_matrix": (lambda p, x: (p.centroidal_matrix(x["q"]),), _chk_centroidal_matrix),
@@ -526,6 +556,9 @@ for _ep in ("energy", "centroidal"):
     CASES += [("explicit", "urdf_mit_humanoid", {}, 300, _ep), ("implicit", "tello_with_arms", {}, 300, _ep),
               ("spanning_tree", "parallel_chain_exp_d10_l16", {}, 300, _ep)]
 CASES += [("explicit", "urdf_mit_humanoid", {}, 300, "centroidal_matrix"), ("implicit", "tello_with_arms", {}, 300, "centroidal_matrix")]
+# contact impulses on the contact sets of the contact_dynamics rows: both routes of the inverse OSIM on the Mini Cheetah, implicit clusters
+CASES += [("efpa", "urdf_mini_cheetah", {}, 300, "contact_impulse"), ("feet", "tello_with_arms", {}, 300, "contact_impulse"),
+          ("no_efpa", "urdf_mini_cheetah", {"GRBDA_NO_EFPA": "1"}, 300, "contact_impulse")]
 IDS = [f"{ep}-{route}-{model}-B{B}" for route, model, env, B, ep in CASES]
 assert len(set(IDS)) == len(IDS)
 # (entry point, model, type) that no file runs, with the reason
@@ -554,6 +587,8 @@ def _host_inputs(blob, n_bodies, B, seed, dtype, max_cond=None):
     rng2 = np.random.default_rng([seed, 20250])
     s["a_des"] = rng2.uniform(-1, 1, (B, len(_contacts(blob)[0]), 3))
     s["tau_T"] = tau[:, None, :] * rng2.uniform(0.4, 1.0, (B, T_ROLL, 1))
+    # v_des: one velocity per contact for contact_impulse, after every key above and from a generator of its own again
+    s["v_des"] = np.random.default_rng([seed, 20251]).uniform(-1, 1, (B, len(_contacts(blob)[0]), 3))
     s = {k: np.asarray(torch.as_tensor(v, dtype=dtype).double()) for k, v in s.items()}
     return s
 

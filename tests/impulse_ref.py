@@ -5,7 +5,9 @@ entry_points._mass_oracle and oracle_py.
 With J_w [3 n, nv] the world-frame Jacobian of the points, v- = J_w qd, H the joint-space inertia, e the restitution, mu the damping:
     (J_w H^-1 J_w^T + mu I) Lambda = v_des - (1 + e) v-
     qd_next = qd + H^-1 J_w^T Lambda
-so that J_w qd_next = v_des - e v- - mu Lambda.  Gravity and tau do not enter."""
+so that J_w qd_next = v_des - e v- - mu Lambda.  Gravity and tau do not enter: H is taken from the description with its gravity set to
+zero (entry_points._mass_oracle subtracts two inverse dynamics that both hold gravity, which moves H by some 1e-14 with it), so the
+arrays returned are the same bit for bit at every gravity (test_contact_refs_gravity_cpu.py)."""
 import functools
 
 import numpy as np
@@ -14,13 +16,22 @@ import contact_ref as C
 import entry_points as EP
 
 
+def without_gravity(blob):
+    """the description with its gravity (six doubles at byte 48, as kinematics_ref._parse reads them) set to zero"""
+    out = bytes(blob[:48]) + bytes(48) + bytes(blob[96:])
+    assert len(out) == len(blob) and not C.K._parse(out)["grav"].any()
+    if EP._big(blob):
+        EP._BIG.add(out)
+    return out
+
+
 def contact_impulse(blob, q, qd, bodies, offsets, v_des=None, e=0.0, mu=0.0):
     """dict: qd_next [B, nv], impulse [B, n, 3], A [B, 3 n, 3 n] = J_w H^-1 J_w^T + mu I, Jw, Hinv, H, v_minus [B, n, 3] -- by dense
     numpy.linalg.solve in float64"""
     q, qd = (np.ascontiguousarray(a, dtype=np.float64) for a in (q, qd))
     B, n = q.shape[0], len(bodies)
     Jw = C.world_jacobian(blob, q, bodies, offsets)
-    H = EP._mass_oracle(blob, q)
+    H = EP._mass_oracle(without_gravity(blob), q)
     Hinv = np.linalg.inv(H)
     A = np.einsum("bij,bjk,blk->bil", Jw, Hinv, Jw) + mu * np.eye(3 * n)[None]
     v_minus = np.einsum("bij,bj->bi", Jw, qd)

@@ -2,7 +2,11 @@
 twenty kernel sites read, and the spanning-tree plan gets it by copy; the other GPU tests run at the gravity their model was built with.
 Here every entry point that reads gravity is held against the oracle at four gravities -- the oracle is fed plan.blob after set_gravity --,
 every entry point that must not read it gives the same bits at two, and a plan that has launched before (device tables cached) follows
-set_gravity on its next call.  Each test builds its own plans: the plans of entry_points.plan_for are shared and keep their gravity."""
+set_gravity on its next call.  The later entry points -- contact dynamics, step / rollout, the inverse-dynamics derivatives, energy and the
+centroidal quantities -- are held the same way with the checkers and bounds of entry_points.py; three of their kernels get the gravity as
+a host-side triple of its own, added back in world axes to what the twists carry as -g in body axes.  contact_points and contact_impulse,
+where gravity cancels, are held to their references at every gravity all the same: an error in the added g shows there at full size.
+Each test builds its own plans: the plans of entry_points.plan_for are shared and keep their gravity."""
 import functools
 
 import numpy as np
@@ -48,6 +52,7 @@ DERIVATIVE_ROUTES = [
     ("manifold", "urdf_four_bar", {}),
 ]
 SPANNING_TREE = ("two_parent", "parallel_chain_exp_d10_l16")
+N_CONTACTS = {"urdf_mini_cheetah": 4, "tello_with_arms": 2, "urdf_mit_humanoid": 8}  # of entry_points.CONTACT_SETS; every other model: 1
 # fp32 forward dynamics on the spanning-tree route against the float oracle, by gravity: (margin = 2 x the measured ratio, the measured
 # ratio: the larger of worst state and median).  Cause: the route factorises the dense mass matrix of the spanning tree and projects onto
 # the constraint; the float oracle runs the cluster recursion on fewer coordinates.  test_term_checker_cpu.py: a term wrong by 1 % still
@@ -66,7 +71,20 @@ def own_plan(model, env, gravity=None):
     assert plan.get_gravity() == list(TS.native_gravity(EP._model(model)) if gravity is None else gravity)
     if EP._big(EP._model(model)):
         EP._BIG.add(blob)  # (the oracle with room for the big clusters)
+    register(model, blob)
     return plan, blob
+
+
+def register(model, blob):
+    """entry_points._contacts and _dt go by the name a blob was made under, and a blob after set_gravity is another blob: without its
+    name a contact row falls back to one point on the last link, and a stepping row to the default time step"""
+    EP._NAMES.setdefault(bytes(blob), model)
+    assert EP._name(blob) == model
+    assert EP._dt(blob) == EP._dt(EP._model(model))
+    bodies, offsets = EP._contacts(blob)
+    assert (list(bodies), [tuple(o) for o in offsets]) == (list(EP._contacts(EP._model(model))[0]), [tuple(o) for o in EP._contacts(EP._model(model))[1]])
+    if model in N_CONTACTS:
+        assert len(bodies) == N_CONTACTS[model], f"{model}: {len(bodies)} contacts"
 
 
 def inputs(model, plan, dtype, gpu, max_cond=None):
@@ -185,9 +203,105 @@ def test_bodies_at_rest_accelerate_against_gravity(model, gname, gpu):
         assert np.abs(V[:, :, 9:12] - want).max() < tol * (1 + np.abs(g).max())
 
 
+# ---- the later entry points: (route, model, plan-time switches, entry point), the rows of entry_points.CASES ---------------------------
+# (the four-bar's draw at SEED: test_entry_draws_cpu.py holds the table's condition on it -- the reference step accepts at least 95 % of
+# the states at dt = 0.05 -- at every gravity of this file; measured 100 %)
+LATER = [
+    ("efpa", "urdf_mini_cheetah", {}, "contact_dynamics"), ("no_efpa", "urdf_mini_cheetah", {"GRBDA_NO_EFPA": "1"}, "contact_dynamics"),
+    ("feet", "tello_with_arms", {}, "contact_dynamics"), ("soles", "urdf_mit_humanoid", {}, "contact_dynamics_damped_fext"),
+    ("explicit", "urdf_mini_cheetah", {}, "step"), ("interpreter", "urdf_mini_cheetah", {}, "step_fext"), ("newton", "urdf_four_bar", {}, "step"),
+    ("explicit", "urdf_mini_cheetah", {}, "rollout"),
+    ("analytic", "urdf_mini_cheetah", {}, "id_derivatives"), ("manifold", "urdf_four_bar", {}, "id_derivatives"),
+    ("differences", "urdf_mini_cheetah", {"GRBDA_NO_ANALYTIC": "1"}, "id_derivatives"),
+]
+LATER += [(r, m, {}, e) for e in ("energy", "centroidal") for r, m in (("explicit", "urdf_mit_humanoid"), ("implicit", "tello_with_arms"),
+                                                                      ("spanning_tree", "parallel_chain_exp_d10_l16"))]
+# where gravity cancels: contact_points adds g to twists that carry -g; contact_impulse subtracts two forward dynamics that both hold it
+CANCELS = [("feet", "urdf_mini_cheetah", {}, "contact_points"), ("feet", "tello_with_arms", {}, "contact_points"),
+           ("spanning_tree", "parallel_chain_exp_d10_l16", {}, "contact_points"),
+           ("efpa", "urdf_mini_cheetah", {}, "contact_impulse"), ("feet", "tello_with_arms", {}, "contact_impulse"),
+           ("no_efpa", "urdf_mini_cheetah", {"GRBDA_NO_EFPA": "1"}, "contact_impulse")]
+assert all((r, m, env, B, e) in EP.CASES for r, m, env, e in LATER + CANCELS if r != "differences")
+# (No fp32 row needs an allowance against the float32 run of its reference: measured on the MI355X, every row below holds TOL32 -- and the
+# 16-eps / 32-eps bounds of the stepping rows -- at all four gravities.)
+
+
+@functools.lru_cache(maxsize=2)
+def id_derivative_references(blob, model, max_cond):
+    """id_derivative_refs.oracle_refs at the fp32-rounded states: one evaluation per (model, gravity) for both precisions"""
+    import torch
+
+    from id_derivative_refs import oracle_refs
+
+    s = EP._host_inputs(EP._model(model), n_bodies_of(blob), B, SEED, torch.float32, max_cond)
+    return oracle_refs(blob, {"q": s["q"], "qd": s["qd"], "ydd": s["tau"]})
+
+
+def hold(route, model, env, entry, gname, gpu):
+    """the row's outputs at gravity `gname`, fp64 and fp32 (less entry_points.NOT_RUN), through the table's checker on plan.blob"""
+    import torch
+
+    plan, blob = own_plan(model, env, GRAVITIES[gname])
+    if entry == "id_derivatives" and model == "urdf_mini_cheetah":
+        assert plan.info().analytic_derivatives == (0 if route == "differences" else 1)
+    bound, got = EP.draw_bound(entry), {}
+    for dtype, tol in dtypes():
+        if (entry, model, "f64" if dtype == torch.float64 else "f32") in EP.NOT_RUN:
+            continue
+        if entry == "id_derivatives":  # (both precisions get the fp32-rounded states, as test_derivatives_follow_gravity's do)
+            s, x = inputs(model, plan, torch.float32, gpu, bound)
+            o = outputs(plan, entry, {k: v.to(dtype) for k, v in x.items()})
+            EP._chk_id_derivs(blob, s, o, tol, id_derivative_references(blob, model, bound))
+        else:
+            s, x = inputs(model, plan, dtype, gpu, bound)
+            o = outputs(plan, entry, x)
+            ENTRY[entry][1](blob, s, o, tol)
+        got[dtype] = o
+    return got
+
+
+@pytest.mark.parametrize("gname", list(GRAVITIES))
+@pytest.mark.parametrize("route,model,env,entry", LATER + CANCELS, ids=[f"{e}-{r}-{m}" for r, m, _, e in LATER + CANCELS])
+def test_later_entry_points_follow_gravity(route, model, env, entry, gname, gpu):
+    """contact dynamics, step / rollout, the inverse-dynamics derivatives, energy and the centroidal quantities against their references
+    on plan.blob at four gravities, by the checkers and bounds of entry_points.py (HELD lines: error of bound); contact points and contact
+    impulses, which gravity must leave alone, the same way"""
+    hold(route, model, env, entry, gname, gpu)
+
+
+@pytest.mark.parametrize("route,model,env,entry", CANCELS, ids=[f"{e}-{r}-{m}" for r, m, _, e in CANCELS])
+def test_gravity_cancels_bit_for_bit_where_nothing_reads_it(route, model, env, entry, gpu):
+    """contact_points: position and velocity read no gravity -- the same bits at the native and the oblique one.  contact_impulse: poses,
+    twists' velocity halves, the inverse OSIM and the solve read none, so the impulse has the same bits; qd_next comes from y1 - y0 of two
+    forward dynamics that both hold gravity, and what that cancellation costs is printed (CANCELLATION ...), not bounded beyond the
+    checker's own bound (test_later_entry_points_follow_gravity).
+
+    Measured on the MI355X, max |qd_next(oblique) - qd_next(zero)|, fp64 / fp32: Mini Cheetah 2.3e-15 / 1.4e-6 of 34, tello_with_arms
+    2.2e-15 / 1.3e-6 of 66, Mini Cheetah under GRBDA_NO_EFPA 2.7e-15 / 1.4e-6 of 34 (5.7e-13 / 1.5e-4 before the change below).
+
+    The GRBDA_NO_EFPA row is what found that the unit-wrench route of the inverse OSIM (capi.cpp, inv_osim_unit) ran its 6 n + 1 rows of
+    forward and inverse dynamics at the plan's gravity and left the cancellation to the subtraction: the impulse then differed between the
+    native and the oblique gravity by 1.5e-13 of 10.4 in fp64 and 8.5e-5 of 10.4 in fp32.  Those rows now run without gravity."""
+    plans = {g: own_plan(model, env, GRAVITIES[g])[0] for g in ("native", "oblique", "zero")}
+    changed = []  # (asserted after both types have printed their figures)
+    for dtype, _ in dtypes():
+        _, x = inputs(model, plans["native"], dtype, gpu)
+        o = {g: outputs(p, entry, x) for g, p in plans.items()}
+        same = (0, 1) if entry == "contact_points" else (1,)
+        for i in same:
+            print(f"SAME BITS {entry} {route} {model} {dtype} output {i}: max |oblique - native| = {np.abs(o['oblique'][i] - o['native'][i]).max():.2e}"
+                  f" of max {np.abs(o['native'][i]).max():.2e}")
+        if entry == "contact_impulse":
+            print(f"CANCELLATION {entry} {route} {model} {dtype}: max |qd_next(oblique) - qd_next(zero)| = {np.abs(o['oblique'][0] - o['zero'][0]).max():.2e}"
+                  f" of max |qd_next| = {np.abs(o['zero'][0]).max():.2e}")
+        changed += [f"{entry} {dtype}: output {i} changes with gravity" for i in same if not np.array_equal(o["native"][i], o["oblique"][i])]
+    assert not changed, changed
+
+
 BLIND = [("urdf_mini_cheetah", e) for e in ("mass_matrix", "fd_dtau", "inv_osim", "apply_test_force", "body_poses")] + \
         [("urdf_four_bar", e) for e in ("mass_matrix", "fd_dtau", "body_poses", "project_positions", "spanning")] + \
-        [("two_parent", "mass_matrix")]
+        [("two_parent", "mass_matrix")] + \
+        [("urdf_mini_cheetah", "integrate"), ("urdf_four_bar", "integrate"), ("urdf_mit_humanoid", "centroidal_matrix"), ("tello_with_arms", "centroidal_matrix")]
 
 
 @pytest.mark.parametrize("model,entry", BLIND, ids=[f"{e}-{m}" for m, e in BLIND])
@@ -205,8 +319,12 @@ def test_what_must_not_read_gravity_gives_the_same_bits(model, entry, gpu):
 ORDER = [("urdf_mini_cheetah", e) for e in ("aba", "aba_fext", "rnea", "rnea_fext", "bias", "fd_dq", "fd_dqd", "fd_derivatives", "body_twists",
                                             "mass_matrix", "fd_dtau", "inv_osim", "apply_test_force", "body_poses")] + \
         [("urdf_four_bar", e) for e in ("aba", "rnea", "fd_dq", "project_positions", "spanning")] + \
-        [("two_parent", e) for e in ("aba", "rnea", "fd_derivatives")]
-CHANGES = ("aba", "aba_fext", "rnea", "rnea_fext", "bias", "fd_dq", "body_twists")  # (where another gravity cannot give the same bits)
+        [("two_parent", e) for e in ("aba", "rnea", "fd_derivatives")] + \
+        [("urdf_mini_cheetah", e) for e in ("contact_dynamics", "contact_points", "step", "id_derivatives", "energy", "centroidal")] + \
+        [("parallel_chain_exp_d10_l16", e) for e in ("contact_points", "centroidal")]  # (the sub-plan the first launch made follows too)
+# (where another gravity cannot give the same bits; contact_points and centroidal are not among them: the acceleration of a point and the
+# rate of the momentum at a given ydd are kinematic, the gravity added at the end answers the -g the twists carry)
+CHANGES = ("aba", "aba_fext", "rnea", "rnea_fext", "bias", "fd_dq", "body_twists", "contact_dynamics", "step", "id_derivatives", "energy")
 
 
 @pytest.mark.parametrize("model,entry", ORDER, ids=[f"{e}-{m}" for m, e in ORDER])
@@ -221,9 +339,11 @@ def test_set_gravity_after_a_launch(model, entry, gpu):
         _, x = inputs(model, plan, dtype, gpu, EP.draw_bound(entry))
         first = outputs(plan, entry, x)
         plan.set_gravity(TS.OBLIQUE)
+        register(model, plan.blob)
         second = outputs(plan, entry, x)
         assert EP.same_bits_np(second, outputs(fresh, entry, x)), f"{entry} {dtype}: set_gravity after a launch is not a plan built at that gravity"
         if entry in CHANGES:
             assert not EP.same_bits_np(second, first), f"{entry} {dtype}: the oblique gravity changed nothing"
         plan.set_gravity(native)
+        register(model, plan.blob)
         assert EP.same_bits_np(outputs(plan, entry, x), first), f"{entry} {dtype}: the native gravity set again gives other bits"
