@@ -8,43 +8,17 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
-from typing import Optional
+from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
+from ._abi import SIGNATURES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
 LIB_PATH = os.environ.get("GRBDA_HIP_LIB") or os.path.join(_HERE, "libgrbda_hip.so")
 
 # every entry point include/grbda_hip.h declares
-C_ABI_SYMBOLS = [
-    "grbda_strerror", "grbda_last_error", "grbda_plan_from_blob", "grbda_plan_from_urdf", "grbda_urdf_to_blob",
-    "grbda_plan_free", "grbda_plan_release_work", "grbda_plan_dims", "grbda_plan_set_gravity", "grbda_plan_get_gravity", "grbda_plan_blob",
-    "grbda_plan_info", "grbda_aba_f64", "grbda_aba_f32", "grbda_rnea_f64", "grbda_rnea_f32",
-    "grbda_aba_host_f64", "grbda_rnea_host_f64", "grbda_time_kernel", "grbda_device_count",
-    "grbda_bias_f64", "grbda_bias_f32", "grbda_mass_matrix_f64", "grbda_mass_matrix_f32",
-    "grbda_fd_dtau_f64", "grbda_fd_dtau_f32", "grbda_fd_dqd_f64", "grbda_fd_dqd_f32",
-    "grbda_aba_sharded_f32", "grbda_aba_sharded_f64", "grbda_rnea_sharded_f32", "grbda_rnea_sharded_f64",
-    "grbda_aba_sharded_dev_f32", "grbda_aba_sharded_dev_f64", "grbda_rnea_sharded_dev_f32", "grbda_rnea_sharded_dev_f64",
-    "grbda_body_poses_host_f64", "grbda_apply_test_force_host_f64",
-    "grbda_inv_osim_host_f64", "grbda_fd_dq_f64", "grbda_fd_dq_f32", "grbda_body_poses_f64", "grbda_body_poses_f32",
-    "grbda_apply_test_force_f64", "grbda_apply_test_force_f32", "grbda_inv_osim_f64", "grbda_inv_osim_f32",
-    "grbda_contact_points_f64", "grbda_contact_points_f32", "grbda_contact_dynamics_f64", "grbda_contact_dynamics_f32",
-    "grbda_contact_points_host_f64", "grbda_contact_dynamics_host_f64",
-    "grbda_contact_impulse_f64", "grbda_contact_impulse_f32", "grbda_contact_impulse_host_f64",
-    "grbda_project_positions_f64", "grbda_project_positions_f32", "grbda_plan_span_dims",
-    "grbda_spanning_f64", "grbda_spanning_f32", "grbda_fd_derivatives_f64", "grbda_fd_derivatives_f32",
-    "grbda_mass_matrix_host_f64", "grbda_fd_derivatives_host_f64",
-    "grbda_body_twists_f64", "grbda_body_twists_f32", "grbda_body_twists_host_f64",
-    "grbda_state_input_dims", "grbda_state_to_independent_f64", "grbda_state_to_independent_f32",
-    "grbda_state_to_independent_host_f64", "grbda_spd_bad_pivots", "grbda_kernel_name", "grbda_contact_solve_launch", "grbda_project_positions_host_f64",
-    "grbda_rnea_derivatives_f64", "grbda_rnea_derivatives_f32", "grbda_rnea_derivatives_host_f64",
-    "grbda_integrate_f64", "grbda_integrate_f32", "grbda_step_f64", "grbda_step_f32", "grbda_rollout_f64", "grbda_rollout_f32",
-    "grbda_integrate_host_f64", "grbda_step_host_f64",
-    "grbda_plan_total_mass", "grbda_energy_f64", "grbda_energy_f32", "grbda_centroidal_f64", "grbda_centroidal_f32",
-    "grbda_centroidal_matrix_f64", "grbda_centroidal_matrix_f32", "grbda_energy_host_f64", "grbda_centroidal_host_f64",
-]
+C_ABI_SYMBOLS = list(SIGNATURES)
 
 
 class GrbdaError(RuntimeError):
@@ -84,97 +58,9 @@ def lib() -> ctypes.CDLL:
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    L.grbda_strerror.restype = c_char_p
-    L.grbda_strerror.argtypes = [c_int]
-    L.grbda_last_error.restype = c_char_p
-    L.grbda_plan_from_blob.argtypes = [c_void_p, c_size_t, POINTER(c_void_p)]
-    L.grbda_plan_from_urdf.argtypes = [c_char_p, c_int, POINTER(c_void_p)]
-    L.grbda_urdf_to_blob.argtypes = [POINTER(c_char_p), c_int, c_int, c_void_p, c_size_t, POINTER(c_size_t)]
-    L.grbda_plan_free.argtypes = [c_void_p]
-    L.grbda_plan_free.restype = None
-    L.grbda_plan_release_work.argtypes = [c_void_p, POINTER(ctypes.c_ulonglong)]
-    for name in ("grbda_aba_sharded_dev_f32", "grbda_aba_sharded_dev_f64", "grbda_rnea_sharded_dev_f32", "grbda_rnea_sharded_dev_f64"):
-        getattr(L, name).argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.grbda_plan_dims.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]
-    L.grbda_plan_set_gravity.argtypes = [c_void_p, POINTER(c_double)]
-    L.grbda_plan_get_gravity.argtypes = [c_void_p, POINTER(c_double)]
-    L.grbda_plan_blob.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]
-    L.grbda_plan_info.argtypes = [c_void_p, POINTER(PlanInfo)]
-    for name in ("grbda_aba_f64", "grbda_aba_f32", "grbda_rnea_f64", "grbda_rnea_f32"):
-        getattr(L, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                     c_void_p]
-    for name in ("grbda_aba_host_f64", "grbda_rnea_host_f64"):
-        getattr(L, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
-    L.grbda_time_kernel.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                    c_void_p, c_int, POINTER(c_float)]
-    L.grbda_device_count.restype = c_int
-    L.grbda_contact_solve_launch.argtypes = [c_int, c_int, c_int, POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_bias_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                                    c_void_p]
-        getattr(L, "grbda_mass_matrix_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_fd_dtau_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_fd_dqd_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                      c_int, c_void_p]
-    L.grbda_plan_span_dims.argtypes = [c_void_p, POINTER(c_int)]
-    for name in ("grbda_aba_sharded_f32", "grbda_aba_sharded_f64", "grbda_rnea_sharded_f32", "grbda_rnea_sharded_f64"):
-        getattr(L, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_body_poses_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_body_twists_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_inv_osim_" + sfx).argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double),
-                                                        c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_contact_points_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double),
-                                                              c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_contact_dynamics_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int),
-                                                                POINTER(c_double), c_void_p, c_double, c_void_p, c_void_p, c_void_p,
-                                                                c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_contact_impulse_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double), c_void_p,
-                                                               c_double, c_double, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_apply_test_force_" + sfx).argtypes = [c_void_p, c_void_p, c_int, POINTER(c_double), c_void_p,
-                                                                c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_fd_dq_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
-                                                     c_size_t, c_int, c_void_p]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_fd_derivatives_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                              c_void_p, c_size_t, c_int, c_void_p]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_rnea_derivatives_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
-                                                                c_void_p, c_size_t, c_int, c_void_p]
-    L.grbda_rnea_derivatives_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
-                                                  c_size_t, c_int]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_project_positions_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                                                 c_double, c_int, c_void_p]
-        getattr(L, "grbda_spanning_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                        c_size_t, c_int, c_void_p]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_integrate_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
-                                                         c_int, c_double, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_step_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
-                                                    c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_rollout_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_void_p,
-                                                       c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-    L.grbda_integrate_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int,
-                                           c_double, c_size_t, c_int]
-    L.grbda_step_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_size_t, c_int]
-    L.grbda_plan_total_mass.argtypes = [c_void_p, POINTER(c_double)]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_energy_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_centroidal_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                          c_size_t, c_int, c_void_p]
-        getattr(L, "grbda_centroidal_matrix_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-    L.grbda_energy_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
-    L.grbda_centroidal_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
-    L.grbda_state_input_dims.argtypes = [c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]
-    for sfx in ("f64", "f32"):
-        getattr(L, "grbda_state_to_independent_" + sfx).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                                    c_void_p, c_void_p, c_void_p, c_size_t, c_double, c_int,
-                                                                    c_void_p]
-    L.grbda_state_to_independent_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                      c_size_t, c_double, c_int]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
     return L
 
@@ -182,6 +68,11 @@ def lib() -> ctypes.CDLL:
 def _check(rc: int):
     if rc != 0:
         raise GrbdaError(rc, (lib().grbda_last_error() or b"").decode() or lib().grbda_strerror(rc).decode())
+
+
+def _suffix(dtype) -> str:
+    """the precision suffix of the entry points for a torch or numpy dtype"""
+    return "f32" if str(dtype).endswith("float32") else "f64"
 
 
 def urdf_to_blob(paths, ori_repr: str = "quaternion") -> bytes:
@@ -254,103 +145,164 @@ class Plan:
     def kernel_name(self, algo: str, dtype: str, B: int, device: int = 0) -> str:
         """The kernel forward ("aba") / inverse ("rnea") dynamics launch for B states in "f32" / "f64" (grbda_kernel_name)."""
         buf = ctypes.create_string_buffer(256)
-        _check(lib().grbda_kernel_name(self._h, 0 if algo == "aba" else 1, 32 if dtype == "f32" else 64, ctypes.c_size_t(B), int(device), buf, 256))
+        _check(lib().grbda_kernel_name(self._h, 0 if algo == "aba" else 1, 32 if dtype == "f32" else 64, B, device, buf, 256))
         return buf.value.decode()
 
-    # ---- batched dynamics on torch device tensors ------------------------------------------------
-    def _launch(self, which: str, q, qd, x, out=None, stream=None, f_ext=None):
+    # ---- the one path from torch device tensors to an entry point ----------------------------------
+    # A tensor is described as name -> (tensor or None, shape): `shape` is the per-state shape, an int or a tuple, the batch
+    # going in front of it -- or the whole shape with "B" where the batch stands.  Bad arguments raise by one rule:
+    #   not a HIP device tensor, or not float32 / float64       GrbdaError(-3): there is no CPU fallback
+    #   dtype or device differs between the tensors of a call   TypeError
+    #   a wrong shape; an `out` / in-place tensor with strides  ValueError naming the expected shapes
+    @staticmethod
+    def _full(shape, B):
+        shape = (shape,) if isinstance(shape, int) else tuple(shape)
+        return tuple(B if d == "B" else d for d in shape) if "B" in shape else (B,) + shape
+
+    def _state(self, q, **velocities):
+        """q[B, nq] and the [B, nv] tensors, by name"""
+        return dict(q=(q, self.nq), **{k: (t, self.nv) for k, t in velocities.items()})
+
+    def _f_ext(self, f_ext):
+        return f_ext, (self.n_bodies, 6)
+
+    def _checked(self, ins, fixed=None):
+        """Steps 1-3 of _call.  ins, fixed: name -> (tensor or None, shape); the first tensor is required and gives the batch B.
+        `fixed` are tensors the call writes to (a caller's `out`, an in-place argument): they are taken as they are, so they must be
+        contiguous.  Returns (B, dtype, device, the tensors by name)."""
         import torch
 
-        if q.dtype not in (torch.float32, torch.float64):
-            raise TypeError("q must be float32 or float64")
-        if not (q.is_cuda and qd.is_cuda and x.is_cuda):
-            raise GrbdaError(-3, "inputs must be HIP device tensors (there is no CPU fallback)")
-        B = q.shape[0]
-        if q.shape != (B, self.nq) or qd.shape != (B, self.nv) or x.shape != (B, self.nv):
-            raise ValueError(f"expected q[B,{self.nq}], qd[B,{self.nv}], x[B,{self.nv}]")
-        q, qd, x = q.contiguous(), qd.contiguous(), x.contiguous()
-        if qd.dtype != q.dtype or x.dtype != q.dtype:
-            raise TypeError("dtype mismatch")
-        if qd.device != q.device or x.device != q.device:
-            raise ValueError("q, qd and x must live on one device")
-        if out is None:
-            out = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
-        elif (out.shape != (B, self.nv) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous [B,{self.nv}] tensor of the inputs' dtype on the inputs' device")
-        fe = None
-        if f_ext is not None:
-            if f_ext.shape != (B, self.n_bodies, 6) or f_ext.dtype != q.dtype or not f_ext.is_cuda:
-                raise ValueError(f"f_ext must be a device tensor [B,{self.n_bodies},6] of the same dtype")
-            f_ext = f_ext.contiguous()
-            fe = f_ext.data_ptr()
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            # contiguous() temporaries and `out` are used on a caller-supplied stream: tell the caching allocator
-            for tns in (q, qd, x, out) + (() if f_ext is None else (f_ext,)):
-                tns.record_stream(s)
-        fn = getattr(lib(), f"grbda_{which}_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), x.data_ptr(), fe, out.data_ptr(), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        return out
+        spec = {**ins, **(fixed or {})}
+        tensors = [t for t, _ in spec.values()]
+        held = tensors[:1] + [t for t in tensors[1:] if t is not None]
+        for t in held:
+            if not getattr(t, "is_cuda", False) or t.dtype not in (torch.float32, torch.float64):
+                raise GrbdaError(-3, "every tensor must be a float32 / float64 HIP device tensor (there is no CPU fallback)")
+        if any(t.dtype != held[0].dtype or t.device != held[0].device for t in held):
+            raise TypeError("all tensors of one call must share dtype and device")
+        B = held[0].shape[0] if held[0].dim() else -1
+        for name, (t, shape) in spec.items():
+            if t is not None and (tuple(t.shape) != self._full(shape, B) or (name in (fixed or ()) and not t.is_contiguous())):
+                want = ", ".join(f"{k}[{','.join(str(d) for d in self._full(shp, 'B'))}]" for k, (_, shp) in spec.items())
+                raise ValueError(f"expected {want}" + (f", with {' and '.join(fixed)} contiguous" if fixed else ""))
+        return B, held[0].dtype, held[0].device, {k: t for k, (t, _) in spec.items()}
 
+    @staticmethod
+    def _contiguous(stream, device, tensors):
+        """Steps 4 and 6 of _call: (the call's stream -- the caller's, or else the device's current one --, the tensors contiguous).
+        The copy of a strided input is enqueued on that stream, ahead of the kernels that read it."""
+        import torch
+
+        if stream is None:
+            return torch.cuda.current_stream(device), {k: None if t is None else t.contiguous() for k, t in tensors.items()}
+        with torch.cuda.stream(stream):
+            return stream, {k: None if t is None else t.contiguous() for k, t in tensors.items()}
+
+    @staticmethod
+    def _hold(stream, *tensors):
+        """Step 7 of _call: on a caller's stream the caching allocator is told of every tensor the call holds -- the inputs as given,
+        their contiguous copies and the outputs, which were allocated on other streams"""
+        if stream is not None:
+            for t in tensors:
+                if t is not None:
+                    t.record_stream(stream)
+
+    def _dispatch(self, stem: str, dtype, *cargs):
+        """Steps 8-9 of _call: grbda_<stem>_<f32|f64>(plan, cargs...), checked"""
+        _check(getattr(lib(), f"grbda_{stem}_{_suffix(dtype)}")(self._h, *cargs))
+
+    def _call(self, stem, stream, ins, outs, args, tail=(), fixed=None, skip_empty=False):
+        """One entry-point call on device tensors:
+        1-3  _checked(ins, fixed): tensor kind, agreement, shapes
+        4, 6 _contiguous: the stream, and the inputs made contiguous on it
+        5    the outputs are allocated -- outs: name -> shape, or int / bool for int32 flags [B], or None for one that is not
+             wanted; a tensor of that name in `fixed` stands in for the output
+        7    _hold: record_stream when the stream is the caller's
+        8-9  grbda_<stem>_<f32|f64>(plan, *args, B, *tail, device, stream), checked: in `args` a str names a tensor, whose address
+             (NULL for None) goes there; everything else is passed as it is.  skip_empty: no call at all for B == 0
+        10   returns the outputs in the order of `outs`, flags asked for as bool converted on the call's stream"""
+        import torch
+
+        B, dtype, device, given = self._checked(ins, fixed)
+        s, t = self._contiguous(stream, device, given)
+        for name, shape in outs.items():
+            if t.get(name) is None:
+                t[name] = (None if shape is None else torch.empty((B,), dtype=torch.int32, device=device) if shape in (int, bool) else
+                           torch.empty(self._full(shape, B), dtype=dtype, device=device))
+        self._hold(stream, *given.values(), *t.values())
+        if not (skip_empty and B == 0):
+            ptr = lambda a: a if not isinstance(a, str) else None if t[a] is None else t[a].data_ptr()
+            self._dispatch(stem, dtype, *[ptr(a) for a in args], B, *tail, device.index or 0, s.cuda_stream)
+        if bool not in outs.values():
+            return tuple(t[name] for name in outs)
+        with torch.cuda.stream(s):
+            return tuple(t[name].bool() if shape is bool else t[name] for name, shape in outs.items())
+
+    @staticmethod
+    def _contacts(bodies, offsets):
+        """the contact set as the entry points take it: (n, bodies[n], offsets[n][3])"""
+        n = len(bodies)
+        if len(offsets) != n or any(len(o) != 3 for o in offsets):
+            raise ValueError("offsets must hold one (x, y, z) per body")
+        return n, (c_int * n)(*[int(b) for b in bodies]), (c_double * (3 * n))(*[float(x) for o in offsets for x in o])
+
+    # ---- batched dynamics on torch device tensors ------------------------------------------------
     def forward_dynamics(self, q, qd, tau, out=None, stream=None, f_ext=None):
         """Batched ClusterTreeModel::forwardDynamics (cluster ABA): returns ydd[B, nv].
         f_ext: optional [B, n_bodies, 6] world-frame spatial forces (TreeModel::setExternalForces)."""
-        return self._launch("aba", q, qd, tau, out, stream, f_ext)
+        return self._call("aba", stream, dict(self._state(q, qd=qd, tau=tau), f_ext=self._f_ext(f_ext)), dict(out=self.nv),
+                          ("q", "qd", "tau", "f_ext", "out"), fixed=dict(out=(out, self.nv)))[0]
 
     def inverse_dynamics(self, q, qd, ydd, out=None, stream=None, f_ext=None):
         """Batched ClusterTreeModel::inverseDynamics (cluster RNEA): returns tau[B, nv]."""
-        return self._launch("rnea", q, qd, ydd, out, stream, f_ext)
+        return self._call("rnea", stream, dict(self._state(q, qd=qd, ydd=ydd), f_ext=self._f_ext(f_ext)), dict(out=self.nv),
+                          ("q", "qd", "ydd", "f_ext", "out"), fixed=dict(out=(out, self.nv)))[0]
 
     # ---- quantities derived from the two recursions (include/grbda_hip.h) ---------------------------
-    @staticmethod
-    def _floating(*tensors):
-        """every tensor: float32 or float64, one dtype, one HIP device (no silent reinterpretation of other dtypes)"""
-        import torch
-
-        t0 = tensors[0]
-        if t0.dtype not in (torch.float32, torch.float64) or not t0.is_cuda:
-            raise GrbdaError(-3, "inputs must be float32/float64 HIP device tensors (there is no CPU fallback)")
-        for t in tensors[1:]:
-            if t.dtype != t0.dtype or t.device != t0.device:
-                raise TypeError("all tensors of one call must share dtype and device")
-
-    def _derived(self, name: str, q, others=(), matrix=True, stream=None, f_ext=None):
-        import torch
-
-        if not q.is_cuda or q.dtype not in (torch.float32, torch.float64):
-            raise GrbdaError(-3, "inputs must be float32/float64 HIP device tensors (there is no CPU fallback)")
-        B = q.shape[0]
-        if q.shape != (B, self.nq) or any(o.shape != (B, self.nv) or o.dtype != q.dtype or not o.is_cuda for o in others):
-            raise ValueError(f"expected q[B,{self.nq}] and [B,{self.nv}] tensors of one dtype on the device")
-        q = q.contiguous()
-        others = [o.contiguous() for o in others]
-        out = torch.empty((B, self.nv, self.nv) if matrix else (B, self.nv), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_{name}_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        args = [self._h, q.data_ptr()] + [o.data_ptr() for o in others]
-        if name == "bias":
-            if f_ext is not None and (f_ext.shape != (B, self.n_bodies, 6) or f_ext.dtype != q.dtype or not f_ext.is_cuda):
-                raise ValueError(f"f_ext must be a device tensor [B,{self.n_bodies},6] of the same dtype")
-            args.append(None if f_ext is None else f_ext.contiguous().data_ptr())
-        _check(fn(*args, out.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        return out
-
     def bias_force(self, q, qd, stream=None, f_ext=None):
         """Batched getBiasForceVector: C(q, qd) = RNEA(q, qd, 0), [B, nv]."""
-        return self._derived("bias", q, (qd,), matrix=False, stream=stream, f_ext=f_ext)
+        return self._call("bias", stream, dict(self._state(q, qd=qd), f_ext=self._f_ext(f_ext)), dict(out=self.nv),
+                          ("q", "qd", "f_ext", "out"))[0]
 
     def mass_matrix(self, q, stream=None):
         """Batched getMassMatrix: H(q), [B, nv, nv]."""
-        return self._derived("mass_matrix", q, stream=stream)
+        return self._call("mass_matrix", stream, self._state(q), dict(out=(self.nv, self.nv)), ("q", "out"))[0]
 
     def fd_dtau(self, q, stream=None):
         """d ydd / d tau = H(q)^-1 through the ABA, [B, nv, nv]."""
-        return self._derived("fd_dtau", q, stream=stream)
+        return self._call("fd_dtau", stream, self._state(q), dict(out=(self.nv, self.nv)), ("q", "out"))[0]
 
     def fd_dqd(self, q, qd, tau, stream=None):
         """d ydd / d qd of the forward dynamics, [B, nv, nv] (exact: the ABA is quadratic in qd)."""
-        return self._derived("fd_dqd", q, (qd, tau), stream=stream)
+        return self._call("fd_dqd", stream, self._state(q, qd=qd, tau=tau), dict(out=(self.nv, self.nv)), ("q", "qd", "tau", "out"))[0]
+
+    def fd_dq(self, q, qd, tau, step: float = 1e-6, stream=None):
+        """d ydd / d q along the reference's tangent step (testHelpers.hpp:50-112), [B, nv, nv].  Explicit models:
+        analytic (`step` unused).  Models with implicit loops: central differences, always taken
+        in fp64 (fp32 tensors are converted on the device), on the constraint manifold."""
+        return self._call("fd_dq", stream, self._state(q, qd=qd, tau=tau), dict(out=(self.nv, self.nv)),
+                          ("q", "qd", "tau", step, "out"))[0]
+
+    def fd_derivatives(self, q, qd, tau, want=("dq", "dqd", "dtau"), stream=None):
+        """d ydd / d q, d ydd / d qd, d ydd / d tau of the forward dynamics in one pass (grbda_fd_derivatives_*): a dict
+        of [B, nv, nv] tensors for the names in `want`.  Explicit models get the analytic recursion + one SPD solve per
+        state (deriv_kernels.hip); the others fall back to fd_dtau / fd_dqd / fd_dq."""
+        names = ("dq", "dqd", "dtau")
+        outs = self._call("fd_derivatives", stream, self._state(q, qd=qd, tau=tau),
+                          {k: (self.nv, self.nv) if k in want else None for k in names}, ("q", "qd", "tau") + names, skip_empty=True)
+        return {k: o for k, o in zip(names, outs) if o is not None}
+
+    def id_derivatives(self, q, qd, ydd, want=("dq", "dqd", "dydd"), step: float = 1e-6, stream=None):
+        """d tau / d q, d tau / d qd, d tau / d ydd (= H) of the inverse dynamics at (q, qd, ydd) (grbda_rnea_derivatives_*): a dict
+        of [B, nv, nv] tensors for the names in `want`, out[b, i, j] = d tau_i / d x_j, the columns of "dq" along the tangent step of
+        fd_dq.  Explicit models with nv <= 64: the analytic recursion alone, no forward dynamics and no solve (`step` unused); the
+        others: difference batches over the inverse dynamics, "dq" with `step`."""
+        names = ("dq", "dqd", "dydd")
+        if not any(k in want for k in names) or any(k not in names for k in want):
+            raise ValueError('want must name at least one of "dq", "dqd", "dydd" and nothing else')
+        outs = self._call("rnea_derivatives", stream, self._state(q, qd=qd, ydd=ydd),
+                          {k: (self.nv, self.nv) if k in want else None for k in names}, ("q", "qd", "ydd", step) + names, skip_empty=True)
+        return {k: o for k, o in zip(names, outs) if o is not None}
 
     # ---- steps either side of the path ------------------------------------------------------------
     @property
@@ -362,18 +314,7 @@ class Plan:
     def project_positions(self, q, max_iter: int = 50, tol: float = 1e-8, stream=None):
         """Newton projection of the dependent coordinates of implicit clusters onto phi(q) = 0, IN PLACE
         (GenericJoint.cpp:289-385).  Returns a bool tensor [B]: the state converged to |phi| < tol."""
-        import torch
-
-        if not q.is_cuda or q.dtype not in (torch.float32, torch.float64) or not q.is_contiguous():
-            raise GrbdaError(-3, "q must be a contiguous float32/float64 HIP device tensor (there is no CPU fallback)")
-        B = q.shape[0]
-        if q.shape != (B, self.nq):
-            raise ValueError(f"expected q[B,{self.nq}]")
-        ok = torch.empty((B,), dtype=torch.int32, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_project_positions_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), ok.data_ptr(), B, max_iter, tol, q.device.index or 0, c_void_p(s.cuda_stream)))
-        return ok.bool()
+        return self._call("project_positions", stream, {}, dict(ok=bool), ("q", "ok"), tail=(max_iter, tol), fixed=self._state(q))[0]
 
     @staticmethod
     def _flag_bytes(flags, n):
@@ -395,26 +336,12 @@ class Plan:
         """ClusterTreeModel::setState(ModelState) for a batch (ClusterJoint.cpp:22-71): per-cluster spanning or independent
         coordinates -> the engine's (q[B,nq], qd[B,nv]) plus status[B] (0 = valid; code + 256 * cluster otherwise) and,
         optionally, cond[B, 2] = (max |K_d^-1 K_i|, max |K_d|_F |K_d^-1|_F) over the implicit clusters."""
-        import torch
-
-        self._floating(*([q_in] if qd_in is None else [q_in, qd_in]))
-        B = q_in.shape[0]
         wq, wv = self.state_input_dims(pos_is_spanning, vel_is_spanning)
-        if q_in.shape != (B, wq) or (qd_in is not None and qd_in.shape != (B, wv)):
-            raise ValueError(f"expected q_in[B,{wq}], qd_in[B,{wv}]")
-        q_in = q_in.contiguous()
-        qd_in = None if qd_in is None else qd_in.contiguous()
-        q = torch.empty((B, self.nq), dtype=q_in.dtype, device=q_in.device)
-        qd = None if qd_in is None else torch.empty((B, self.nv), dtype=q_in.dtype, device=q_in.device)
-        status = torch.empty((B,), dtype=torch.int32, device=q_in.device)
-        gmax = torch.empty((B, 2), dtype=q_in.dtype, device=q_in.device) if want_gmax else None
-        s = torch.cuda.current_stream(q_in.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_state_to_independent_{'f32' if q_in.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, self._flag_bytes(pos_is_spanning, self.n_clusters), self._flag_bytes(vel_is_spanning, self.n_clusters),
-                  q_in.data_ptr(), None if qd_in is None else qd_in.data_ptr(), q.data_ptr(),
-                  None if qd is None else qd.data_ptr(), status.data_ptr(), None if gmax is None else gmax.data_ptr(), B, tol,
-                  q_in.device.index or 0, c_void_p(s.cuda_stream)))
-        return (q, qd, status, gmax) if want_gmax else (q, qd, status)
+        outs = self._call("state_to_independent", stream, dict(q_in=(q_in, wq), qd_in=(qd_in, wv)),
+                          dict(q=self.nq, qd=None if qd_in is None else self.nv, status=int, cond=2 if want_gmax else None),
+                          (self._flag_bytes(pos_is_spanning, self.n_clusters), self._flag_bytes(vel_is_spanning, self.n_clusters),
+                           "q_in", "qd_in", "q", "qd", "status", "cond"), tail=(tol,))
+        return outs if want_gmax else outs[:3]
 
     def constraint_gain(self, q, tol: float = 1e-8, stream=None):
         """(gmax[B], kcond[B], status[B]) of engine-coordinate positions q[B,nq]: max |K_d^-1 K_i| and max |K_d|_F |K_d^-1|_F
@@ -424,85 +351,25 @@ class Plan:
 
     def spanning(self, q, qd, ydd, stream=None):
         """qd_span = G yd and qdd_span = G ydd + g for every body joint: two tensors [B, n_span_vel]."""
-        import torch
-
-        self._floating(q, qd, ydd)
-
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq) or qd.shape != (B, self.nv) or ydd.shape != (B, self.nv):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}]")
-        q, qd, ydd = q.contiguous(), qd.contiguous(), ydd.contiguous()
         n = self.n_span_vel
-        v = torch.empty((B, n), dtype=q.dtype, device=q.device)
-        a = torch.empty((B, n), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_spanning_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), ydd.data_ptr(), v.data_ptr(), a.data_ptr(), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        return v, a
+        return self._call("spanning", stream, self._state(q, qd=qd, ydd=ydd), dict(v=n, a=n), ("q", "qd", "ydd", "v", "a"))
 
     # ---- time stepping (include/grbda_hip.h "time stepping") ---------------------------------------------
-    def _state_args(self, q, qd, x, what: str):
-        """q[B,nq], qd[B,nv], x[B,nv]: contiguous device tensors of one floating dtype on one device; returns B"""
-        self._floating(q, qd, x)
-        B = q.shape[0]
-        if q.shape != (B, self.nq) or qd.shape != (B, self.nv) or x.shape != (B, self.nv):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], {what}[B,{self.nv}]")
-        return B
-
     def integrate(self, q, qd, ydd, dt: float, out=None, max_iter: int = 50, tol: float = 1e-8, stream=None):
         """One semi-implicit Euler step on the configuration manifold (first order): yd' = yd + dt ydd, then the positions with yd'
         -- y + dt yd' for explicit clusters, the quaternion base by ori::integrateQuatImplicit, implicit clusters by
         q_span + dt G yd' and the Newton projection of project_positions.  Returns (q_next, qd_next, ok[B] bool).
         out: (q_next, qd_next) to write to; they may be q and qd themselves."""
-        import torch
-
-        B = self._state_args(q, qd, ydd, "ydd")
-        q, qd, ydd = q.contiguous(), qd.contiguous(), ydd.contiguous()
-        if out is None:
-            qn = torch.empty((B, self.nq), dtype=q.dtype, device=q.device)
-            vn = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
-        else:
-            qn, vn = out
-            for t, ref in ((qn, q), (vn, qd)):
-                if t.shape != ref.shape or t.dtype != q.dtype or t.device != q.device or not t.is_contiguous():
-                    raise ValueError("out must be contiguous (q_next[B,nq], qd_next[B,nv]) tensors of the inputs' dtype on the inputs' device")
-        ok = torch.empty((B,), dtype=torch.int32, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            for t in (q, qd, ydd, qn, vn, ok):
-                t.record_stream(s)
-        fn = getattr(lib(), f"grbda_integrate_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), ydd.data_ptr(), float(dt), qn.data_ptr(), vn.data_ptr(), ok.data_ptr(),
-                  int(max_iter), float(tol), B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
-            return qn, vn, ok.bool()
+        qn, vn = (None, None) if out is None else out
+        return self._call("integrate", stream, self._state(q, qd=qd, ydd=ydd), dict(q_next=self.nq, qd_next=self.nv, ok=bool),
+                          ("q", "qd", "ydd", float(dt), "q_next", "qd_next", "ok", int(max_iter), float(tol)),
+                          fixed=dict(q_next=(qn, self.nq), qd_next=(vn, self.nv)))
 
     def step(self, q, qd, tau, dt: float, f_ext=None, stream=None):
         """forward_dynamics followed by integrate on one stream (grbda_step_*): returns (q_next, qd_next, ydd, ok[B] bool)."""
-        import torch
-
-        B = self._state_args(q, qd, tau, "tau")
-        q, qd, tau = q.contiguous(), qd.contiguous(), tau.contiguous()
-        fe = None
-        if f_ext is not None:
-            if f_ext.shape != (B, self.n_bodies, 6) or f_ext.dtype != q.dtype or not f_ext.is_cuda:
-                raise ValueError(f"f_ext must be a device tensor [B,{self.n_bodies},6] of the same dtype")
-            f_ext = f_ext.contiguous()
-            fe = f_ext.data_ptr()
-        qn = torch.empty((B, self.nq), dtype=q.dtype, device=q.device)
-        vn = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
-        ydd = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
-        ok = torch.empty((B,), dtype=torch.int32, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            for t in (q, qd, tau, qn, vn, ydd, ok) + (() if f_ext is None else (f_ext,)):
-                t.record_stream(s)
-        fn = getattr(lib(), f"grbda_step_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), fe, float(dt), ydd.data_ptr(), qn.data_ptr(), vn.data_ptr(),
-                  ok.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
-            return qn, vn, ydd, ok.bool()
+        return self._call("step", stream, dict(self._state(q, qd=qd, tau=tau), f_ext=self._f_ext(f_ext)),
+                          dict(q_next=self.nq, qd_next=self.nv, ydd=self.nv, ok=bool),
+                          ("q", "qd", "tau", "f_ext", float(dt), "ydd", "q_next", "qd_next", "ok"))
 
     def rollout(self, q, qd, tau, dt: float, T: int, record: bool = False, stream=None):
         """T steps from (q, qd), which are left untouched (grbda_rollout_* on copies).  tau: [B, nv], held for all steps, or [T, B, nv].
@@ -512,169 +379,68 @@ class Plan:
 
         T = int(T)
         per_step = tau.dim() == 3
-        if per_step and tau.shape[0] != T:
-            raise ValueError(f"expected tau[B,{self.nv}] or tau[{T},B,{self.nv}]")
-        B = self._state_args(q, qd, tau[0] if per_step and T > 0 else (tau if not per_step else qd), "tau")
-        tau = tau.contiguous()
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        with torch.cuda.stream(s):
+        B, dtype, device, _ = self._checked(dict(self._state(q, qd=qd), tau=(tau, (T, "B", self.nv) if per_step else self.nv)))
+        s, t = self._contiguous(stream, device, dict(tau=tau))
+        self._hold(stream, q, qd, tau, t["tau"])
+        with torch.cuda.stream(s):  # (the copies are enqueued, and everything the steps write is allocated, on the call's stream)
             qT, vT = q.clone(memory_format=torch.contiguous_format), qd.clone(memory_format=torch.contiguous_format)
             work = torch.empty_like(vT)
-            ok = torch.ones((B,), dtype=torch.int32, device=q.device)
-            qt = torch.empty((T, B, self.nq), dtype=q.dtype, device=q.device) if record else None
-            vt = torch.empty((T, B, self.nv), dtype=q.dtype, device=q.device) if record else None
-        if stream is not None:
-            for t in (q, qd, tau):
-                t.record_stream(s)
-        fn = getattr(lib(), f"grbda_rollout_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, qT.data_ptr(), vT.data_ptr(), tau.data_ptr(), T if per_step else 1, float(dt), T, work.data_ptr(),
-                  None if qt is None else qt.data_ptr(), None if vt is None else vt.data_ptr(), ok.data_ptr(), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
+            ok = torch.ones((B,), dtype=torch.int32, device=device)
+            qt = torch.empty((T, B, self.nq), dtype=dtype, device=device) if record else None
+            vt = torch.empty((T, B, self.nv), dtype=dtype, device=device) if record else None
+            self._dispatch("rollout", dtype, qT.data_ptr(), vT.data_ptr(), t["tau"].data_ptr(), T if per_step else 1, float(dt), T,
+                           work.data_ptr(), None if qt is None else qt.data_ptr(), None if vt is None else vt.data_ptr(), ok.data_ptr(), B,
+                           device.index or 0, s.cuda_stream)
             return (qT, vT, ok.bool(), qt, vt) if record else (qT, vT, ok.bool())
 
     # ---- contact side ---------------------------------------------------------------------------------
     def body_poses(self, q, stream=None):
         """Absolute transforms world -> body (TreeNode::Xa_): [B, n_bodies, 12] = E (9, row-major) then r (3)."""
-        import torch
-
-        self._floating(q)
-
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq):
-            raise ValueError(f"expected a device tensor q[B,{self.nq}]")
-        q = q.contiguous()
-        out = torch.empty((B, self.n_bodies, 12), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_body_poses_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), out.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        return out
+        return self._call("body_poses", stream, self._state(q), dict(out=(self.n_bodies, 12)), ("q", "out"))[0]
 
     def body_twists(self, q, qd, ydd, stream=None):
         """Spatial velocity and acceleration of every body in its own coordinates (TreeNode::v_ / a_ after
         forwardAccelerationKinematics): [B, n_bodies, 12] = v (6) then a (6), each [angular; linear]; the acceleration
         carries the base's -gravity as in the reference."""
-        import torch
-
-        self._floating(q, qd, ydd)
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq) or qd.shape != (B, self.nv) or ydd.shape != (B, self.nv):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}]")
-        q, qd, ydd = q.contiguous(), qd.contiguous(), ydd.contiguous()
-        out = torch.empty((B, self.n_bodies, 12), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_body_twists_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), ydd.data_ptr(), out.data_ptr(), B, q.device.index or 0,
-                  c_void_p(s.cuda_stream)))
-        return out
+        return self._call("body_twists", stream, self._state(q, qd=qd, ydd=ydd), dict(out=(self.n_bodies, 12)),
+                          ("q", "qd", "ydd", "out"))[0]
 
     def apply_test_force(self, q, body: int, offset, force, stream=None):
         """Batched ClusterTreeModel::applyTestForce: world-frame force[B,3] at the body-fixed point `offset` of
         `body`; returns (lambda_inv[B], dstate[B,nv]) = (f^T J H^-1 J^T f, H^-1 J^T f)."""
-        import torch
-
-        self._floating(q, force)
-
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq) or force.shape != (B, 3) or force.dtype != q.dtype:
-            raise ValueError(f"expected device tensors q[B,{self.nq}], force[B,3] of one dtype")
-        q, force = q.contiguous(), force.contiguous()
-        lam = torch.empty((B,), dtype=q.dtype, device=q.device)
-        ds = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
         off = (c_double * 3)(*[float(x) for x in offset])
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_apply_test_force_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), body, off, force.data_ptr(), lam.data_ptr(), ds.data_ptr(), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        return lam, ds
+        return self._call("apply_test_force", stream, dict(self._state(q), force=(force, 3)), dict(lambda_inv=(), dstate=self.nv),
+                          ("q", body, off, "force", "lambda_inv", "dstate"))
 
     def inv_osim(self, q, bodies, offsets, with_jacobian: bool = False, stream=None):
         """Batched inverseOperationalSpaceInertiaMatrix for contact frames (body index, body-fixed offset):
         Linv[B, 6n, 6n] (and the frame Jacobians J[B, 6n, nv] when asked)."""
-        import torch
-
-        self._floating(q)
-
-        B, n = q.shape[0], len(bodies)
-        if not q.is_cuda or q.shape != (B, self.nq):
-            raise ValueError(f"expected a device tensor q[B,{self.nq}]")
-        q = q.contiguous()
-        Linv = torch.empty((B, 6 * n, 6 * n), dtype=q.dtype, device=q.device)
-        J = torch.empty((B, 6 * n, self.nv), dtype=q.dtype, device=q.device) if with_jacobian else None
-        bod = (c_int * n)(*[int(b) for b in bodies])
-        off = (c_double * (3 * n))(*[float(x) for o in offsets for x in o])
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_inv_osim_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), n, bod, off, Linv.data_ptr(), None if J is None else J.data_ptr(), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        return (Linv, J) if with_jacobian else Linv
-
-    def _contacts(self, bodies, offsets):
-        n = len(bodies)
-        if len(offsets) != n or any(len(o) != 3 for o in offsets):
-            raise ValueError("offsets must hold one (x, y, z) per body")
-        return n, (c_int * n)(*[int(b) for b in bodies]), (c_double * (3 * n))(*[float(x) for o in offsets for x in o])
+        c = self._contacts(bodies, offsets)
+        n = c[0]
+        outs = self._call("inv_osim", stream, self._state(q), dict(Linv=(6 * n, 6 * n), J=(6 * n, self.nv) if with_jacobian else None),
+                          ("q", *c, "Linv", "J"))
+        return outs if with_jacobian else outs[0]
 
     def contact_points(self, q, bodies, offsets, qd=None, ydd=None, stream=None):
         """World-frame position, velocity and classical acceleration of body-fixed points (grbda_contact_points_*): point offsets[c]
         (body coordinates) of body bodies[c].  Returns (pos, vel, acc), [B, n, 3] each; vel is None without qd, acc is None without qd
         and ydd."""
-        import torch
-
-        given = [t for t in (qd, ydd) if t is not None]
-        self._floating(q, *given)
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq) or any(t.shape != (B, self.nv) or t.dtype != q.dtype or t.device != q.device for t in given):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}] of one dtype")
-        n, bod, off = self._contacts(bodies, offsets)
-        q = q.contiguous()
-        qd = None if qd is None else qd.contiguous()
-        ydd = None if ydd is None else ydd.contiguous()
-        new = lambda: torch.empty((B, n, 3), dtype=q.dtype, device=q.device)
-        pos, vel, acc = new(), (None if qd is None else new()), (None if qd is None or ydd is None else new())
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            for t in (q, qd, ydd, pos, vel, acc):
-                if t is not None:
-                    t.record_stream(s)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        fn = getattr(lib(), f"grbda_contact_points_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), ptr(qd), ptr(ydd), n, bod, off, ptr(pos), ptr(vel), ptr(acc), B, q.device.index or 0,
-                  c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
-            return pos, vel, acc
+        c = self._contacts(bodies, offsets)
+        shape = (c[0], 3)
+        return self._call("contact_points", stream, self._state(q, qd=qd, ydd=ydd),
+                          dict(pos=shape, vel=None if qd is None else shape, acc=None if qd is None or ydd is None else shape),
+                          ("q", "qd", "ydd", *c, "pos", "vel", "acc"))
 
     def contact_dynamics(self, q, qd, tau, bodies, offsets, a_des=None, damping: float = 0.0, f_ext=None, stream=None):
         """Forward dynamics with the points offsets[c] of bodies[c] held to the world-frame accelerations a_des[B, n, 3] (None: zero)
         (grbda_contact_dynamics_*): (J_w H^-1 J_w^T + damping I) lambda = a_des - p_ddot(ydd_free).  Returns (ydd[B, nv], lambda[B, n, 3]
         -- world-frame forces on the bodies at the points --, ydd_free[B, nv]).  Redundant contacts need damping > 0; a state whose
         matrix is not positive definite gets NaN and is counted by spd_bad_pivots()."""
-        import torch
-
-        B = self._state_args(q, qd, tau, "tau")
-        n, bod, off = self._contacts(bodies, offsets)
-        q, qd, tau = q.contiguous(), qd.contiguous(), tau.contiguous()
-        if f_ext is not None:
-            if f_ext.shape != (B, self.n_bodies, 6) or f_ext.dtype != q.dtype or not f_ext.is_cuda:
-                raise ValueError(f"f_ext must be a device tensor [B,{self.n_bodies},6] of the same dtype")
-            f_ext = f_ext.contiguous()
-        if a_des is not None:
-            if a_des.shape != (B, n, 3) or a_des.dtype != q.dtype or not a_des.is_cuda:
-                raise ValueError(f"a_des must be a device tensor [B,{n},3] of the same dtype")
-            a_des = a_des.contiguous()
-        ydd = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
-        free = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
-        lam = torch.empty((B, n, 3), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            for t in (q, qd, tau, ydd, free, lam) + tuple(t for t in (f_ext, a_des) if t is not None):
-                t.record_stream(s)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        fn = getattr(lib(), f"grbda_contact_dynamics_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), ptr(f_ext), n, bod, off, ptr(a_des), float(damping), ydd.data_ptr(),
-                  lam.data_ptr(), free.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
-            return ydd, lam, free
+        c = self._contacts(bodies, offsets)
+        return self._call("contact_dynamics", stream,
+                          dict(self._state(q, qd=qd, tau=tau), f_ext=self._f_ext(f_ext), a_des=(a_des, (c[0], 3))),
+                          dict(ydd=self.nv, lam=(c[0], 3), ydd_free=self.nv),
+                          ("q", "qd", "tau", "f_ext", *c, "a_des", float(damping), "ydd", "lam", "ydd_free"))
 
     def contact_impulse(self, q, qd, bodies, offsets, v_des=None, restitution: float = 0.0, damping: float = 0.0, stream=None):
         """The instant the points offsets[c] of bodies[c] close (grbda_contact_impulse_*): (J_w H^-1 J_w^T + damping I) Lambda =
@@ -682,26 +448,10 @@ class Plan:
         (qd_next[B, nv], impulse[B, n, 3] -- world-frame impulses on the bodies at the points); the points then move at
         v_des - restitution J_w qd - damping impulse.  q does not change; gravity and tau do not enter.  Redundant contacts need
         damping > 0; a state whose matrix is not positive definite gets NaN and is counted by spd_bad_pivots()."""
-        import torch
-
-        B = self._state_args(q, qd, qd, "qd")
-        n, bod, off = self._contacts(bodies, offsets)
-        q, qd = q.contiguous(), qd.contiguous()
-        if v_des is not None:
-            if v_des.shape != (B, n, 3) or v_des.dtype != q.dtype or not v_des.is_cuda:
-                raise ValueError(f"v_des must be a device tensor [B,{n},3] of the same dtype")
-            v_des = v_des.contiguous()
-        qd_next = torch.empty((B, self.nv), dtype=q.dtype, device=q.device)
-        impulse = torch.empty((B, n, 3), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            for t in (q, qd, qd_next, impulse) + (() if v_des is None else (v_des,)):
-                t.record_stream(s)
-        fn = getattr(lib(), f"grbda_contact_impulse_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), n, bod, off, None if v_des is None else v_des.data_ptr(), float(restitution),
-                  float(damping), qd_next.data_ptr(), impulse.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
-            return qd_next, impulse
+        c = self._contacts(bodies, offsets)
+        return self._call("contact_impulse", stream, dict(self._state(q, qd=qd), v_des=(v_des, (c[0], 3))),
+                          dict(qd_next=self.nv, impulse=(c[0], 3)),
+                          ("q", "qd", *c, "v_des", float(restitution), float(damping), "qd_next", "impulse"))
 
     # ---- energy and centroidal quantities -----------------------------------------------------------
     def total_mass(self) -> float:
@@ -710,36 +460,10 @@ class Plan:
         _check(lib().grbda_plan_total_mass(self._h, byref(m)))
         return m.value
 
-    def _centroidal_call(self, name: str, q, qd, ydd, shapes, stream):
-        """one call of grbda_energy_* / grbda_centroidal_*: `shapes` maps every output to its per-state shape, or to None when it is
-        not asked for; returns the outputs in that order (None where not asked for)"""
-        import torch
-
-        given = [t for t in (qd, ydd) if t is not None]
-        self._floating(q, *given)
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq) or any(t.shape != (B, self.nv) or t.dtype != q.dtype or t.device != q.device for t in given):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}] of one dtype")
-        q = q.contiguous()
-        qd = None if qd is None else qd.contiguous()
-        ydd = None if ydd is None else ydd.contiguous()
-        outs = [None if shp is None else torch.empty((B,) + shp, dtype=q.dtype, device=q.device) for shp in shapes]
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            for t in [q, qd, ydd] + outs:
-                if t is not None:
-                    t.record_stream(s)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        fn = getattr(lib(), f"grbda_{name}_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        ins = (ptr(qd),) if name == "energy" else (ptr(qd), ptr(ydd))
-        _check(fn(self._h, q.data_ptr(), *ins, *[ptr(o) for o in outs], B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
-            return outs
-
     def energy(self, q, qd=None, stream=None):
         """(kinetic[B], potential[B]) (grbda_energy_*): 1/2 yd^T H yd, None without qd; -g . sum m_i c_i, zero at the world origin."""
-        kinetic, potential = self._centroidal_call("energy", q, qd, None, [None if qd is None else (), ()], stream)
-        return kinetic, potential
+        return self._call("energy", stream, self._state(q, qd=qd), dict(kinetic=None if qd is None else (), potential=()),
+                          ("q", "qd", "kinetic", "potential"))
 
     def centroidal(self, q, qd=None, ydd=None, want=("com", "com_vel", "h", "hdot"), stream=None):
         """Centre of mass, its velocity, the centroidal momentum and its rate (grbda_centroidal_*): a dict of the names in `want` --
@@ -751,106 +475,24 @@ class Plan:
             raise ValueError(f"want holds names out of {names}")
         default = tuple(want) == names
         need = {"com": (), "com_vel": (qd,), "h": (qd,), "hdot": (qd, ydd)}
-        shape = {"com": (3,), "com_vel": (3,), "h": (6,), "hdot": (6,)}
-        ask = [n in want and not (default and any(t is None for t in need[n])) for n in names]
-        outs = self._centroidal_call("centroidal", q, qd, ydd, [shape[n] if a else None for n, a in zip(names, ask)], stream)
-        return {n: o for n, o, a in zip(names, outs, ask) if a}
+        shape = {"com": 3, "com_vel": 3, "h": 6, "hdot": 6}
+        ask = {n: n in want and not (default and any(t is None for t in need[n])) for n in names}
+        outs = self._call("centroidal", stream, self._state(q, qd=qd, ydd=ydd), {n: shape[n] if ask[n] else None for n in names},
+                          ("q", "qd", "ydd") + names)
+        return {n: o for n, o in zip(names, outs) if ask[n]}
 
     def centroidal_matrix(self, q, stream=None):
         """The centroidal momentum matrix A[B, 6, nv], h = A(q) yd (grbda_centroidal_matrix_*)."""
-        import torch
-
-        self._floating(q)
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq):
-            raise ValueError(f"expected a device tensor q[B,{self.nq}]")
-        q = q.contiguous()
-        A = torch.empty((B, 6, self.nv), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        if stream is not None:
-            q.record_stream(s)
-            A.record_stream(s)
-        fn = getattr(lib(), f"grbda_centroidal_matrix_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), A.data_ptr(), B, q.device.index or 0, c_void_p(s.cuda_stream)))
-        with torch.cuda.stream(s):
-            return A
-
-    def fd_derivatives(self, q, qd, tau, want=("dq", "dqd", "dtau"), stream=None):
-        """d ydd / d q, d ydd / d qd, d ydd / d tau of the forward dynamics in one pass (grbda_fd_derivatives_*): a dict
-        of [B, nv, nv] tensors for the names in `want`.  Explicit models get the analytic recursion + one SPD solve per
-        state (deriv_kernels.hip); the others fall back to fd_dtau / fd_dqd / fd_dq."""
-        import torch
-
-        self._floating(q, qd, tau)
-        B = q.shape[0]
-        if q.shape != (B, self.nq) or qd.shape != (B, self.nv) or tau.shape != (B, self.nv):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], tau[B,{self.nv}]")
-        q, qd, tau = q.contiguous(), qd.contiguous(), tau.contiguous()
-        out = {k: torch.empty((B, self.nv, self.nv), dtype=q.dtype, device=q.device) for k in ("dq", "dqd", "dtau") if k in want}
-        if B == 0:
-            return out
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_fd_derivatives_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        ptr = lambda k: out[k].data_ptr() if k in out else None
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), ptr("dq"), ptr("dqd"), ptr("dtau"), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        return out
-
-    def id_derivatives(self, q, qd, ydd, want=("dq", "dqd", "dydd"), step: float = 1e-6, stream=None):
-        """d tau / d q, d tau / d qd, d tau / d ydd (= H) of the inverse dynamics at (q, qd, ydd) (grbda_rnea_derivatives_*): a dict
-        of [B, nv, nv] tensors for the names in `want`, out[b, i, j] = d tau_i / d x_j, the columns of "dq" along the tangent step of
-        fd_dq.  Explicit models with nv <= 64: the analytic recursion alone, no forward dynamics and no solve (`step` unused); the
-        others: difference batches over the inverse dynamics, "dq" with `step`."""
-        import torch
-
-        self._floating(q, qd, ydd)
-        B = q.shape[0]
-        if q.shape != (B, self.nq) or qd.shape != (B, self.nv) or ydd.shape != (B, self.nv):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], ydd[B,{self.nv}]")
-        names = [k for k in ("dq", "dqd", "dydd") if k in want]
-        if not names or any(k not in ("dq", "dqd", "dydd") for k in want):
-            raise ValueError('want must name at least one of "dq", "dqd", "dydd" and nothing else')
-        q, qd, ydd = q.contiguous(), qd.contiguous(), ydd.contiguous()
-        out = {k: torch.empty((B, self.nv, self.nv), dtype=q.dtype, device=q.device) for k in names}
-        if B == 0:
-            return out
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_rnea_derivatives_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        ptr = lambda k: out[k].data_ptr() if k in out else None
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), ydd.data_ptr(), step, ptr("dq"), ptr("dqd"), ptr("dydd"), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        return out
-
-    def fd_dq(self, q, qd, tau, step: float = 1e-6, stream=None):
-        """d ydd / d q along the reference's tangent step (testHelpers.hpp:50-112), [B, nv, nv].  Explicit models:
-        analytic (`step` unused).  Models with implicit loops: central differences, always taken
-        in fp64 (fp32 tensors are converted on the device), on the constraint manifold."""
-        import torch
-
-        self._floating(q, qd, tau)
-
-        B = q.shape[0]
-        if not q.is_cuda or q.shape != (B, self.nq) or qd.shape != (B, self.nv) or tau.shape != (B, self.nv):
-            raise ValueError(f"expected device tensors q[B,{self.nq}], qd[B,{self.nv}], tau[B,{self.nv}]")
-        q, qd, tau = q.contiguous(), qd.contiguous(), tau.contiguous()
-        out = torch.empty((B, self.nv, self.nv), dtype=q.dtype, device=q.device)
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
-        fn = getattr(lib(), f"grbda_fd_dq_{'f32' if q.dtype == torch.float32 else 'f64'}")
-        _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), step, out.data_ptr(), B,
-                  q.device.index or 0, c_void_p(s.cuda_stream)))
-        return out
+        return self._call("centroidal_matrix", stream, self._state(q), dict(A=(6, self.nv)), ("q", "A"))[0]
 
     def time_kernel(self, which: str, q, qd, x, out, iters: int = 20, stream=None) -> float:
         """Average kernel duration in ms, hipEvents on the launch stream (grbda_time_kernel)."""
-        import torch
-
-        self._floating(q, qd, x, out)
-
-        s = torch.cuda.current_stream(q.device) if stream is None else stream
+        B, dtype, device, given = self._checked(self._state(q, qd=qd, x=x), dict(out=(out, self.nv)))
+        s, t = self._contiguous(stream, device, given)
+        self._hold(stream, *given.values(), *t.values())
         ms = c_float(0)
-        _check(lib().grbda_time_kernel(self._h, 0 if which == "aba" else 1, 32 if q.dtype == torch.float32 else 64,
-                                       q.data_ptr(), qd.data_ptr(), x.data_ptr(), out.data_ptr(), q.shape[0],
-                                       q.device.index or 0, c_void_p(s.cuda_stream), iters, byref(ms)))
+        _check(lib().grbda_time_kernel(self._h, 0 if which == "aba" else 1, int(_suffix(dtype)[1:]), t["q"].data_ptr(), t["qd"].data_ptr(),
+                                       t["x"].data_ptr(), out.data_ptr(), B, device.index or 0, s.cuda_stream, iters, byref(ms)))
         return ms.value
 
     def sharded_device(self, which: str, qs, qds, xs, outs=None, gathered=None, streams=None):
@@ -863,63 +505,53 @@ class Plan:
         n = len(qs)
         if n < 1 or len(qds) != n or len(xs) != n:
             raise ValueError("one q, qd, x tensor per shard")
-        dt = qs[0].dtype
-        for g in range(n):
-            self._floating(qs[g], qds[g], xs[g])
-            if qs[g].dtype != dt or qs[g].shape[1:] != (self.nq,) or qds[g].shape != (qs[g].shape[0], self.nv) or xs[g].shape != qds[g].shape:
-                raise ValueError(f"shard {g}: expected q[B,{self.nq}], qd[B,{self.nv}], x[B,{self.nv}] of one dtype")
-        qs, qds, xs = [t.contiguous() for t in qs], [t.contiguous() for t in qds], [t.contiguous() for t in xs]
-        Bs = [int(t.shape[0]) for t in qs]
+        shards = [self._checked(self._state(qs[g], qd=qds[g], x=xs[g]), dict(out=(None if outs is None else outs[g], self.nv)))
+                  for g in range(n)]
+        Bs, dt, devices = [sh[0] for sh in shards], shards[0][1], [sh[2] for sh in shards]
+        if gathered is not None:
+            rows, gdt, gdev, _ = self._checked({}, dict(gathered=(gathered, self.nv)))
+            if rows != sum(Bs):
+                raise ValueError(f"expected gathered[{sum(Bs)},{self.nv}], contiguous")
+        if any(sh[1] != dt for sh in shards) or (gathered is not None and (gdt != dt or gdev != devices[0])):
+            raise TypeError("every shard, and gathered on the first shard's device, must have one dtype")
         if outs is None and gathered is None:
-            outs = [torch.empty((Bs[g], self.nv), dtype=dt, device=qs[g].device) for g in range(n)]
-        if gathered is not None and outs is None:
+            outs = [torch.empty((Bs[g], self.nv), dtype=dt, device=devices[g]) for g in range(n)]
+        elif outs is None:
             # shards on the gather device write straight into their place; the others need a slab of their own
-            outs = [None if qs[g].device == gathered.device else torch.empty((Bs[g], self.nv), dtype=dt, device=qs[g].device) for g in range(n)]
-        if gathered is not None and (gathered.shape != (sum(Bs), self.nv) or gathered.dtype != dt or not gathered.is_contiguous()
-                                     or gathered.device != qs[0].device):
-            raise ValueError("gathered must be a contiguous [sum B, nv] tensor of the shards' dtype on the first shard's device")
-        if streams is None:
-            streams = [torch.cuda.current_stream(t.device) for t in qs]
-        P = ctypes.c_void_p
+            outs = [None if devices[g] == gathered.device else torch.empty((Bs[g], self.nv), dtype=dt, device=devices[g]) for g in range(n)]
+        on = [self._contiguous(None if streams is None else streams[g], devices[g], shards[g][3]) for g in range(n)]
+        for g in range(n):
+            self._hold(None if streams is None else streams[g], *shards[g][3].values(), *on[g][1].values(), outs[g], gathered)
+        P = c_void_p
         arr = lambda ts: (P * n)(*[None if t is None else t.data_ptr() for t in ts])
-        devs = (c_int * n)(*[t.device.index or 0 for t in qs])
-        Bc = (ctypes.c_size_t * n)(*Bs)
-        st = (P * n)(*[s.cuda_stream for s in streams])
-        fn = getattr(lib(), f"grbda_{which}_sharded_dev_{'f32' if dt == torch.float32 else 'f64'}")
-        _check(fn(self._h, n, devs, arr(qs), arr(qds), arr(xs), arr(outs), Bc, st, None if gathered is None else gathered.data_ptr()))
+        self._dispatch(which + "_sharded_dev", dt, n, (c_int * n)(*[d.index or 0 for d in devices]), arr([t["q"] for _, t in on]),
+                       arr([t["qd"] for _, t in on]), arr([t["x"] for _, t in on]), arr(outs), (c_size_t * n)(*Bs),
+                       (P * n)(*[s.cuda_stream for s, _ in on]), None if gathered is None else gathered.data_ptr())
         return outs, gathered
+
+    # ---- host convenience (numpy) -----------------------------------------------------------------
+    def _host(self, name: str, dt, arrays, *tail):
+        """grbda_<name>(plan, arrays..., out, B, *tail) on host arrays (q, qd, x[, f_ext]) of dtype dt; `out` is shaped like x"""
+        import numpy as np
+
+        arrays = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a in arrays]
+        out = np.empty_like(arrays[2])
+        _check(getattr(lib(), "grbda_" + name)(self._h, *[None if a is None else a.ctypes.data for a in arrays], out.ctypes.data,
+                                               arrays[0].shape[0], *tail))
+        return out
 
     def sharded_host(self, which: str, q, qd, x, n_gpus: int):
         """Host numpy arrays (float32 or float64), batch split over devices 0 .. n_gpus-1 in this process."""
         import numpy as np
 
-        dt = np.float32 if q.dtype == np.float32 else np.float64
-        q, qd, x = (np.ascontiguousarray(a, dtype=dt) for a in (q, qd, x))
-        out = np.empty_like(x)
-        fn = getattr(lib(), f"grbda_{which}_sharded_{'f32' if dt == np.float32 else 'f64'}")
-        _check(fn(self._h, q.ctypes.data, qd.ctypes.data, x.ctypes.data, out.ctypes.data, q.shape[0], n_gpus))
-        return out
+        dt = "float32" if q.dtype == np.float32 else "float64"
+        return self._host(f"{which}_sharded_{_suffix(dt)}", dt, (q, qd, x), n_gpus)
 
-    # ---- host convenience (numpy, fp64) -----------------------------------------------------------
     def forward_dynamics_host(self, q, qd, tau, device: int = 0, f_ext=None):
-        import numpy as np
-
-        q, qd, tau = (np.ascontiguousarray(a, dtype=np.float64) for a in (q, qd, tau))
-        fe = None if f_ext is None else np.ascontiguousarray(f_ext, dtype=np.float64)
-        out = np.empty_like(tau)
-        _check(lib().grbda_aba_host_f64(self._h, q.ctypes.data, qd.ctypes.data, tau.ctypes.data,
-                                        None if fe is None else fe.ctypes.data, out.ctypes.data, q.shape[0], device))
-        return out
+        return self._host("aba_host_f64", "float64", (q, qd, tau, f_ext), device)
 
     def inverse_dynamics_host(self, q, qd, ydd, device: int = 0, f_ext=None):
-        import numpy as np
-
-        q, qd, ydd = (np.ascontiguousarray(a, dtype=np.float64) for a in (q, qd, ydd))
-        fe = None if f_ext is None else np.ascontiguousarray(f_ext, dtype=np.float64)
-        out = np.empty_like(ydd)
-        _check(lib().grbda_rnea_host_f64(self._h, q.ctypes.data, qd.ctypes.data, ydd.ctypes.data,
-                                         None if fe is None else fe.ctypes.data, out.ctypes.data, q.shape[0], device))
-        return out
+        return self._host("rnea_host_f64", "float64", (q, qd, ydd, f_ext), device)
 
 
 def device_count() -> int:
@@ -930,7 +562,7 @@ def spd_bad_pivots(device: int = 0, reset: bool = True) -> int:
     """States whose joint-space inertia was not positive definite in the SPD solves of the derivative entry points since the
     last reset (their results are NaN / Inf); synchronises the device (grbda_spd_bad_pivots)."""
     n = ctypes.c_ulonglong(0)
-    _check(lib().grbda_spd_bad_pivots(int(device), ctypes.byref(n), 1 if reset else 0))
+    _check(lib().grbda_spd_bad_pivots(device, byref(n), 1 if reset else 0))
     return int(n.value)
 
 

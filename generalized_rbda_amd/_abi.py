@@ -1,0 +1,81 @@
+"""The C signatures of include/grbda_hip.h as ctypes sees them: SIGNATURES, exported name -> (restype, argtypes).
+
+Written by hand, not read from the header: an installed package does not ship include/.  tests/test_abi_table_cpu.py holds
+the table to the header, parameter by parameter.  `lib()` applies it to every symbol in one loop.
+"""
+from ctypes import POINTER, c_char_p, c_double, c_int, c_size_t, c_ulonglong, c_void_p
+
+# P: any pointer ctypes need not look into -- the plan, a device or host array, a stream (an integer address, a ctypes array,
+# byref(...), bytes and None all pass)
+P, I, Z, D = c_void_p, c_int, c_size_t, c_double
+BODIES, OFFSETS = POINTER(c_int), POINTER(c_double)  # the host arrays of a contact set (and the one offset[3] of the test force)
+TAIL = (Z, I, P)                                     # size_t B, int device, void *stream
+
+# grbda_<stem>_f64 and grbda_<stem>_f32: the two differ in nothing ctypes can see.  The plan comes first everywhere.
+_PAIRS = {
+    "aba": (P, P, P, P, P, P, *TAIL),                                    # q qd tau f_ext ydd
+    "rnea": (P, P, P, P, P, P, *TAIL),                                   # q qd ydd f_ext tau
+    "bias": (P, P, P, P, P, *TAIL),                                      # q qd f_ext out
+    "mass_matrix": (P, P, P, *TAIL),                                     # q H
+    "fd_dtau": (P, P, P, *TAIL),                                         # q Hinv
+    "fd_dqd": (P, P, P, P, P, *TAIL),                                    # q qd tau J
+    "fd_dq": (P, P, P, P, D, P, *TAIL),                                  # q qd tau step J
+    "fd_derivatives": (P, P, P, P, P, P, P, *TAIL),                      # q qd tau dq dqd dtau
+    "rnea_derivatives": (P, P, P, P, D, P, P, P, *TAIL),                 # q qd ydd step dq dqd dydd
+    "project_positions": (P, P, P, Z, I, D, I, P),                       # q ok B max_iter tol device stream
+    "state_to_independent": (P, P, P, P, P, P, P, P, P, Z, D, I, P),     # pos vel q_in qd_in q qd status cond B tol device stream
+    "spanning": (P, P, P, P, P, P, *TAIL),                               # q qd ydd qd_span qdd_span
+    "integrate": (P, P, P, P, D, P, P, P, I, D, *TAIL),                  # q qd ydd dt q_next qd_next ok max_iter tol
+    "step": (P, P, P, P, P, D, P, P, P, P, *TAIL),                       # q qd tau f_ext dt ydd q_next qd_next ok
+    "rollout": (P, P, P, P, I, D, I, P, P, P, P, *TAIL),                 # q qd tau tau_steps dt T ydd_work q_traj qd_traj ok
+    "body_poses": (P, P, P, *TAIL),                                      # q Xa
+    "body_twists": (P, P, P, P, P, *TAIL),                               # q qd ydd V
+    "apply_test_force": (P, P, I, OFFSETS, P, P, P, *TAIL),              # q body offset force lambda_inv dstate
+    "inv_osim": (P, P, I, BODIES, OFFSETS, P, P, *TAIL),                 # q n bodies offsets Linv J
+    "contact_points": (P, P, P, P, I, BODIES, OFFSETS, P, P, P, *TAIL),  # q qd ydd n bodies offsets pos vel acc
+    "contact_dynamics": (P, P, P, P, P, I, BODIES, OFFSETS, P, D, P, P, P, *TAIL),  # q qd tau f_ext n bodies offsets a_des damping ydd lambda ydd_free
+    "contact_impulse": (P, P, P, I, BODIES, OFFSETS, P, D, D, P, P, *TAIL),         # q qd n bodies offsets v_des restitution damping qd_next impulse
+    "energy": (P, P, P, P, P, *TAIL),                                    # q qd kinetic potential
+    "centroidal": (P, P, P, P, P, P, P, P, *TAIL),                       # q qd ydd com com_vel h hdot
+    "centroidal_matrix": (P, P, P, *TAIL),                               # q A
+    "aba_sharded": (P, P, P, P, P, Z, I),                                # q qd tau ydd B n_gpus (host arrays)
+    "rnea_sharded": (P, P, P, P, P, Z, I),
+    "aba_sharded_dev": (P, I, P, P, P, P, P, P, P, P),                   # n_gpus devices q qd tau ydd B streams gathered
+    "rnea_sharded_dev": (P, I, P, P, P, P, P, P, P, P),
+}
+
+# grbda_<stem>_host_f64: the device form without the trailing void *stream
+_HOST = ("aba", "rnea", "mass_matrix", "fd_derivatives", "rnea_derivatives", "project_positions", "integrate", "step", "body_poses",
+         "body_twists", "apply_test_force", "inv_osim", "contact_points", "contact_dynamics", "contact_impulse", "energy", "centroidal")
+
+_SINGLES = {
+    "strerror": (I,),
+    "last_error": (),
+    "plan_from_blob": (P, Z, POINTER(c_void_p)),
+    "plan_from_urdf": (c_char_p, I, POINTER(c_void_p)),
+    "urdf_to_blob": (POINTER(c_char_p), I, I, P, Z, POINTER(c_size_t)),
+    "plan_free": (P,),
+    "plan_release_work": (P, POINTER(c_ulonglong)),
+    "plan_dims": (P, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)),
+    "plan_set_gravity": (P, POINTER(c_double)),
+    "plan_get_gravity": (P, POINTER(c_double)),
+    "plan_blob": (P, POINTER(c_void_p), POINTER(c_size_t)),
+    "plan_info": (P, P),                                                 # (PlanInfo lives in the package's __init__)
+    "plan_span_dims": (P, POINTER(c_int)),
+    "plan_total_mass": (P, POINTER(c_double)),
+    "state_input_dims": (P, P, P, POINTER(c_int), POINTER(c_int)),
+    "state_to_independent_host_f64": (P, P, P, P, P, P, P, Z, D, I),     # (no status, no cond: not the device form)
+    "spd_bad_pivots": (I, POINTER(c_ulonglong), I),
+    "kernel_name": (P, I, I, Z, I, P, Z),                                # kind precision B device buf cap
+    "contact_solve_launch": (I, I, I, POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)),
+    "time_kernel": (P, I, I, P, P, P, P, Z, I, P, I, P),                 # kind precision q qd x out B device stream iters avg_ms
+    "device_count": (),
+}
+_RESTYPE = {"grbda_strerror": c_char_p, "grbda_last_error": c_char_p, "grbda_plan_free": None}  # every other: int
+
+SIGNATURES = {"grbda_" + name: args for name, args in _SINGLES.items()}
+for _stem, _args in _PAIRS.items():
+    SIGNATURES[f"grbda_{_stem}_f64"] = SIGNATURES[f"grbda_{_stem}_f32"] = _args
+for _stem in _HOST:
+    SIGNATURES[f"grbda_{_stem}_host_f64"] = _PAIRS[_stem][:-1]
+SIGNATURES = {name: (_RESTYPE.get(name, c_int), args) for name, args in SIGNATURES.items()}

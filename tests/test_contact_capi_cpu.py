@@ -94,10 +94,6 @@ def test_empty_batch_is_ok(plan, arrays):
     assert points(plan, arrays, 1, [1], B=0) == OK
     assert dynamics(plan, arrays, 1, [1], B=0) == OK
     L = G.lib()
-    L.grbda_contact_points_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double), c_void_p,
-                                                c_void_p, c_void_p, c_size_t, c_int]
-    L.grbda_contact_dynamics_host_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double),
-                                                  c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
     bod, off, p = (c_int * 1)(1), (c_double * 3)(), lambda k: _ptr(arrays[k])
     assert L.grbda_contact_points_host_f64(plan._h, p("q"), p("qd"), p("ydd"), 1, bod, off, p("pos"), p("vel"), p("acc"), 0, 0) == OK
     assert L.grbda_contact_dynamics_host_f64(plan._h, p("q"), p("qd"), p("tau"), None, 1, bod, off, None, 0.0, p("ydd"), p("lam"), None, 0,

@@ -245,8 +245,6 @@ def test_host_variant_equals_the_device_call(gpu):
     ydd, lam, free = np.empty((B, nv)), np.empty((B, n, 3)), np.empty((B, nv))
     p = lambda a: a.ctypes.data_as(c_void_p)
     fn = G.lib().grbda_contact_dynamics_host_f64
-    fn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_double), c_void_p, c_double,
-                   c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int]
     rc = fn(plan._h, p(h[0]), p(h[1]), p(h[2]), None, n, (c_int * n)(*bodies), (c_double * (3 * n))(*[x for o in offsets for x in o]), p(h[3]),
             0.0, p(ydd), p(lam), p(free), B, 0)
     assert rc == 0
@@ -255,8 +253,6 @@ def test_host_variant_equals_the_device_call(gpu):
     # the points likewise
     pos, vel, acc = (np.empty((B, n, 3)) for _ in range(3))
     fp = G.lib().grbda_contact_points_host_f64
-    fp.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_double), c_void_p, c_void_p, c_void_p,
-                   ctypes.c_size_t, c_int]
     rc = fp(plan._h, p(h[0]), p(h[1]), p(ydd), n, (c_int * n)(*bodies), (c_double * (3 * n))(*[x for o in offsets for x in o]), p(pos), p(vel),
             p(acc), B, 0)
     assert rc == 0

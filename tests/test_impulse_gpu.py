@@ -203,8 +203,6 @@ def test_host_variant_equals_the_device_call(gpu):
     qn, imp = np.empty((B, nv)), np.empty((B, n, 3))
     p = lambda a: a.ctypes.data_as(c_void_p)
     fn = G.lib().grbda_contact_impulse_host_f64
-    fn.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_double), c_void_p, c_double, c_double, c_void_p,
-                   c_void_p, ctypes.c_size_t, c_int]
     bod, off = (c_int * n)(*bodies), (c_double * (3 * n))(*[x for o in offsets for x in o])
     assert fn(plan._h, p(h[0]), p(h[1]), n, bod, off, p(h[2]), e, mu, p(qn), p(imp), B, 0) == 0
     assert np.array_equal(qn, want[0]) and np.array_equal(imp, want[1])
