@@ -11,7 +11,7 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import SIGNATURES
+from ._abi import SIGNATURES, VJP_SIGNATURES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
@@ -61,6 +61,11 @@ def lib() -> ctypes.CDLL:
     for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
+    # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
+    for name, (restype, argtypes) in VJP_SIGNATURES.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
     return L
 
@@ -88,7 +93,54 @@ def urdf_to_blob(paths, ori_repr: str = "quaternion") -> bytes:
     return buf.raw[: need.value]
 
 
-class Plan:
+class _VjpMethods:
+    """The vector-Jacobian products and the autograd functions of Plan (include/grbda_hip_vjp.h): kept apart from Plan's own methods as
+    that header is kept apart from grbda_hip.h.  They go through Plan._call like every other method; tests/test_vjp_gpu.py holds them to
+    the argument rules of the tensor methods (strided inputs, the one exception rule, a side stream)."""
+
+    def _vjp(self, stem, last, q, qd, x, g, want, step, stream):
+        names = ("q", "qd", last)
+        if not any(k in want for k in names) or any(k not in names + (("ydd",) if stem == "aba_vjp" else ()) for k in want):
+            raise ValueError(f'want must name at least one of "q", "qd", "{last}"' + (' and besides them only "ydd"' if stem == "aba_vjp" else " and nothing else"))
+        outs = {"grad_" + k: self.nv if k in want else None for k in names}
+        if stem == "aba_vjp":
+            outs["ydd_out"] = self.nv if "ydd" in want else None
+        got = self._call(stem, stream, dict(self._state(q, qd=qd, **{last: x}), g=(g, self.nv)), outs, ("q", "qd", last, "g", step) + tuple(outs),
+                         skip_empty=True)
+        return {k.replace("grad_", "").replace("ydd_out", "ydd"): o for k, o in zip(outs, got) if o is not None}
+
+    def id_vjp(self, q, qd, ydd, g, want=("q", "qd", "ydd"), step: float = 1e-6, stream=None):
+        """g^T d tau / d q, g^T d tau / d qd, g^T d tau / d ydd of the inverse dynamics at (q, qd, ydd) for the cotangent g[B, nv]
+        (grbda_rnea_vjp_*): a dict of [B, nv] tensors for the names in `want`, out[b, j] = sum_i g[b, i] d tau_i / d x_j -- the rows of
+        id_derivatives contracted inside the library, "q" along the tangent step of fd_dq (nv entries).  "ydd" alone runs no
+        derivative recursion (H g by two inverse dynamics); `step` as in id_derivatives."""
+        return self._vjp("rnea_vjp", "ydd", q, qd, ydd, g, want, step, stream)
+
+    def fd_vjp(self, q, qd, tau, g, want=("q", "qd", "tau"), step: float = 1e-6, stream=None):
+        """g^T d ydd / d q, g^T d ydd / d qd, g^T d ydd / d tau of the forward dynamics for the cotangent g[B, nv] (grbda_aba_vjp_*): a dict
+        of [B, nv] tensors for the names in `want`.  mu = H^-1 g comes from two forward dynamics at zero velocity ("tau": mu itself),
+        "q" and "qd" are -mu^T d tau / d (q, qd) at ydd = FD(q, qd, tau): no factorisation, no solve, no [B, nv, nv] tensor.
+        "ydd" in `want` also returns that FD(q, qd, tau)."""
+        return self._vjp("aba_vjp", "tau", q, qd, tau, g, want, step, stream)
+
+    def _ad(self, forward, q, qd, x):
+        if q.requires_grad and self.nq != self.nv:
+            entry = "fd_vjp" if forward else "id_vjp"
+            raise ValueError(f"q requires grad on a plan with nq = {self.nq} != nv = {self.nv} (a quaternion base or implicit clusters): a gradient "
+                             f"along the tangent step has no unique pull-back to the nq position coordinates -- call {entry} for the tangent gradient")
+        return _autograd_function(forward).apply(self, q, qd, x)
+
+    def forward_dynamics_ad(self, q, qd, tau):
+        """forward_dynamics as a differentiable torch function (the same bits); backward is fd_vjp for the inputs that require grad.  A
+        gradient for q only on plans with nq == nv (fixed or roll-pitch-yaw base, explicit clusters), where the tangent step is q + dq."""
+        return self._ad(True, q, qd, tau)
+
+    def inverse_dynamics_ad(self, q, qd, ydd):
+        """inverse_dynamics as a differentiable torch function (the same bits); backward is id_vjp; q as in forward_dynamics_ad."""
+        return self._ad(False, q, qd, ydd)
+
+
+class Plan(_VjpMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):
@@ -552,6 +604,45 @@ class Plan:
 
     def inverse_dynamics_host(self, q, qd, ydd, device: int = 0, f_ext=None):
         return self._host("rnea_host_f64", "float64", (q, qd, ydd, f_ext), device)
+
+
+_ad_functions = {}
+
+
+def _autograd_function(forward: bool):
+    """the torch.autograd.Function behind Plan.forward_dynamics_ad (forward) / inverse_dynamics_ad, made on first use (torch is imported
+    by the calls, not by the package)"""
+    if forward not in _ad_functions:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        names = ("q", "qd", "tau" if forward else "ydd")
+
+        class Dynamics(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, plan, q, qd, x):
+                ctx.plan = plan
+                ctx.save_for_backward(q, qd, x)
+                return plan.forward_dynamics(q, qd, x) if forward else plan.inverse_dynamics(q, qd, x)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, g):
+                want = tuple(k for k, needed in zip(names, ctx.needs_input_grad[1:]) if needed)
+                got = (ctx.plan.fd_vjp if forward else ctx.plan.id_vjp)(*ctx.saved_tensors, g, want=want)
+                return (None,) + tuple(got.get(k) for k in names)
+
+        Dynamics.__name__ = Dynamics.__qualname__ = "ForwardDynamics" if forward else "InverseDynamics"
+        _ad_functions[forward] = Dynamics
+    return _ad_functions[forward]
+
+
+def vjp_contract_launch(nv: int, B: int, n_cu: int):
+    """(units, grid) of the contraction kernel of id_vjp / fd_vjp for B states on a device with n_cu compute units
+    (grbda_vjp_contract_launch): units > grid means a workgroup takes a second trip of its grid-stride loop"""
+    units, grid = c_size_t(0), c_size_t(0)
+    _check(lib().grbda_vjp_contract_launch(nv, B, n_cu, byref(units), byref(grid)))
+    return units.value, grid.value
 
 
 def device_count() -> int:

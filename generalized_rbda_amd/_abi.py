@@ -79,3 +79,15 @@ for _stem, _args in _PAIRS.items():
 for _stem in _HOST:
     SIGNATURES[f"grbda_{_stem}_host_f64"] = _PAIRS[_stem][:-1]
 SIGNATURES = {name: (_RESTYPE.get(name, c_int), args) for name, args in SIGNATURES.items()}
+
+# include/grbda_hip_vjp.h, the vector-Jacobian products: a table of its own (SIGNATURES is the table of grbda_hip.h and nothing else);
+# `lib()` applies it after SIGNATURES, and tests/test_vjp_args_cpu.py holds it to that header the same way
+_VJP_PAIRS = {
+    "rnea_vjp": (P, P, P, P, P, D, P, P, P, *TAIL),                      # q qd ydd g_tau step grad_q grad_qd grad_ydd
+    "aba_vjp": (P, P, P, P, P, D, P, P, P, P, *TAIL),                    # q qd tau g_ydd step grad_q grad_qd grad_tau ydd
+}
+VJP_SIGNATURES = {"grbda_vjp_contract_launch": (I, Z, I, POINTER(c_size_t), POINTER(c_size_t))}  # nv nb n_cu units grid
+for _stem, _args in _VJP_PAIRS.items():
+    VJP_SIGNATURES[f"grbda_{_stem}_f64"] = VJP_SIGNATURES[f"grbda_{_stem}_f32"] = _args
+    VJP_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
+VJP_SIGNATURES = {name: (c_int, args) for name, args in VJP_SIGNATURES.items()}

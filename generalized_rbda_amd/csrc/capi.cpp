@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/grbda_hip.h"
+#include "../../include/grbda_hip_vjp.h"
 #include "../../include/grbda_model_desc.h"
 #include "devplan.h"
 
@@ -129,6 +130,7 @@ struct grbda_plan {
     mutable SlabPool work;       // expanded batches of the derived quantities
     mutable SlabPool work_cvt;   // fp64 copies of fp32 inputs (through_f64)
     mutable SlabPool work_proj;  // projection_run (called from inside the users of `work`)
+    mutable SlabPool work_vjp;   // vjp_run (its id_derivs stage carves `work` on the difference routes)
     // the chunk decision of the last eager analytic_derivs call per (device, stream): a capture of the same call replays it
     struct DerivChunk {
         size_t B = 0, per_state_bytes = 0, chunk = 0;
@@ -2711,6 +2713,103 @@ int rnea_derivatives(const grbda_plan *p, const T *q, const T *qd, const T *ydd,
     return id_derivs<T>(p, q, qd, ydd, step, dq, dqd, B, device, stream);
 }
 
+// ---- vector-Jacobian products (include/grbda_hip_vjp.h): grbda_rnea_vjp_* / grbda_aba_vjp_* -------------------------------------------
+// the argument rules of both (device and host arrays alike); x: ydd / tau, g: the cotangent, grad_x: grad_ydd / grad_tau, ydd_out: the
+// forward dynamics' optional result.  Everything that can be refused is refused here, before a device is looked at.
+template <class T>
+int vjp_args(const grbda_plan *p, const T *q, const T *qd, const T *x, const T *g, double step, const T *grad_q, const T *grad_qd, const T *grad_x,
+             const T *ydd_out, size_t B)
+{
+    if (!q || !qd || !x || !g) return set_err(GRBDA_EINVAL, "null argument");
+    if (!grad_q && !grad_qd && !grad_x) return set_err(GRBDA_EINVAL, "no output asked for");
+    const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
+    const void *const in[4] = {q, qd, x, g}, *const out[4] = {grad_q, grad_qd, grad_x, ydd_out};
+    const size_t in_bytes[4] = {bq, bv, bv, bv}, out_bytes[4] = {bv, bv, bv, bv};
+    if (int rc = no_overlap(in, in_bytes, out, out_bytes)) return rc;
+    // (the one use of `step`: d tau / d q by central differences, id_derivs off the analytic route)
+    if (grad_q && !analytic_covers(p) && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+    return GRBDA_OK;
+}
+// Chunk by chunk through the plan's work_vjp slab.  forward: ydd = ABA(q, qd, tau); mu = H^-1 g as ABA(q, 0, g) - ABA(q, 0, 0); d tau / d q and
+// d tau / d qd at (q, qd, ydd) by id_derivs into the slab, row-major; grad_q = -mu^T d tau / d q, grad_qd = -mu^T d tau / d qd, grad_tau = mu
+// (vjp_contract_kernel forms the difference and writes all three).  Inverse: the matrices at the caller's ydd contracted with g, and
+// grad_ydd = H g as RNEA(q, 0, g) - RNEA(q, 0, 0).  The runs of a zero-velocity pair carry no gravity (run(), gravity = false): on plans
+// without the spanning-tree route the second of them is then exactly zero and the first is not rounded against a bias it does not need.
+// Only the stages the asked-for outputs need are enqueued, and each output has the same bits in every subset.
+template <class T>
+int vjp_run(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *g, double step, T *grad_q, T *grad_qd, T *grad_x,
+            T *ydd_out, size_t B, int device, void *stream)
+{
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
+    const bool need_d = grad_q || grad_qd;
+    const bool need_pair = forward || grad_x;                        // the two launches at zero velocity
+    const bool need_ydd = forward && (need_d || ydd_out);
+    // per state: the matrices asked for; zeros, and the two results of the zero-velocity pair; ydd when the caller keeps none
+    const size_t per_state = (grad_q ? nn : 0) + (grad_qd ? nn : 0) + (need_pair ? 3 * nv : 0) + (need_ydd && !ydd_out ? nv : 0);
+    const Chunk c = budgeted_chunk(p, p->work_vjp, device, stream, 4096ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work_vjp, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, c.chunk * per_state);
+    auto take = [&](bool wanted, size_t per) { return wanted ? w.take(c.chunk * per) : nullptr; };
+    T *Mq = take(grad_q, nn), *Mqd = take(grad_qd, nn), *zeros = take(need_pair, nv), *r1 = take(need_pair, nv), *r0 = take(need_pair, nv);
+    T *ydd_slab = take(need_ydd && !ydd_out, nv);
+    assert(w.taken == w.cap);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int nvi = static_cast<int>(nv);
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        const T *qc = q + b0 * nq, *qdc = qd + b0 * nv, *xc = x + b0 * nv, *gc = g + b0 * nv;
+        T *ydd = ydd_out ? ydd_out + b0 * nv : ydd_slab;
+        T *oq = grad_q ? grad_q + b0 * nv : nullptr, *oqd = grad_qd ? grad_qd + b0 * nv : nullptr, *ox = grad_x ? grad_x + b0 * nv : nullptr;
+        if (need_ydd)
+            if (int rc = run<T>(p, false, qc, qdc, xc, nullptr, ydd, nb, device, stream)) return rc;
+        if (need_pair) {
+            if (hipError_t e = hipMemsetAsync(zeros, 0, nb * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+            if (int rc = run<T>(p, !forward, qc, zeros, gc, nullptr, r1, nb, device, stream, false)) return rc;
+            if (int rc = run<T>(p, !forward, qc, zeros, zeros, nullptr, r0, nb, device, stream, false)) return rc;
+        }
+        if (need_d)
+            if (int rc = id_derivs<T>(p, qc, qdc, forward ? ydd : xc, step, Mq, Mqd, nb, device, stream)) return rc;
+        const VjpLaunch L = vjp_contract_launch(nvi, sizeof(T), t->n_cu, nb);
+        hipError_t e = hipSuccess;
+        if (forward) {
+            e = launch_vjp_contract<T>(L, Mq, Mqd, r1, r0, T(-1), nvi, nb, oq, oqd, ox, hs);
+        } else {
+            if (ox) e = launch_vjp_contract<T>(L, nullptr, nullptr, r1, r0, T(1), nvi, nb, nullptr, nullptr, ox, hs);
+            if (e == hipSuccess && need_d) e = launch_vjp_contract<T>(L, Mq, Mqd, gc, nullptr, T(1), nvi, nb, oq, oqd, nullptr, hs);
+        }
+        if (e != hipSuccess) return hip_err(e, "vjp contraction launch");
+    }
+    return GRBDA_OK;
+}
+template <class T>
+int vjp(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *g, double step, T *grad_q, T *grad_qd, T *grad_x, T *ydd_out,
+        size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = vjp_args<T>(p, q, qd, x, g, step, grad_q, grad_qd, grad_x, ydd_out, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    return vjp_run<T>(p, forward, q, qd, x, g, step, grad_q, grad_qd, grad_x, ydd_out, B, device, stream);
+}
+int vjp_host_f64(const grbda_plan *p, bool forward, const double *q, const double *qd, const double *x, const double *g, double step, double *grad_q,
+                 double *grad_qd, double *grad_x, double *ydd_out, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = vjp_args<double>(p, q, qd, x, g, step, grad_q, grad_qd, grad_x, ydd_out, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    DeviceTables *t = nullptr;
+    if (int rc0 = ensure_device(p, device, &t)) return rc0;  // `device` current before anything is allocated on it
+    HostStage st;
+    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bx = st.in(x, B * nv), *bg = st.in(g, B * nv);
+    double *b1 = grad_q ? st.out(grad_q, B * nv) : nullptr, *b2 = grad_qd ? st.out(grad_qd, B * nv) : nullptr,
+           *b3 = grad_x ? st.out(grad_x, B * nv) : nullptr, *b4 = ydd_out ? st.out(ydd_out, B * nv) : nullptr;
+    return st.run([&] { return vjp_run<double>(p, forward, bq, bqd, bx, bg, step, b1, b2, b3, b4, B, device, nullptr); });
+}
+
 // the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
 template <class T>
 static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B)
@@ -3070,7 +3169,7 @@ void grbda_plan_free(grbda_plan *p)
         }
         for (int w = 0; w < kLayouts; w++) { (void)hipFree(t.acc_k[w]); (void)hipFree(t.clusters[w]); (void)hipFree(t.rnea_clusters[w]); (void)hipFree(t.bodies[w]); (void)hipFree(t.rnea_bodies[w]); }
     }
-    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj})
+    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj, &p->work_vjp})
         for (auto &kv : *m) {
             if (hipSetDevice(kv.first.first) != hipSuccess) continue;
             if (kv.second.ptr) (void)hipFree(kv.second.ptr);
@@ -3082,7 +3181,7 @@ void grbda_plan_free(grbda_plan *p)
 // (and of its spanning-tree plan) is checked first, so that a refused release frees nothing.
 static bool holds_capturing_slab(const grbda_plan *p)
 {
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp})
         for (auto &kv : *m)
             if (kv.second.ptr && is_capturing(kv.first.second)) return true;
     return p->span && holds_capturing_slab(p->span);
@@ -3095,7 +3194,7 @@ int grbda_plan_release_work(grbda_plan *p, unsigned long long *bytes_released)
     if (holds_capturing_slab(p))
         return set_err(GRBDA_EINVAL, "a stream of this plan is capturing: its work buffers cannot be released now");
     unsigned long long total = 0;
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp})
         for (auto &kv : *m) {
             if (!kv.second.ptr) continue;
             hipError_t e = hipSetDevice(kv.first.first);
@@ -3566,6 +3665,44 @@ int grbda_rnea_derivatives_host_f64(const grbda_plan *p, const double *q, const 
     double *b1 = dtau_dq ? st.out(dtau_dq, B * nn) : nullptr, *b2 = dtau_dqd ? st.out(dtau_dqd, B * nn) : nullptr,
            *b3 = dtau_dydd ? st.out(dtau_dydd, B * nn) : nullptr;
     return st.run([&] { return grbda_rnea_derivatives_f64(p, bq, bqd, by, step, b1, b2, b3, B, device, nullptr); });
+}
+int grbda_rnea_vjp_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, const double *g_tau, double step, double *grad_q,
+                       double *grad_qd, double *grad_ydd, size_t B, int device, void *stream)
+{
+    return vjp<double>(p, false, q, qd, ydd, g_tau, step, grad_q, grad_qd, grad_ydd, nullptr, B, device, stream);
+}
+int grbda_rnea_vjp_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, const float *g_tau, double step, float *grad_q,
+                       float *grad_qd, float *grad_ydd, size_t B, int device, void *stream)
+{
+    return vjp<float>(p, false, q, qd, ydd, g_tau, step, grad_q, grad_qd, grad_ydd, nullptr, B, device, stream);
+}
+int grbda_rnea_vjp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, const double *g_tau, double step,
+                            double *grad_q, double *grad_qd, double *grad_ydd, size_t B, int device)
+{
+    return vjp_host_f64(p, false, q, qd, ydd, g_tau, step, grad_q, grad_qd, grad_ydd, nullptr, B, device);
+}
+int grbda_aba_vjp_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *g_ydd, double step, double *grad_q,
+                      double *grad_qd, double *grad_tau, double *ydd, size_t B, int device, void *stream)
+{
+    return vjp<double>(p, true, q, qd, tau, g_ydd, step, grad_q, grad_qd, grad_tau, ydd, B, device, stream);
+}
+int grbda_aba_vjp_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, const float *g_ydd, double step, float *grad_q,
+                      float *grad_qd, float *grad_tau, float *ydd, size_t B, int device, void *stream)
+{
+    return vjp<float>(p, true, q, qd, tau, g_ydd, step, grad_q, grad_qd, grad_tau, ydd, B, device, stream);
+}
+int grbda_aba_vjp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *g_ydd, double step,
+                           double *grad_q, double *grad_qd, double *grad_tau, double *ydd, size_t B, int device)
+{
+    return vjp_host_f64(p, true, q, qd, tau, g_ydd, step, grad_q, grad_qd, grad_tau, ydd, B, device);
+}
+int grbda_vjp_contract_launch(int nv, size_t nb, int n_cu, size_t *units, size_t *grid)
+{
+    if (nv < 1 || n_cu < 1) return set_err(GRBDA_EINVAL, "nv and n_cu must be positive");
+    const VjpLaunch L = vjp_contract_launch(nv, sizeof(double), n_cu, nb);  // (units and grid do not depend on the precision)
+    if (units) *units = L.units;
+    if (grid) *grid = L.grid;
+    return GRBDA_OK;
 }
 int grbda_plan_span_dims(const grbda_plan *p, int *n_span_vel)
 {

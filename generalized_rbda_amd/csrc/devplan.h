@@ -256,6 +256,20 @@ hipError_t launch_centroidal(const DevPlan<T> &P, int n_clusters, int n_span, co
                              const T *qd_span, const T *qdd_span, const T g[3], T mass, const CentroidalOut<T> &out, size_t nb, T *scratch,
                              hipStream_t stream);
 
+// the contraction of the vector-Jacobian products (vjp_kernels.hip): out_q[b][j] = sign sum_i w[b][i] Mq[b][i][j] and the same for Mqd,
+// w = w_add - w_sub (w_sub may be null), over nb states of row-major [nv][nv] matrices; Mq / out_q and Mqd / out_qd may be null; out_w
+// (may be null) receives w.  One launch rule, read by the launcher and by grbda_vjp_contract_launch.
+constexpr size_t kVjpWavesPerCu = 16;
+struct VjpLaunch {
+    size_t units;      // packs of states x column blocks
+    size_t grid;       // one-wavefront workgroups
+    size_t lds_bytes;  // the weights of one unit
+};
+VjpLaunch vjp_contract_launch(int nv, size_t elem, int n_cu, size_t nb);
+template <class T>
+hipError_t launch_vjp_contract(const VjpLaunch &L, const T *Mq, const T *Mqd, const T *w_add, const T *w_sub, T sign, int nv, size_t nb, T *out_q,
+                               T *out_qd, T *out_w, hipStream_t stream);
+
 // composite-rigid-body algorithm (crba_kernels.hip)
 template <class T>
 hipError_t launch_crba(const DevPlan<T> &P, const CrbaBody *cb, int n_clusters, int n_rows, const T *q, T *H, size_t B, T *scratch,
