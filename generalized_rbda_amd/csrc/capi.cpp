@@ -2819,14 +2819,15 @@ static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_
     const char *alg = kind == 0 ? "aba" : "rnea";
     const Route r = kind == 0 ? choose_aba<T>(p, n_cu, B, false) : choose_rnea<T>(p, n_cu, B, false);
     char buf[160];
-    const auto format = [&](const auto &cp, int gen1_waves) {
+    const auto format = [&](const auto &cp, int gen1_waves, bool inreg = false) {
         const int segs = !cp.gens.empty() ? 2 : (!cp.diffs.empty() ? 1 : 0);
         if (r.path == ROUTE_GEN1)
             std::snprintf(buf, sizeof buf, "grbda_hip::%s_gen1_kernel<%s, %d, %s, %d>", alg, tn, cp.gens[0].n, cp.gens[0].kind ? "true" : "false", gen1_waves);
         else if (r.path == ROUTE_LM)
             std::snprintf(buf, sizeof buf, "grbda_hip::%s_chain_lm_kernel<%s, %d%s>", alg, tn, r.lm_waves, cp.diffs.empty() ? "" : ", true");
         else if (kind == 0)
-            std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_kernel<%s, %d, %d>", tn, (sizeof(T) == 8 && !cp.gens.empty()) ? 1 : 2, segs);
+            std::snprintf(buf, sizeof buf, "grbda_hip::aba_chain_kernel<%s, %d, %d>", tn, (sizeof(T) == 8 && !cp.gens.empty()) ? 1 : 2,
+                          inreg ? kModeInReg : segs);
         else
             std::snprintf(buf, sizeof buf, "grbda_hip::rnea_chain_kernel<%s, %d, %s>", tn, segs, cp.n_glb > 0 ? "true" : "false");
     };
@@ -2835,7 +2836,9 @@ static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_
         for (const ClusterRec &cr : h.lay64.clusters) loop = loop || cr.kind == CK_LOOP;
         std::snprintf(buf, sizeof buf, "grbda_hip::%s_kernel<%s, %s>", alg, tn, loop ? "true" : "false");
     } else if (kind == 0) {
-        format(h.chain[r.slot], r.path == ROUTE_GEN1 ? gen1_waves_per_simd<T>(h.chain[r.slot].gens[0].n) : 0);
+        const ChainProgram &cp = h.chain[r.slot];
+        format(cp, r.path == ROUTE_GEN1 ? gen1_waves_per_simd<T>(cp.gens[0].n) : 0,
+               chain_inputs_in_registers(sizeof(T), static_cast<int>(cp.gens.size()), static_cast<int>(cp.diffs.size()), cp.sv_global ? 1 : 0, h.nq, h.nv));
     } else {
         // (The four-wavefronts-per-SIMD route keeps the name of the two-per-SIMD program, as it always has: the batch-ladder tests compare
         // the names either side of a threshold.  Its own program may spill where that one does not -- Mini Cheetah then runs

@@ -181,6 +181,22 @@ struct ChainMem {
     }
 };
 
+// The tile's inputs in REGISTERS instead of slab rows (aba_chain_kernel<float, 2, kModeInReg>): every lane keeps its own state's q, qd and
+// tau in three arrays of kInRegCols (devplan.h) entries.  The column numbers come from the plan records, which are wave-uniform, so an
+// access is an indexed register move (s_set_gpr_idx_on / v_mov_b32 / s_set_gpr_idx_off) -- no address arithmetic, no vmcnt wait and no
+// slab traffic; the prologue writes no input row (stage_inputs_reg, devmath.h).  The arrays are VECTOR values, not C arrays: the
+// compiler turns a dynamically indexed C array into registers only within a budget of a quarter of the register file for the whole
+// kernel (two of these three would go to scratch), a vector is a register tuple to begin with.  Everything else (slots, [K | y0]
+// blocks, result rows) is ChainMem's.
+template <class T>
+struct ChainMemR : ChainMem<T> {
+    typedef T Row __attribute__((ext_vector_type(kInRegCols)));
+    Row rq, rqd, rx;
+    __device__ __forceinline__ T q(int j) const { return rq[j]; }
+    __device__ __forceinline__ T qd(int j) const { return rqd[j]; }
+    __device__ __forceinline__ T x(int j) const { return rx[j]; }
+};
+
 // c = v x (z qd) for a joint about z: (v1, -v0, 0, v4, -v3, 0) qd   (Spatial.h:131-143)
 template <class T>
 __device__ __forceinline__ void vxz(const T (&v)[6], T qd, T (&c)[6])
@@ -331,8 +347,8 @@ __device__ __forceinline__ void link_force_up(int perm, T s, T c, cptr<T> C, con
     }
 }
 
-template <class T, bool SVG>
-__device__ __forceinline__ void run_fwd(const ChainTables<T> &P, const ChainMem<T> &M, const ChainSeg &sg)
+template <class T, bool SVG, class MM>
+__device__ __forceinline__ void run_fwd(const ChainTables<T> &P, const MM &M, const ChainSeg &sg)
 {
     T vp[6];
     {
@@ -381,8 +397,8 @@ __device__ __forceinline__ void run_fwd(const ChainTables<T> &P, const ChainMem<
 // that latency at every link (profiles/r5_chain_phase_profile.txt: ~780 cycles per link at the loop top); here it is exposed once
 // per chunk.  Runs of the URDF robots are 3-7 links long.
 constexpr int kChunk = 4;
-template <class T>
-__device__ __forceinline__ void run_fwd_c(const ChainTables<T> &P, const ChainMem<T> &M, const ChainSeg &sg)
+template <class T, class MM>
+__device__ __forceinline__ void run_fwd_c(const ChainTables<T> &P, const MM &M, const ChainSeg &sg)
 {
     // Two phases per chunk: A -- everything of a link that does not depend on its parent (constants, sin / cos,
     // E = Rz(q) Et, the offset r, the joint rate), four links side by side: the scalar loads of all four are in flight together and the
@@ -470,8 +486,8 @@ __device__ __forceinline__ void congruence_k(T s, T c, const T (&E)[9], cptr<T> 
 }
 
 // K1, K2: compile-time ChainPair::perm of the two links (-1: general rotation)
-template <class T, bool OSIM, int K1, int K2>
-__device__ __forceinline__ void pair_bwd_k(const ChainTables<T> &P, const ChainMem<T> &M, const ChainPair &pr, T (&IA)[21],
+template <class T, bool OSIM, int K1, int K2, class MM>
+__device__ __forceinline__ void pair_bwd_k(const ChainTables<T> &P, const MM &M, const ChainPair &pr, T (&IA)[21],
                                            T (&psi)[6])
 {
     cptr<T> C1 = P.consts + pr.cofs[0], C2 = P.consts + pr.cofs[1];
@@ -598,8 +614,8 @@ __device__ __forceinline__ void pair_bwd_k(const ChainTables<T> &P, const ChainM
         for (int cc = r; cc < 6; cc++) IA[sidx(r, cc)] -= F0[r] * blk[cc] + F1[r] * blk[6 + cc];
     }
 }
-template <class T, bool OSIM>
-__device__ __forceinline__ void pair_bwd(const ChainTables<T> &P, const ChainMem<T> &M, const ChainPair &pr, T (&IA)[21],
+template <class T, bool OSIM, class MM>
+__device__ __forceinline__ void pair_bwd(const ChainTables<T> &P, const MM &M, const ChainPair &pr, T (&IA)[21],
                                          T (&psi)[6])
 {
     // (the knee-ankle pairs of the MIT Humanoid: both tree rotations the identity)
@@ -1053,8 +1069,8 @@ __device__ __forceinline__ void diff_acc(const ChainTables<T> &P, const ChainMem
 // ROT (ChainSeg::rot_kind, plan.cpp): 1 -- every link of the run carries an axisymmetric rotor, 2 -- none carries a rotor: the link body
 // is then ONE basic block (no wave-uniform branch on the rotor kind), so the rotor's constants and the parent velocity are fetched with
 // the link's own at the top of the iteration and its arithmetic is scheduled between the link's; 0 -- mixed, the branches stay.
-template <class T, bool OSIM, bool SVG, int ROT = 0>
-__device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const ChainMem<T> &M, const ChainSeg &sg)
+template <class T, bool OSIM, bool SVG, int ROT = 0, class MM>
+__device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const MM &M, const ChainSeg &sg)
 {
     T IAc[21], psic[6];  // what the link below handed up (register hand-over inside the run)
     if (sg.head == HEAD_PAIR) {
@@ -1317,8 +1333,8 @@ __device__ __forceinline__ void run_acc(const ChainTables<T> &P, const ChainMem<
 // written by the backward sweep tens of microseconds earlier and come back from the Infinity Cache (~1 300 cycles measured at the loop
 // top of run_acc, where the block of the NEXT link was requested and -- the compiler's wait-count pass merges the loop's entry states --
 // waited for at once); a link of this run is 20-150 instructions.
-template <class T>
-__device__ __forceinline__ void run_acc_c(const ChainTables<T> &P, const ChainMem<T> &M, const ChainSeg &sg)
+template <class T, class MM>
+__device__ __forceinline__ void run_acc_c(const ChainTables<T> &P, const MM &M, const ChainSeg &sg)
 {
     // (two phases per chunk as in run_fwd_c: the recursion a_i = X_i a_(i-1) + c_i + z g0 ydd_i with ydd_i = y0_i - K_i a_(i-1) runs on
     // register operands prepared for all four links beforehand)
@@ -1410,8 +1426,8 @@ __device__ __forceinline__ void run_acc_c(const ChainTables<T> &P, const ChainMe
 // ---------------------------------------------------------------------------------------------------------------
 // floating base (FreeJoint.cpp:10-46): S = 1, D = IA, c = 0
 // ---------------------------------------------------------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ void free_fwd(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f)
+template <class T, class MM>
+__device__ __forceinline__ void free_fwd(const ChainTables<T> &P, const MM &M, const ChainFree &f)
 {
     if (f.lds_v < 0) return;
     T v[6];
@@ -1420,13 +1436,13 @@ __device__ __forceinline__ void free_fwd(const ChainTables<T> &P, const ChainMem
     M.lds_st(f.lds_v, v);
 }
 
-template <class T>
-__device__ __forceinline__ void free_acc_inputs(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f, T (&o)[4], T (&r)[3]);
+template <class T, class MM>
+__device__ __forceinline__ void free_acc_inputs(const ChainTables<T> &P, const MM &M, const ChainFree &f, T (&o)[4], T (&r)[3]);
 template <class T>
 __device__ __forceinline__ void free_acc_core(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f, const T (&y0)[6],
                                               const T (&o)[4], const T (&r)[3], const T (&vb)[6]);
-template <class T, bool OSIM>
-__device__ __forceinline__ void free_bwd(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f, bool fuse_acc = false)
+template <class T, bool OSIM, class MM>
+__device__ __forceinline__ void free_bwd(const ChainTables<T> &P, const MM &M, const ChainFree &f, bool fuse_acc = false)
 {
     cptr<T> Ic = P.consts + f.bofs;  // bias inertia (ChainLink::bofs)
     cptr<T> Ib = P.consts + f.iofs;
@@ -1496,8 +1512,8 @@ __device__ __forceinline__ void free_bwd(const ChainTables<T> &P, const ChainMem
 
 // (y0 in registers: the tail of free_bwd when the two segments are fused, ChainDev::fuse; the base's seven positions are requested by
 // free_acc_inputs -- in the fused segment at its very start, next to the backward segment's own rows: one wait instead of two)
-template <class T>
-__device__ __forceinline__ void free_acc_inputs(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f, T (&o)[4], T (&r)[3])
+template <class T, class MM>
+__device__ __forceinline__ void free_acc_inputs(const ChainTables<T> &P, const MM &M, const ChainFree &f, T (&o)[4], T (&r)[3])
 {
     const int nori = P.ori_repr == 0 ? 4 : 3;
 #pragma unroll
@@ -1527,8 +1543,8 @@ __device__ __forceinline__ void free_acc_core(const ChainTables<T> &P, const Cha
         M.lds_st(f.lds_va, va);
     }
 }
-template <class T>
-__device__ __forceinline__ void free_acc(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f)
+template <class T, class MM>
+__device__ __forceinline__ void free_acc(const ChainTables<T> &P, const MM &M, const ChainFree &f)
 {
     T y0[6], o[4], r[3], vb[6];
     M.glb_ld(f.glb_y0, y0);
@@ -1691,13 +1707,14 @@ template hipError_t launch_aba_gen1<double>(const ChainDev<double> &, int, int, 
 // ---------------------------------------------------------------------------------------------------------------
 // MODE 1: the program has differential clusters (ChainDiff).  A kernel variant of its own, so that the models without them
 // (every URDF robot of the reference) keep the register allocation of the plain run / pair / free code.  MODE 2: the program
-// has generic clusters (ChainGen; gen_segments.h) and possibly differentials: translation unit 2.
+// has generic clusters (ChainGen; gen_segments.h) and possibly differentials: translation unit 2.  MODE kModeInReg: the program of MODE 0
+// with the tile's inputs held in registers (ChainMemR above; launch_aba_chain decides).
 template <class T, int WPS, int MODE>
 __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, const T *__restrict__ q, const T *__restrict__ qd,
                                                              const T *__restrict__ tau, T *__restrict__ ydd, size_t B,
                                                              T *__restrict__ scratch)
 {
-    constexpr bool DIFF = MODE >= 1, GEN = MODE == 2;
+    constexpr bool DIFF = MODE == 1 || MODE == 2, GEN = MODE == 2, INREG = MODE == kModeInReg;
     ChainTables<T> P;
     P.segs = (cptr<ChainSeg>)DP.segs;
     P.links = (cptr<ChainLink>)DP.links;
@@ -1717,7 +1734,7 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
     const int lane = threadIdx.x;
     // wave slab: [nq + 2 nv input rows][n_glb_slots rows], 64 scalars per row
     T *slab = scratch + (size_t)blockIdx.x * (size_t)(DP.n_glb_slots + P.nq + 2 * P.nv) * kWave;
-    ChainMem<T> M;
+    std::conditional_t<INREG, ChainMemR<T>, ChainMem<T>> M;
     M.lane = lane;
     M.lane_b = (unsigned)lane * (unsigned)sizeof(T);
     M.gmul = 1;
@@ -1734,7 +1751,8 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t left = B - tile * kWave;
         const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
-        stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
+        if constexpr (INREG) stage_inputs_reg<kInRegCols>(q, qd, tau, tile, rows_valid, P.nq, P.nv, M.rq, M.rqd, M.rx, lane, DP.lds_bytes);
+        else stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
         if (DP.fuse & 1) {  // the floating base's velocity: from the lane's row of the staged block (still there) to its LDS slot
             const T *mine = reinterpret_cast<const T *>(grbda_smem) + (kWave * P.nq + lane * P.nv + DP.stage_v_index);
             T v[6];
@@ -2401,6 +2419,12 @@ hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const
             return launch_aba_chain_diff_f64(P, q, qd, tau, ydd, B, scratch, grid, lds_bytes, stream);  // (unit 1, below)
         } else {
             hipLaunchKernelGGL((aba_chain_kernel<T, 2, 1>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
+            return hipGetLastError();
+        }
+    }
+    if constexpr (sizeof(T) == 4) {
+        if (chain_inputs_in_registers(sizeof(T), P.n_gens, P.n_diffs, P.sv_global, P.nq, P.nv)) {
+            hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
             return hipGetLastError();
         }
     }
@@ -3173,6 +3197,7 @@ hipError_t set_max_dynamic_lds_chain()
 {
     const void *const kernels[] = {
         reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 0>), reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 1>),
+        reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, kModeInReg>),
         reinterpret_cast<const void *>(&aba_chain_kernel<double, 2, 0>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<float, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<float, 1, false>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<double, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<double, 1, false>),

@@ -469,6 +469,70 @@ __device__ __forceinline__ void stage_inputs(const T *__restrict__ q, const T *_
     }
 }
 
+// The prologue of the kernel that keeps a tile's inputs in registers (chain_kernels.hip, ChainMemR): the same asynchronous copies, then
+// every lane reads ITS OWN row of each staged block into a per-lane register vector of N entries -- 16-byte reads where
+// stage_transpose uses them, 4-byte reads otherwise (an odd row stride: conflict-free).  No slab row is written.  The loops are
+// unrolled over all N entries with a wave-uniform test per read, so that every index is a constant; entries from ncols on keep what
+// they held.  When LDS holds all three blocks at once they are still there when this returns (the caller may read the base's
+// velocity from them).  Needs nq, nv <= N (devplan.h, chain_inputs_in_registers).
+template <class T, int N, class ROW>
+__device__ __forceinline__ void stage_row_regs(int ncols, unsigned lds_byte_off, ROW &r, int lane)
+{
+    const T *stage = reinterpret_cast<const T *>(grbda_smem + lds_byte_off);
+    constexpr int V = 16 / (int)sizeof(T);
+    static_assert(N % V == 0, "whole 16-byte reads");
+    if ((ncols % V) == 0 && (lds_byte_off % 16u) == 0) {
+        struct alignas(16) Vec { T v[V]; };
+        const Vec *rows = reinterpret_cast<const Vec *>(stage + lane * ncols);
+#pragma unroll
+        for (int c = 0; c < N; c += V) {
+            if (c < ncols) {
+                const Vec x = rows[c / V];
+#pragma unroll
+                for (int k = 0; k < V; k++) r[c + k] = x.v[k];
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < N; c++)
+        if (c < ncols) r[c] = stage[lane * ncols + c];
+}
+template <int N, class T, class ROW>
+__device__ __forceinline__ void stage_inputs_reg(const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ x, size_t tile,
+                                                 int rows_valid, int nq, int nv, ROW &rq, ROW &rqd, ROW &rx, int lane, int lds_bytes)
+{
+    const unsigned bq = (unsigned)(kWave * nq) * (unsigned)sizeof(T), bv = (unsigned)(kWave * nv) * (unsigned)sizeof(T);
+    if ((int)(bq + 2 * bv) <= lds_bytes) {
+        stage_issue(q, tile, rows_valid, nq, 0u, lane);
+        stage_issue(qd, tile, rows_valid, nv, bq, lane);
+        stage_issue(x, tile, rows_valid, nv, bq + bv, lane);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wave_lds_fence();
+        stage_row_regs<T, N>(nq, 0u, rq, lane);
+        stage_row_regs<T, N>(nv, bq, rqd, lane);
+        stage_row_regs<T, N>(nv, bq + bv, rx, lane);
+        wave_lds_fence();
+    } else {
+        // LDS too small for the whole tile: one array at a time (see stage_inputs)
+        stage_issue(q, tile, rows_valid, nq, 0u, lane);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wave_lds_fence();
+        stage_row_regs<T, N>(nq, 0u, rq, lane);
+        wave_lds_fence();
+        stage_issue(qd, tile, rows_valid, nv, 0u, lane);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wave_lds_fence();
+        stage_row_regs<T, N>(nv, 0u, rqd, lane);
+        wave_lds_fence();
+        stage_issue(x, tile, rows_valid, nv, 0u, lane);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wave_lds_fence();
+        stage_row_regs<T, N>(nv, 0u, rx, lane);
+        wave_lds_fence();
+    }
+}
+
 // Tile epilogue: the nv result rows of the slab ([coordinate][state]) become the tile's [state][coordinate]
 // block of the output array, transposed through LDS (free again: the tile's state is dead) so that the
 // global stores are contiguous.

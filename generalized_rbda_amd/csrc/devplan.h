@@ -105,6 +105,15 @@ struct ChainDev {
     unsigned long long *bad_count;
     T a_root[6];
 };
+// aba_chain_kernel<float, 2, kModeInReg>: the plain program (no differentials, no generic clusters) with every lane's q, qd and tau in
+// three register arrays of kInRegCols entries instead of slab rows (chain_kernels.hip, ChainMemR).  Which launch runs it -- ONE rule,
+// read by launch_aba_chain and by grbda_kernel_name: fp32, [sin, cos, v] blocks in LDS, at most kInRegCols columns per input.
+constexpr int kInRegCols = 32;
+constexpr int kModeInReg = 3;
+inline bool chain_inputs_in_registers(size_t elem, int n_gens, int n_diffs, int sv_global, int nq, int nv)
+{
+    return elem == 4 && n_gens == 0 && n_diffs == 0 && !sv_global && nq <= kInRegCols && nv <= kInRegCols;
+}
 template <class T>
 hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch, int grid,
                             size_t lds_bytes, hipStream_t stream);
