@@ -11,7 +11,7 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import SIGNATURES, VJP_SIGNATURES
+from ._abi import SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
@@ -62,7 +62,8 @@ def lib() -> ctypes.CDLL:
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
-    for name, (restype, argtypes) in VJP_SIGNATURES.items():
+    # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule
+    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
@@ -140,7 +141,118 @@ class _VjpMethods:
         return self._ad(False, q, qd, ydd)
 
 
-class Plan(_VjpMethods):
+class _StepVjpMethods:
+    """The vector-Jacobian products of integrate, step and rollout and the autograd functions built on them (include/grbda_hip_step_vjp.h),
+    kept apart like _VjpMethods.  Every position cotangent and gradient is [..., nv], along the tangent step of fd_dq; tangent_cotangent
+    takes an ambient [..., nq] cotangent there."""
+
+    @staticmethod
+    def _wanted(want, names):
+        if not want or any(k not in names for k in want):
+            raise ValueError("want must name at least one of " + ", ".join(f'"{k}"' for k in names) + " and nothing else")
+
+    @staticmethod
+    def _cotangents(g_q, g_qd):
+        if g_q is None and g_qd is None:
+            raise ValueError("g_q and g_qd cannot both be None")
+
+    def integrate_vjp(self, qd_next, dt: float, g_q=None, g_qd=None, want=("q", "qd", "ydd"), stream=None):
+        """The cotangents (g_q, g_qd) of the state AFTER integrate pulled back to (q, qd, ydd) (grbda_integrate_vjp_*): a dict of [B, nv]
+        tensors for the names in `want`.  qd_next[B, nv]: the velocities integrate / step returned; either cotangent may be None (zero).
+        One kernel launch; q does not enter."""
+        names = ("q", "qd", "ydd")
+        self._wanted(want, names)
+        self._cotangents(g_q, g_qd)
+        outs = {"grad_" + k: self.nv if k in want else None for k in names}
+        got = self._call("integrate_vjp", stream, dict(qd_next=(qd_next, self.nv), g_q=(g_q, self.nv), g_qd=(g_qd, self.nv)), outs,
+                         ("qd_next", float(dt), "g_q", "g_qd") + tuple(outs), skip_empty=True)
+        return {k: o for k, o in zip(names, got) if o is not None}
+
+    def step_vjp(self, q, qd, tau, qd_next, dt: float, g_q=None, g_qd=None, want=("q", "qd", "tau"), step: float = 1e-6, stream=None):
+        """The cotangents of the state after step(q, qd, tau, dt) pulled back to (q, qd, tau) (grbda_step_vjp_*): integrate_vjp, fd_vjp
+        on its grad_ydd, and the two sums, on one stream -- a dict of [B, nv] tensors for the names in `want`.  "tau" alone runs no
+        derivative recursion; `step` as in fd_vjp."""
+        names = ("q", "qd", "tau")
+        self._wanted(want, names)
+        self._cotangents(g_q, g_qd)
+        outs = {"grad_" + k: self.nv if k in want else None for k in names}
+        ins = dict(self._state(q, qd=qd, tau=tau, qd_next=qd_next), g_q=(g_q, self.nv), g_qd=(g_qd, self.nv))
+        got = self._call("step_vjp", stream, ins, outs, ("q", "qd", "tau", "qd_next", float(dt), "g_q", "g_qd", float(step)) + tuple(outs),
+                         skip_empty=True)
+        return {k: o for k, o in zip(names, got) if o is not None}
+
+    def rollout_vjp(self, q0, qd0, tau, dt: float, q_traj, qd_traj, g_q=None, g_qd=None, want=("q", "qd", "tau"), step: float = 1e-6,
+                    stream=None):
+        """The cotangents of the states of rollout(q0, qd0, tau, dt, T, record=True) pulled back to (q0, qd0, tau) (grbda_rollout_vjp_*):
+        the loop of step_vjp from state T to state 0, inside the library.  q_traj[T, B, nq], qd_traj[T, B, nv]: the recorded states
+        1 .. T (T is read there).  g_q, g_qd: [B, nv], cotangents of state T alone, or [T, B, nv] for states 1 .. T; either may be
+        None.  Returns a dict for the names in `want`: "q", "qd" [B, nv] of state 0 and "tau", shaped like tau (one tau held for all
+        steps: the sum over the steps)."""
+        names = ("q", "qd", "tau")
+        self._wanted(want, names)
+        self._cotangents(g_q, g_qd)
+        T = qd_traj.shape[0] if qd_traj.dim() == 3 else 0  # (any other rank fails the shape rule below)
+        per_step = lambda t: (T, "B", self.nv) if t is not None and t.dim() == 3 else self.nv
+        g_shape = per_step(g_q if g_q is not None else g_qd)
+        ins = dict(self._state(q0, qd0=qd0), q_traj=(q_traj, (T, "B", self.nq)), qd_traj=(qd_traj, (T, "B", self.nv)), tau=(tau, per_step(tau)),
+                   g_q=(g_q, g_shape), g_qd=(g_qd, g_shape))
+        outs = dict(grad_q=self.nv if "q" in want else None, grad_qd=self.nv if "qd" in want else None,
+                    grad_tau=per_step(tau) if "tau" in want else None)
+        got = self._call("rollout_vjp", stream, ins, outs,
+                         ("q", "qd0", "q_traj", "qd_traj", "tau", T if tau.dim() == 3 else 1, float(dt), T, "g_q", "g_qd",
+                          T if g_shape != self.nv else 1, float(step)) + tuple(outs), skip_empty=True)
+        return {k: o for k, o in zip(names, got) if o is not None}
+
+    def tangent_cotangent(self, q, g):
+        """The pull-back of an ambient cotangent g[..., nq] of the positions q[..., nq] through the tangent step at q: [..., nv], entry i
+        = <g, d plus(q, d) / d d_i at d = 0>.  Explicit coordinates: the identity; base position: R(quat) g_p, into body axes; base
+        rotation: entry i = (quat x (0, e_i)) . g_quat / 2.  Plain torch operations (CPU tensors too).  Plans with implicit clusters
+        raise ValueError: their tangent step re-projects the dependent coordinates."""
+        import torch
+
+        from .modeldesc import C_FREE, C_LOOP_POSITION, C_TRIG_POLY
+        from .states import parse_clusters
+
+        if tuple(q.shape) != tuple(g.shape) or q.shape[-1] != self.nq:
+            raise ValueError(f"expected q[..., {self.nq}] and g of the same shape")
+        out = g.new_zeros(tuple(g.shape[:-1]) + (self.nv,))
+        for c in parse_clusters(self._blob)["clusters"]:
+            qi, npos, vi, nvel, ctype = c[3], c[4], c[5], c[6], c[9]
+            if ctype in (C_LOOP_POSITION, C_TRIG_POLY):
+                raise ValueError("tangent_cotangent does not cover plans with implicit clusters")
+            if ctype != C_FREE or npos != 7:  # (a roll-pitch-yaw base steps like explicit coordinates: q + dq)
+                out[..., vi:vi + nvel] = g[..., qi:qi + nvel]
+                continue
+            e0, e1, e2, e3 = q[..., qi + 3:qi + 7].unbind(-1)
+            # R(quat)^T, body axes into world axes, as integrate applies it; R g_p is its transpose times g_p
+            M = torch.stack([1 - 2 * (e2 * e2 + e3 * e3), 2 * (e1 * e2 - e0 * e3), 2 * (e1 * e3 + e0 * e2),
+                             2 * (e1 * e2 + e0 * e3), 1 - 2 * (e1 * e1 + e3 * e3), 2 * (e2 * e3 - e0 * e1),
+                             2 * (e1 * e3 - e0 * e2), 2 * (e2 * e3 + e0 * e1), 1 - 2 * (e1 * e1 + e2 * e2)], dim=-1).reshape(tuple(q.shape[:-1]) + (3, 3))
+            out[..., vi + 3:vi + 6] = (M * g[..., qi:qi + 3].unsqueeze(-1)).sum(dim=-2)
+            w, v = q[..., qi + 3:qi + 4], q[..., qi + 4:qi + 7]
+            gw, gv = g[..., qi + 3:qi + 4], g[..., qi + 4:qi + 7]
+            out[..., vi:vi + 3] = 0.5 * (w * gv - gw * v + torch.linalg.cross(gv, v, dim=-1))
+        return out
+
+    def _step_ad_check(self, q, entry):
+        if q.requires_grad and self.nq != self.nv:
+            raise ValueError(f"q requires grad on a plan with nq = {self.nq} != nv = {self.nv} (a quaternion base or implicit clusters): a gradient "
+                             f"along the tangent step has no unique pull-back to the nq position coordinates -- call {entry} for the tangent gradient")
+
+    def step_ad(self, q, qd, tau, dt: float):
+        """step as a differentiable torch function: (q_next, qd_next) with the bits of step; backward is step_vjp for the inputs that
+        require grad, the ambient cotangent of q_next pulled back with tangent_cotangent.  A gradient for q only on plans with nq == nv."""
+        self._step_ad_check(q, "step_vjp")
+        return _step_autograd_function(False).apply(self, q, qd, tau, float(dt), 1)
+
+    def rollout_ad(self, q, qd, tau, dt: float, T: int):
+        """rollout(record=True) as a differentiable torch function: (q_traj[T, B, nq], qd_traj[T, B, nv]) with its bits; backward is
+        rollout_vjp; q as in step_ad."""
+        self._step_ad_check(q, "rollout_vjp")
+        return _step_autograd_function(True).apply(self, q, qd, tau, float(dt), int(T))
+
+
+class Plan(_VjpMethods, _StepVjpMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):
@@ -635,6 +747,44 @@ def _autograd_function(forward: bool):
         Dynamics.__name__ = Dynamics.__qualname__ = "ForwardDynamics" if forward else "InverseDynamics"
         _ad_functions[forward] = Dynamics
     return _ad_functions[forward]
+
+
+def _step_autograd_function(rollout: bool):
+    """the torch.autograd.Function behind Plan.step_ad / rollout_ad, made on first use like _autograd_function"""
+    key = ("step", rollout)
+    if key not in _ad_functions:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        names = ("q", "qd", "tau")
+
+        class Step(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, plan, q, qd, tau, dt, T):
+                ctx.plan, ctx.dt = plan, dt
+                if rollout:
+                    q_out, qd_out = plan.rollout(q, qd, tau, dt, T, record=True)[3:]
+                else:
+                    q_out, qd_out = plan.step(q, qd, tau, dt)[:2]
+                ctx.save_for_backward(q, qd, tau, q_out, qd_out)
+                return q_out, qd_out
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, g_q_ambient, g_qd):
+                q, qd, tau, q_out, qd_out = ctx.saved_tensors
+                plan = ctx.plan
+                want = tuple(k for k, needed in zip(names, ctx.needs_input_grad[1:4]) if needed)
+                g_q = plan.tangent_cotangent(q_out, g_q_ambient)
+                if rollout:
+                    got = plan.rollout_vjp(q, qd, tau, ctx.dt, q_out, qd_out, g_q, g_qd, want=want)
+                else:
+                    got = plan.step_vjp(q, qd, tau, qd_out, ctx.dt, g_q, g_qd, want=want)
+                return (None,) + tuple(got.get(k) for k in names) + (None, None)
+
+        Step.__name__ = Step.__qualname__ = "Rollout" if rollout else "Step"
+        _ad_functions[key] = Step
+    return _ad_functions[key]
 
 
 def vjp_contract_launch(nv: int, B: int, n_cu: int):

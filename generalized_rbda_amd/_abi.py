@@ -91,3 +91,16 @@ for _stem, _args in _VJP_PAIRS.items():
     VJP_SIGNATURES[f"grbda_{_stem}_f64"] = VJP_SIGNATURES[f"grbda_{_stem}_f32"] = _args
     VJP_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
 VJP_SIGNATURES = {name: (c_int, args) for name, args in VJP_SIGNATURES.items()}
+
+# include/grbda_hip_step_vjp.h, the vector-Jacobian products of integrate, step and rollout: the third table, applied by `lib()` after the
+# other two; tests/test_step_vjp_args_cpu.py holds it to that header
+_STEP_VJP_PAIRS = {
+    "integrate_vjp": (P, P, D, P, P, P, P, P, *TAIL),                    # qd_next dt g_q_next g_qd_next grad_q grad_qd grad_ydd
+    "step_vjp": (P, P, P, P, P, D, P, P, D, P, P, P, *TAIL),             # q qd tau qd_next dt g_q_next g_qd_next step grad_q grad_qd grad_tau
+    "rollout_vjp": (P, P, P, P, P, P, I, D, I, P, P, I, D, P, P, P, *TAIL),  # q0 qd0 q_traj qd_traj tau tau_steps dt T g_q g_qd g_steps step grad_q0 grad_qd0 grad_tau
+}
+STEP_VJP_SIGNATURES = {}
+for _stem, _args in _STEP_VJP_PAIRS.items():
+    STEP_VJP_SIGNATURES[f"grbda_{_stem}_f64"] = STEP_VJP_SIGNATURES[f"grbda_{_stem}_f32"] = _args
+STEP_VJP_SIGNATURES["grbda_step_vjp_host_f64"] = _STEP_VJP_PAIRS["step_vjp"][:-1]
+STEP_VJP_SIGNATURES = {name: (c_int, args) for name, args in STEP_VJP_SIGNATURES.items()}

@@ -15,6 +15,7 @@
 
 #include "../../include/grbda_hip.h"
 #include "../../include/grbda_hip_vjp.h"
+#include "../../include/grbda_hip_step_vjp.h"
 #include "../../include/grbda_model_desc.h"
 #include "devplan.h"
 
@@ -131,6 +132,7 @@ struct grbda_plan {
     mutable SlabPool work_cvt;   // fp64 copies of fp32 inputs (through_f64)
     mutable SlabPool work_proj;  // projection_run (called from inside the users of `work`)
     mutable SlabPool work_vjp;   // vjp_run (its id_derivs stage carves `work` on the difference routes)
+    mutable SlabPool work_step_vjp;  // step_vjp_run / rollout_vjp (they call vjp_run, which carves work_vjp)
     // the chunk decision of the last eager analytic_derivs call per (device, stream): a capture of the same call replays it
     struct DerivChunk {
         size_t B = 0, per_state_bytes = 0, chunk = 0;
@@ -2810,6 +2812,201 @@ int vjp_host_f64(const grbda_plan *p, bool forward, const double *q, const doubl
     return st.run([&] { return vjp_run<double>(p, forward, bq, bqd, bx, bg, step, b1, b2, b3, b4, B, device, nullptr); });
 }
 
+// ---- vector-Jacobian products of integrate, step and rollout (include/grbda_hip_step_vjp.h; step_vjp_kernels.hip) ---------------------
+// The plans the three families refuse: what grbda_step_* refuses, and every implicit cluster (the Jacobian of the Newton re-projection is
+// not built).  *base: the index of the quaternion base's cluster record, -1 for a plan without one.
+int step_vjp_plan(const grbda_plan *p, int *base)
+{
+    *base = -1;
+    const std::vector<ClusterRec> &cl = p->host.lay64.clusters;
+    for (size_t c = 0; c < cl.size(); c++) {
+        if (cl[c].kind != CK_FREE) continue;
+        if (p->host.ori_repr != 0)
+            return set_err(GRBDA_EUNSUPPORTED, "time stepping covers the quaternion floating base only: the rate map of a roll-pitch-yaw base is not built");
+        if (*base >= 0 || cl[c].n != 6 || cl[c].v_index + 6 > p->host.nv) return set_err(GRBDA_EUNSUPPORTED, "the step's vector-Jacobian product covers one floating base");
+        *base = static_cast<int>(c);
+    }
+    if (has_loop_clusters(p))
+        return set_err(GRBDA_EUNSUPPORTED, "the vector-Jacobian products of integrate, step and rollout do not cover implicit clusters: the Jacobian of "
+                                           "the Newton re-projection is not built");
+    return GRBDA_OK;
+}
+// the rules the three share once their pointers are sorted into inputs and outputs: a cotangent, an output, a finite dt, no overlap, the
+// plan, and the step where grbda_aba_vjp_* will take differences in q (need_q)
+template <size_t NI, size_t NO>
+int step_vjp_rules(const grbda_plan *p, const void *g_q, const void *g_qd, double dt, bool differentiates, bool need_q, double step,
+                   const void *const (&in)[NI], const size_t (&in_bytes)[NI], const void *const (&out)[NO], const size_t (&out_bytes)[NO], int *base)
+{
+    if (!g_q && !g_qd) return set_err(GRBDA_EINVAL, "both cotangents are null");
+    bool any = false;
+    for (const void *o : out) any = any || o;
+    if (!any) return set_err(GRBDA_EINVAL, "no output asked for");
+    if (!std::isfinite(dt)) return set_err(GRBDA_EINVAL, "dt is not finite");
+    if (int rc = no_overlap(in, in_bytes, out, out_bytes)) return rc;
+    if (int rc = step_vjp_plan(p, base)) return rc;
+    if (differentiates && need_q && !analytic_covers(p) && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+    return GRBDA_OK;
+}
+template <class T>
+int integrate_vjp_args(const grbda_plan *p, const T *qd_next, double dt, const T *g_q, const T *g_qd, const T *grad_q, const T *grad_qd,
+                       const T *grad_ydd, size_t B, int *base)
+{
+    if (!qd_next) return set_err(GRBDA_EINVAL, "null argument");
+    const size_t bv = B * p->host.nv * sizeof(T);
+    const void *const in[3] = {qd_next, g_q, g_qd}, *const out[3] = {grad_q, grad_qd, grad_ydd};
+    const size_t in_bytes[3] = {bv, bv, bv}, out_bytes[3] = {bv, bv, bv};
+    return step_vjp_rules(p, g_q, g_qd, dt, false, false, 0.0, in, in_bytes, out, out_bytes, base);
+}
+template <class T>
+int step_vjp_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *g_q, const T *g_qd, double step,
+                  const T *grad_q, const T *grad_qd, const T *grad_tau, size_t B, int *base)
+{
+    if (!q || !qd || !tau || !qd_next) return set_err(GRBDA_EINVAL, "null argument");
+    const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
+    const void *const in[6] = {q, qd, tau, qd_next, g_q, g_qd}, *const out[3] = {grad_q, grad_qd, grad_tau};
+    const size_t in_bytes[6] = {bq, bv, bv, bv, bv, bv}, out_bytes[3] = {bv, bv, bv};
+    return step_vjp_rules(p, g_q, g_qd, dt, true, grad_q != nullptr, step, in, in_bytes, out, out_bytes, base);
+}
+template <class T>
+hipError_t integrate_vjp_launch(const DeviceTables &t, int base, const T *qd_next, double dt, const T *g_q, const T *g_qd, T *grad_q, T *grad_qd,
+                                T *grad_ydd, int nv, size_t B, void *stream)
+{
+    // (the record of the fp64 layout: the cluster's v_index is the same in every layout)
+    return launch_integrate_vjp<T>(base >= 0 ? t.clusters[1] + base : nullptr, qd_next, static_cast<T>(dt), g_q, g_qd, grad_q, grad_qd, grad_ydd, nv, B,
+                                   static_cast<hipStream_t>(stream));
+}
+constexpr size_t kStepVjpRows = 5, kRolloutVjpRows = 10;  // [B][nv] arrays of the slab: one step's; with the loop's adjoints behind them
+// The three stages of grbda_step_vjp_* (arguments checked, B > 0, device found); `w`: kStepVjpRows [B][nv] arrays.  Every sum is one
+// launch of vjp_add_kernel, here and in the loop of the rollout.
+template <class T>
+int step_vjp_run(const grbda_plan *p, const DeviceTables &t, int base, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *g_q,
+                 const T *g_qd, double step, T *grad_q, T *grad_qd, T *grad_tau, size_t B, int device, void *stream, T *w)
+{
+    const size_t n = B * p->host.nv;
+    const int nvi = static_cast<int>(p->host.nv);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    T *i_q = grad_q ? w : nullptr, *i_qd = grad_qd ? w + n : nullptr, *g_ydd = w + 2 * n, *a_q = grad_q ? w + 3 * n : nullptr,
+      *a_qd = grad_qd ? w + 4 * n : nullptr;
+    if (hipError_t e = integrate_vjp_launch<T>(t, base, qd_next, dt, g_q, g_qd, i_q, i_qd, g_ydd, nvi, B, stream); e != hipSuccess)
+        return hip_err(e, "integrate vjp launch");
+    if (int rc = vjp_run<T>(p, true, q, qd, tau, g_ydd, step, a_q, a_qd, grad_tau, nullptr, B, device, stream)) return rc;
+    hipError_t e = hipSuccess;
+    if (grad_q) e = launch_vjp_add<T>(i_q, a_q, grad_q, n, hs);
+    if (e == hipSuccess && grad_qd) e = launch_vjp_add<T>(i_qd, a_qd, grad_qd, n, hs);
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "vjp add launch");
+}
+template <class T>
+int step_vjp_slab(const grbda_plan *p, size_t rows, size_t B, int device, void *stream, T **w)
+{
+    void *ptr = nullptr;
+    if (int rc = ensure_work(p, p->work_step_vjp, device, stream, rows * B * p->host.nv * sizeof(T) + 256, &ptr)) return rc;
+    *w = static_cast<T *>(ptr);
+    return GRBDA_OK;
+}
+template <class T>
+int integrate_vjp(const grbda_plan *p, const T *qd_next, double dt, const T *g_q, const T *g_qd, T *grad_q, T *grad_qd, T *grad_ydd, size_t B, int device,
+                  void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    int base = -1;
+    if (int rc = integrate_vjp_args<T>(p, qd_next, dt, g_q, g_qd, grad_q, grad_qd, grad_ydd, B, &base)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    hipError_t e = integrate_vjp_launch<T>(*t, base, qd_next, dt, g_q, g_qd, grad_q, grad_qd, grad_ydd, static_cast<int>(p->host.nv), B, stream);
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate vjp launch");
+}
+template <class T>
+int step_vjp(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *g_q, const T *g_qd, double step, T *grad_q,
+             T *grad_qd, T *grad_tau, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    int base = -1;
+    if (int rc = step_vjp_args<T>(p, q, qd, tau, qd_next, dt, g_q, g_qd, step, grad_q, grad_qd, grad_tau, B, &base)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    T *w = nullptr;
+    if (int rc = step_vjp_slab<T>(p, kStepVjpRows, B, device, stream, &w)) return rc;
+    return step_vjp_run<T>(p, *t, base, q, qd, tau, qd_next, dt, g_q, g_qd, step, grad_q, grad_qd, grad_tau, B, device, stream, w);
+}
+int step_vjp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt, const double *g_q,
+                      const double *g_qd, double step, double *grad_q, double *grad_qd, double *grad_tau, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    int base = -1;
+    if (int rc = step_vjp_args<double>(p, q, qd, tau, qd_next, dt, g_q, g_qd, step, grad_q, grad_qd, grad_tau, B, &base)) return rc;
+    if (B == 0) return GRBDA_OK;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;  // `device` current before anything is allocated on it
+    HostStage st;
+    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bt = st.in(tau, B * nv), *bn = st.in(qd_next, B * nv);
+    const double *bgq = g_q ? st.in(g_q, B * nv) : nullptr, *bgqd = g_qd ? st.in(g_qd, B * nv) : nullptr;
+    double *o1 = grad_q ? st.out(grad_q, B * nv) : nullptr, *o2 = grad_qd ? st.out(grad_qd, B * nv) : nullptr,
+           *o3 = grad_tau ? st.out(grad_tau, B * nv) : nullptr;
+    return st.run([&] {
+        double *w = nullptr;
+        if (int rc = step_vjp_slab<double>(p, kStepVjpRows, B, device, nullptr, &w)) return rc;
+        return step_vjp_run<double>(p, *t, base, bq, bqd, bt, bn, dt, bgq, bgqd, step, o1, o2, o3, B, device, nullptr, w);
+    });
+}
+// The loop of grbda_step_vjp_* from state T back to state 0.  The adjoint lambda_k is the step's output gamma itself, or gamma + g[k] in a
+// second pair of arrays where the caller has a cotangent for state k; the last step writes the caller's grad_q0 / grad_qd0.  grad_tau: the
+// step writes row k, or -- one tau held for all steps -- the first step (k = T-1) writes grad_tau and every later one is added to it.
+template <class T>
+int rollout_vjp(const grbda_plan *p, const T *q0, const T *qd0, const T *q_traj, const T *qd_traj, const T *tau, int tau_steps, double dt, int n_steps,
+                const T *g_q, const T *g_qd, int g_steps, double step, T *grad_q0, T *grad_qd0, T *grad_tau, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (!q0 || !qd0 || !q_traj || !qd_traj || !tau) return set_err(GRBDA_EINVAL, "null argument");
+    if (n_steps < 0) return set_err(GRBDA_EINVAL, "T is negative");
+    if (tau_steps != 1 && tau_steps != n_steps) return set_err(GRBDA_EINVAL, "tau_steps must be 1 or T");
+    if (g_steps != 1 && g_steps != n_steps) return set_err(GRBDA_EINVAL, "g_steps must be 1 or T");
+    const size_t nq = p->host.nq, nv = p->host.nv, bq = B * nq * sizeof(T), bv = B * nv * sizeof(T), steps = static_cast<size_t>(n_steps);
+    const size_t ts = static_cast<size_t>(tau_steps), gs = static_cast<size_t>(g_steps);
+    const void *const in[7] = {q0, qd0, q_traj, qd_traj, tau, g_q, g_qd}, *const out[3] = {grad_q0, grad_qd0, grad_tau};
+    const size_t in_bytes[7] = {bq, bv, steps * bq, steps * bv, ts * bv, gs * bv, gs * bv}, out_bytes[3] = {bv, bv, ts * bv};
+    int base = -1;
+    // (the steps k >= 1 hand their position gradient on, whatever the caller asks of state 0)
+    if (int rc = step_vjp_rules(p, g_q, g_qd, dt, true, grad_q0 || n_steps > 1, step, in, in_bytes, out, out_bytes, &base)) return rc;
+    if (B == 0 || n_steps == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    T *w = nullptr;
+    if (int rc = step_vjp_slab<T>(p, kRolloutVjpRows, B, device, stream, &w)) return rc;
+    const size_t n = B * nv;
+    T *gam_q = w + kStepVjpRows * n, *gam_qd = gam_q + n, *sum_q = gam_qd + n, *sum_qd = sum_q + n, *gam_tau = sum_qd + n;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const T *lam_q = g_q ? g_q + (g_steps > 1 ? (steps - 1) * n : 0) : nullptr, *lam_qd = g_qd ? g_qd + (g_steps > 1 ? (steps - 1) * n : 0) : nullptr;
+    for (size_t k = steps; k-- > 0;) {
+        const T *qk = k ? q_traj + (k - 1) * B * nq : q0, *qdk = k ? qd_traj + (k - 1) * n : qd0, *tk = tau + (tau_steps > 1 ? k * n : 0);
+        T *oq = k ? gam_q : grad_q0, *oqd = k ? gam_qd : grad_qd0;
+        T *otau = !grad_tau ? nullptr : (tau_steps > 1 ? grad_tau + k * n : (k == steps - 1 ? grad_tau : gam_tau));
+        if (int rc = step_vjp_run<T>(p, *t, base, qk, qdk, tk, qd_traj + k * n, dt, lam_q, lam_qd, step, oq, oqd, otau, B, device, stream, w)) return rc;
+        hipError_t e = hipSuccess;
+        if (otau == gam_tau && grad_tau) e = launch_vjp_add<T>(grad_tau, gam_tau, grad_tau, n, hs);
+        lam_q = gam_q;
+        lam_qd = gam_qd;
+        if (k && g_steps > 1) {  // (state k's own cotangent is row k - 1)
+            if (e == hipSuccess && g_q) {
+                e = launch_vjp_add<T>(gam_q, g_q + (k - 1) * n, sum_q, n, hs);
+                lam_q = sum_q;
+            }
+            if (e == hipSuccess && g_qd) {
+                e = launch_vjp_add<T>(gam_qd, g_qd + (k - 1) * n, sum_qd, n, hs);
+                lam_qd = sum_qd;
+            }
+        }
+        if (e != hipSuccess) return hip_err(e, "vjp add launch");
+    }
+    return GRBDA_OK;
+}
+
 // the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
 template <class T>
 static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B)
@@ -3172,7 +3369,7 @@ void grbda_plan_free(grbda_plan *p)
         }
         for (int w = 0; w < kLayouts; w++) { (void)hipFree(t.acc_k[w]); (void)hipFree(t.clusters[w]); (void)hipFree(t.rnea_clusters[w]); (void)hipFree(t.bodies[w]); (void)hipFree(t.rnea_bodies[w]); }
     }
-    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj, &p->work_vjp})
+    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp})
         for (auto &kv : *m) {
             if (hipSetDevice(kv.first.first) != hipSuccess) continue;
             if (kv.second.ptr) (void)hipFree(kv.second.ptr);
@@ -3184,7 +3381,7 @@ void grbda_plan_free(grbda_plan *p)
 // (and of its spanning-tree plan) is checked first, so that a refused release frees nothing.
 static bool holds_capturing_slab(const grbda_plan *p)
 {
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp})
         for (auto &kv : *m)
             if (kv.second.ptr && is_capturing(kv.first.second)) return true;
     return p->span && holds_capturing_slab(p->span);
@@ -3197,7 +3394,7 @@ int grbda_plan_release_work(grbda_plan *p, unsigned long long *bytes_released)
     if (holds_capturing_slab(p))
         return set_err(GRBDA_EINVAL, "a stream of this plan is capturing: its work buffers cannot be released now");
     unsigned long long total = 0;
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp})
         for (auto &kv : *m) {
             if (!kv.second.ptr) continue;
             hipError_t e = hipSetDevice(kv.first.first);
@@ -3706,6 +3903,47 @@ int grbda_vjp_contract_launch(int nv, size_t nb, int n_cu, size_t *units, size_t
     if (units) *units = L.units;
     if (grid) *grid = L.grid;
     return GRBDA_OK;
+}
+int grbda_integrate_vjp_f64(const grbda_plan *p, const double *qd_next, double dt, const double *g_q_next, const double *g_qd_next, double *grad_q,
+                            double *grad_qd, double *grad_ydd, size_t B, int device, void *stream)
+{
+    return integrate_vjp<double>(p, qd_next, dt, g_q_next, g_qd_next, grad_q, grad_qd, grad_ydd, B, device, stream);
+}
+int grbda_integrate_vjp_f32(const grbda_plan *p, const float *qd_next, double dt, const float *g_q_next, const float *g_qd_next, float *grad_q,
+                            float *grad_qd, float *grad_ydd, size_t B, int device, void *stream)
+{
+    return integrate_vjp<float>(p, qd_next, dt, g_q_next, g_qd_next, grad_q, grad_qd, grad_ydd, B, device, stream);
+}
+int grbda_step_vjp_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt,
+                       const double *g_q_next, const double *g_qd_next, double step, double *grad_q, double *grad_qd, double *grad_tau, size_t B,
+                       int device, void *stream)
+{
+    return step_vjp<double>(p, q, qd, tau, qd_next, dt, g_q_next, g_qd_next, step, grad_q, grad_qd, grad_tau, B, device, stream);
+}
+int grbda_step_vjp_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, const float *qd_next, double dt, const float *g_q_next,
+                       const float *g_qd_next, double step, float *grad_q, float *grad_qd, float *grad_tau, size_t B, int device, void *stream)
+{
+    return step_vjp<float>(p, q, qd, tau, qd_next, dt, g_q_next, g_qd_next, step, grad_q, grad_qd, grad_tau, B, device, stream);
+}
+int grbda_step_vjp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt,
+                            const double *g_q_next, const double *g_qd_next, double step, double *grad_q, double *grad_qd, double *grad_tau,
+                            size_t B, int device)
+{
+    return step_vjp_host_f64(p, q, qd, tau, qd_next, dt, g_q_next, g_qd_next, step, grad_q, grad_qd, grad_tau, B, device);
+}
+int grbda_rollout_vjp_f64(const grbda_plan *p, const double *q0, const double *qd0, const double *q_traj, const double *qd_traj, const double *tau,
+                          int tau_steps, double dt, int T, const double *g_q, const double *g_qd, int g_steps, double step, double *grad_q0,
+                          double *grad_qd0, double *grad_tau, size_t B, int device, void *stream)
+{
+    return rollout_vjp<double>(p, q0, qd0, q_traj, qd_traj, tau, tau_steps, dt, T, g_q, g_qd, g_steps, step, grad_q0, grad_qd0, grad_tau, B, device,
+                               stream);
+}
+int grbda_rollout_vjp_f32(const grbda_plan *p, const float *q0, const float *qd0, const float *q_traj, const float *qd_traj, const float *tau,
+                          int tau_steps, double dt, int T, const float *g_q, const float *g_qd, int g_steps, double step, float *grad_q0,
+                          float *grad_qd0, float *grad_tau, size_t B, int device, void *stream)
+{
+    return rollout_vjp<float>(p, q0, qd0, q_traj, qd_traj, tau, tau_steps, dt, T, g_q, g_qd, g_steps, step, grad_q0, grad_qd0, grad_tau, B, device,
+                              stream);
 }
 int grbda_plan_span_dims(const grbda_plan *p, int *n_span_vel)
 {

@@ -279,6 +279,16 @@ template <class T>
 hipError_t launch_vjp_contract(const VjpLaunch &L, const T *Mq, const T *Mqd, const T *w_add, const T *w_sub, T sign, int nv, size_t nb, T *out_q,
                                T *out_qd, T *out_w, hipStream_t stream);
 
+// the manifold part of the step's vector-Jacobian product (step_vjp_kernels.hip, include/grbda_hip_step_vjp.h): the cotangents of the stepped
+// state pulled back through q' = q (+) dt qd', qd' = qd + dt ydd, over nb states.  `base`: the device record of the quaternion base's cluster
+// (its v_index is read there) or null for a plan without one.  g_q / g_qd may be null (zero), and so may every output.
+template <class T>
+hipError_t launch_integrate_vjp(const ClusterRec *base, const T *qd_next, T dt, const T *g_q, const T *g_qd, T *grad_q, T *grad_qd, T *grad_ydd,
+                                int nv, size_t nb, hipStream_t stream);
+// out[i] = a[i] + b[i] over n scalars: one rounding, operands in this order (out may be a or b)
+template <class T>
+hipError_t launch_vjp_add(const T *a, const T *b, T *out, size_t n, hipStream_t stream);
+
 // composite-rigid-body algorithm (crba_kernels.hip)
 template <class T>
 hipError_t launch_crba(const DevPlan<T> &P, const CrbaBody *cb, int n_clusters, int n_rows, const T *q, T *H, size_t B, T *scratch,
