@@ -11,7 +11,7 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES
+from ._abi import SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
@@ -63,7 +63,7 @@ def lib() -> ctypes.CDLL:
         fn.restype, fn.argtypes = restype, list(argtypes)
     # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
     # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule
-    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
@@ -252,7 +252,64 @@ class _StepVjpMethods:
         return _step_autograd_function(True).apply(self, q, qd, tau, float(dt), int(T))
 
 
-class Plan(_VjpMethods, _StepVjpMethods):
+class _WrenchMethods:
+    """Forward and inverse dynamics with sparse body wrenches (include/grbda_hip_wrench.h): kept apart from Plan's own methods as that
+    header is kept apart from grbda_hip.h.  They go through Plan._call like every other method; tests/test_wrench_gpu.py holds them to
+    the argument rules of the tensor methods (strided inputs, the one exception rule, a side stream)."""
+
+    @staticmethod
+    def _wrench_list(bodies, frame):
+        """the body list as the entry points take it: (n, bodies[n]), and the frame constant"""
+        if frame not in ("body", "world"):
+            raise ValueError('frame must be "body" or "world"')
+        n = len(bodies)
+        return n, (c_int * max(n, 1))(*[int(b) for b in bodies]), 0 if frame == "body" else 1
+
+    def forward_dynamics_wrench(self, q, qd, tau, bodies, wrench, frame="body", out=None, stream=None):
+        """Forward dynamics with external wrenches on a short list of bodies (grbda_aba_wrench_*; TreeModel::setExternalForces): returns
+        ydd[B, nv].  bodies: up to 16 plan body indices (a body may repeat: its wrenches add); wrench[B, n, 6]: the spatial force
+        [moment; force] on bodies[i], in the body's own frame at its origin (frame="body") or with the meaning of a row of f_ext
+        (frame="world").  No bodies: the plain forward dynamics, wrench may be None."""
+        n, arr, fr = self._wrench_list(bodies, frame)
+        return self._call("aba_wrench", stream, dict(self._state(q, qd=qd, tau=tau), wrench=(wrench, (n, 6))), dict(out=self.nv),
+                          ("q", "qd", "tau", n, arr, "wrench", fr, "out"), fixed=dict(out=(out, self.nv)))[0]
+
+    def inverse_dynamics_wrench(self, q, qd, ydd, bodies, wrench, frame="body", out=None, stream=None):
+        """Inverse dynamics with external wrenches on a short list of bodies (grbda_rnea_wrench_*): returns tau[B, nv]; the arguments
+        of forward_dynamics_wrench."""
+        n, arr, fr = self._wrench_list(bodies, frame)
+        return self._call("rnea_wrench", stream, dict(self._state(q, qd=qd, ydd=ydd), wrench=(wrench, (n, 6))), dict(out=self.nv),
+                          ("q", "qd", "ydd", n, arr, "wrench", fr, "out"), fixed=dict(out=(out, self.nv)))[0]
+
+    def wrench_kernel_name(self, algo: str, dtype: str, bodies, frame: str, B: int, device: int = 0) -> str:
+        """The kernel the dynamics of forward_dynamics_wrench ("aba") / inverse_dynamics_wrench ("rnea") launch for this body list
+        and B states in "f32" / "f64" (grbda_wrench_kernel_name): a wrench-carrying chain kernel, or the interpreter's."""
+        n, arr, fr = self._wrench_list(bodies, frame)
+        buf = ctypes.create_string_buffer(256)
+        _check(lib().grbda_wrench_kernel_name(self._h, 0 if algo == "aba" else 1, 32 if dtype == "f32" else 64, n, arr, fr, B, device, buf, 256))
+        return buf.value.decode()
+
+    def _wrench_host(self, name: str, q, qd, x, bodies, wrench, frame, device):
+        import numpy as np
+
+        n, arr, fr = self._wrench_list(bodies, frame)
+        q, qd, x = (np.ascontiguousarray(a, dtype="float64") for a in (q, qd, x))
+        w = None if wrench is None else np.ascontiguousarray(wrench, dtype="float64")
+        if w is not None and w.shape != (q.shape[0], n, 6):
+            raise ValueError(f"expected wrench[{q.shape[0]},{n},6]")
+        out = np.empty_like(x)
+        _check(getattr(lib(), "grbda_" + name)(self._h, q.ctypes.data, qd.ctypes.data, x.ctypes.data, n, arr, None if w is None else w.ctypes.data,
+                                               fr, out.ctypes.data, q.shape[0], device))
+        return out
+
+    def forward_dynamics_wrench_host(self, q, qd, tau, bodies, wrench, frame="body", device: int = 0):
+        return self._wrench_host("aba_wrench_host_f64", q, qd, tau, bodies, wrench, frame, device)
+
+    def inverse_dynamics_wrench_host(self, q, qd, ydd, bodies, wrench, frame="body", device: int = 0):
+        return self._wrench_host("rnea_wrench_host_f64", q, qd, ydd, bodies, wrench, frame, device)
+
+
+class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):

@@ -104,3 +104,15 @@ for _stem, _args in _STEP_VJP_PAIRS.items():
     STEP_VJP_SIGNATURES[f"grbda_{_stem}_f64"] = STEP_VJP_SIGNATURES[f"grbda_{_stem}_f32"] = _args
 STEP_VJP_SIGNATURES["grbda_step_vjp_host_f64"] = _STEP_VJP_PAIRS["step_vjp"][:-1]
 STEP_VJP_SIGNATURES = {name: (c_int, args) for name, args in STEP_VJP_SIGNATURES.items()}
+
+# include/grbda_hip_wrench.h, forward and inverse dynamics with sparse body wrenches: the fourth table, applied by `lib()` after the other
+# three; tests/test_wrench_args_cpu.py holds it to that header
+_WRENCH_PAIRS = {
+    "aba_wrench": (P, P, P, P, I, BODIES, P, I, P, *TAIL),               # q qd tau n bodies wrench frame ydd
+    "rnea_wrench": (P, P, P, P, I, BODIES, P, I, P, *TAIL),              # q qd ydd n bodies wrench frame tau
+}
+WRENCH_SIGNATURES = {"grbda_wrench_kernel_name": (P, I, I, I, BODIES, I, Z, I, P, Z)}  # algo precision n bodies frame B device buf len
+for _stem, _args in _WRENCH_PAIRS.items():
+    WRENCH_SIGNATURES[f"grbda_{_stem}_f64"] = WRENCH_SIGNATURES[f"grbda_{_stem}_f32"] = _args
+    WRENCH_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
+WRENCH_SIGNATURES = {name: (c_int, args) for name, args in WRENCH_SIGNATURES.items()}

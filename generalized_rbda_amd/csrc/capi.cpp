@@ -16,6 +16,7 @@
 #include "../../include/grbda_hip.h"
 #include "../../include/grbda_hip_vjp.h"
 #include "../../include/grbda_hip_step_vjp.h"
+#include "../../include/grbda_hip_wrench.h"
 #include "../../include/grbda_model_desc.h"
 #include "devplan.h"
 
@@ -174,6 +175,7 @@ int upload_chain_program(const Program &cp, Tables &ct)
         (e = up(cp.gbodies, &ct.gbodies)) != hipSuccess)
         return hip_err(e, "plan upload");
     if ((e = set_max_dynamic_lds_chain()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
+    if ((e = set_max_dynamic_lds_chain_wrench()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     return 0;
 }
 template <class Tables>
@@ -665,7 +667,7 @@ Route choose_rnea(const grbda_plan *p, int n_cu, size_t B, bool f_ext)
 
 template <class T>
 int run_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const T *q, const T *qd, const T *tau, T *ydd, size_t B, int device,
-              void *stream, bool gravity = true)
+              void *stream, bool gravity = true, const WrenchList<T> *wrenches = nullptr)  // wrenches: ROUTE_CHAIN only (wrench_route)
 {
     const HostPlan &h = p->host;
     const ChainProgram &cp = h.chain[r.slot];
@@ -718,13 +720,14 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const 
     }
     d.lds_bytes = static_cast<int>(s.lds_bytes);
     if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, static_cast<size_t>(cp.n_glb) + in_rows, sizeof(T)), &scratch)) return rc;
-    hipError_t e = launch_aba_chain<T>(d, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes, hs);
+    hipError_t e = wrenches ? launch_aba_chain_wrench<T>(d, *wrenches, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes, hs)
+                            : launch_aba_chain<T>(d, q, qd, tau, ydd, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "aba chain launch");
 }
 
 template <class T>
 int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const T *q, const T *qd, const T *ydd, T *tau, size_t B, int device,
-                   void *stream, bool gravity = true)
+                   void *stream, bool gravity = true, const WrenchList<T> *wrenches = nullptr)  // wrenches: ROUTE_CHAIN only (wrench_route)
 {
     const HostPlan &h = p->host;
     const RneaChainProgram &rp = h.rchain[r.slot];
@@ -762,7 +765,10 @@ int run_rnea_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, c
                                        static_cast<size_t>(wide ? p->opt.chain32w_lds_bytes : p->opt.lds_bytes_per_wave[kid]), true);
     d.lds_bytes = static_cast<int>(s.lds_bytes);
     if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, in_rows + static_cast<size_t>(rp.n_glb), sizeof(T)), &scratch)) return rc;
-    hipError_t e = launch_rnea_chain<T>(d, q, qd, ydd, tau, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes, hs);
+    const std::vector<ChainFree> &bases = h.chain[r.slot].frees;
+    hipError_t e = wrenches ? launch_rnea_chain_wrench<T>(d, *wrenches, bases.empty() ? -1 : bases[0].body, q, qd, ydd, tau, B, static_cast<T *>(scratch),
+                                                          static_cast<int>(s.grid), s.lds_bytes, hs)
+                            : launch_rnea_chain<T>(d, q, qd, ydd, tau, B, static_cast<T *>(scratch), static_cast<int>(s.grid), s.lds_bytes, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "rnea chain launch");
 }
 
@@ -1917,6 +1923,127 @@ int contact_dynamics(const grbda_plan *p, const T *q, const T *qd, const T *tau,
     return GRBDA_OK;
 }
 
+// ---- sparse body wrenches (include/grbda_hip_wrench.h) --------------------------------------------------------------------------------
+// Everything grbda_aba_wrench_* / grbda_rnea_wrench_* refuse, on the host and before any device call; fills the kernels' list.
+template <class T>
+int wrench_args(const grbda_plan *p, const T *q, const T *qd, const T *x, int n, const int *bodies, const T *wrench, int frame, const T *out, size_t B,
+                WrenchList<T> &W)
+{
+    if (!q || !qd || !x || !out) return set_err(GRBDA_EINVAL, "null argument");
+    if (n < 0 || n > kMaxWrenches) return set_err(GRBDA_EINVAL, "0..16 body wrenches per call");
+    if (frame != GRBDA_WRENCH_BODY && frame != GRBDA_WRENCH_WORLD) return set_err(GRBDA_EINVAL, "frame must be GRBDA_WRENCH_BODY or GRBDA_WRENCH_WORLD");
+    if (n > 0 && (!bodies || !wrench)) return set_err(GRBDA_EINVAL, "null argument");
+    W.n = n;
+    W.w = wrench;
+    W.canon = 0;
+    for (int i = 0; i < kMaxWrenches; i++) {
+        if (i < n && (bodies[i] < 0 || bodies[i] >= p->host.n_bodies)) return set_err(GRBDA_EINVAL, "body index out of range");
+        W.body[i] = i < n ? bodies[i] : -1;
+        if (i < n) W.canon |= static_cast<unsigned>(p->host.lay64.bodies[bodies[i]].canon_axis & 3) << (2 * i);
+    }
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const void *const in[4] = {q, qd, x, n > 0 ? wrench : nullptr}, *const outs[1] = {out};
+    const size_t in_bytes[4] = {bq, bv, bv, B * static_cast<size_t>(n) * 6 * sizeof(T)}, out_bytes[1] = {bv};
+    return no_overlap(in, in_bytes, outs, out_bytes);
+}
+// The route of a call with a non-empty list: ROUTE_CHAIN on the one-wavefront program of the precision (the wrench-carrying kernels of
+// chain_kernels.hip, unit 4) or ROUTE_INTERPRETER (a dense world-frame f_ext chunk through run()).  ONE definition, read by wrench_run and
+// by grbda_wrench_kernel_name.  The chain route needs the plain program -- no differentials, no generic clusters -- a batch the launch
+// rule gives to the one-wavefront kernels (latency mode carries no wrench hook), and every listed body among the link bodies, pair links
+// and bases of the program: a rotor evaluated in closed form has no bias force of its own to take a wrench off.
+template <class T>
+Route wrench_route(const grbda_plan *p, bool rnea, int n_cu, size_t B, const WrenchList<T> &W)
+{
+    const HostPlan &h = p->host;
+    const ChainSlot base = chain_slot(sizeof(T) == 8);
+    const Route fallback{ROUTE_INTERPRETER, base, 0};
+    if (h.projection_only) return fallback;
+    const Route r = rnea ? choose_rnea<T>(p, n_cu, B, false) : choose_aba<T>(p, n_cu, B, false);
+    if (r.path != ROUTE_CHAIN) return fallback;
+    const ChainProgram &cp = h.chain[base];
+    const RneaChainProgram &rp = h.rchain[base];
+    if (!cp.ok || !cp.diffs.empty() || !cp.gens.empty() || cp.frees.size() > 1) return fallback;
+    if (rnea && (!rp.ok || !rp.diffs.empty() || !rp.gens.empty())) return fallback;
+    for (int i = 0; i < W.n; i++) {
+        bool found = false;
+        for (const ChainFree &f : cp.frees) found = found || f.body == W.body[i];
+        for (const ChainLink &l : cp.links) found = found || l.body == W.body[i];
+        for (const ChainPair &pr : cp.pairs) found = found || pr.body[0] == W.body[i] || pr.body[1] == W.body[i];
+        if (!found) return fallback;
+    }
+    return {ROUTE_CHAIN, base, 0};
+}
+// Forward / inverse dynamics with the listed wrenches.  Chain route, body frame: one launch on the caller's arrays, no work memory.  Chain
+// route, world frame: per chunk the poses, wrench_to_body_kernel, the launch.  Fallback: per chunk a zeroed dense chunk, (body frame: the
+// poses,) wrench_scatter_kernel, run().  The chunks come off p->work (run() itself uses the scratch slab and work_proj only).
+template <class T>
+int wrench_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, int n, const int *bodies, const T *wrench, int frame, T *out,
+               size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    WrenchList<T> W;
+    if (int rc = wrench_args<T>(p, q, qd, x, n, bodies, wrench, frame, out, B, W)) return rc;
+    if (n == 0) return run<T>(p, rnea, q, qd, x, nullptr, out, B, device, stream);
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const Route r = wrench_route<T>(p, rnea, t->n_cu, B, W);
+    const bool chain = r.path == ROUTE_CHAIN;
+    const auto launch = [&](const WrenchList<T> &Wc, size_t b0, size_t nb) {
+        const size_t nq = p->host.nq, nv = p->host.nv;
+        return rnea ? run_rnea_chain<T>(p, *t, r, q + b0 * nq, qd + b0 * nv, x + b0 * nv, out + b0 * nv, nb, device, stream, true, &Wc)
+                    : run_chain<T>(p, *t, r, q + b0 * nq, qd + b0 * nv, x + b0 * nv, out + b0 * nv, nb, device, stream, true, &Wc);
+    };
+    if (chain && frame == GRBDA_WRENCH_BODY) return launch(W, 0, B);
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, n6 = static_cast<size_t>(n) * 6;
+    const bool rotate = chain || frame == GRBDA_WRENCH_BODY;  // (the poses are computed only then)
+    const size_t per_state = (rotate ? nbod * 12 : 0) + (chain ? n6 : nbod * 6);
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        T *Xa = rotate ? w.take(nb * nbod * 12) : nullptr;
+        WrenchList<T> Wc = W;
+        Wc.w = wrench + b0 * n6;
+        if (rotate)
+            if (int rc = poses_stage<T>(p, *t, q + b0 * nq, Xa, nb, stream)) return rc;
+        if (chain) {
+            T *wb = w.take(nb * n6);
+            hipError_t e = launch_wrench_to_body<T>(Wc, Xa, static_cast<int>(nbod), nb, wb, hs);
+            if (e != hipSuccess) return hip_err(e, "wrench rotation launch");
+            Wc.w = wb;
+            if (int rc = launch(Wc, b0, nb)) return rc;
+        } else {
+            T *fext = w.take(nb * nbod * 6);
+            hipError_t e = hipMemsetAsync(fext, 0, nb * nbod * 6 * sizeof(T), hs);
+            if (e == hipSuccess) e = launch_wrench_scatter<T>(Wc, Xa, frame == GRBDA_WRENCH_BODY, static_cast<int>(nbod), nb, fext, hs);
+            if (e != hipSuccess) return hip_err(e, "wrench scatter launch");
+            if (int rc = run<T>(p, rnea, q + b0 * nq, qd + b0 * nv, x + b0 * nv, fext, out + b0 * nv, nb, device, stream)) return rc;
+        }
+    }
+    return GRBDA_OK;
+}
+int wrench_host_f64(const grbda_plan *p, bool rnea, const double *q, const double *qd, const double *x, int n, const int *bodies, const double *wrench,
+                    int frame, double *out, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    WrenchList<double> W;
+    if (int rc = wrench_args<double>(p, q, qd, x, n, bodies, wrench, frame, out, B, W)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dx = st.in(x, B * nv);
+    const double *dw = n > 0 ? st.in(wrench, B * static_cast<size_t>(n) * 6) : nullptr;
+    double *dout = st.out(out, B * nv);
+    return st.run([&] { return wrench_run<double>(p, rnea, dq, dqd, dx, n, bodies, dw, frame, dout, B, device, nullptr); });
+}
+
 // Everything grbda_contact_impulse_* refuses, on the host and before any device call.  qd_next may BE qd (equal pointers, as for
 // grbda_integrate_*); any other overlap of an output with an input or with the other output is refused.
 template <class T>
@@ -3009,7 +3136,7 @@ int rollout_vjp(const grbda_plan *p, const T *q0, const T *qd0, const T *q_traj,
 
 // the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
 template <class T>
-static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B)
+static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B, bool interpreter = false)  // interpreter: that route's name, whatever the batch
 {
     const HostPlan &h = p->host;
     const char *tn = sizeof(T) == 4 ? "float" : "double";
@@ -3028,7 +3155,7 @@ static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_
         else
             std::snprintf(buf, sizeof buf, "grbda_hip::rnea_chain_kernel<%s, %d, %s>", tn, segs, cp.n_glb > 0 ? "true" : "false");
     };
-    if (r.path == ROUTE_INTERPRETER) {
+    if (r.path == ROUTE_INTERPRETER || interpreter) {
         bool loop = false;
         for (const ClusterRec &cr : h.lay64.clusters) loop = loop || cr.kind == CK_LOOP;
         std::snprintf(buf, sizeof buf, "grbda_hip::%s_kernel<%s, %s>", alg, tn, loop ? "true" : "false");
@@ -3044,6 +3171,34 @@ static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_
         format(rp, r.path == ROUTE_GEN1 ? rnea_gen1_waves_per_simd<T>(rp.gens[0].n) : 0);
     }
     return buf;
+}
+
+// what a call with body wrenches launches for its dynamics (wrench_route): a wrench-carrying chain kernel, or the interpreter on the dense chunk
+template <class T>
+static int wrench_kernel_name_of(const grbda_plan *p, int kind, int n, const int *bodies, int frame, size_t B, int device, std::string &name)
+{
+    if (n < 0 || n > kMaxWrenches) return set_err(GRBDA_EINVAL, "0..16 body wrenches per call");
+    if (frame != GRBDA_WRENCH_BODY && frame != GRBDA_WRENCH_WORLD) return set_err(GRBDA_EINVAL, "frame must be GRBDA_WRENCH_BODY or GRBDA_WRENCH_WORLD");
+    if (n > 0 && !bodies) return set_err(GRBDA_EINVAL, "null argument");
+    WrenchList<T> W{};
+    W.n = n;
+    for (int i = 0; i < n; i++) {
+        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+        W.body[i] = bodies[i];
+    }
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const char *tn = sizeof(T) == 4 ? "float" : "double";
+    if (n == 0) {
+        name = kernel_name_of<T>(p, kind, t->n_cu, B);
+    } else if (wrench_route<T>(p, kind == 1, t->n_cu, B, W).path != ROUTE_CHAIN) {
+        name = kernel_name_of<T>(p, kind, t->n_cu, B, true);
+    } else if (kind == 0) {
+        name = std::string("grbda_hip::aba_chain_wrench_kernel<") + tn + ">";
+    } else {
+        name = std::string("grbda_hip::rnea_chain_wrench_kernel<") + tn + (p->host.rchain[chain_slot(sizeof(T) == 8)].n_glb > 0 ? ", true>" : ", false>");
+    }
+    return GRBDA_OK;
 }
 
 // ---- one process, several devices: contiguous batch shards, plan replicated ------------------------
@@ -3568,6 +3723,48 @@ int grbda_kernel_name(const grbda_plan *p, int kind, int precision, size_t B, in
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const std::string name = precision == 32 ? kernel_name_of<float>(p, kind, t->n_cu, B) : kernel_name_of<double>(p, kind, t->n_cu, B);
+    std::snprintf(buf, cap, "%s", name.c_str());
+    return GRBDA_OK;
+}
+int grbda_aba_wrench_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, int n, const int *bodies, const double *wrench,
+                         int frame, double *ydd, size_t B, int device, void *stream)
+{
+    return wrench_run<double>(p, false, q, qd, tau, n, bodies, wrench, frame, ydd, B, device, stream);
+}
+int grbda_aba_wrench_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, int n, const int *bodies, const float *wrench,
+                         int frame, float *ydd, size_t B, int device, void *stream)
+{
+    return wrench_run<float>(p, false, q, qd, tau, n, bodies, wrench, frame, ydd, B, device, stream);
+}
+int grbda_rnea_wrench_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, int n, const int *bodies, const double *wrench,
+                          int frame, double *tau, size_t B, int device, void *stream)
+{
+    return wrench_run<double>(p, true, q, qd, ydd, n, bodies, wrench, frame, tau, B, device, stream);
+}
+int grbda_rnea_wrench_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, int n, const int *bodies, const float *wrench,
+                          int frame, float *tau, size_t B, int device, void *stream)
+{
+    return wrench_run<float>(p, true, q, qd, ydd, n, bodies, wrench, frame, tau, B, device, stream);
+}
+int grbda_aba_wrench_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, int n, const int *bodies,
+                              const double *wrench, int frame, double *ydd, size_t B, int device)
+{
+    return wrench_host_f64(p, false, q, qd, tau, n, bodies, wrench, frame, ydd, B, device);
+}
+int grbda_rnea_wrench_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, int n, const int *bodies,
+                               const double *wrench, int frame, double *tau, size_t B, int device)
+{
+    return wrench_host_f64(p, true, q, qd, ydd, n, bodies, wrench, frame, tau, B, device);
+}
+int grbda_wrench_kernel_name(const grbda_plan *p, int algo, int precision, int n, const int *bodies, int frame, size_t B, int device, char *buf,
+                             size_t cap)
+{
+    if (!p || !buf || cap == 0 || (algo != 0 && algo != 1) || (precision != 32 && precision != 64)) return set_err(GRBDA_EINVAL, "bad argument");
+    GRBDA_CALL_SCOPE(p);
+    std::string name;
+    if (int rc = precision == 32 ? wrench_kernel_name_of<float>(p, algo, n, bodies, frame, B, device, name)
+                                 : wrench_kernel_name_of<double>(p, algo, n, bodies, frame, B, device, name))
+        return rc;
     std::snprintf(buf, cap, "%s", name.c_str());
     return GRBDA_OK;
 }

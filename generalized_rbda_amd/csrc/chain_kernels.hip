@@ -20,7 +20,8 @@
 // (kernels.hip); the plan compiler decides (ChainProgram::ok).  The same file holds the inverse dynamics on the chains
 // (rnea_chain_kernel) and the force-propagation kernel of the contact side (osim_chain_kernel).
 //
-// Four translation units are built from this file (Makefile; unit 3: see GRBDA_KLDS below).  GRBDA_CHAIN_UNIT == 2 carries the kernels of programs with
+// Five translation units are built from this file (Makefile; unit 3: see GRBDA_KLDS below; unit 4: the wrench-carrying kernels
+// aba_chain_wrench_kernel / rnea_chain_wrench_kernel, a unit of their own so that no other kernel's code generation sees them).  GRBDA_CHAIN_UNIT == 2 carries the kernels of programs with
 // generic clusters (gen_segments.h: aba_chain_kernel<T, 2, 2>), GRBDA_CHAIN_UNIT == 1 carries the two fp64 kernels with the deepest
 // register pressure -- aba_chain_lm_kernel<double, 2> and aba_chain_kernel<double, 2, true> (the program with differentials); unit 0
 // is everything else.  Both fp64 kernels spill, and how much depends on what else the compiler sees in the unit: measured in
@@ -179,6 +180,8 @@ struct ChainMem {
     {
         *reinterpret_cast<T *>(reinterpret_cast<char *>(out_u + (size_t)(unsigned)(j * kWave)) + (size_t)lane_b) = v;
     }
+    // external wrench on plan body `body`, body frame, taken off a bias force / body force p: nothing here, ChainMemW below carries a list
+    __device__ __forceinline__ void wrench(int, T (&)[6]) const {}
 };
 
 // The tile's inputs in REGISTERS instead of slab rows (aba_chain_kernel<float, 2, kModeInReg>): every lane keeps its own state's q, qd and
@@ -195,6 +198,34 @@ struct ChainMemR : ChainMem<T> {
     __device__ __forceinline__ T q(int j) const { return rq[j]; }
     __device__ __forceinline__ T qd(int j) const { return rqd[j]; }
     __device__ __forceinline__ T x(int j) const { return rx[j]; }
+};
+
+// Sparse body wrenches (devplan.h, WrenchList; aba_chain_wrench_kernel / rnea_chain_wrench_kernel): the call's body list in scalar
+// registers, this lane's wrench rows behind one pointer.  The lookup is wave-uniform -- the body index comes from a plan record -- and
+// costs a compare per list entry on the scalar unit; a hit is six loads and six subtractions, entries of one body in list order.
+template <class T>
+struct ChainMemW : ChainMem<T> {
+    int wbody[kMaxWrenches];  // -1 behind the list
+    unsigned wcanon;          // WrenchList::canon
+    const T *wl;              // [n][6] of this lane's state (a lane beyond the batch: of the batch's last state)
+    __device__ __forceinline__ void wrench(int body, T (&p)[6]) const
+    {
+        unsigned hits = 0;
+#pragma unroll
+        for (int i = 0; i < kMaxWrenches; i++) hits |= (wbody[i] == body ? 1u : 0u) << i;
+        while (hits) {
+            const int i = __builtin_ctz(hits);
+            hits &= hits - 1;
+            const T *w = wl + i * 6;
+            const int shift = (int)((wcanon >> (2 * i)) & 3u) + 1;  // reference axes -> the plan's (WrenchList::canon)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const int k = (j + shift) % 3;
+                p[j] -= w[k];
+                p[3 + j] -= w[3 + k];
+            }
+        }
+    }
 };
 
 // c = v x (z qd) for a joint about z: (v1, -v0, 0, v4, -v3, 0) qd   (Spatial.h:131-143)
@@ -523,6 +554,7 @@ __device__ __forceinline__ void pair_bwd_k(const ChainTables<T> &P, const MM &M,
         cptr<T> I2 = C2 + 12;
         T p2[6], h2[6];
         bias_force(I2, v2, p2);
+        M.wrench(pr.body[1], p2);
 #pragma unroll
         for (int i = 0; i < 6; i++) h2[i] = I2[sidx(i, 2)];
         T bj = p2[2];
@@ -548,6 +580,7 @@ __device__ __forceinline__ void pair_bwd_k(const ChainTables<T> &P, const MM &M,
         cptr<T> I1 = C1 + 12;
         T p1[6];
         bias_force(I1, v1, p1);
+        M.wrench(pr.body[0], p1);
 #pragma unroll
         for (int j = 0; j < 21; j++) IA1[j] += I1[j];
 #pragma unroll
@@ -1122,6 +1155,7 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const MM &M, co
 
         T IA[21], psi[6];
         bias_force(Ic, v, psi);
+        M.wrench(l.body, psi);
 #pragma unroll
         for (int j = 0; j < 21; j++) IA[j] = Ib[j] + IAc[j];
 #pragma unroll
@@ -1454,6 +1488,7 @@ __device__ __forceinline__ void free_bwd(const ChainTables<T> &P, const MM &M, c
         if (fuse_acc) free_acc_inputs(P, M, f, o_, r_);
     }
     bias_force(Ic, v, psi);
+    M.wrench(f.body, psi);
     if (f.lds_acc != -1) {
         T acc[27];
         M.acc_ld(f.lds_acc, acc);
@@ -2460,6 +2495,120 @@ template hipError_t launch_aba_chain_gen<float>(const ChainDev<float> &, const f
                                                 float *, int, size_t, hipStream_t);
 template hipError_t launch_aba_chain_gen<double>(const ChainDev<double> &, const double *, const double *, const double *, double *,
                                                  size_t, double *, int, size_t, hipStream_t);
+#elif GRBDA_CHAIN_UNIT == 4
+// ---------------------------------------------------------------------------------------------------------------
+// Forward dynamics with sparse body wrenches (include/grbda_hip_wrench.h; TreeModel::setExternalForces with a short list of bodies):
+// aba_chain_kernel<T, 2, 0> -- the plain program, inputs in slab rows -- on ChainMemW, whose wrench hook takes a listed body's
+// wrench off its bias force in run_bwd, pair_bwd_k and free_bwd.  Wrenches arrive in the BODY frame (capi.cpp rotates world-frame
+// ones with the poses first), so no absolute transform exists in here.
+// ---------------------------------------------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ void wrench_setup(ChainMemW<T> &M, const WrenchList<T> &W)
+{
+#pragma unroll
+    for (int i = 0; i < kMaxWrenches; i++) M.wbody[i] = W.body[i];
+    M.wcanon = W.canon;
+}
+// (a lane beyond the batch reads the rows of the batch's last state: inside the array, and its results are never written)
+template <class T>
+__device__ __forceinline__ void wrench_tile(ChainMemW<T> &M, const WrenchList<T> &W, size_t tile, size_t B)
+{
+    const size_t st = tile * kWave + (size_t)M.lane;
+    M.wl = W.w + (st < B ? st : B - 1) * (size_t)(W.n * 6);
+}
+template <class T>
+__global__ __launch_bounds__(kWave, 2) void aba_chain_wrench_kernel(ChainDev<T> DP, WrenchList<T> W, const T *__restrict__ q,
+                                                                   const T *__restrict__ qd, const T *__restrict__ tau, T *__restrict__ ydd,
+                                                                   size_t B, T *__restrict__ scratch)
+{
+    ChainTables<T> P;
+    P.segs = (cptr<ChainSeg>)DP.segs;
+    P.links = (cptr<ChainLink>)DP.links;
+    P.pairs = (cptr<ChainPair>)DP.pairs;
+    P.frees = (cptr<ChainFree>)DP.frees;
+    P.diffs = nullptr;
+    P.gens = nullptr;
+    P.gbodies = nullptr;
+    P.cints = nullptr;
+    P.consts = (cptr<T>)DP.consts;
+    P.n_segs = DP.n_segs;
+    P.nq = DP.nq;
+    P.nv = DP.nv;
+    P.ori_repr = DP.ori_repr;
+#pragma unroll
+    for (int i = 0; i < 6; i++) P.a_root[i] = DP.a_root[i];
+    const int lane = threadIdx.x;
+    // wave slab: [nq + 2 nv input rows][n_glb_slots rows], 64 scalars per row
+    T *slab = scratch + (size_t)blockIdx.x * (size_t)(DP.n_glb_slots + P.nq + 2 * P.nv) * kWave;
+    ChainMemW<T> M;
+    M.lane = lane;
+    M.lane_b = (unsigned)lane * (unsigned)sizeof(T);
+    M.gmul = 1;
+    M.amask = ~0;
+    M.glb_u = slab + (size_t)(P.nq + 2 * P.nv) * kWave;
+    M.in_q_u = slab;
+    M.in_qd_u = slab + (size_t)P.nq * kWave;
+    M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
+    M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
+    M.set_out(DP.out_lds);
+    M.bad = 0;
+    wrench_setup(M, W);
+
+    const size_t n_tiles = (B + kWave - 1) / kWave;
+    for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const size_t left = B - tile * kWave;
+        const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
+        wrench_tile(M, W, tile, B);
+        stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
+        if (DP.fuse & 1) {  // (aba_chain_kernel)
+            const T *mine = reinterpret_cast<const T *>(grbda_smem) + (kWave * P.nq + lane * P.nv + DP.stage_v_index);
+            T v[6];
+#pragma unroll
+            for (int j = 0; j < 6; j++) v[j] = mine[j];
+            wave_lds_fence();
+            M.lds_st(DP.stage_lds_v, v);
+        }
+        for (int s = 0; s < P.n_segs; s++) {
+            const ChainSeg sg = load_rec(P.segs + s);
+            switch (sg.op) {
+                case SEG_RUN_FWD:
+                    if (DP.sv_global) run_fwd<T, true>(P, M, sg);
+                    else run_fwd_c(P, M, sg);
+                    break;
+                case SEG_RUN_BWD:
+                    if (DP.sv_global) run_bwd<T, false, true>(P, M, sg);
+                    else if (sg.rot_kind == 1) run_bwd<T, false, false, 1>(P, M, sg);
+                    else run_bwd<T, false, false>(P, M, sg);
+                    break;
+                case SEG_RUN_ACC: run_acc_c(P, M, sg); break;
+                case SEG_PAIR_ACC: pair_acc(P, M, load_rec(P.pairs + sg.first)); break;
+                case SEG_FREE_FWD:
+                    if (!((DP.fuse & 1) && s == 0)) free_fwd(P, M, load_rec(P.frees + sg.first));
+                    break;
+                case SEG_FREE_BWD: free_bwd<T, false>(P, M, load_rec(P.frees + sg.first), (DP.fuse & 2) != 0); break;
+                case SEG_FREE_ACC:
+                    if (!(DP.fuse & 2)) free_acc(P, M, load_rec(P.frees + sg.first));
+                    break;
+                default: break;  // (no differential, no generic cluster: capi.cpp, wrench_route)
+            }
+        }
+        if (M.out_row >= 0) write_outputs_lds<T>(M.out_row, ydd, tile, rows_valid, P.nv, lane);
+        else write_outputs(slab + (size_t)(P.nq + P.nv) * kWave, ydd, tile, rows_valid, P.nv, lane);
+        M.flush_bad(DP.bad_count, rows_valid);
+    }
+}
+template <class T>
+hipError_t launch_aba_chain_wrench(const ChainDev<T> &P, const WrenchList<T> &W, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch,
+                                   int grid, size_t lds_bytes, hipStream_t stream)
+{
+    if (P.n_gens > 0 || P.n_diffs > 0 || W.n < 1 || W.n > kMaxWrenches) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((aba_chain_wrench_kernel<T>), dim3(grid), dim3(kWave), lds_bytes, stream, P, W, q, qd, tau, ydd, B, scratch);
+    return hipGetLastError();
+}
+template hipError_t launch_aba_chain_wrench<float>(const ChainDev<float> &, const WrenchList<float> &, const float *, const float *, const float *,
+                                                   float *, size_t, float *, int, size_t, hipStream_t);
+template hipError_t launch_aba_chain_wrench<double>(const ChainDev<double> &, const WrenchList<double> &, const double *, const double *,
+                                                    const double *, double *, size_t, double *, int, size_t, hipStream_t);
 #endif
 
 
@@ -2540,8 +2689,8 @@ __device__ __forceinline__ void add6(const ChainMem<T> &M, int slot, const T (&x
     else M.lds_st(slot, y);
 }
 
-template <class T, bool GLB>
-__device__ __forceinline__ void rnea_run_fwd(const RneaTables<T> &P, const ChainMem<T> &M, const RneaSeg &sg)
+template <class T, bool GLB, class MM>
+__device__ __forceinline__ void rnea_run_fwd(const RneaTables<T> &P, const MM &M, const RneaSeg &sg)
 {
     T vp[6], ap[6];
     if (sg.lds_pva >= 0) {
@@ -2583,6 +2732,7 @@ __device__ __forceinline__ void rnea_run_fwd(const RneaTables<T> &P, const Chain
         a[4] -= v[3] * qdi;
         a[2] += g0 * yddi;
         body_force_c(C + 12, v, a, f);
+        M.wrench(l.body, f);
         blk[8] = 0;
         if (l.rofs >= 0 && !l.general_rotor) {
             cptr<T> Cr = P.consts + l.rofs;
@@ -2654,8 +2804,8 @@ __device__ __forceinline__ void rnea_run_bwd(const RneaTables<T> &P, const Chain
 }
 
 // leaf pair cluster: link1 (on P), link2 (on link1), two axisymmetric rotors on P (see pair_bwd)
-template <class T, bool GLB>
-__device__ __forceinline__ void rnea_pair(const RneaTables<T> &P, const ChainMem<T> &M, const RneaPair &pr)
+template <class T, bool GLB, class MM>
+__device__ __forceinline__ void rnea_pair(const RneaTables<T> &P, const MM &M, const RneaPair &pr)
 {
     cptr<T> C1 = P.consts + pr.cofs[0], C2 = P.consts + pr.cofs[1];
     T va[12], vp[6], ap[6];
@@ -2685,6 +2835,8 @@ __device__ __forceinline__ void rnea_pair(const RneaTables<T> &P, const ChainMem
     a2[2] += ydd2;
     body_force_c(C1 + 12, v1, a1, f1);
     body_force_c(C2 + 12, v2, a2, f2);
+    M.wrench(pr.body[0], f1);
+    M.wrench(pr.body[1], f2);
     T tau1, tau2 = f2[2], f21[6], fp[6];
     xforce_inv(E2, C2 + 9, f2, f21);
 #pragma unroll
@@ -2814,8 +2966,9 @@ __device__ __forceinline__ void rnea_diff_bwd(const RneaTables<T> &P, const Chai
     M.put(d.v_index + 1, M.got(d.v_index + 1) + blk[11] * tl1 + blk[13] * tl2);
 }
 
-template <class T>
-__device__ __forceinline__ void rnea_free_fwd(const RneaTables<T> &P, const ChainMem<T> &M, const RneaFree &f)
+// (body: the base's plan body index -- RneaFree has no int left for it, the wrench-carrying kernel passes it from its argument block)
+template <class T, class MM>
+__device__ __forceinline__ void rnea_free_fwd(const RneaTables<T> &P, const MM &M, const RneaFree &f, int body = -1)
 {
     T o[4], E[9], r[3], g[6], a[6], v[6], fo[6];
     const int nori = P.ori_repr == 0 ? 4 : 3;
@@ -2833,6 +2986,7 @@ __device__ __forceinline__ void rnea_free_fwd(const RneaTables<T> &P, const Chai
         a[j] += M.x(f.v_index + j);
     }
     body_force_c(P.consts + f.cofs + 12, v, a, fo);
+    M.wrench(body, fo);
     M.lds_st(f.lds_f, fo);
     if (f.lds_va >= 0) {
         T va[12];
@@ -3178,6 +3332,82 @@ template hipError_t launch_rnea_chain<float>(const RneaChainDev<float> &, const 
                                              float *, int, size_t, hipStream_t);
 template hipError_t launch_rnea_chain<double>(const RneaChainDev<double> &, const double *, const double *, const double *, double *,
                                               size_t, double *, int, size_t, hipStream_t);
+#elif GRBDA_CHAIN_UNIT == 4
+// Inverse dynamics with sparse body wrenches: rnea_chain_kernel<T, 0, GLB> on ChainMemW -- a listed body's wrench comes off its body force
+// f = I a + v x* I v in the forward segments, before tau = S^T f and the hand-over to the parent.  base_body: the base's plan body index
+// (rnea_free_fwd).
+template <class T, bool GLB>
+__global__ __launch_bounds__(kWave, 2) void rnea_chain_wrench_kernel(RneaChainDev<T> DP, WrenchList<T> W, int base_body, const T *__restrict__ q,
+                                                                     const T *__restrict__ qd, const T *__restrict__ ydd, T *__restrict__ tau,
+                                                                     size_t B, T *__restrict__ scratch)
+{
+    RneaTables<T> P;
+    P.segs = (cptr<RneaSeg>)DP.segs;
+    P.links = (cptr<RneaLink>)DP.links;
+    P.pairs = (cptr<RneaPair>)DP.pairs;
+    P.frees = (cptr<RneaFree>)DP.frees;
+    P.diffs = nullptr;
+    P.gens = nullptr;
+    P.gbodies = nullptr;
+    P.cints = nullptr;
+    P.consts = (cptr<T>)DP.consts;
+    P.n_segs = DP.n_segs;
+    P.nq = DP.nq;
+    P.nv = DP.nv;
+    P.ori_repr = DP.ori_repr;
+#pragma unroll
+    for (int i = 0; i < 6; i++) P.a_root[i] = DP.a_root[i];
+    const int lane = threadIdx.x;
+    // wave slab: [nq + 2 nv input / result rows][n_glb_slots rows]
+    T *slab = scratch + (size_t)blockIdx.x * (size_t)(P.nq + 2 * P.nv + DP.n_glb_slots) * kWave;
+    ChainMemW<T> M;
+    M.bad = 0;
+    M.lane = lane;
+    M.lane_b = (unsigned)lane * (unsigned)sizeof(T);
+    M.gmul = 1;
+    M.amask = ~0;
+    M.glb_u = slab + (size_t)(P.nq + 2 * P.nv) * kWave;
+    M.in_q_u = slab;
+    M.in_qd_u = slab + (size_t)P.nq * kWave;
+    M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
+    M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
+    M.set_out(-1);
+    wrench_setup(M, W);
+    const size_t n_tiles = (B + kWave - 1) / kWave;
+    for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const size_t left = B - tile * kWave;
+        const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
+        wrench_tile(M, W, tile, B);
+        stage_inputs(q, qd, ydd, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
+        for (int s = 0; s < P.n_segs; s++) {
+            const RneaSeg sg = load_rec(P.segs + s);
+            switch (sg.op) {
+                case RSEG_RUN_FWD: rnea_run_fwd<T, GLB>(P, M, sg); break;
+                case RSEG_RUN_BWD: rnea_run_bwd<T, GLB>(P, M, sg); break;
+                case RSEG_PAIR: rnea_pair<T, GLB>(P, M, load_rec(P.pairs + sg.first)); break;
+                case RSEG_FREE_FWD: rnea_free_fwd(P, M, load_rec(P.frees + sg.first), base_body); break;
+                case RSEG_FREE_BWD: rnea_free_bwd(P, M, load_rec(P.frees + sg.first)); break;
+                default: break;  // (no differential, no generic cluster: capi.cpp, wrench_route)
+            }
+        }
+        write_outputs(slab + (size_t)(P.nq + P.nv) * kWave, tau, tile, rows_valid, P.nv, lane);
+    }
+}
+template <class T>
+hipError_t launch_rnea_chain_wrench(const RneaChainDev<T> &P, const WrenchList<T> &W, int base_body, const T *q, const T *qd, const T *ydd, T *tau,
+                                    size_t B, T *scratch, int grid, size_t lds_bytes, hipStream_t stream)
+{
+    if (P.n_gens > 0 || P.n_diffs > 0 || W.n < 1 || W.n > kMaxWrenches) return hipErrorInvalidValue;
+    if (P.n_glb_slots > 0)
+        hipLaunchKernelGGL((rnea_chain_wrench_kernel<T, true>), dim3(grid), dim3(kWave), lds_bytes, stream, P, W, base_body, q, qd, ydd, tau, B, scratch);
+    else
+        hipLaunchKernelGGL((rnea_chain_wrench_kernel<T, false>), dim3(grid), dim3(kWave), lds_bytes, stream, P, W, base_body, q, qd, ydd, tau, B, scratch);
+    return hipGetLastError();
+}
+template hipError_t launch_rnea_chain_wrench<float>(const RneaChainDev<float> &, const WrenchList<float> &, int, const float *, const float *,
+                                                    const float *, float *, size_t, float *, int, size_t, hipStream_t);
+template hipError_t launch_rnea_chain_wrench<double>(const RneaChainDev<double> &, const WrenchList<double> &, int, const double *, const double *,
+                                                     const double *, double *, size_t, double *, int, size_t, hipStream_t);
 #endif
 
 
@@ -3228,6 +3458,14 @@ hipError_t set_max_dynamic_lds_chain_unit3()
                                    reinterpret_cast<const void *>(&rnea_chain_lm_kernel<double, 2>), reinterpret_cast<const void *>(&rnea_chain_lm_kernel<double, 4>),
                                    reinterpret_cast<const void *>(&rnea_chain_lm_kernel<float, 2, true>), reinterpret_cast<const void *>(&rnea_chain_lm_kernel<float, 4, true>)};
     return set_max_dynamic_lds(kernels, 11);
+}
+#elif GRBDA_CHAIN_UNIT == 4
+hipError_t set_max_dynamic_lds_chain_wrench()
+{
+    const void *const kernels[] = {reinterpret_cast<const void *>(&aba_chain_wrench_kernel<float>), reinterpret_cast<const void *>(&aba_chain_wrench_kernel<double>),
+                                   reinterpret_cast<const void *>(&rnea_chain_wrench_kernel<float, false>), reinterpret_cast<const void *>(&rnea_chain_wrench_kernel<float, true>),
+                                   reinterpret_cast<const void *>(&rnea_chain_wrench_kernel<double, false>), reinterpret_cast<const void *>(&rnea_chain_wrench_kernel<double, true>)};
+    return set_max_dynamic_lds(kernels, 6);
 }
 #else
 hipError_t set_max_dynamic_lds_chain_unit2()

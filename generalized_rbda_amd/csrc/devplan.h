@@ -158,6 +158,36 @@ template <class T>
 hipError_t launch_rnea_chain_lm(const RneaChainDev<T> &P, const T *q, const T *qd, const T *ydd, T *tau, size_t B, T *scratch, int grid, size_t lds_bytes,
                                 hipStream_t stream, int n_waves);
 
+// Sparse body wrenches of one call (include/grbda_hip_wrench.h): capi.cpp builds it from the caller's host list and it travels by value
+// in the kernel arguments, like ContactSet.  body[i] is a plan body index, -1 from entry n on; w holds the BODY-frame wrenches
+// [B][n][6] ([moment 3; force 3] at the body's origin) in the REFERENCE's body axes; canon: two bits per entry, BodyRec::canon_axis of the
+// body -- the plan's frame has that axis on z (plan.cpp, canonical joint axes), component i of a plan-frame vector is component
+// (i + canon_axis + 1) % 3 of the reference-frame one, and the chain kernels permute as they load.  The wrench-carrying chain kernels (chain_kernels.hip, unit 4:
+// aba_chain_wrench_kernel, rnea_chain_wrench_kernel) run the plain one-wavefront program -- no differentials, no generic clusters, [sin,
+// cos, v] blocks in LDS -- and subtract a listed body's wrench from its bias force (forward dynamics) or its body force (inverse dynamics).
+constexpr int kMaxWrenches = 16;
+template <class T>
+struct WrenchList {
+    int n;
+    int body[kMaxWrenches];
+    unsigned canon;
+    const T *w;
+};
+template <class T>
+hipError_t launch_aba_chain_wrench(const ChainDev<T> &P, const WrenchList<T> &W, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch,
+                                   int grid, size_t lds_bytes, hipStream_t stream);
+template <class T>
+hipError_t launch_rnea_chain_wrench(const RneaChainDev<T> &P, const WrenchList<T> &W, int base_body, const T *q, const T *qd, const T *ydd, T *tau,
+                                    size_t B, T *scratch, int grid, size_t lds_bytes, hipStream_t stream);  // base_body: ChainFree::body or -1
+hipError_t set_max_dynamic_lds_chain_wrench();
+// The frames of the sparse wrenches (wrench_kernels.hip), over nb states with the poses Xa [nb][n_bodies][12] of poses_stage:
+// to_body: out[nb][n][6] = Xa_body w (world -> body, in front of the chain route); otherwise the fallback's dense world-frame chunk
+// fext[nb][n_bodies][6] (zeroed by the caller) += w, rotated body -> world when from_body is set (Xa may be null when it is not).
+template <class T>
+hipError_t launch_wrench_to_body(const WrenchList<T> &W, const T *Xa, int n_bodies, size_t nb, T *out, hipStream_t stream);
+template <class T>
+hipError_t launch_wrench_scatter(const WrenchList<T> &W, const T *Xa, int from_body, int n_bodies, size_t nb, T *fext, hipStream_t stream);
+
 // single-cluster programs (RneaChainProgram::single_gen; chain_kernels.hip, rnea_gen1_kernel): P.lds_bytes = the work area, lds_bytes =
 // work area + nq + 2 nv rows of staged inputs
 template <class T>

@@ -1222,6 +1222,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     pr.q_index = cr.q_index;
                     pr.v_index = cr.v_index;
                     pr.cofs[0] = bodies[l1].cofs; pr.cofs[1] = bodies[l2].cofs; pr.cofs[2] = bodies[r[0]].cofs; pr.cofs[3] = bodies[r[1]].cofs;
+                    pr.body[0] = l1; pr.body[1] = l2;
                     pair_rotors[c] = {r[0], r[1]};
                     pr.perm[0] = cyclic_shift(P.consts, pr.cofs[0]);
                     pr.perm[1] = cyclic_shift(P.consts, pr.cofs[1]);
@@ -1295,6 +1296,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     const BodyRec &br = bodies[cr.first_body];
                     f.q_index = cr.q_index; f.v_index = cr.v_index; f.cofs = br.cofs; f.iofs = br.xofs >= 0 ? br.xofs : br.cofs + 12;
                     f.bofs = bias_inertia(cr.first_body, closed_rotors[cr.first_body]);
+                    f.body = cr.first_body;
                     f.lds_v = f.lds_acc = f.lds_va = f.lds_acc2 = f.lds_acc3 = f.lds_acc4 = -1;
                     f.glb_y0 = k_lds ? -1 : glb(33);  // [y0 6] (+ OSIM pass: Cholesky factor of the base's articulated inertia, L 21 + 1/diag 6)
                 } else if (cls[c] == 1 || cls[c] == 2 || cls[c] == 4) {
@@ -1302,6 +1304,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                     l = ChainLink();
                     const BodyRec &br = bodies[tip[c]];
                     l.q_index = cr.q_index; l.v_index = cr.v_index; l.cofs = br.cofs;
+                    l.body = tip[c];
                     l.rofs = cls[c] == 2 ? bodies[cr.rotor_body].cofs : (cls[c] == 4 ? bodies[gen_rotor[c]].cofs : -1);
                     l.rpre = cls[c] == 2 ? rotor_constants(cr.rotor_body) : -1;  // rofs >= 0 with rpre < 0: a general rotor
                     l.iofs = br.xofs >= 0 ? br.xofs : br.cofs + 12;
@@ -1687,6 +1690,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                         l.rofs = cls[c] == 2 ? bodies[cr.rotor_body].cofs : (cls[c] == 4 ? bodies[gen_rotor[c]].cofs : -1);
                         l.general_rotor = cls[c] == 4;
                         l.perm = link_of[c].perm; l.rperm = link_of[c].rperm;
+                        l.body = link_of[c].body;
                         l.lds_blk = l.lds_va = l.lds_pf = -1;
                     } else if (cls[c] == 7) {
                         rg[c] = gen_of[c];
@@ -1723,6 +1727,7 @@ int compile_plan(const void *blob, size_t bytes, const PlanOptions &opt, HostPla
                         pr = RneaPair();
                         pr.q_index = cr.q_index; pr.v_index = cr.v_index;
                         for (int i = 0; i < 4; i++) pr.cofs[i] = pair_of[c].cofs[i];
+                        pr.body[0] = pair_of[c].body[0]; pr.body[1] = pair_of[c].body[1];
                         pr.lds_pva = pr.lds_pf = -1;
                     }
                 }

@@ -202,7 +202,7 @@ struct ChainLink {
                         // equals iofs when those are all its axisymmetric leaf children, cofs + 12 when there are none
     int32_t rquad;      // -1; else the rotor's own X0^T I X0 (21): the body it hangs off belongs to a generic cluster, whose bias force
                         // does not carry the rotor's quadratic term, and the run adds vp x* (X0^T I X0) vp itself
-    int32_t reserved[1];
+    int32_t body;       // plan body index of the link body (the wrench-carrying kernels look it up in the call's body list)
 };
 
 // a RevolutePairWithRotor-shaped leaf cluster (32 ints)
@@ -214,7 +214,8 @@ struct ChainPair {
     int32_t lds_pva;    // acceleration sweep: parent body's [v 6][a 6]
     int32_t rpre[2];    // rotor1, rotor2: [X0^T h (6)][h_z]
     int32_t perm[2];    // link1, link2: ChainLink::perm
-    int32_t reserved[19];
+    int32_t body[2];    // plan body indices of link1, link2 (ChainLink::body)
+    int32_t reserved[17];
 };
 
 // An implicit two-rotor differential (the Tello hip and knee-ankle differentials, src/Robots/Tello.cpp:77-261 with
@@ -332,7 +333,8 @@ struct ChainFree {      // 16 ints
     int32_t lds_acc2;   // latency-mode programs: the accumulator the SECOND wavefront's limbs add into (-1: none)
     int32_t lds_acc3, lds_acc4;  // ... the third's and the fourth's (ChainProgram::n_waves = 4)
     int32_t bofs;       // bias inertia (ChainLink::bofs)
-    int32_t reserved[4];
+    int32_t body;       // plan body index of the base (ChainLink::body)
+    int32_t reserved[3];
 };
 
 // ---- inverse dynamics on the same chains (chain_kernels.hip, rnea_chain_kernel) ------------------------------------
@@ -349,14 +351,16 @@ struct RneaLink {       // 16 ints
     int32_t lds_pf;         // LDS slot of the parent body's force (first 6 of its block / the base's), -1: ground
     int32_t general_rotor;  // 1: the rotor is not axisymmetric about its axis and is evaluated at its own angle
     int32_t perm, rperm;    // ChainLink::perm / rperm
-    int32_t reserved[6];
+    int32_t body;           // ChainLink::body
+    int32_t reserved[5];
 };
 struct RneaPair {       // 16 ints
     int32_t q_index, v_index;
     int32_t cofs[4];        // link1, link2, rotor1, rotor2
     int32_t lds_pva;        // parent body's [v 6][a 6]
     int32_t lds_pf;         // parent body's force
-    int32_t reserved[8];
+    int32_t body[2];        // ChainPair::body
+    int32_t reserved[6];
 };
 struct RneaSeg {        // 8 ints
     int32_t op, first, count;
