@@ -11,7 +11,7 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
+from ._abi import JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
@@ -62,8 +62,8 @@ def lib() -> ctypes.CDLL:
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
-    # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule
-    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES}.items():
+    # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule; then grbda_hip_wrench.h and grbda_hip_jvp.h
+    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES, **JVP_SIGNATURES}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
@@ -309,7 +309,54 @@ class _WrenchMethods:
         return self._wrench_host("rnea_wrench_host_f64", q, qd, ydd, bodies, wrench, frame, device)
 
 
-class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods):
+class _JvpMethods:
+    """The Jacobian-vector products of Plan (include/grbda_hip_jvp.h), kept apart like _VjpMethods.  Every tangent is [B, nv]; a position
+    tangent lies along the tangent step of fd_dq, the coordinates of the "q" gradients of id_vjp / fd_vjp / step_vjp, so that
+    <g, jvp(u)> = <vjp(g), u> without conversion.  A tangent that is None is zero; not all tangents of a call may be None."""
+
+    @staticmethod
+    def _tangents(*tangents):
+        if all(t is None for t in tangents):
+            raise ValueError("the tangents of a call cannot all be None")
+
+    def id_jvp(self, q, qd, ydd, dq=None, dqd=None, dydd=None, step: float = 1e-6, stream=None):
+        """d tau / d q dq + d tau / d qd dqd + H dydd of the inverse dynamics at (q, qd, ydd) (grbda_rnea_jvp_*): dtau[B, nv] -- the
+        matrices of id_derivatives summed along their rows inside the library, H dydd by two inverse dynamics.  dydd alone runs no
+        derivative recursion; `step` as in id_derivatives."""
+        self._tangents(dq, dqd, dydd)
+        ins = dict(self._state(q, qd=qd, ydd=ydd), dq=(dq, self.nv), dqd=(dqd, self.nv), dydd=(dydd, self.nv))
+        return self._call("rnea_jvp", stream, ins, dict(out=self.nv), ("q", "qd", "ydd", "dq", "dqd", "dydd", float(step), "out"), skip_empty=True)[0]
+
+    def fd_jvp(self, q, qd, tau, dq=None, dqd=None, dtau=None, step: float = 1e-6, with_ydd: bool = False, stream=None):
+        """d ydd / d q dq + d ydd / d qd dqd + d ydd / d tau dtau of the forward dynamics (grbda_aba_jvp_*): dydd[B, nv], or
+        (dydd, ydd) with with_ydd -- ydd = FD(q, qd, tau), which the call computes anyway whenever dq or dqd is given.
+        dydd = H^-1 (dtau - d tau / d q dq - d tau / d qd dqd) by two forward dynamics at zero velocity: no factorisation, no solve, no
+        [B, nv, nv] tensor."""
+        self._tangents(dq, dqd, dtau)
+        ins = dict(self._state(q, qd=qd, tau=tau), dq=(dq, self.nv), dqd=(dqd, self.nv), dtau=(dtau, self.nv))
+        got = self._call("aba_jvp", stream, ins, dict(out=self.nv, ydd_out=self.nv if with_ydd else None),
+                         ("q", "qd", "tau", "dq", "dqd", "dtau", float(step), "out", "ydd_out"), skip_empty=True)
+        return got if with_ydd else got[0]
+
+    def integrate_jvp(self, qd_next, dt: float, dq=None, dqd=None, dydd=None, stream=None):
+        """The tangents (dq, dqd, dydd) pushed through integrate (grbda_integrate_jvp_*): (dq_next, dqd_next), each [B, nv].
+        qd_next[B, nv]: the velocities integrate / step returned.  One kernel launch; q does not enter."""
+        self._tangents(dq, dqd, dydd)
+        ins = dict(qd_next=(qd_next, self.nv), dq=(dq, self.nv), dqd=(dqd, self.nv), dydd=(dydd, self.nv))
+        return self._call("integrate_jvp", stream, ins, dict(dq_next=self.nv, dqd_next=self.nv),
+                          ("qd_next", float(dt), "dq", "dqd", "dydd", "dq_next", "dqd_next"), skip_empty=True)
+
+    def step_jvp(self, q, qd, tau, qd_next, dt: float, dq=None, dqd=None, dtau=None, step: float = 1e-6, stream=None):
+        """The tangents (dq, dqd, dtau) pushed through step(q, qd, tau, dt) (grbda_step_jvp_*): fd_jvp, then integrate_jvp on its
+        result, on one stream -- (dq_next, dqd_next), the product A dx + B du of the step's discrete-time matrices, which are never
+        built.  `step` as in fd_jvp."""
+        self._tangents(dq, dqd, dtau)
+        ins = dict(self._state(q, qd=qd, tau=tau, qd_next=qd_next), dq=(dq, self.nv), dqd=(dqd, self.nv), dtau=(dtau, self.nv))
+        return self._call("step_jvp", stream, ins, dict(dq_next=self.nv, dqd_next=self.nv),
+                          ("q", "qd", "tau", "qd_next", float(dt), "dq", "dqd", "dtau", float(step), "dq_next", "dqd_next"), skip_empty=True)
+
+
+class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _JvpMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):
@@ -842,6 +889,15 @@ def _step_autograd_function(rollout: bool):
         Step.__name__ = Step.__qualname__ = "Rollout" if rollout else "Step"
         _ad_functions[key] = Step
     return _ad_functions[key]
+
+
+def jvp_contract_launch(nv: int, B: int, n_cu: int):
+    """(units, grid) of the contraction kernel of id_jvp / fd_jvp for B states on a device with n_cu compute units
+    (grbda_jvp_contract_launch; the grid of the float64 launch): units > grid means a workgroup takes a second trip of its grid-stride
+    loop"""
+    units, grid = c_size_t(), c_size_t()
+    _check(lib().grbda_jvp_contract_launch(nv, B, n_cu, byref(units), byref(grid)))
+    return units.value, grid.value
 
 
 def vjp_contract_launch(nv: int, B: int, n_cu: int):

@@ -116,3 +116,18 @@ for _stem, _args in _WRENCH_PAIRS.items():
     WRENCH_SIGNATURES[f"grbda_{_stem}_f64"] = WRENCH_SIGNATURES[f"grbda_{_stem}_f32"] = _args
     WRENCH_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
 WRENCH_SIGNATURES = {name: (c_int, args) for name, args in WRENCH_SIGNATURES.items()}
+
+# include/grbda_hip_jvp.h, the Jacobian-vector products: a table of its own, applied by `lib()` after the others;
+# tests/test_jvp_args_cpu.py holds it to that header
+_JVP_PAIRS = {
+    "rnea_jvp": (P, P, P, P, P, P, P, D, P, *TAIL),                      # q qd ydd dq dqd dydd step dtau_out
+    "aba_jvp": (P, P, P, P, P, P, P, D, P, P, *TAIL),                    # q qd tau dq dqd dtau step dydd_out ydd
+    "integrate_jvp": (P, P, D, P, P, P, P, P, *TAIL),                    # qd_next dt dq dqd dydd dq_next dqd_next
+    "step_jvp": (P, P, P, P, P, D, P, P, P, D, P, P, *TAIL),             # q qd tau qd_next dt dq dqd dtau step dq_next dqd_next
+}
+JVP_SIGNATURES = {"grbda_jvp_contract_launch": (I, Z, I, POINTER(c_size_t), POINTER(c_size_t))}  # nv nb n_cu units grid
+for _stem, _args in _JVP_PAIRS.items():
+    JVP_SIGNATURES[f"grbda_{_stem}_f64"] = JVP_SIGNATURES[f"grbda_{_stem}_f32"] = _args
+    if _stem != "integrate_jvp":
+        JVP_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
+JVP_SIGNATURES = {name: (c_int, args) for name, args in JVP_SIGNATURES.items()}

@@ -16,6 +16,7 @@
 #include "../../include/grbda_hip.h"
 #include "../../include/grbda_hip_vjp.h"
 #include "../../include/grbda_hip_step_vjp.h"
+#include "../../include/grbda_hip_jvp.h"
 #include "../../include/grbda_hip_wrench.h"
 #include "../../include/grbda_model_desc.h"
 #include "devplan.h"
@@ -134,6 +135,8 @@ struct grbda_plan {
     mutable SlabPool work_proj;  // projection_run (called from inside the users of `work`)
     mutable SlabPool work_vjp;   // vjp_run (its id_derivs stage carves `work` on the difference routes)
     mutable SlabPool work_step_vjp;  // step_vjp_run / rollout_vjp (they call vjp_run, which carves work_vjp)
+    mutable SlabPool work_jvp;       // jvp_run (its id_derivs stage carves `work` on the difference routes)
+    mutable SlabPool work_step_jvp;  // step_jvp_run: dydd between jvp_run and the integrate kernel
     // the chunk decision of the last eager analytic_derivs call per (device, stream): a capture of the same call replays it
     struct DerivChunk {
         size_t B = 0, per_state_bytes = 0, chunk = 0;
@@ -3134,6 +3137,216 @@ int rollout_vjp(const grbda_plan *p, const T *q0, const T *qd0, const T *q_traj,
     return GRBDA_OK;
 }
 
+// ---- Jacobian-vector products (include/grbda_hip_jvp.h; jvp_kernels.hip, integrate_jvp_kernel of step_vjp_kernels.hip) ----------------
+// The rules every entry point of the header shares once its pointers are sorted into state inputs, tangents and outputs, in this order:
+// a state input, a tangent, an output, a finite dt, no overlap, the plan (stepping entry points), the step where differences in q are taken.
+// Everything that can be refused is refused here, before a device is looked at.  *base: as step_vjp_plan gives it.
+template <size_t NS, size_t NO>
+int jvp_rules(const grbda_plan *p, size_t elem, size_t B, const void *const (&state)[NS], const size_t (&state_width)[NS], const void *dq,
+              const void *dqd, const void *dx, const void *const (&out)[NO], bool need_out0, const double *dt, bool stepping, bool differentiates,
+              double step, int *base)
+{
+    for (const void *s : state)
+        if (!s) return set_err(GRBDA_EINVAL, "null argument");
+    if (!dq && !dqd && !dx) return set_err(GRBDA_EINVAL, "all tangents are null");
+    bool any = false;
+    for (const void *o : out) any = any || o;
+    if (need_out0 ? !out[0] : !any) return set_err(GRBDA_EINVAL, "no output asked for");
+    if (dt && !std::isfinite(*dt)) return set_err(GRBDA_EINVAL, "dt is not finite");
+    const size_t bv = B * p->host.nv * elem;
+    const void *in[NS + 3];
+    size_t in_bytes[NS + 3], out_bytes[NO];
+    for (size_t i = 0; i < NS; i++) {
+        in[i] = state[i];
+        in_bytes[i] = B * state_width[i] * elem;
+    }
+    in[NS] = dq, in[NS + 1] = dqd, in[NS + 2] = dx;
+    in_bytes[NS] = in_bytes[NS + 1] = in_bytes[NS + 2] = bv;
+    for (size_t i = 0; i < NO; i++) out_bytes[i] = bv;
+    if (int rc = no_overlap(reinterpret_cast<const void *const(&)[NS + 3]>(in), in_bytes, out, out_bytes)) return rc;
+    if (stepping)
+        if (int rc = step_vjp_plan(p, base)) return rc;
+    // (the one use of `step`: d tau / d q by central differences, id_derivs off the analytic route)
+    if (differentiates && dq && !analytic_covers(p) && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+    return GRBDA_OK;
+}
+// x: ydd / tau, dx: dydd / dtau, out: dtau_out / dydd_out, ydd_out: the forward dynamics' optional result
+template <class T>
+int jvp_args(const grbda_plan *p, const T *q, const T *qd, const T *x, const T *dq, const T *dqd, const T *dx, double step, const T *out, const T *ydd_out,
+             size_t B)
+{
+    const void *const state[3] = {q, qd, x}, *const outs[2] = {out, ydd_out};
+    const size_t nq = p->host.nq, nv = p->host.nv, width[3] = {nq, nv, nv};
+    return jvp_rules(p, sizeof(T), B, state, width, dq, dqd, dx, outs, true, nullptr, false, true, step, nullptr);
+}
+// Chunk by chunk through the plan's work_jvp slab.  Inverse: d tau / d q, d tau / d qd at (q, qd, ydd) by id_derivs into the slab (each only
+// when its tangent is given), H dydd = RNEA(q, 0, dydd) - RNEA(q, 0, 0) (vjp_contract_kernel without matrices forms the difference), and
+// jvp_contract_kernel sums the rows against the tangents on top of it.  Forward: ydd = ABA(q, qd, tau); r = dtau - d tau / d q dq -
+// d tau / d qd dqd at ydd (the same kernel, sign -1, dtau added in); dydd = ABA(q, 0, r) - ABA(q, 0, 0).  The runs of a zero-velocity pair
+// carry no gravity, as in vjp_run.  Only the stages the given tangents need are enqueued.
+template <class T>
+int jvp_run(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *dq, const T *dqd, const T *dx, double step, T *out,
+            T *ydd_out, size_t B, int device, void *stream)
+{
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
+    const bool need_d = dq || dqd;
+    const bool need_pair = forward || dx;  // the two launches at zero velocity
+    const bool need_ydd = forward && (need_d || ydd_out);
+    const bool need_mid = need_d && need_pair;  // forward: r; inverse: H dydd, before the rows are summed on top of it
+    // per state: the matrices of the given tangents; zeros, and the two results of the zero-velocity pair; the vector in between; ydd when
+    // the caller keeps none
+    const size_t per_state = (dq ? nn : 0) + (dqd ? nn : 0) + (need_pair ? 3 * nv : 0) + (need_mid ? nv : 0) + (need_ydd && !ydd_out ? nv : 0);
+    const Chunk c = budgeted_chunk(p, p->work_jvp, device, stream, 4096ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work_jvp, device, stream, c.bytes, &wptr)) return rc;
+    Carver<T> w(wptr, c.chunk * per_state);
+    auto take = [&](bool wanted, size_t per) { return wanted ? w.take(c.chunk * per) : nullptr; };
+    T *Mq = take(dq, nn), *Mqd = take(dqd, nn), *zeros = take(need_pair, nv), *r1 = take(need_pair, nv), *r0 = take(need_pair, nv);
+    T *mid = take(need_mid, nv), *ydd_slab = take(need_ydd && !ydd_out, nv);
+    assert(w.taken == w.cap);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int nvi = static_cast<int>(nv);
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        const T *qc = q + b0 * nq, *qdc = qd + b0 * nv, *xc = x + b0 * nv;
+        const T *dqc = dq ? dq + b0 * nv : nullptr, *dqdc = dqd ? dqd + b0 * nv : nullptr, *dxc = dx ? dx + b0 * nv : nullptr;
+        T *ydd = ydd_out ? ydd_out + b0 * nv : ydd_slab, *oc = out + b0 * nv;
+        const JvpLaunch J = jvp_contract_launch(nvi, sizeof(T), t->n_cu, nb);
+        const VjpLaunch V = vjp_contract_launch(nvi, sizeof(T), t->n_cu, nb);
+        if (need_ydd)
+            if (int rc = run<T>(p, false, qc, qdc, xc, nullptr, ydd, nb, device, stream)) return rc;
+        if (need_d)
+            if (int rc = id_derivs<T>(p, qc, qdc, forward ? ydd : xc, step, Mq, Mqd, nb, device, stream)) return rc;
+        const T *rhs = dxc;  // what the pair runs on: dydd; forward: dtau, or r once the rows are taken off it
+        if (forward && need_d) {
+            if (hipError_t e = launch_jvp_contract<T>(J, Mq, Mqd, dqc, dqdc, dxc, T(-1), nvi, nb, mid, hs); e != hipSuccess)
+                return hip_err(e, "jvp contraction launch");
+            rhs = mid;
+        }
+        if (need_pair) {
+            if (hipError_t e = hipMemsetAsync(zeros, 0, nb * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+            if (int rc = run<T>(p, !forward, qc, zeros, rhs, nullptr, r1, nb, device, stream, false)) return rc;
+            if (int rc = run<T>(p, !forward, qc, zeros, zeros, nullptr, r0, nb, device, stream, false)) return rc;
+            // (out_w = r1 - r0 and nothing else: the difference of the pair as vjp_run forms it)
+            T *diff = !forward && need_d ? mid : oc;
+            if (hipError_t e = launch_vjp_contract<T>(V, nullptr, nullptr, r1, r0, T(1), nvi, nb, nullptr, nullptr, diff, hs); e != hipSuccess)
+                return hip_err(e, "pair difference launch");
+        }
+        if (!forward && need_d)
+            if (hipError_t e = launch_jvp_contract<T>(J, Mq, Mqd, dqc, dqdc, need_pair ? mid : nullptr, T(1), nvi, nb, oc, hs); e != hipSuccess)
+                return hip_err(e, "jvp contraction launch");
+    }
+    return GRBDA_OK;
+}
+template <class T>
+int jvp(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *dq, const T *dqd, const T *dx, double step, T *out, T *ydd_out,
+        size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = jvp_args<T>(p, q, qd, x, dq, dqd, dx, step, out, ydd_out, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    return jvp_run<T>(p, forward, q, qd, x, dq, dqd, dx, step, out, ydd_out, B, device, stream);
+}
+int jvp_host_f64(const grbda_plan *p, bool forward, const double *q, const double *qd, const double *x, const double *dq, const double *dqd,
+                 const double *dx, double step, double *out, double *ydd_out, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = jvp_args<double>(p, q, qd, x, dq, dqd, dx, step, out, ydd_out, B)) return rc;
+    if (B == 0) return GRBDA_OK;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    DeviceTables *t = nullptr;
+    if (int rc0 = ensure_device(p, device, &t)) return rc0;  // `device` current before anything is allocated on it
+    HostStage st;
+    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bx = st.in(x, B * nv);
+    const double *bdq = dq ? st.in(dq, B * nv) : nullptr, *bdqd = dqd ? st.in(dqd, B * nv) : nullptr, *bdx = dx ? st.in(dx, B * nv) : nullptr;
+    double *b1 = st.out(out, B * nv), *b2 = ydd_out ? st.out(ydd_out, B * nv) : nullptr;
+    return st.run([&] { return jvp_run<double>(p, forward, bq, bqd, bx, bdq, bdqd, bdx, step, b1, b2, B, device, nullptr); });
+}
+template <class T>
+int integrate_jvp_args(const grbda_plan *p, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dydd, const T *dq_next, const T *dqd_next,
+                       size_t B, int *base)
+{
+    const void *const state[1] = {qd_next}, *const outs[2] = {dq_next, dqd_next};
+    const size_t nv = p->host.nv, width[1] = {nv};
+    return jvp_rules(p, sizeof(T), B, state, width, dq, dqd, dydd, outs, false, &dt, true, false, 0.0, base);
+}
+template <class T>
+int step_jvp_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dtau,
+                  double step, const T *dq_next, const T *dqd_next, size_t B, int *base)
+{
+    const void *const state[4] = {q, qd, tau, qd_next}, *const outs[2] = {dq_next, dqd_next};
+    const size_t nq = p->host.nq, nv = p->host.nv, width[4] = {nq, nv, nv, nv};
+    return jvp_rules(p, sizeof(T), B, state, width, dq, dqd, dtau, outs, false, &dt, true, true, step, base);
+}
+template <class T>
+hipError_t integrate_jvp_launch(const DeviceTables &t, int base, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dydd, T *dq_next,
+                                T *dqd_next, int nv, size_t B, void *stream)
+{
+    // (the record of the fp64 layout, as integrate_vjp_launch takes it)
+    return launch_integrate_jvp<T>(base >= 0 ? t.clusters[1] + base : nullptr, qd_next, static_cast<T>(dt), dq, dqd, dydd, dq_next, dqd_next, nv, B,
+                                   static_cast<hipStream_t>(stream));
+}
+template <class T>
+int integrate_jvp(const grbda_plan *p, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dydd, T *dq_next, T *dqd_next, size_t B, int device,
+                  void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    int base = -1;
+    if (int rc = integrate_jvp_args<T>(p, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, B, &base)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    hipError_t e = integrate_jvp_launch<T>(*t, base, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, static_cast<int>(p->host.nv), B, stream);
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate jvp launch");
+}
+// The two stages of grbda_step_jvp_* (arguments checked, B > 0, device found): grbda_aba_jvp_* into the [B][nv] work array, then the
+// integrate kernel on it.
+template <class T>
+int step_jvp_run(const grbda_plan *p, const DeviceTables &t, int base, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *dq,
+                 const T *dqd, const T *dtau, double step, T *dq_next, T *dqd_next, size_t B, int device, void *stream)
+{
+    void *ptr = nullptr;
+    if (int rc = ensure_work(p, p->work_step_jvp, device, stream, B * p->host.nv * sizeof(T) + 256, &ptr)) return rc;
+    T *dydd = static_cast<T *>(ptr);
+    if (int rc = jvp_run<T>(p, true, q, qd, tau, dq, dqd, dtau, step, dydd, nullptr, B, device, stream)) return rc;
+    hipError_t e = integrate_jvp_launch<T>(t, base, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, static_cast<int>(p->host.nv), B, stream);
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate jvp launch");
+}
+template <class T>
+int step_jvp(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dtau, double step,
+             T *dq_next, T *dqd_next, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    int base = -1;
+    if (int rc = step_jvp_args<T>(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, &base)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    return step_jvp_run<T>(p, *t, base, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, device, stream);
+}
+int step_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt, const double *dq,
+                      const double *dqd, const double *dtau, double step, double *dq_next, double *dqd_next, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    int base = -1;
+    if (int rc = step_jvp_args<double>(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, &base)) return rc;
+    if (B == 0) return GRBDA_OK;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;  // `device` current before anything is allocated on it
+    HostStage st;
+    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bt = st.in(tau, B * nv), *bn = st.in(qd_next, B * nv);
+    const double *bdq = dq ? st.in(dq, B * nv) : nullptr, *bdqd = dqd ? st.in(dqd, B * nv) : nullptr, *bdt = dtau ? st.in(dtau, B * nv) : nullptr;
+    double *o1 = dq_next ? st.out(dq_next, B * nv) : nullptr, *o2 = dqd_next ? st.out(dqd_next, B * nv) : nullptr;
+    return st.run([&] { return step_jvp_run<double>(p, *t, base, bq, bqd, bt, bn, dt, bdq, bdqd, bdt, step, o1, o2, B, device, nullptr); });
+}
+
 // the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
 template <class T>
 static std::string kernel_name_of(const grbda_plan *p, int kind, int n_cu, size_t B, bool interpreter = false)  // interpreter: that route's name, whatever the batch
@@ -3524,7 +3737,7 @@ void grbda_plan_free(grbda_plan *p)
         }
         for (int w = 0; w < kLayouts; w++) { (void)hipFree(t.acc_k[w]); (void)hipFree(t.clusters[w]); (void)hipFree(t.rnea_clusters[w]); (void)hipFree(t.bodies[w]); (void)hipFree(t.rnea_bodies[w]); }
     }
-    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp})
+    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp})
         for (auto &kv : *m) {
             if (hipSetDevice(kv.first.first) != hipSuccess) continue;
             if (kv.second.ptr) (void)hipFree(kv.second.ptr);
@@ -3536,7 +3749,7 @@ void grbda_plan_free(grbda_plan *p)
 // (and of its spanning-tree plan) is checked first, so that a refused release frees nothing.
 static bool holds_capturing_slab(const grbda_plan *p)
 {
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp})
         for (auto &kv : *m)
             if (kv.second.ptr && is_capturing(kv.first.second)) return true;
     return p->span && holds_capturing_slab(p->span);
@@ -3549,7 +3762,7 @@ int grbda_plan_release_work(grbda_plan *p, unsigned long long *bytes_released)
     if (holds_capturing_slab(p))
         return set_err(GRBDA_EINVAL, "a stream of this plan is capturing: its work buffers cannot be released now");
     unsigned long long total = 0;
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp})
         for (auto &kv : *m) {
             if (!kv.second.ptr) continue;
             hipError_t e = hipSetDevice(kv.first.first);
@@ -4141,6 +4354,71 @@ int grbda_rollout_vjp_f32(const grbda_plan *p, const float *q0, const float *qd0
 {
     return rollout_vjp<float>(p, q0, qd0, q_traj, qd_traj, tau, tau_steps, dt, T, g_q, g_qd, g_steps, step, grad_q0, grad_qd0, grad_tau, B, device,
                               stream);
+}
+int grbda_rnea_jvp_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, const double *dq, const double *dqd, const double *dydd,
+                       double step, double *dtau_out, size_t B, int device, void *stream)
+{
+    return jvp<double>(p, false, q, qd, ydd, dq, dqd, dydd, step, dtau_out, nullptr, B, device, stream);
+}
+int grbda_rnea_jvp_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, const float *dq, const float *dqd, const float *dydd,
+                       double step, float *dtau_out, size_t B, int device, void *stream)
+{
+    return jvp<float>(p, false, q, qd, ydd, dq, dqd, dydd, step, dtau_out, nullptr, B, device, stream);
+}
+int grbda_rnea_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, const double *dq, const double *dqd,
+                            const double *dydd, double step, double *dtau_out, size_t B, int device)
+{
+    return jvp_host_f64(p, false, q, qd, ydd, dq, dqd, dydd, step, dtau_out, nullptr, B, device);
+}
+int grbda_aba_jvp_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *dq, const double *dqd, const double *dtau,
+                      double step, double *dydd_out, double *ydd, size_t B, int device, void *stream)
+{
+    return jvp<double>(p, true, q, qd, tau, dq, dqd, dtau, step, dydd_out, ydd, B, device, stream);
+}
+int grbda_aba_jvp_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, const float *dq, const float *dqd, const float *dtau,
+                      double step, float *dydd_out, float *ydd, size_t B, int device, void *stream)
+{
+    return jvp<float>(p, true, q, qd, tau, dq, dqd, dtau, step, dydd_out, ydd, B, device, stream);
+}
+int grbda_aba_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *dq, const double *dqd,
+                           const double *dtau, double step, double *dydd_out, double *ydd, size_t B, int device)
+{
+    return jvp_host_f64(p, true, q, qd, tau, dq, dqd, dtau, step, dydd_out, ydd, B, device);
+}
+int grbda_integrate_jvp_f64(const grbda_plan *p, const double *qd_next, double dt, const double *dq, const double *dqd, const double *dydd,
+                            double *dq_next, double *dqd_next, size_t B, int device, void *stream)
+{
+    return integrate_jvp<double>(p, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, B, device, stream);
+}
+int grbda_integrate_jvp_f32(const grbda_plan *p, const float *qd_next, double dt, const float *dq, const float *dqd, const float *dydd, float *dq_next,
+                            float *dqd_next, size_t B, int device, void *stream)
+{
+    return integrate_jvp<float>(p, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, B, device, stream);
+}
+int grbda_step_jvp_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt, const double *dq,
+                       const double *dqd, const double *dtau, double step, double *dq_next, double *dqd_next, size_t B, int device, void *stream)
+{
+    return step_jvp<double>(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, device, stream);
+}
+int grbda_step_jvp_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, const float *qd_next, double dt, const float *dq,
+                       const float *dqd, const float *dtau, double step, float *dq_next, float *dqd_next, size_t B, int device, void *stream)
+{
+    return step_jvp<float>(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, device, stream);
+}
+int grbda_step_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt, const double *dq,
+                            const double *dqd, const double *dtau, double step, double *dq_next, double *dqd_next, size_t B, int device)
+{
+    return step_jvp_host_f64(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, device);
+}
+int grbda_jvp_contract_launch(int nv, size_t nb, int n_cu, size_t *units, size_t *grid)
+{
+    if (nv < 1 || n_cu < 1) return set_err(GRBDA_EINVAL, "nv and n_cu must be positive");
+    // (the units do not depend on the precision; the grid is the fp64 launch's -- an fp32 tile is half the bytes, so where the LDS of a CU
+    // and not kJvpWavesPerCu bounds the grid, from nv = 18 on, the fp32 launch may hold more workgroups per CU)
+    const JvpLaunch L = jvp_contract_launch(nv, sizeof(double), n_cu, nb);
+    if (units) *units = L.units;
+    if (grid) *grid = L.grid;
+    return GRBDA_OK;
 }
 int grbda_plan_span_dims(const grbda_plan *p, int *n_span_vel)
 {

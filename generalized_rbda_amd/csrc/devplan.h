@@ -309,11 +309,31 @@ template <class T>
 hipError_t launch_vjp_contract(const VjpLaunch &L, const T *Mq, const T *Mqd, const T *w_add, const T *w_sub, T sign, int nv, size_t nb, T *out_q,
                                T *out_qd, T *out_w, hipStream_t stream);
 
+// the contraction of the Jacobian-vector products (jvp_kernels.hip): out[b][i] = w_add[b][i] + sign (sum_j Mq[b][i][j] uq[b][j] + sum_j
+// Mqd[b][i][j] uqd[b][j]) over nb states of row-major [nv][nv] matrices; Mq / uq and Mqd / uqd may be null (as pairs), and so may w_add
+// (zero).  One launch rule, read by the launcher and by grbda_jvp_contract_launch.
+constexpr size_t kJvpWavesPerCu = 16;
+constexpr size_t kJvpMaxLdsBytes = 64 * 1024;  // what a launch gets without asking for more: nv up to some 1 900 in fp64
+struct JvpLaunch {
+    size_t units;      // packs of states x row blocks
+    size_t grid;       // one-wavefront workgroups
+    size_t lds_bytes;  // two staged vectors and one tile of rows
+};
+JvpLaunch jvp_contract_launch(int nv, size_t elem, int n_cu, size_t nb);
+template <class T>
+hipError_t launch_jvp_contract(const JvpLaunch &L, const T *Mq, const T *Mqd, const T *uq, const T *uqd, const T *w_add, T sign, int nv, size_t nb,
+                               T *out, hipStream_t stream);
+
 // the manifold part of the step's vector-Jacobian product (step_vjp_kernels.hip, include/grbda_hip_step_vjp.h): the cotangents of the stepped
 // state pulled back through q' = q (+) dt qd', qd' = qd + dt ydd, over nb states.  `base`: the device record of the quaternion base's cluster
 // (its v_index is read there) or null for a plan without one.  g_q / g_qd may be null (zero), and so may every output.
 template <class T>
 hipError_t launch_integrate_vjp(const ClusterRec *base, const T *qd_next, T dt, const T *g_q, const T *g_qd, T *grad_q, T *grad_qd, T *grad_ydd,
+                                int nv, size_t nb, hipStream_t stream);
+// its forward map (include/grbda_hip_jvp.h): the tangents (dq, dqd, dydd) of a state and its acceleration pushed through the same step.  Any
+// tangent may be null (zero); either output may be null.
+template <class T>
+hipError_t launch_integrate_jvp(const ClusterRec *base, const T *qd_next, T dt, const T *dq, const T *dqd, const T *dydd, T *dq_next, T *dqd_next,
                                 int nv, size_t nb, hipStream_t stream);
 // out[i] = a[i] + b[i] over n scalars: one rounding, operands in this order (out may be a or b)
 template <class T>

@@ -1,4 +1,5 @@
-// step_vjp_kernels.hip -- the two kernels of the step / rollout vector-Jacobian products (include/grbda_hip_step_vjp.h).
+// step_vjp_kernels.hip -- the two kernels of the step / rollout vector-Jacobian products (include/grbda_hip_step_vjp.h), and
+// integrate_jvp_kernel, the forward map of the first (include/grbda_hip_jvp.h; described where it stands).
 //
 // integrate_vjp_kernel: the cotangents (g_q', g_qd') of a stepped state pulled back through qd' = qd + dt ydd, q' = q (+) dt qd'.  One
 // thread per scalar of [B][nv], consecutive threads consecutive addresses.  Explicit coordinates are element-wise:
@@ -42,13 +43,29 @@ __device__ inline void rodrigues(const T phi[3], T k1, T k2, const T g[3], T out
     for (int i = 0; i < 3; i++) out[i] = g[i] + k1 * x1[i] + k2 * x2[i];
 }
 
+// phi = w dt, and the coefficients a, b, c of E and J_r at theta = |phi| (a = 1, b = 1/2, c = 1/6 at theta = 0; c by its series below 0.1):
+// the one evaluation integrate_vjp_kernel and integrate_jvp_kernel share
+template <class T>
+__device__ inline void so3_coefficients(const T w[3], T dt, T phi[3], T &ka, T &kb, T &kc)
+{
+    constexpr T kSeriesBelow = T(0.1);
+    for (int a = 0; a < 3; a++) phi[a] = w[a] * dt;
+    const T theta = sqrt(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]);
+    ka = T(1), kb = T(0.5), kc = T(1.0 / 6.0);
+    if (theta > T(0)) {
+        const T sn = sin(theta), sh = sin(T(0.5) * theta) / theta, t2 = theta * theta;
+        ka = sn / theta;
+        kb = T(2) * sh * sh;
+        kc = theta < kSeriesBelow ? T(1.0 / 6.0) - t2 * (T(1.0 / 120.0) - t2 * T(1.0 / 5040.0)) : (theta - sn) / (t2 * theta);
+    }
+}
+
 template <class T>
 __global__ void __launch_bounds__(kStepVjpThreads) integrate_vjp_kernel(const ClusterRec *__restrict__ base, const T *__restrict__ qd_next, T dt,
                                                                         const T *__restrict__ g_q, const T *__restrict__ g_qd,
                                                                         T *__restrict__ grad_q, T *__restrict__ grad_qd,
                                                                         T *__restrict__ grad_ydd, int nv, size_t n)
 {
-    constexpr T kSeriesBelow = T(0.1);
     const int bv = base ? base->v_index : -1;  // (wave-uniform: one record)
     const size_t stride = static_cast<size_t>(gridDim.x) * kStepVjpThreads;
     for (size_t i = static_cast<size_t>(blockIdx.x) * kStepVjpThreads + threadIdx.x; i < n; i += stride) {
@@ -64,15 +81,8 @@ __global__ void __launch_bounds__(kStepVjpThreads) integrate_vjp_kernel(const Cl
                 hw[a] = g_qd ? g_qd[i + a] : T(0);
                 hv[a] = g_qd ? g_qd[i + 3 + a] : T(0);
             }
-            const T phi[3] = {w[0] * dt, w[1] * dt, w[2] * dt};
-            const T theta = sqrt(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]);
-            T ka = T(1), kb = T(0.5), kc = T(1.0 / 6.0);
-            if (theta > T(0)) {
-                const T sn = sin(theta), sh = sin(T(0.5) * theta) / theta, t2 = theta * theta;
-                ka = sn / theta;
-                kb = T(2) * sh * sh;
-                kc = theta < kSeriesBelow ? T(1.0 / 6.0) - t2 * (T(1.0 / 120.0) - t2 * T(1.0 / 5040.0)) : (theta - sn) / (t2 * theta);
-            }
+            T phi[3], ka, kb, kc;
+            so3_coefficients(w, dt, phi, ka, kb, kc);
             T Egr[3], Egp[3], Jgr[3], vx[3];
             rodrigues(phi, ka, kb, gr, Egr);
             rodrigues(phi, ka, kb, gp, Egp);
@@ -100,6 +110,57 @@ __global__ void __launch_bounds__(kStepVjpThreads) integrate_vjp_kernel(const Cl
         if (grad_q) grad_q[i] = gq;
         if (grad_qd) grad_qd[i] = gv;
         if (grad_ydd) grad_ydd[i] = dt * gv;
+    }
+}
+
+// The forward map of the same step (include/grbda_hip_jvp.h), shaped as its twin above: one thread per scalar, the six base coordinates in
+// the registers of the thread of the first.  E^T = I - a [phi]x + b [phi]x^2 and J_r = I - b [phi]x + c [phi]x^2 are the transposes of what
+// the pull-back applies, so the same rodrigues() with the first coefficient negated:
+//     dqd' = dqd + dt dydd,   d' = d + dt dqd',   d_r' = E^T d_r + dt J_r dw',   d_p' = E^T (d_p - dt v' x d_r + dt dv').
+template <class T>
+__global__ void __launch_bounds__(kStepVjpThreads) integrate_jvp_kernel(const ClusterRec *__restrict__ base, const T *__restrict__ qd_next, T dt,
+                                                                        const T *__restrict__ dq, const T *__restrict__ dqd,
+                                                                        const T *__restrict__ dydd, T *__restrict__ dq_next,
+                                                                        T *__restrict__ dqd_next, int nv, size_t n)
+{
+    const int bv = base ? base->v_index : -1;  // (wave-uniform: one record)
+    const size_t stride = static_cast<size_t>(gridDim.x) * kStepVjpThreads;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * kStepVjpThreads + threadIdx.x; i < n; i += stride) {
+        const int j = static_cast<int>(i % static_cast<size_t>(nv));
+        if (bv >= 0 && j >= bv && j < bv + 6) {
+            if (j != bv) continue;
+            T w[3], v[3], dr[3], dp[3], dw[3], dv[3];  // i .. i + 5 are this state's base entries: bv + 6 <= nv
+            for (int a = 0; a < 3; a++) {
+                w[a] = qd_next[i + a];
+                v[a] = qd_next[i + 3 + a];
+                dr[a] = dq ? dq[i + a] : T(0);
+                dp[a] = dq ? dq[i + 3 + a] : T(0);
+                dw[a] = (dqd ? dqd[i + a] : T(0)) + dt * (dydd ? dydd[i + a] : T(0));
+                dv[a] = (dqd ? dqd[i + 3 + a] : T(0)) + dt * (dydd ? dydd[i + 3 + a] : T(0));
+            }
+            T phi[3], ka, kb, kc;
+            so3_coefficients(w, dt, phi, ka, kb, kc);
+            T Edr[3], Jdw[3], vx[3], t[3], Et[3];
+            rodrigues(phi, -ka, kb, dr, Edr);
+            rodrigues(phi, -kb, kc, dw, Jdw);
+            cross3(v, dr, vx);
+            for (int a = 0; a < 3; a++) t[a] = dp[a] - dt * vx[a] + dt * dv[a];
+            rodrigues(phi, -ka, kb, t, Et);
+            for (int a = 0; a < 3; a++) {
+                if (dq_next) {
+                    dq_next[i + a] = Edr[a] + dt * Jdw[a];
+                    dq_next[i + 3 + a] = Et[a];
+                }
+                if (dqd_next) {
+                    dqd_next[i + a] = dw[a];
+                    dqd_next[i + 3 + a] = dv[a];
+                }
+            }
+            continue;
+        }
+        const T vn = (dqd ? dqd[i] : T(0)) + dt * (dydd ? dydd[i] : T(0));
+        if (dq_next) dq_next[i] = (dq ? dq[i] : T(0)) + dt * vn;
+        if (dqd_next) dqd_next[i] = vn;
     }
 }
 
@@ -131,6 +192,21 @@ template hipError_t launch_integrate_vjp<float>(const ClusterRec *, const float 
                                                 size_t, hipStream_t);
 template hipError_t launch_integrate_vjp<double>(const ClusterRec *, const double *, double, const double *, const double *, double *, double *, double *,
                                                  int, size_t, hipStream_t);
+
+template <class T>
+hipError_t launch_integrate_jvp(const ClusterRec *base, const T *qd_next, T dt, const T *dq, const T *dqd, const T *dydd, T *dq_next, T *dqd_next,
+                                int nv, size_t nb, hipStream_t stream)
+{
+    const size_t n = nb * static_cast<size_t>(nv);
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL((integrate_jvp_kernel<T>), dim3(step_vjp_grid(n)), dim3(kStepVjpThreads), 0, stream, base, qd_next, dt, dq, dqd, dydd, dq_next,
+                       dqd_next, nv, n);
+    return hipGetLastError();
+}
+template hipError_t launch_integrate_jvp<float>(const ClusterRec *, const float *, float, const float *, const float *, const float *, float *, float *, int,
+                                                size_t, hipStream_t);
+template hipError_t launch_integrate_jvp<double>(const ClusterRec *, const double *, double, const double *, const double *, const double *, double *,
+                                                 double *, int, size_t, hipStream_t);
 
 template <class T>
 hipError_t launch_vjp_add(const T *a, const T *b, T *out, size_t n, hipStream_t stream)
