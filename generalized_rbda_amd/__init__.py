@@ -11,7 +11,7 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
+from ._abi import BODIES_SIGNATURES, JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
@@ -62,8 +62,9 @@ def lib() -> ctypes.CDLL:
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
-    # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule; then grbda_hip_wrench.h and grbda_hip_jvp.h
-    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES, **JVP_SIGNATURES}.items():
+    # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule; then grbda_hip_wrench.h, grbda_hip_jvp.h and
+    # grbda_hip_bodies.h
+    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES, **JVP_SIGNATURES, **BODIES_SIGNATURES}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
@@ -309,6 +310,55 @@ class _WrenchMethods:
         return self._wrench_host("rnea_wrench_host_f64", q, qd, ydd, bodies, wrench, frame, device)
 
 
+class _BodyListMethods:
+    """Poses and twists of a listed few bodies (include/grbda_hip_bodies.h), kept apart like _WrenchMethods.  bodies: up to 16 plan body
+    indices in any order; a body may repeat and may stand next to its ancestors.  Slot i of a result is row bodies[i] of body_poses /
+    body_twists."""
+
+    @staticmethod
+    def _body_list(bodies):
+        n = len(bodies)
+        return n, (c_int * max(n, 1))(*[int(b) for b in bodies])
+
+    def body_poses_list(self, q, bodies, stream=None):
+        """[B, n, 12] = E (9, row-major) then r (3) of the listed bodies (grbda_body_poses_list_*)."""
+        n, arr = self._body_list(bodies)
+        return self._call("body_poses_list", stream, self._state(q), dict(out=(n, 12)), ("q", n, arr, "out"))[0]
+
+    def body_twists_list(self, q, qd, ydd, bodies, stream=None):
+        """[B, n, 12] = v (6) then a (6) of the listed bodies in their own coordinates, the acceleration carrying -gravity
+        (grbda_body_twists_list_*)."""
+        n, arr = self._body_list(bodies)
+        return self._call("body_twists_list", stream, self._state(q, qd=qd, ydd=ydd), dict(out=(n, 12)), ("q", "qd", "ydd", n, arr, "out"))[0]
+
+    def body_list_walk(self, bodies):
+        """(walk_len, max_saved, route) of a body list (grbda_body_list_walk; no device): the bodies the kernels visit, the peak number of
+        branch-point values held at once, and the route -- 0 the walk, 1 the full kernel and a gather."""
+        n, arr = self._body_list(bodies)
+        a, b, c = c_int(0), c_int(0), c_int(0)
+        _check(lib().grbda_body_list_walk(self._h, n, arr, byref(a), byref(b), byref(c)))
+        return a.value, b.value, c.value
+
+    def body_poses_list_host(self, q, bodies, device: int = 0):
+        import numpy as np
+
+        n, arr = self._body_list(bodies)
+        q = np.ascontiguousarray(q, dtype="float64")
+        out = np.empty((q.shape[0], n, 12))
+        _check(lib().grbda_body_poses_list_host_f64(self._h, q.ctypes.data, n, arr, out.ctypes.data, q.shape[0], device))
+        return out
+
+    def body_twists_list_host(self, q, qd, ydd, bodies, device: int = 0):
+        import numpy as np
+
+        n, arr = self._body_list(bodies)
+        q, qd, ydd = (np.ascontiguousarray(a, dtype="float64") for a in (q, qd, ydd))
+        out = np.empty((q.shape[0], n, 12))
+        _check(lib().grbda_body_twists_list_host_f64(self._h, q.ctypes.data, qd.ctypes.data, ydd.ctypes.data, n, arr, out.ctypes.data, q.shape[0],
+                                                     device))
+        return out
+
+
 class _JvpMethods:
     """The Jacobian-vector products of Plan (include/grbda_hip_jvp.h), kept apart like _VjpMethods.  Every tangent is [B, nv]; a position
     tangent lies along the tangent step of fd_dq, the coordinates of the "q" gradients of id_vjp / fd_vjp / step_vjp, so that
@@ -356,7 +406,7 @@ class _JvpMethods:
                           ("q", "qd", "tau", "qd_next", float(dt), "dq", "dqd", "dtau", float(step), "dq_next", "dqd_next"), skip_empty=True)
 
 
-class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _JvpMethods):
+class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _BodyListMethods, _JvpMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):

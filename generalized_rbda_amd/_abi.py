@@ -131,3 +131,15 @@ for _stem, _args in _JVP_PAIRS.items():
     if _stem != "integrate_jvp":
         JVP_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
 JVP_SIGNATURES = {name: (c_int, args) for name, args in JVP_SIGNATURES.items()}
+
+# include/grbda_hip_bodies.h, poses and twists of a listed few bodies: a table of its own, applied by `lib()` after the others;
+# tests/test_body_list_args_cpu.py holds it to that header
+_BODIES_PAIRS = {
+    "body_poses_list": (P, P, I, BODIES, P, *TAIL),                      # q n bodies Xa_list
+    "body_twists_list": (P, P, P, P, I, BODIES, P, *TAIL),               # q qd ydd n bodies V_list
+}
+BODIES_SIGNATURES = {"grbda_body_list_walk": (P, I, BODIES, POINTER(c_int), POINTER(c_int), POINTER(c_int))}  # n bodies walk_len max_saved route
+for _stem, _args in _BODIES_PAIRS.items():
+    BODIES_SIGNATURES[f"grbda_{_stem}_f64"] = BODIES_SIGNATURES[f"grbda_{_stem}_f32"] = _args
+    BODIES_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
+BODIES_SIGNATURES = {name: (c_int, args) for name, args in BODIES_SIGNATURES.items()}

@@ -18,6 +18,7 @@
 #include "../../include/grbda_hip_step_vjp.h"
 #include "../../include/grbda_hip_jvp.h"
 #include "../../include/grbda_hip_wrench.h"
+#include "../../include/grbda_hip_bodies.h"
 #include "../../include/grbda_model_desc.h"
 #include "devplan.h"
 
@@ -1306,6 +1307,209 @@ int twists(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *V, siz
     return twists_stage<T>(p, *t, q, qd, ydd, V, vs, as, B, device, stream);
 }
 
+// ---- poses and twists of a listed few bodies (include/grbda_hip_bodies.h; body_list_kernels.hip) ----------------------------------------
+// The walk of a body list (devplan.h, BodyWalkStep): the precision-independent part, built on the host per call.  walk_len and max_saved are
+// counted in full even when they pass kMaxWalk / kMaxSaved (or an index does not fit a step's fields): `route` is then 1, the full kernel
+// and a gather, and the steps are not used.
+struct BodyWalkHost {
+    int walk_len = 0, max_saved = 0, route = 0, n = 0;
+    uint8_t slot[kMaxBodyList] = {};
+    BodyWalkStep step[kMaxWalk] = {};
+    BodyList list{};
+};
+// (n and every index checked by the caller)
+BodyWalkHost build_body_walk(const HostPlan &h, const Layout &L, int n, const int *bodies)
+{
+    BodyWalkHost W;
+    W.n = W.list.n = n;
+    for (int i = 0; i < kMaxBodyList; i++) W.list.body[i] = i < n ? bodies[i] : -1;
+    const int nbod = h.n_bodies;
+    std::vector<char> in_walk(static_cast<size_t>(nbod), 0);
+    for (int i = 0; i < n; i++)
+        for (int b = bodies[i]; b >= 0 && !in_walk[b]; b = L.bodies[b].parent) in_walk[b] = 1;
+    // per body: its cluster and its place in it; the cluster's first spanning rate
+    std::vector<int> cluster_of(static_cast<size_t>(nbod), -1), span_at(L.clusters.size(), 0);
+    int at = 0;
+    for (size_t ci = 0; ci < L.clusters.size(); ci++) {
+        const ClusterRec &c = L.clusters[ci];
+        span_at[ci] = at;
+        for (int i = 0; i < c.k; i++) cluster_of[c.first_body + i] = static_cast<int>(ci);
+        at += c.kind == CK_FREE ? 6 : c.k;
+    }
+    // children in the walk, in index order (a parent precedes its children in the plan's body order); a floating base hangs off nothing
+    std::vector<std::vector<int>> kids(static_cast<size_t>(nbod));
+    std::vector<int> roots;
+    const auto parent_of = [&](int b) { return L.clusters[cluster_of[b]].kind == CK_FREE ? -1 : L.bodies[b].parent; };
+    for (int b = 0; b < nbod; b++) {
+        if (!in_walk[b]) continue;
+        const int par = parent_of(b);
+        (par < 0 ? roots : kids[par]).push_back(b);
+    }
+    bool fits = nbod <= 32767 && h.nq <= 32767 && at <= 32767;
+    std::vector<char> slot_used;
+    std::vector<int> slot_of(static_cast<size_t>(nbod), -1);
+    int in_use = 0, n_slots_out = 0;
+    // depth first, iteratively: (body, restore slot or -1, whether this is the last child to read that slot)
+    struct Item {
+        int body, restore;
+        bool last;
+    };
+    std::vector<Item> stack;
+    for (auto it = roots.rbegin(); it != roots.rend(); ++it) stack.push_back({*it, -1, false});
+    while (!stack.empty()) {
+        const Item item = stack.back();
+        stack.pop_back();
+        const int b = item.body;
+        if (item.restore >= 0 && item.last) {  // (the step reads the slot before it writes one of its own)
+            slot_used[item.restore] = 0;
+            in_use--;
+        }
+        int save = -1;
+        if (kids[b].size() >= 2) {
+            size_t sl = 0;
+            while (sl < slot_used.size() && slot_used[sl]) sl++;
+            if (sl == slot_used.size()) slot_used.push_back(0);
+            slot_used[sl] = 1;
+            save = static_cast<int>(sl);
+            in_use++;
+            W.max_saved = std::max(W.max_saved, in_use);
+        }
+        const int s = W.walk_len++;
+        int n_out = 0;
+        for (int i = 0; i < n; i++)
+            if (bodies[i] == b) {
+                W.slot[n_slots_out++] = static_cast<uint8_t>(i);
+                n_out++;
+            }
+        if (s < kMaxWalk && fits) {
+            const int ci = cluster_of[b];
+            const ClusterRec &c = L.clusters[ci];
+            const BodyRec &br = L.bodies[b];
+            const int i = b - c.first_body;
+            BodyWalkStep &st = W.step[s];
+            st.cofs = br.cofs;
+            st.body = static_cast<int16_t>(b);
+            st.free = c.kind == CK_FREE;
+            st.q_col = static_cast<int16_t>(c.kind == CK_LOOP ? c.q_index + i : c.q_index);
+            st.span_col = static_cast<int16_t>(span_at[ci] + (c.kind == CK_FREE ? 0 : i));
+            st.n = static_cast<uint8_t>(c.kind == CK_LOOP || c.kind == CK_FREE ? 0 : c.n);
+            fits = fits && (c.kind == CK_LOOP || c.kind == CK_FREE || (c.n >= 1 && c.n <= 255));
+            st.axis = static_cast<uint8_t>(br.axis);
+            st.canon = static_cast<uint8_t>(br.canon_axis);
+            st.root = parent_of(b) < 0;
+            st.save = static_cast<uint8_t>(save >= 0 && save < kMaxSaved ? save : kWalkNone);
+            st.restore = static_cast<uint8_t>(item.restore >= 0 && item.restore < kMaxSaved ? item.restore : kWalkNone);
+            st.n_out = static_cast<uint8_t>(n_out);
+        }
+        // the first child continues from the running value; the others start from the saved one, the last of them frees it
+        for (size_t k = kids[b].size(); k-- > 0;) stack.push_back({kids[b][k], k == 0 ? -1 : save, k + 1 == kids[b].size()});
+    }
+    W.route = (W.walk_len > kMaxWalk || W.max_saved > kMaxSaved || !fits) ? 1 : 0;
+    return W;
+}
+template <class T>
+BodyWalk<T> device_body_walk(const grbda_plan *p, const DeviceTables &t, const BodyWalkHost &H)
+{
+    BodyWalk<T> W{};
+    W.n_steps = H.walk_len;
+    W.n_list = H.n;
+    W.n_saved = H.max_saved;
+    W.nq = p->host.nq;
+    W.n_span = span_count(p);
+    W.ori_repr = p->host.ori_repr;
+    W.consts = consts_of<T>(t);
+    for (int i = 0; i < 6; i++) W.a_root[i] = static_cast<T>(-p->host.gravity[i]);
+    std::memcpy(W.slot, H.slot, sizeof(W.slot));
+    std::memcpy(W.step, H.step, sizeof(W.step));
+    return W;
+}
+// Everything the list entry points refuse, on the host and before any device call.  qd == nullptr && ydd == nullptr: the poses.
+template <class T>
+int body_list_args(const grbda_plan *p, bool twists, const T *q, const T *qd, const T *ydd, int n, const int *bodies, const T *out, size_t B)
+{
+    if (!q || (twists && (!qd || !ydd))) return set_err(GRBDA_EINVAL, "null argument");
+    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
+    if (n > 0 && (!bodies || !out)) return set_err(GRBDA_EINVAL, "null argument");
+    for (int i = 0; i < n; i++)
+        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const void *const in[3] = {q, twists ? qd : nullptr, twists ? ydd : nullptr}, *const outs[1] = {n > 0 ? out : nullptr};
+    const size_t in_bytes[3] = {bq, bv, bv}, out_bytes[1] = {B * static_cast<size_t>(n) * 12 * sizeof(T)};
+    return no_overlap(in, in_bytes, outs, out_bytes);
+}
+// One pass over nb states (arguments checked, nb > 0, n > 0, device found): the walk kernel, or -- route 1 -- the full kernel into `full`
+// [nb][n_bodies][12] and the gather.  Twists: the spanning rates into vs, as [nb][span_count] first, as twists_stage.
+template <class T>
+int body_list_stage(const grbda_plan *p, const DeviceTables &t, const BodyWalkHost &H, bool twists, const T *q, const T *qd, const T *ydd, T *out,
+                    T *full, T *vs, T *as, size_t nb, int device, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (H.route == 1) {
+        if (int rc = twists ? twists_stage<T>(p, t, q, qd, ydd, full, vs, as, nb, device, stream) : poses_stage<T>(p, t, q, full, nb, stream)) return rc;
+        hipError_t e = launch_body_gather<T>(H.list, full, p->host.n_bodies, nb, out, hs);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "body gather launch");
+    }
+    const BodyWalk<T> W = device_body_walk<T>(p, t, H);
+    // eight one-wavefront workgroups per CU as the full kernels, fewer where the saved values' LDS holds fewer
+    const size_t per_cu = std::min<size_t>(8, lds_workgroups_per_cu(static_cast<size_t>(H.max_saved) * 12 * kWave * sizeof(T)));
+    const int grid = static_cast<int>(tile_grid(t.n_cu, per_cu, nb));
+    hipError_t e;
+    if (twists) {
+        if (int rc = spanning<T>(p, q, qd, ydd, vs, as, nb, device, stream)) return rc;
+        e = launch_body_twists_list<T>(W, q, vs, as, out, nb, grid, hs);
+    } else {
+        e = launch_body_poses_list<T>(W, q, out, nb, grid, hs);
+    }
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "body list launch");
+}
+// elements of work memory per state of a pass: the full rows of route 1, the spanning rates of the twists
+size_t body_list_per_state(const grbda_plan *p, const BodyWalkHost &H, bool twists)
+{
+    return (H.route == 1 ? static_cast<size_t>(p->host.n_bodies) * 12 : 0) + (twists ? 2 * static_cast<size_t>(span_count(p)) : 0);
+}
+template <class T>
+int body_list_run(const grbda_plan *p, bool twists, const T *q, const T *qd, const T *ydd, int n, const int *bodies, T *out, size_t B, int device,
+                  void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = body_list_args<T>(p, twists, q, qd, ydd, n, bodies, out, B)) return rc;
+    if (n == 0 || B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const BodyWalkHost H = build_body_walk(p->host, layout_of(p->host, sizeof(T) == 4 ? 0 : 1), n, bodies);
+    const size_t per_state = body_list_per_state(p, H, twists);
+    if (per_state == 0) return body_list_stage<T>(p, *t, H, false, q, nullptr, nullptr, out, nullptr, nullptr, nullptr, B, device, stream);
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n12 = static_cast<size_t>(n) * 12;
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        T *full = H.route == 1 ? w.take(nb * nbod * 12) : nullptr;
+        T *vs = twists ? w.take(nb * ns) : nullptr, *as = twists ? w.take(nb * ns) : nullptr;
+        if (int rc = body_list_stage<T>(p, *t, H, twists, q + b0 * nq, twists ? qd + b0 * nv : nullptr, twists ? ydd + b0 * nv : nullptr, out + b0 * n12,
+                                        full, vs, as, nb, device, stream))
+            return rc;
+    }
+    return GRBDA_OK;
+}
+int body_list_host_f64(const grbda_plan *p, bool twists, const double *q, const double *qd, const double *ydd, int n, const int *bodies, double *out,
+                       size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = body_list_args<double>(p, twists, q, qd, ydd, n, bodies, out, B)) return rc;
+    if (n == 0 || B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = twists ? st.in(qd, B * nv) : nullptr, *dy = twists ? st.in(ydd, B * nv) : nullptr;
+    double *dout = st.out(out, B * static_cast<size_t>(n) * 12);
+    return st.run([&] { return body_list_run<double>(p, twists, dq, dqd, dy, n, bodies, dout, B, device, nullptr); });
+}
+
 // ---- energy, centre of mass, centroidal momentum (centroidal_kernels.hip; include/grbda_hip.h) -----------------------------------
 // sum of the body masses: entry (3, 3) of the 21 packed inertia constants behind BodyRec::cofs + 12 (devmath.h, sidx(3, 3) = 15)
 double plan_total_mass(const grbda_plan *p)
@@ -1977,8 +2181,8 @@ Route wrench_route(const grbda_plan *p, bool rnea, int n_cu, size_t B, const Wre
     return {ROUTE_CHAIN, base, 0};
 }
 // Forward / inverse dynamics with the listed wrenches.  Chain route, body frame: one launch on the caller's arrays, no work memory.  Chain
-// route, world frame: per chunk the poses, wrench_to_body_kernel, the launch.  Fallback: per chunk a zeroed dense chunk, (body frame: the
-// poses,) wrench_scatter_kernel, run().  The chunks come off p->work (run() itself uses the scratch slab and work_proj only).
+// route, world frame: per chunk the poses of the listed bodies (body_list_stage), wrench_to_body_kernel, the launch.  Fallback: per chunk a
+// zeroed dense chunk, (body frame: the listed poses,) wrench_scatter_kernel, run().  The chunks come off p->work (run() itself uses the scratch slab and work_proj only).
 template <class T>
 int wrench_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, int n, const int *bodies, const T *wrench, int frame, T *out,
                size_t B, int device, void *stream)
@@ -2001,21 +2205,25 @@ int wrench_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T 
     if (chain && frame == GRBDA_WRENCH_BODY) return launch(W, 0, B);
     const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, n6 = static_cast<size_t>(n) * 6;
     const bool rotate = chain || frame == GRBDA_WRENCH_BODY;  // (the poses are computed only then)
-    const size_t per_state = (rotate ? nbod * 12 : 0) + (chain ? n6 : nbod * 6);
+    const size_t n12 = static_cast<size_t>(n) * 12;
+    // the poses of the listed bodies alone, in list order (body_list_stage); a list past the walk's caps takes the full rows as well
+    const BodyWalkHost H = rotate ? build_body_walk(p->host, layout_of(p->host, sizeof(T) == 4 ? 0 : 1), n, bodies) : BodyWalkHost{};
+    const size_t per_state = (rotate ? n12 + body_list_per_state(p, H, false) : 0) + (chain ? n6 : nbod * 6);
     const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         Carver<T> w(wptr, c.chunk * per_state);
-        T *Xa = rotate ? w.take(nb * nbod * 12) : nullptr;
+        T *Xa = rotate ? w.take(nb * n12) : nullptr;
+        T *full = rotate && H.route == 1 ? w.take(nb * nbod * 12) : nullptr;
         WrenchList<T> Wc = W;
         Wc.w = wrench + b0 * n6;
         if (rotate)
-            if (int rc = poses_stage<T>(p, *t, q + b0 * nq, Xa, nb, stream)) return rc;
+            if (int rc = body_list_stage<T>(p, *t, H, false, q + b0 * nq, nullptr, nullptr, Xa, full, nullptr, nullptr, nb, device, stream)) return rc;
         if (chain) {
             T *wb = w.take(nb * n6);
-            hipError_t e = launch_wrench_to_body<T>(Wc, Xa, static_cast<int>(nbod), nb, wb, hs);
+            hipError_t e = launch_wrench_to_body<T>(Wc, Xa, nb, wb, hs);
             if (e != hipSuccess) return hip_err(e, "wrench rotation launch");
             Wc.w = wb;
             if (int rc = launch(Wc, b0, nb)) return rc;
@@ -4001,6 +4209,47 @@ int grbda_body_twists_f32(const grbda_plan *p, const float *q, const float *qd, 
                           void *stream)
 {
     return twists<float>(p, q, qd, ydd, V, B, device, stream);
+}
+int grbda_body_poses_list_f64(const grbda_plan *p, const double *q, int n, const int *bodies, double *Xa_list, size_t B, int device, void *stream)
+{
+    return body_list_run<double>(p, false, q, nullptr, nullptr, n, bodies, Xa_list, B, device, stream);
+}
+int grbda_body_poses_list_f32(const grbda_plan *p, const float *q, int n, const int *bodies, float *Xa_list, size_t B, int device, void *stream)
+{
+    return body_list_run<float>(p, false, q, nullptr, nullptr, n, bodies, Xa_list, B, device, stream);
+}
+int grbda_body_poses_list_host_f64(const grbda_plan *p, const double *q, int n, const int *bodies, double *Xa_list, size_t B, int device)
+{
+    return body_list_host_f64(p, false, q, nullptr, nullptr, n, bodies, Xa_list, B, device);
+}
+int grbda_body_twists_list_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, int n, const int *bodies, double *V_list,
+                               size_t B, int device, void *stream)
+{
+    return body_list_run<double>(p, true, q, qd, ydd, n, bodies, V_list, B, device, stream);
+}
+int grbda_body_twists_list_f32(const grbda_plan *p, const float *q, const float *qd, const float *ydd, int n, const int *bodies, float *V_list,
+                               size_t B, int device, void *stream)
+{
+    return body_list_run<float>(p, true, q, qd, ydd, n, bodies, V_list, B, device, stream);
+}
+int grbda_body_twists_list_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, int n, const int *bodies,
+                                    double *V_list, size_t B, int device)
+{
+    return body_list_host_f64(p, true, q, qd, ydd, n, bodies, V_list, B, device);
+}
+int grbda_body_list_walk(const grbda_plan *p, int n, const int *bodies, int *walk_len, int *max_saved, int *route)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
+    if (n > 0 && !bodies) return set_err(GRBDA_EINVAL, "null argument");
+    for (int i = 0; i < n; i++)
+        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    const BodyWalkHost H = build_body_walk(p->host, p->host.lay64, n, bodies);
+    if (walk_len) *walk_len = H.walk_len;
+    if (max_saved) *max_saved = H.max_saved;
+    if (route) *route = H.route;
+    return GRBDA_OK;
 }
 int grbda_body_poses_f64(const grbda_plan *p, const double *q, double *Xa, size_t B, int device, void *stream)
 {

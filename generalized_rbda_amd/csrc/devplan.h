@@ -180,13 +180,64 @@ template <class T>
 hipError_t launch_rnea_chain_wrench(const RneaChainDev<T> &P, const WrenchList<T> &W, int base_body, const T *q, const T *qd, const T *ydd, T *tau,
                                     size_t B, T *scratch, int grid, size_t lds_bytes, hipStream_t stream);  // base_body: ChainFree::body or -1
 hipError_t set_max_dynamic_lds_chain_wrench();
-// The frames of the sparse wrenches (wrench_kernels.hip), over nb states with the poses Xa [nb][n_bodies][12] of poses_stage:
+// The frames of the sparse wrenches (wrench_kernels.hip), over nb states with the poses Xa [nb][n][12] of the listed bodies in list order:
 // to_body: out[nb][n][6] = Xa_body w (world -> body, in front of the chain route); otherwise the fallback's dense world-frame chunk
 // fext[nb][n_bodies][6] (zeroed by the caller) += w, rotated body -> world when from_body is set (Xa may be null when it is not).
 template <class T>
-hipError_t launch_wrench_to_body(const WrenchList<T> &W, const T *Xa, int n_bodies, size_t nb, T *out, hipStream_t stream);
+hipError_t launch_wrench_to_body(const WrenchList<T> &W, const T *Xa, size_t nb, T *out, hipStream_t stream);
 template <class T>
 hipError_t launch_wrench_scatter(const WrenchList<T> &W, const T *Xa, int from_body, int n_bodies, size_t nb, T *fext, hipStream_t stream);
+
+// Poses and twists of a listed few bodies (include/grbda_hip_bodies.h; body_list_kernels.hip).  capi.cpp builds the WALK per call from the
+// caller's host list and it travels by value in the kernel arguments, like WrenchList and ContactSet: the union of the listed bodies'
+// ancestors, each body once, depth first from the roots with the children in index order.  A step computes its body from the running value
+// of the root path, which the kernels hold in registers: the step before it is its tree parent, unless `restore` names the saved value of a
+// branch point to start from.  `save` names the slot that keeps the body's value for its later children (a body with two or more children
+// in the walk); a slot is free again once the last child has read it.  Saved values live in LDS, [slot][value 12][lane].  The n_out
+// output slots a step stores are the next n_out entries of BodyWalk::slot.
+constexpr int kMaxBodyList = 16;
+// steps of a walk: the MIT humanoid's two feet take 11, the sixteen last bodies of the humanoid, Tello and the Mini Cheetah 17 to 18.  The cap
+// is kept where a list can pass it on a model of the test set (all sixteen of the 20 bodies of parallel_chain_exp_d10_l16 walk 20), so that
+// the fallback is a route that runs; a step is 20 bytes of kernel arguments, and nothing but this constant stands against a longer walk
+constexpr int kMaxWalk = 19;
+constexpr int kMaxSaved = 4;   // values saved at once: 4 x 12 x 64 lanes x 8 bytes = 24 KiB of LDS in fp64
+constexpr int kWalkNone = 0xFF;
+struct BodyWalkStep {
+    int32_t cofs;      // BodyRec::cofs
+    int16_t body;      // plan body index
+    int16_t q_col;     // first position column the joint angle reads (an implicit cluster: the body's own spanning position)
+    int16_t span_col;  // the body's first spanning rate
+    uint8_t free;      // 1: the floating base (its own pose and twist, no parent)
+    uint8_t n;         // explicit clusters: the angle is the body's G row times the cluster's n positions; 0: q[q_col] itself
+    uint8_t axis;      // BodyRec::axis
+    uint8_t canon;     // BodyRec::canon_axis
+    uint8_t root;      // 1: no tree parent
+    uint8_t save;      // slot to keep the body's value in, or kWalkNone
+    uint8_t restore;   // slot to start from, or kWalkNone: the running value
+    uint8_t n_out;     // output slots stored after the step
+};
+template <class T>
+struct BodyWalk {
+    int n_steps, n_list, n_saved;  // steps, outputs per state, peak number of saved values
+    int nq, n_span, ori_repr;
+    const T *consts;
+    T a_root[6];  // -gravity
+    uint8_t slot[kMaxBodyList];
+    BodyWalkStep step[kMaxWalk];
+};
+static_assert(sizeof(BodyWalk<double>) <= 2048, "the walk travels in the kernel arguments");
+// out[nb][n_list][12]; qd_span / qdd_span: the spanning rates of spanning_kernel, [nb][n_span]
+template <class T>
+hipError_t launch_body_poses_list(const BodyWalk<T> &W, const T *q, T *out, size_t nb, int grid, hipStream_t stream);
+template <class T>
+hipError_t launch_body_twists_list(const BodyWalk<T> &W, const T *q, const T *qd_span, const T *qdd_span, T *out, size_t nb, int grid, hipStream_t stream);
+// the walk's fallback: out[nb][n][12] = full[nb][n_bodies][12] at the listed bodies
+struct BodyList {
+    int n;
+    int body[kMaxBodyList];
+};
+template <class T>
+hipError_t launch_body_gather(const BodyList &L, const T *full, int n_bodies, size_t nb, T *out, hipStream_t stream);
 
 // single-cluster programs (RneaChainProgram::single_gen; chain_kernels.hip, rnea_gen1_kernel): P.lds_bytes = the work area, lds_bytes =
 // work area + nq + 2 nv rows of staged inputs
