@@ -11,7 +11,7 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import BODIES_SIGNATURES, JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
+from ._abi import BODIES_SIGNATURES, JACOBIAN_SIGNATURES, JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
@@ -63,8 +63,9 @@ def lib() -> ctypes.CDLL:
         fn.restype, fn.argtypes = restype, list(argtypes)
     # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
     # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule; then grbda_hip_wrench.h, grbda_hip_jvp.h and
-    # grbda_hip_bodies.h
-    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES, **JVP_SIGNATURES, **BODIES_SIGNATURES}.items():
+    # grbda_hip_bodies.h, and last grbda_hip_jacobians.h
+    for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES, **JVP_SIGNATURES, **BODIES_SIGNATURES,
+                                      **JACOBIAN_SIGNATURES}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
@@ -359,6 +360,60 @@ class _BodyListMethods:
         return out
 
 
+class _JacobianMethods:
+    """Frame Jacobians and their drift at a listed few body frames (include/grbda_hip_jacobians.h), kept apart like _WrenchMethods.  A frame
+    is the body-fixed point offsets[i] (the reference's body axes; None: the body origins) of body bodies[i], with the body's axes
+    (frame="body") or world axes (frame="world"); up to 16 frames, a body may repeat."""
+
+    @staticmethod
+    def _frames(bodies, offsets, frame):
+        if frame not in ("body", "world"):
+            raise ValueError('frame must be "body" or "world"')
+        n = len(bodies)
+        if offsets is not None and (len(offsets) != n or any(len(o) != 3 for o in offsets)):
+            raise ValueError("offsets must hold one (x, y, z) per body")
+        off = None if offsets is None else (c_double * max(3 * n, 1))(*[float(x) for o in offsets for x in o])
+        return n, (c_int * max(n, 1))(*[int(b) for b in bodies]), off, 0 if frame == "body" else 1
+
+    def frame_jacobians(self, q, bodies, offsets=None, frame="body", qd=None, drift=False, stream=None):
+        """J[B, n, 6, nv] with v_frame = J qd, each frame [angular 3; linear 3], structural zeros written (grbda_frame_jacobians_*).
+        drift=True (needs qd): returns (J, drift[B, n, 6]), drift = Jdot qd, the frame's acceleration at ydd = 0 without gravity, so that
+        a_frame = J ydd + drift."""
+        n, arr, off, fr = self._frames(bodies, offsets, frame)
+        if drift and qd is None:
+            raise ValueError("the drift needs qd")
+        ins = self._state(q, qd=qd) if drift else self._state(q)
+        outs = self._call("frame_jacobians", stream, ins, dict(J=(n, 6, self.nv), drift=(n, 6) if drift else None),
+                          ("q", "qd" if drift else None, n, arr, off, fr, "J", "drift"))
+        return outs if drift else outs[0]
+
+    def frame_drift(self, q, qd, bodies, offsets=None, frame="body", stream=None):
+        """drift[B, n, 6] alone (grbda_frame_jacobians_* with a NULL J)."""
+        n, arr, off, fr = self._frames(bodies, offsets, frame)
+        return self._call("frame_jacobians", stream, self._state(q, qd=qd), dict(J=None, drift=(n, 6)), ("q", "qd", n, arr, off, fr, "J", "drift"))[1]
+
+    def frame_jacobians_route(self, bodies):
+        """(route, walk_len, max_saved) of a frame list (grbda_frame_jacobians_route; no device): 0 the walk kernel, 1 the expanded batch
+        through the listed twists; the bodies the walk visits and the peak number of branch-point values it holds at once."""
+        n = len(bodies)
+        a, b, c = c_int(0), c_int(0), c_int(0)
+        _check(lib().grbda_frame_jacobians_route(self._h, n, (c_int * max(n, 1))(*[int(x) for x in bodies]), byref(a), byref(b), byref(c)))
+        return a.value, b.value, c.value
+
+    def frame_jacobians_host(self, q, bodies, offsets=None, frame="body", qd=None, drift=False, device: int = 0):
+        import numpy as np
+
+        n, arr, off, fr = self._frames(bodies, offsets, frame)
+        if drift and qd is None:
+            raise ValueError("the drift needs qd")
+        q = np.ascontiguousarray(q, dtype="float64")
+        qd = np.ascontiguousarray(qd, dtype="float64") if drift else None
+        J, d = np.empty((q.shape[0], n, 6, self.nv)), np.empty((q.shape[0], n, 6)) if drift else None
+        _check(lib().grbda_frame_jacobians_host_f64(self._h, q.ctypes.data, qd.ctypes.data if drift else None, n, arr, off, fr, J.ctypes.data,
+                                                    d.ctypes.data if drift else None, q.shape[0], device))
+        return (J, d) if drift else J
+
+
 class _JvpMethods:
     """The Jacobian-vector products of Plan (include/grbda_hip_jvp.h), kept apart like _VjpMethods.  Every tangent is [B, nv]; a position
     tangent lies along the tangent step of fd_dq, the coordinates of the "q" gradients of id_vjp / fd_vjp / step_vjp, so that
@@ -406,7 +461,7 @@ class _JvpMethods:
                           ("q", "qd", "tau", "qd_next", float(dt), "dq", "dqd", "dtau", float(step), "dq_next", "dqd_next"), skip_empty=True)
 
 
-class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _BodyListMethods, _JvpMethods):
+class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _BodyListMethods, _JacobianMethods, _JvpMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):

@@ -143,3 +143,14 @@ for _stem, _args in _BODIES_PAIRS.items():
     BODIES_SIGNATURES[f"grbda_{_stem}_f64"] = BODIES_SIGNATURES[f"grbda_{_stem}_f32"] = _args
     BODIES_SIGNATURES[f"grbda_{_stem}_host_f64"] = _args[:-1]
 BODIES_SIGNATURES = {name: (c_int, args) for name, args in BODIES_SIGNATURES.items()}
+
+# include/grbda_hip_jacobians.h, frame Jacobians and their drift at a listed few body frames: a table of its own, applied by `lib()` after
+# the others; tests/test_frame_jacobians_args_cpu.py holds it to that header
+_JACOBIAN_PAIR = (P, P, P, I, BODIES, OFFSETS, I, P, P, *TAIL)           # q qd n bodies offsets frame J drift
+JACOBIAN_SIGNATURES = {
+    "grbda_frame_jacobians_f64": _JACOBIAN_PAIR,
+    "grbda_frame_jacobians_f32": _JACOBIAN_PAIR,
+    "grbda_frame_jacobians_host_f64": _JACOBIAN_PAIR[:-1],
+    "grbda_frame_jacobians_route": (P, I, BODIES, POINTER(c_int), POINTER(c_int), POINTER(c_int)),  # n bodies route walk_len max_saved
+}
+JACOBIAN_SIGNATURES = {name: (c_int, args) for name, args in JACOBIAN_SIGNATURES.items()}

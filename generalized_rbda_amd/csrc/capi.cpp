@@ -19,6 +19,7 @@
 #include "../../include/grbda_hip_jvp.h"
 #include "../../include/grbda_hip_wrench.h"
 #include "../../include/grbda_hip_bodies.h"
+#include "../../include/grbda_hip_jacobians.h"
 #include "../../include/grbda_model_desc.h"
 #include "devplan.h"
 
@@ -1267,10 +1268,12 @@ int poses_stage(const grbda_plan *p, const DeviceTables &t, const T *q, T *Xa, s
 }
 template <class T>
 int twists_stage(const grbda_plan *p, const DeviceTables &t, const T *q, const T *qd, const T *ydd, T *V, T *vs, T *as, size_t nb, int device,
-                 void *stream)
+                 void *stream, bool gravity = true)
 {
     if (int rc = spanning<T>(p, q, qd, ydd, vs, as, nb, device, stream)) return rc;
-    const DevPlan<T> d = make_dev_plan<T>(p, t, false, false);
+    DevPlan<T> d = make_dev_plan<T>(p, t, false, false);
+    if (!gravity)  // (the frame drift: the root's acceleration is zero)
+        for (T &x : d.a_root) x = 0;
     hipError_t e = launch_twists<T>(d, p->host.n_clusters, span_count(p), q, vs, as, V, nb, static_cast<int>(tile_grid(t.n_cu, 8, nb)),
                                     static_cast<hipStream_t>(stream));
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "twists launch");
@@ -1441,15 +1444,18 @@ int body_list_args(const grbda_plan *p, bool twists, const T *q, const T *qd, co
 // [nb][n_bodies][12] and the gather.  Twists: the spanning rates into vs, as [nb][span_count] first, as twists_stage.
 template <class T>
 int body_list_stage(const grbda_plan *p, const DeviceTables &t, const BodyWalkHost &H, bool twists, const T *q, const T *qd, const T *ydd, T *out,
-                    T *full, T *vs, T *as, size_t nb, int device, void *stream)
+                    T *full, T *vs, T *as, size_t nb, int device, void *stream, bool gravity = true)
 {
     hipStream_t hs = static_cast<hipStream_t>(stream);
     if (H.route == 1) {
-        if (int rc = twists ? twists_stage<T>(p, t, q, qd, ydd, full, vs, as, nb, device, stream) : poses_stage<T>(p, t, q, full, nb, stream)) return rc;
+        if (int rc = twists ? twists_stage<T>(p, t, q, qd, ydd, full, vs, as, nb, device, stream, gravity) : poses_stage<T>(p, t, q, full, nb, stream))
+            return rc;
         hipError_t e = launch_body_gather<T>(H.list, full, p->host.n_bodies, nb, out, hs);
         return e == hipSuccess ? GRBDA_OK : hip_err(e, "body gather launch");
     }
-    const BodyWalk<T> W = device_body_walk<T>(p, t, H);
+    BodyWalk<T> W = device_body_walk<T>(p, t, H);
+    if (!gravity)
+        for (T &x : W.a_root) x = 0;
     // eight one-wavefront workgroups per CU as the full kernels, fewer where the saved values' LDS holds fewer
     const size_t per_cu = std::min<size_t>(8, lds_workgroups_per_cu(static_cast<size_t>(H.max_saved) * 12 * kWave * sizeof(T)));
     const int grid = static_cast<int>(tile_grid(t.n_cu, per_cu, nb));
@@ -1643,6 +1649,235 @@ int centroidal_matrix(const grbda_plan *p, const T *q, T *A, size_t B, int devic
         if (int rc = centroidal_stage<T>(p, *t, q_x, qd_x, static_cast<const T *>(nullptr), o, vs, as, nb * nv, device, stream)) return rc;
     }
     return GRBDA_OK;
+}
+
+// ---- frame Jacobians and their drift at a listed few body frames (include/grbda_hip_jacobians.h; frame_jacobian_kernels.hip) ------------
+// The walk of route 0 (devplan.h, JacWalkStep), built on the host per call like build_body_walk: the same depth-first order, except that a
+// body's in-cluster child comes first among its children, so that the cluster's axes go on accumulating in registers from the one step
+// to the next.  walk_len and max_saved are counted in full; `route` is 1 -- the expanded batch through the listed twists -- when a root
+// path holds anything but the floating base and explicit clusters of 1..kJacMaxDof coordinates, on the spanning-tree route, when a body of
+// the walk has two in-cluster children, and past the caps: kMaxWalk steps, kJacMaxSlots frames and saved values together, 128 velocities.
+// cols: per frame, the velocity columns on its root path (on either route).
+struct JacWalkHost {
+    int walk_len = 0, max_saved = 0, route = 0, n = 0;
+    JacWalkStep step[kMaxWalk] = {};
+    uint64_t cols[kMaxBodyList][kJacMaskWords] = {};
+    uint8_t canon[kMaxBodyList] = {};
+};
+// (n and every index checked by the caller)
+JacWalkHost build_jac_walk(const HostPlan &h, const Layout &L, int n, const int *bodies)
+{
+    JacWalkHost W;
+    W.n = n;
+    const int nbod = h.n_bodies;
+    std::vector<int> cluster_of(static_cast<size_t>(nbod), -1);
+    for (size_t ci = 0; ci < L.clusters.size(); ci++)
+        for (int i = 0; i < L.clusters[ci].k; i++) cluster_of[L.clusters[ci].first_body + i] = static_cast<int>(ci);
+    const auto parent_of = [&](int b) { return L.clusters[cluster_of[b]].kind == CK_FREE ? -1 : L.bodies[b].parent; };
+    bool ok = !h.big_clusters && h.nv <= 64 * kJacMaskWords && nbod <= 32767 && h.nq <= 32767;
+    const bool masks = h.nv <= 64 * kJacMaskWords;
+    std::vector<unsigned> below(static_cast<size_t>(nbod), 0);
+    for (int i = 0; i < n; i++) {
+        W.canon[i] = static_cast<uint8_t>(L.bodies[bodies[i]].canon_axis);
+        if (!masks) W.cols[i][0] = W.cols[i][1] = ~0ull;
+        for (int b = bodies[i]; b >= 0; b = parent_of(b)) {
+            below[b] |= 1u << i;
+            const ClusterRec &c = L.clusters[cluster_of[b]];
+            const int nc = c.kind == CK_FREE ? 6 : c.n;
+            if (masks)
+                for (int k = c.v_index; k < c.v_index + nc; k++) W.cols[i][k >> 6] |= 1ull << (k & 63);
+            if (c.kind == CK_FREE) ok = ok && L.bodies[b].canon_axis == 2;
+            else ok = ok && c.kind == CK_STATIC && c.n >= 1 && c.n <= kJacMaxDof && L.bodies[b].jtype == 0;
+        }
+    }
+    // children in the walk: the in-cluster child first, the others in index order
+    std::vector<std::vector<int>> kids(static_cast<size_t>(nbod));
+    std::vector<int> roots;
+    for (int b = 0; b < nbod; b++) {
+        if (!below[b]) continue;
+        const int par = parent_of(b);
+        if (par < 0) roots.push_back(b);
+        else if (L.bodies[b].lam == par && cluster_of[b] == cluster_of[par]) {
+            if (!kids[par].empty() && L.bodies[kids[par][0]].lam == par && cluster_of[kids[par][0]] == cluster_of[par]) ok = false;
+            kids[par].insert(kids[par].begin(), b);
+        } else kids[par].push_back(b);
+    }
+    std::vector<char> slot_used;
+    int in_use = 0;
+    struct Item {
+        int body, restore;
+        bool last;
+    };
+    std::vector<Item> stack;
+    for (auto it = roots.rbegin(); it != roots.rend(); ++it) stack.push_back({*it, -1, false});
+    while (!stack.empty()) {
+        const Item item = stack.back();
+        stack.pop_back();
+        const int b = item.body;
+        if (item.restore >= 0 && item.last) {  // (the step reads the slot before it writes one of its own)
+            slot_used[item.restore] = 0;
+            in_use--;
+        }
+        int save = -1;
+        if (kids[b].size() >= 2) {
+            size_t sl = 0;
+            while (sl < slot_used.size() && slot_used[sl]) sl++;
+            if (sl == slot_used.size()) slot_used.push_back(0);
+            slot_used[sl] = 1;
+            save = static_cast<int>(sl);
+            in_use++;
+            W.max_saved = std::max(W.max_saved, in_use);
+        }
+        const int s = W.walk_len++;
+        if (s < kMaxWalk && ok) {
+            const ClusterRec &c = L.clusters[cluster_of[b]];
+            const BodyRec &br = L.bodies[b];
+            JacWalkStep &st = W.step[s];
+            st.cofs = br.cofs;
+            st.free = c.kind == CK_FREE;
+            st.q_col = static_cast<int16_t>(c.q_index);
+            st.v_col = static_cast<int16_t>(c.v_index);
+            st.n = static_cast<uint8_t>(st.free ? 0 : c.n);
+            st.axis = static_cast<uint8_t>(br.axis);
+            st.root = parent_of(b) < 0;
+            st.save = static_cast<uint8_t>(save >= 0 && save < kJacMaxSlots ? save : kWalkNone);
+            st.restore = static_cast<uint8_t>(item.restore >= 0 && item.restore < kJacMaxSlots ? item.restore : kWalkNone);
+            const bool in_cluster = !st.root && br.lam == br.parent && cluster_of[b] == cluster_of[br.parent];
+            st.cont = in_cluster;
+            st.below = static_cast<uint16_t>(below[b]);
+            unsigned deeper = 0;  // frames that meet the cluster again further down
+            if (!kids[b].empty() && L.bodies[kids[b][0]].lam == b && cluster_of[kids[b][0]] == cluster_of[b]) deeper = below[kids[b][0]];
+            st.emit = static_cast<uint16_t>(below[b] & ~deeper);
+            for (int i = 0; i < n; i++)
+                if (bodies[i] == b) st.own |= static_cast<uint16_t>(1u << i);
+        }
+        for (size_t k = kids[b].size(); k-- > 0;) stack.push_back({kids[b][k], k == 0 ? -1 : save, k + 1 == kids[b].size()});
+    }
+    W.route = (!ok || W.walk_len > kMaxWalk || n + W.max_saved > kJacMaxSlots) ? 1 : 0;
+    return W;
+}
+template <class T>
+JacWalk<T> device_jac_walk(const grbda_plan *p, const DeviceTables &t, const JacWalkHost &H, const double *offsets, int frame)
+{
+    JacWalk<T> W{};
+    W.n_steps = H.walk_len;
+    W.n_list = H.n;
+    W.n_saved = H.max_saved;
+    W.nq = p->host.nq;
+    W.nv = p->host.nv;
+    W.ori_repr = p->host.ori_repr;
+    W.world = frame == GRBDA_WRENCH_WORLD;
+    W.consts = consts_of<T>(t);
+    for (int i = 0; i < H.n; i++)  // component k of a plan-frame vector is component (k + canon + 1) % 3 of the reference-frame one
+        for (int k = 0; k < 3; k++) W.off[i][k] = offsets ? static_cast<T>(offsets[3 * i + (k + H.canon[i] + 1) % 3]) : T(0);
+    std::memcpy(W.cols, H.cols, sizeof(W.cols));
+    std::memcpy(W.canon, H.canon, sizeof(W.canon));
+    std::memcpy(W.step, H.step, sizeof(W.step));
+    return W;
+}
+// Everything the entry points refuse, on the host and before any device call
+template <class T>
+int frame_jacobians_args(const grbda_plan *p, const T *q, const T *qd, int n, const int *bodies, int frame, const T *J, const T *drift, size_t B)
+{
+    if (!q) return set_err(GRBDA_EINVAL, "null argument");
+    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
+    if (n > 0 && !bodies) return set_err(GRBDA_EINVAL, "null argument");
+    for (int i = 0; i < n; i++)
+        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    if (frame != GRBDA_WRENCH_BODY && frame != GRBDA_WRENCH_WORLD) return set_err(GRBDA_EINVAL, "frame must be GRBDA_WRENCH_BODY or GRBDA_WRENCH_WORLD");
+    if (n > 0 && !J && !drift) return set_err(GRBDA_EINVAL, "no output asked for: J and drift are both null");
+    if (n > 0 && drift && !qd) return set_err(GRBDA_EINVAL, "the drift needs qd");
+    const size_t nv = p->host.nv;
+    const void *const in[2] = {q, drift ? qd : nullptr}, *const outs[2] = {n > 0 ? J : nullptr, n > 0 ? drift : nullptr};
+    const size_t in_bytes[2] = {B * static_cast<size_t>(p->host.nq) * sizeof(T), B * nv * sizeof(T)};
+    const size_t out_bytes[2] = {B * static_cast<size_t>(n) * 6 * nv * sizeof(T), B * static_cast<size_t>(n) * 6 * sizeof(T)};
+    return no_overlap(in, in_bytes, outs, out_bytes);
+}
+// Route 0: the walk kernel writes J.  Route 1: per chunk the expanded batch (nv rows per state: q, the unit velocities, zero accelerations)
+// through body_list_stage and the finishing kernel.  The drift, on both routes: the listed twists at (q, qd, 0) with a zero root
+// acceleration, and the finishing kernel.  World frames read the listed poses (body_list_stage) in both finishing kernels.
+template <class T>
+int frame_jacobians_run(const grbda_plan *p, const T *q, const T *qd, int n, const int *bodies, const double *offsets, int frame, T *J, T *drift,
+                        size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = frame_jacobians_args<T>(p, q, qd, n, bodies, frame, J, drift, B)) return rc;
+    if (n == 0 || B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const Layout &L = layout_of(p->host, sizeof(T) == 4 ? 0 : 1);
+    const JacWalkHost JH = build_jac_walk(p->host, L, n, bodies);
+    const BodyWalkHost H = build_body_walk(p->host, L, n, bodies);
+    FrameSet<T> F{};
+    F.n = n;
+    F.world = frame == GRBDA_WRENCH_WORLD;
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) F.off[i][k] = offsets ? static_cast<T>(offsets[3 * i + k]) : T(0);
+    std::memcpy(F.cols, JH.cols, sizeof(F.cols));
+    const bool walk = J && JH.route == 0, columns = J && JH.route == 1, poses = F.world && (columns || drift);
+    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n12 = static_cast<size_t>(n) * 12;
+    const size_t full = H.route == 1 ? nbod * 12 : 0, jn = static_cast<size_t>(n) * 6 * nv;
+    const auto launch_walk = [&](size_t b0, size_t nb) {
+        const JacWalk<T> W = device_jac_walk<T>(p, *t, JH, offsets, frame);
+        const size_t lds = static_cast<size_t>(JH.max_saved + n) * 12 * kWave * sizeof(T);
+        const int grid = static_cast<int>(tile_grid(t->n_cu, std::min<size_t>(8, lds_workgroups_per_cu(lds)), nb));
+        hipError_t e = launch_frame_jacobian_walk<T>(W, q + b0 * nq, J + b0 * jn, nb, grid, hs);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "frame Jacobian walk launch");
+    };
+    const size_t per_state = (poses ? n12 + full : 0) + (columns ? nv * (nq + 2 * nv + n12 + full + 2 * ns) : 0) + (drift ? nv + n12 + full + 2 * ns : 0);
+    if (per_state == 0) return launch_walk(0, B);
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        const T *qc = q + b0 * nq;
+        T *Xa = nullptr;
+        if (poses) {
+            Xa = w.take(nb * n12);
+            T *fl = full ? w.take(nb * full) : nullptr;
+            if (int rc = body_list_stage<T>(p, *t, H, false, qc, nullptr, nullptr, Xa, fl, nullptr, nullptr, nb, device, stream)) return rc;
+        }
+        if (walk)
+            if (int rc = launch_walk(b0, nb)) return rc;
+        if (columns) {
+            const size_t rows = nb * nv;
+            T *q_x = w.take(rows * nq), *qd_x = w.take(rows * nv), *z_x = w.take(rows * nv), *Vx = w.take(rows * n12);
+            T *fl = full ? w.take(rows * full) : nullptr, *vs = w.take(rows * ns), *as = w.take(rows * ns);
+            hipLaunchKernelGGL((unit_velocity_rows_kernel<T>), dim3(blocks_for(rows * (nq + nv))), dim3(256), 0, hs, qc, static_cast<int>(nq),
+                               static_cast<int>(nv), nb, q_x, qd_x);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_err(e, "unit velocity rows launch");
+            if (hipError_t e = hipMemsetAsync(z_x, 0, rows * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+            if (int rc = body_list_stage<T>(p, *t, H, true, q_x, qd_x, z_x, Vx, fl, vs, as, rows, device, stream)) return rc;
+            if (hipError_t e = launch_frame_jacobian_columns<T>(F, Vx, Xa, static_cast<int>(nv), nb, J + b0 * jn, hs); e != hipSuccess)
+                return hip_err(e, "frame Jacobian columns launch");
+        }
+        if (drift) {
+            T *z = w.take(nb * nv), *V = w.take(nb * n12), *fl = full ? w.take(nb * full) : nullptr, *vs = w.take(nb * ns), *as = w.take(nb * ns);
+            if (hipError_t e = hipMemsetAsync(z, 0, nb * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+            if (int rc = body_list_stage<T>(p, *t, H, true, qc, qd + b0 * nv, z, V, fl, vs, as, nb, device, stream, false)) return rc;
+            if (hipError_t e = launch_frame_drift<T>(F, V, Xa, nb, drift + b0 * static_cast<size_t>(n) * 6, hs); e != hipSuccess)
+                return hip_err(e, "frame drift launch");
+        }
+    }
+    return GRBDA_OK;
+}
+int frame_jacobians_host_f64(const grbda_plan *p, const double *q, const double *qd, int n, const int *bodies, const double *offsets, int frame,
+                             double *J, double *drift, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = frame_jacobians_args<double>(p, q, qd, n, bodies, frame, J, drift, B)) return rc;
+    if (n == 0 || B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = drift ? st.in(qd, B * nv) : nullptr;
+    double *dJ = J ? st.out(J, B * static_cast<size_t>(n) * 6 * nv) : nullptr, *dd = drift ? st.out(drift, B * static_cast<size_t>(n) * 6) : nullptr;
+    return st.run([&] { return frame_jacobians_run<double>(p, dq, dqd, n, bodies, offsets, frame, dJ, dd, B, device, nullptr); });
 }
 
 // ---- inverse operational-space inertia of a set of contact frames (include/grbda_hip.h) -----------------------
@@ -4249,6 +4484,35 @@ int grbda_body_list_walk(const grbda_plan *p, int n, const int *bodies, int *wal
     if (walk_len) *walk_len = H.walk_len;
     if (max_saved) *max_saved = H.max_saved;
     if (route) *route = H.route;
+    return GRBDA_OK;
+}
+int grbda_frame_jacobians_f64(const grbda_plan *p, const double *q, const double *qd, int n, const int *bodies, const double *offsets, int frame,
+                              double *J, double *drift, size_t B, int device, void *stream)
+{
+    return frame_jacobians_run<double>(p, q, qd, n, bodies, offsets, frame, J, drift, B, device, stream);
+}
+int grbda_frame_jacobians_f32(const grbda_plan *p, const float *q, const float *qd, int n, const int *bodies, const double *offsets, int frame,
+                              float *J, float *drift, size_t B, int device, void *stream)
+{
+    return frame_jacobians_run<float>(p, q, qd, n, bodies, offsets, frame, J, drift, B, device, stream);
+}
+int grbda_frame_jacobians_host_f64(const grbda_plan *p, const double *q, const double *qd, int n, const int *bodies, const double *offsets,
+                                   int frame, double *J, double *drift, size_t B, int device)
+{
+    return frame_jacobians_host_f64(p, q, qd, n, bodies, offsets, frame, J, drift, B, device);
+}
+int grbda_frame_jacobians_route(const grbda_plan *p, int n, const int *bodies, int *route, int *walk_len, int *max_saved)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
+    if (n > 0 && !bodies) return set_err(GRBDA_EINVAL, "null argument");
+    for (int i = 0; i < n; i++)
+        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    const JacWalkHost H = build_jac_walk(p->host, p->host.lay64, n, bodies);
+    if (route) *route = H.route;
+    if (walk_len) *walk_len = H.walk_len;
+    if (max_saved) *max_saved = H.max_saved;
     return GRBDA_OK;
 }
 int grbda_body_poses_f64(const grbda_plan *p, const double *q, double *Xa, size_t B, int device, void *stream)

@@ -239,6 +239,51 @@ struct BodyList {
 template <class T>
 hipError_t launch_body_gather(const BodyList &L, const T *full, int n_bodies, size_t nb, T *out, hipStream_t stream);
 
+// Frame Jacobians and their drift at a listed few body frames (include/grbda_hip_jacobians.h; frame_jacobian_kernels.hip).  A frame is the
+// body-fixed point off[i] of body bodies[i]; FrameSet travels by value like ContactSet: the offsets in the REFERENCE's body axes, and per
+// frame the bit mask of the velocity columns on its root path (every other column of J is a structural zero; all ones when nv > 128).
+constexpr int kJacMaskWords = 2;
+template <class T>
+struct FrameSet {
+    int n, world;  // world: 0 the body's axes, 1 world axes (origin at the point either way)
+    T off[kMaxBodyList][3];
+    uint64_t cols[kMaxBodyList][kJacMaskWords];
+};
+// The walk of route 0: the steps of a BodyWalk with, per step, the frames at or below the body (`below`), the frames that ARE the body
+// (`own`: the first pass leaves their [E | point] in LDS slot n_saved + i) and the frames whose columns of the body's cluster are complete
+// at this step (`emit`: the body is the deepest one of its cluster on their root paths).  cont: the step before is the body's in-cluster
+// parent and the cluster's world-frame axes A[n][6] go on accumulating; otherwise they start from zero.  Only the floating base and
+// explicit clusters of 1..kJacMaxDof coordinates walk; G rows at kBodyConstFixed.  off: the offsets in the PLAN's (canonical) body axes.
+constexpr int kJacMaxDof = 4;
+constexpr int kJacMaxSlots = 10;  // saved values + frames: 10 x 12 x 64 lanes x 8 bytes = 60 KiB of LDS in fp64, what a launch gets unasked
+struct JacWalkStep {
+    int32_t cofs;
+    int16_t q_col, v_col;
+    uint16_t below, own, emit;
+    uint8_t free, n, axis, root, save, restore, cont, pad[3];
+};
+template <class T>
+struct JacWalk {
+    int n_steps, n_list, n_saved;
+    int nq, nv, ori_repr, world;
+    const T *consts;
+    T off[kMaxBodyList][3];
+    uint64_t cols[kMaxBodyList][kJacMaskWords];
+    uint8_t canon[kMaxBodyList];
+    JacWalkStep step[kMaxWalk];
+};
+static_assert(sizeof(JacWalk<double>) <= 2048, "the walk travels in the kernel arguments");
+// J[nb][n][6][nv], every entry written once (route 0)
+template <class T>
+hipError_t launch_frame_jacobian_walk(const JacWalk<T> &W, const T *q, T *J, size_t nb, int grid, hipStream_t stream);
+// route 1: Vx[nb * nv][n][12], the listed twists of the expanded batch (row (b, k): state b at the unit velocity e_k); Xa[nb][n][12] the
+// listed poses (read for world frames only, may be null otherwise) -> J[nb][n][6][nv]
+template <class T>
+hipError_t launch_frame_jacobian_columns(const FrameSet<T> &F, const T *Vx, const T *Xa, int nv, size_t nb, T *J, hipStream_t stream);
+// V[nb][n][12], the listed twists at (q, qd, 0) without gravity; Xa as above -> drift[nb][n][6]
+template <class T>
+hipError_t launch_frame_drift(const FrameSet<T> &F, const T *V, const T *Xa, size_t nb, T *drift, hipStream_t stream);
+
 // single-cluster programs (RneaChainProgram::single_gen; chain_kernels.hip, rnea_gen1_kernel): P.lds_bytes = the work area, lds_bytes =
 // work area + nq + 2 nv rows of staged inputs
 template <class T>

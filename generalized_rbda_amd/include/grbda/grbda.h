@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../../include/grbda_hip.h"
+#include "../../../include/grbda_hip_jacobians.h"
 #include "ModelDescription.h"
 
 namespace grbda {
@@ -1328,6 +1329,15 @@ public:
                          int device = 0)
     {
         check(grbda_centroidal_host_f64(plan(), q, qd, ydd, com, com_vel, h, hdot, B, device));
+    }
+    // Frame Jacobians and their drift at n body-fixed points of B states on host arrays (include/grbda_hip_jacobians.h; the batched form of
+    // contactJacobianBodyFrame / contactJacobianWorldFrame, Pinocchio: computeFrameJacobian, getFrameClassicalAcceleration).  Point c is
+    // offsets[3 c ..] of body bodies[c] (offsets null: the body origins); world_frame: world axes instead of the body's.  J[B][n][6][nv],
+    // drift[B][n][6] = Jdot qd; either may be null, not both; qd is read for the drift only.
+    void frameJacobiansBatch(const double *q, const double *qd, int n, const int *bodies, const double *offsets, bool world_frame, double *J,
+                             double *drift, size_t B, int device = 0)
+    {
+        check(grbda_frame_jacobians_host_f64(plan(), q, qd, n, bodies, offsets, world_frame ? 1 : 0, J, drift, B, device));
     }
     // The instant contacts close, for B states on host arrays (include/grbda_hip.h "contact impulses"; Pinocchio: impulseDynamics):
     // (J_w H^-1 J_w^T + damping I) Lambda = v_des - (1 + restitution) J_w qd, qd_next = qd + H^-1 J_w^T Lambda.  Point c is offsets[3 c ..]
