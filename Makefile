@@ -44,11 +44,11 @@ $(OBJ)/wrench_kernels.o: $(CSRC)/wrench_kernels.hip $(CSRC)/plan.h $(CSRC)/devpl
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
 # poses and twists of a listed few bodies (include/grbda_hip_bodies.h)
-$(OBJ)/body_list_kernels.o: $(CSRC)/body_list_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h
+$(OBJ)/body_list_kernels.o: $(CSRC)/body_list_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h $(CSRC)/walk.h $(CSRC)/walk_dev.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
 # frame Jacobians and their drift at a listed few body frames (include/grbda_hip_jacobians.h)
-$(OBJ)/frame_jacobian_kernels.o: $(CSRC)/frame_jacobian_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h
+$(OBJ)/frame_jacobian_kernels.o: $(CSRC)/frame_jacobian_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h $(CSRC)/walk.h $(CSRC)/walk_dev.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
 $(OBJ)/crba_kernels.o: $(CSRC)/crba_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h
@@ -78,17 +78,21 @@ $(OBJ)/jvp_kernels.o: $(CSRC)/jvp_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h
 $(OBJ)/step_vjp_kernels.o: $(CSRC)/step_vjp_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
-$(OBJ)/capi.o: $(CSRC)/capi.cpp $(CSRC)/plan.h $(CSRC)/devplan.h include/grbda_hip.h include/grbda_hip_vjp.h include/grbda_hip_step_vjp.h include/grbda_hip_jvp.h include/grbda_hip_wrench.h include/grbda_hip_bodies.h include/grbda_hip_jacobians.h include/grbda_model_desc.h
+$(OBJ)/capi.o: $(CSRC)/capi.cpp $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/walk.h include/grbda_hip.h include/grbda_hip_vjp.h include/grbda_hip_step_vjp.h include/grbda_hip_jvp.h include/grbda_hip_wrench.h include/grbda_hip_bodies.h include/grbda_hip_jacobians.h include/grbda_model_desc.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(OBJ)/plan.o: $(CSRC)/plan.cpp $(CSRC)/plan.h include/grbda_hip.h include/grbda_model_desc.h
+	@mkdir -p $(OBJ)
+	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
+# the ancestor walks of the listed-body and frame-Jacobian paths: plain C++ like the plan compiler (make asan drives it too)
+$(OBJ)/walk.o: $(CSRC)/walk.cpp $(CSRC)/walk.h $(CSRC)/plan.h
 	@mkdir -p $(OBJ)
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 $(OBJ)/urdf.o: $(CSRC)/urdf.cpp include/grbda_hip.h include/grbda_model_desc.h generalized_rbda_amd/include/grbda/ModelDescription.h
 	@mkdir -p $(OBJ)
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 
-$(LIB): $(OBJ)/kernels.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/chain_kernels_u4.o $(OBJ)/wrench_kernels.o $(OBJ)/body_list_kernels.o $(OBJ)/frame_jacobian_kernels.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/contact_kernels.o $(OBJ)/centroidal_kernels.o $(OBJ)/vjp_kernels.o $(OBJ)/jvp_kernels.o $(OBJ)/step_vjp_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/urdf.o
+$(LIB): $(OBJ)/kernels.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/chain_kernels_u4.o $(OBJ)/wrench_kernels.o $(OBJ)/body_list_kernels.o $(OBJ)/frame_jacobian_kernels.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/contact_kernels.o $(OBJ)/centroidal_kernels.o $(OBJ)/vjp_kernels.o $(OBJ)/jvp_kernels.o $(OBJ)/step_vjp_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/walk.o $(OBJ)/urdf.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle:
@@ -103,12 +107,12 @@ clean:
 .PHONY: all oracle ref clean
 
 # AddressSanitizer + UBSan build of the HOST-side code (CPU only: GPU sanitizers are not available on this pool): the plan
-# compiler, the URDF+ reader and the oracle, driven by tools/asan_driver.cpp over every robot URDF and a serialised model.
+# compiler, the walk builders, the URDF+ reader and the oracle, driven by tools/asan_driver.cpp over every robot URDF and a serialised model.
 #   make asan && build/asan/asan_driver tests/golden/robot-models/*.urdf
 asan:
 	@mkdir -p build/asan
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Wall \
-	    -DGRBDA_ASAN_DRIVER -I include -I generalized_rbda_amd/include tools/asan_driver.cpp $(CSRC)/plan.cpp $(CSRC)/urdf.cpp \
+	    -DGRBDA_ASAN_DRIVER -I include -I generalized_rbda_amd/include tools/asan_driver.cpp $(CSRC)/plan.cpp $(CSRC)/walk.cpp $(CSRC)/urdf.cpp \
 	    -x c oracle/grbda_oracle.c -x none -lm -lpthread -o build/asan/asan_driver
 .PHONY: asan
 

@@ -1,11 +1,12 @@
 // body_list_kernels.hip -- poses and twists of a listed few bodies (include/grbda_hip_bodies.h; capi.cpp, body_list_run).
 //
 // poses_kernel / twists_kernel (kernels.hip) write every body of every state and read each parent back from that global output row.  The
-// kernels here follow a WALK (devplan.h, BodyWalk) over the listed bodies' ancestors only: one state per lane, a grid-stride loop over tiles
-// of 64 states, the running [E | r] (poses) or [v | a] (twists) of the current root path in registers, the values of branch points in LDS
-// ([slot][value][lane]: a lane reads what it wrote, lane == bank, no barrier), and nothing read back from global memory.  The walk is
-// wave-uniform -- it sits in the kernel arguments and is read through the scalar unit -- so every branch on it is a scalar branch and no
-// per-lane array is indexed at run time.  The per-body formulas are those of poses_kernel / twists_kernel, term by term, on the same device
+// kernels here follow a WALK (walk.h, BodyWalkStep; devplan.h, BodyWalk) over the listed bodies' ancestors only: one state per lane, a
+// grid-stride loop over tiles of 64 states, the running [E | r] (poses) or [v | a] (twists) of the current root path in registers, the
+// values of branch points in LDS ([slot][value][lane]: a lane reads what it wrote, lane == bank, no barrier), and nothing read back from
+// global memory.  The walk is wave-uniform -- it sits in the kernel arguments and is read through the scalar unit -- so every branch on it is
+// a scalar branch and no per-lane array is indexed at run time.  The LDS slots, the joint angle and the pose step are walk_dev.h's, which
+// frame_jacobian_kernels.hip uses too.  The per-body formulas are those of poses_kernel / twists_kernel, term by term, on the same device
 // functions; as there, values are composed in the plan's canonical body frames and permuted to the reference's axes as they are stored.
 #include <hip/hip_runtime.h>
 
@@ -16,31 +17,10 @@
 namespace grbda_hip {
 
 #include "devmath.h"
+#include "walk_dev.h"
 
 namespace {
 
-template <class T>
-__device__ __forceinline__ T joint_angle(const BodyWalkStep &st, cptr<T> C, const T *qr)
-{
-    if (st.n == 0) return qr[st.q_col];
-    T qi = 0;
-    for (int a = 0; a < st.n; a++) qi += C[kBodyConstFixed + a] * qr[st.q_col + a];
-    return qi;
-}
-template <class T>
-__device__ __forceinline__ void saved_put(int slot, int lane, const T (&x)[12])
-{
-    T *p = reinterpret_cast<T *>(grbda_smem) + slot * 12 * kWave + lane;
-#pragma unroll
-    for (int k = 0; k < 12; k++) p[k * kWave] = x[k];
-}
-template <class T>
-__device__ __forceinline__ void saved_get(int slot, int lane, T (&x)[12])
-{
-    const T *p = reinterpret_cast<const T *>(grbda_smem) + slot * 12 * kWave + lane;
-#pragma unroll
-    for (int k = 0; k < 12; k++) x[k] = p[k * kWave];
-}
 // one row of the output in the reference's body axes.  ROWS 3: a pose, the rows of E move (E_ref = Rc^T E) and r stays; ROWS 4: a twist, the
 // components of each of the four 3-vectors move (poses_kernel / twists_kernel, tail loops)
 template <class T, int ROWS>
@@ -72,7 +52,7 @@ __device__ __forceinline__ void store_row(T *o, const T (&x)[12], int canon)
 
 }  // namespace
 
-// X = [E 9 | r 3] of the step's body from Xp, its parent's (TreeNode::Xa_; poses_kernel)
+// X = [E 9 | r 3] of the step's body from its parent's (walk_dev.h, walk_pose_step)
 template <class T>
 __global__ __launch_bounds__(kWave, 1) void body_poses_list_kernel(BodyWalk<T> W, const T *__restrict__ q, T *__restrict__ out, size_t B)
 {
@@ -90,39 +70,7 @@ __global__ __launch_bounds__(kWave, 1) void body_poses_list_kernel(BodyWalk<T> W
         int oi = 0;
         for (int s = 0; s < W.n_steps; s++) {
             const BodyWalkStep st = W.step[s];
-            if (st.restore != kWalkNone) saved_get(st.restore, lane, X);
-            T E[9], rr[3];
-            if (st.free) {
-                T o[4];
-                const int nori = W.ori_repr == 0 ? 4 : 3;
-                for (int j = 0; j < 4; j++) o[j] = j < nori ? qr[st.q_col + 3 + j] : T(0);
-                free_rotation(W.ori_repr, o, E);
-                for (int j = 0; j < 3; j++) rr[j] = qr[st.q_col + j];
-            } else {
-                cptr<T> C = consts + st.cofs;
-                const T qi = joint_angle(st, C, qr);
-                T sn, cs, El[9];
-                sincos_t(qi, &sn, &cs);
-                build_E((int)st.axis, sn, cs, C, El);
-                if (!st.root) {  // Xa = X * Xa_parent: E = E_l E_p, r = r_p + E_p^T r_l
-#pragma unroll
-                    for (int u = 0; u < 3; u++)
-#pragma unroll
-                        for (int w = 0; w < 3; w++) E[3 * u + w] = El[3 * u] * X[w] + El[3 * u + 1] * X[3 + w] + El[3 * u + 2] * X[6 + w];
-#pragma unroll
-                    for (int u = 0; u < 3; u++) rr[u] = X[9 + u] + X[u] * C[9] + X[3 + u] * C[10] + X[6 + u] * C[11];
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 9; u++) E[u] = El[u];
-#pragma unroll
-                    for (int u = 0; u < 3; u++) rr[u] = C[9 + u];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 9; u++) X[u] = E[u];
-#pragma unroll
-            for (int u = 0; u < 3; u++) X[9 + u] = rr[u];
-            if (st.save != kWalkNone) saved_put(st.save, lane, X);
+            walk_pose_step(st, consts, W.ori_repr, qr, lane, X);
             for (int k = 0; k < st.n_out; k++) store_row<T, 3>(orow + (size_t)W.slot[oi++] * 12, X, st.canon);
         }
     }
@@ -148,7 +96,7 @@ __global__ __launch_bounds__(kWave, 1) void body_twists_list_kernel(BodyWalk<T> 
         int oi = 0;
         for (int s = 0; s < W.n_steps; s++) {
             const BodyWalkStep st = W.step[s];
-            if (st.restore != kWalkNone) saved_get(st.restore, lane, X);
+            if (st.restore != kWalkNone) slot_get(st.restore, lane, X);
             T v[6], a[6];
             if (st.free) {  // S = 1, the rates are the base twist; a = X (-gravity) + ydd
                 T o[4], E[9];
@@ -217,7 +165,7 @@ __global__ __launch_bounds__(kWave, 1) void body_twists_list_kernel(BodyWalk<T> 
                 X[j] = v[j];
                 X[6 + j] = a[j];
             }
-            if (st.save != kWalkNone) saved_put(st.save, lane, X);
+            if (st.save != kWalkNone) slot_put(st.save, lane, X);
             for (int k = 0; k < st.n_out; k++) store_row<T, 4>(orow + (size_t)W.slot[oi++] * 12, X, st.canon);
         }
     }

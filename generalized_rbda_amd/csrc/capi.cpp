@@ -1311,105 +1311,7 @@ int twists(const grbda_plan *p, const T *q, const T *qd, const T *ydd, T *V, siz
 }
 
 // ---- poses and twists of a listed few bodies (include/grbda_hip_bodies.h; body_list_kernels.hip) ----------------------------------------
-// The walk of a body list (devplan.h, BodyWalkStep): the precision-independent part, built on the host per call.  walk_len and max_saved are
-// counted in full even when they pass kMaxWalk / kMaxSaved (or an index does not fit a step's fields): `route` is then 1, the full kernel
-// and a gather, and the steps are not used.
-struct BodyWalkHost {
-    int walk_len = 0, max_saved = 0, route = 0, n = 0;
-    uint8_t slot[kMaxBodyList] = {};
-    BodyWalkStep step[kMaxWalk] = {};
-    BodyList list{};
-};
-// (n and every index checked by the caller)
-BodyWalkHost build_body_walk(const HostPlan &h, const Layout &L, int n, const int *bodies)
-{
-    BodyWalkHost W;
-    W.n = W.list.n = n;
-    for (int i = 0; i < kMaxBodyList; i++) W.list.body[i] = i < n ? bodies[i] : -1;
-    const int nbod = h.n_bodies;
-    std::vector<char> in_walk(static_cast<size_t>(nbod), 0);
-    for (int i = 0; i < n; i++)
-        for (int b = bodies[i]; b >= 0 && !in_walk[b]; b = L.bodies[b].parent) in_walk[b] = 1;
-    // per body: its cluster and its place in it; the cluster's first spanning rate
-    std::vector<int> cluster_of(static_cast<size_t>(nbod), -1), span_at(L.clusters.size(), 0);
-    int at = 0;
-    for (size_t ci = 0; ci < L.clusters.size(); ci++) {
-        const ClusterRec &c = L.clusters[ci];
-        span_at[ci] = at;
-        for (int i = 0; i < c.k; i++) cluster_of[c.first_body + i] = static_cast<int>(ci);
-        at += c.kind == CK_FREE ? 6 : c.k;
-    }
-    // children in the walk, in index order (a parent precedes its children in the plan's body order); a floating base hangs off nothing
-    std::vector<std::vector<int>> kids(static_cast<size_t>(nbod));
-    std::vector<int> roots;
-    const auto parent_of = [&](int b) { return L.clusters[cluster_of[b]].kind == CK_FREE ? -1 : L.bodies[b].parent; };
-    for (int b = 0; b < nbod; b++) {
-        if (!in_walk[b]) continue;
-        const int par = parent_of(b);
-        (par < 0 ? roots : kids[par]).push_back(b);
-    }
-    bool fits = nbod <= 32767 && h.nq <= 32767 && at <= 32767;
-    std::vector<char> slot_used;
-    std::vector<int> slot_of(static_cast<size_t>(nbod), -1);
-    int in_use = 0, n_slots_out = 0;
-    // depth first, iteratively: (body, restore slot or -1, whether this is the last child to read that slot)
-    struct Item {
-        int body, restore;
-        bool last;
-    };
-    std::vector<Item> stack;
-    for (auto it = roots.rbegin(); it != roots.rend(); ++it) stack.push_back({*it, -1, false});
-    while (!stack.empty()) {
-        const Item item = stack.back();
-        stack.pop_back();
-        const int b = item.body;
-        if (item.restore >= 0 && item.last) {  // (the step reads the slot before it writes one of its own)
-            slot_used[item.restore] = 0;
-            in_use--;
-        }
-        int save = -1;
-        if (kids[b].size() >= 2) {
-            size_t sl = 0;
-            while (sl < slot_used.size() && slot_used[sl]) sl++;
-            if (sl == slot_used.size()) slot_used.push_back(0);
-            slot_used[sl] = 1;
-            save = static_cast<int>(sl);
-            in_use++;
-            W.max_saved = std::max(W.max_saved, in_use);
-        }
-        const int s = W.walk_len++;
-        int n_out = 0;
-        for (int i = 0; i < n; i++)
-            if (bodies[i] == b) {
-                W.slot[n_slots_out++] = static_cast<uint8_t>(i);
-                n_out++;
-            }
-        if (s < kMaxWalk && fits) {
-            const int ci = cluster_of[b];
-            const ClusterRec &c = L.clusters[ci];
-            const BodyRec &br = L.bodies[b];
-            const int i = b - c.first_body;
-            BodyWalkStep &st = W.step[s];
-            st.cofs = br.cofs;
-            st.body = static_cast<int16_t>(b);
-            st.free = c.kind == CK_FREE;
-            st.q_col = static_cast<int16_t>(c.kind == CK_LOOP ? c.q_index + i : c.q_index);
-            st.span_col = static_cast<int16_t>(span_at[ci] + (c.kind == CK_FREE ? 0 : i));
-            st.n = static_cast<uint8_t>(c.kind == CK_LOOP || c.kind == CK_FREE ? 0 : c.n);
-            fits = fits && (c.kind == CK_LOOP || c.kind == CK_FREE || (c.n >= 1 && c.n <= 255));
-            st.axis = static_cast<uint8_t>(br.axis);
-            st.canon = static_cast<uint8_t>(br.canon_axis);
-            st.root = parent_of(b) < 0;
-            st.save = static_cast<uint8_t>(save >= 0 && save < kMaxSaved ? save : kWalkNone);
-            st.restore = static_cast<uint8_t>(item.restore >= 0 && item.restore < kMaxSaved ? item.restore : kWalkNone);
-            st.n_out = static_cast<uint8_t>(n_out);
-        }
-        // the first child continues from the running value; the others start from the saved one, the last of them frees it
-        for (size_t k = kids[b].size(); k-- > 0;) stack.push_back({kids[b][k], k == 0 ? -1 : save, k + 1 == kids[b].size()});
-    }
-    W.route = (W.walk_len > kMaxWalk || W.max_saved > kMaxSaved || !fits) ? 1 : 0;
-    return W;
-}
+// (the walk of a body list, BodyWalkHost and build_body_walk: walk.h)
 template <class T>
 BodyWalk<T> device_body_walk(const grbda_plan *p, const DeviceTables &t, const BodyWalkHost &H)
 {
@@ -1426,15 +1328,22 @@ BodyWalk<T> device_body_walk(const grbda_plan *p, const DeviceTables &t, const B
     std::memcpy(W.step, H.step, sizeof(W.step));
     return W;
 }
+// What every entry point that takes a body list refuses of the list (wrench_args and contact_set: their own caps and messages).
+// with_list: the one other array that a list of n > 0 needs (the listed output), or `bodies` again
+int body_list_check(const grbda_plan *p, int n, const int *bodies, const void *with_list)
+{
+    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
+    if (n > 0 && (!bodies || !with_list)) return set_err(GRBDA_EINVAL, "null argument");
+    for (int i = 0; i < n; i++)
+        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    return GRBDA_OK;
+}
 // Everything the list entry points refuse, on the host and before any device call.  qd == nullptr && ydd == nullptr: the poses.
 template <class T>
 int body_list_args(const grbda_plan *p, bool twists, const T *q, const T *qd, const T *ydd, int n, const int *bodies, const T *out, size_t B)
 {
     if (!q || (twists && (!qd || !ydd))) return set_err(GRBDA_EINVAL, "null argument");
-    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
-    if (n > 0 && (!bodies || !out)) return set_err(GRBDA_EINVAL, "null argument");
-    for (int i = 0; i < n; i++)
-        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    if (int rc = body_list_check(p, n, bodies, out)) return rc;
     const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
     const void *const in[3] = {q, twists ? qd : nullptr, twists ? ydd : nullptr}, *const outs[1] = {n > 0 ? out : nullptr};
     const size_t in_bytes[3] = {bq, bv, bv}, out_bytes[1] = {B * static_cast<size_t>(n) * 12 * sizeof(T)};
@@ -1468,10 +1377,31 @@ int body_list_stage(const grbda_plan *p, const DeviceTables &t, const BodyWalkHo
     }
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "body list launch");
 }
-// elements of work memory per state of a pass: the full rows of route 1, the spanning rates of the twists
-size_t body_list_per_state(const grbda_plan *p, const BodyWalkHost &H, bool twists)
+// The work memory of one body_list_stage call, in elements per state: the listed output (n x 12; n = 0: the stage writes the caller's
+// array), the full rows of route 1, each of the two spanning rates of the twists.  ONE definition of what a call site counts into its
+// chunk and of what it takes from the slab, in that order.
+struct ListWork {
+    size_t out = 0, full = 0, span = 0;
+    size_t per_state() const { return out + full + 2 * span; }
+    template <class T>
+    struct Arrays {
+        T *out, *full, *vs, *as;
+    };
+    template <class T>
+    Arrays<T> take(Carver<T> &w, size_t nb) const
+    {
+        Arrays<T> a{};
+        a.out = out ? w.take(nb * out) : nullptr;
+        a.full = full ? w.take(nb * full) : nullptr;
+        a.vs = span ? w.take(nb * span) : nullptr;
+        a.as = span ? w.take(nb * span) : nullptr;
+        return a;
+    }
+};
+ListWork list_work(const grbda_plan *p, const BodyWalkHost &H, bool twists, int n)
 {
-    return (H.route == 1 ? static_cast<size_t>(p->host.n_bodies) * 12 : 0) + (twists ? 2 * static_cast<size_t>(span_count(p)) : 0);
+    return {static_cast<size_t>(n) * 12, H.route == 1 ? static_cast<size_t>(p->host.n_bodies) * 12 : 0,
+            twists ? static_cast<size_t>(span_count(p)) : 0};
 }
 template <class T>
 int body_list_run(const grbda_plan *p, bool twists, const T *q, const T *qd, const T *ydd, int n, const int *bodies, T *out, size_t B, int device,
@@ -1484,18 +1414,18 @@ int body_list_run(const grbda_plan *p, bool twists, const T *q, const T *qd, con
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     const BodyWalkHost H = build_body_walk(p->host, layout_of(p->host, sizeof(T) == 4 ? 0 : 1), n, bodies);
-    const size_t per_state = body_list_per_state(p, H, twists);
+    const ListWork lw = list_work(p, H, twists, 0);  // (the output is the caller's)
+    const size_t per_state = lw.per_state();
     if (per_state == 0) return body_list_stage<T>(p, *t, H, false, q, nullptr, nullptr, out, nullptr, nullptr, nullptr, B, device, stream);
-    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n12 = static_cast<size_t>(n) * 12;
+    const size_t nq = p->host.nq, nv = p->host.nv, n12 = static_cast<size_t>(n) * 12;
     const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         Carver<T> w(wptr, c.chunk * per_state);
-        T *full = H.route == 1 ? w.take(nb * nbod * 12) : nullptr;
-        T *vs = twists ? w.take(nb * ns) : nullptr, *as = twists ? w.take(nb * ns) : nullptr;
+        const auto m = lw.take(w, nb);
         if (int rc = body_list_stage<T>(p, *t, H, twists, q + b0 * nq, twists ? qd + b0 * nv : nullptr, twists ? ydd + b0 * nv : nullptr, out + b0 * n12,
-                                        full, vs, as, nb, device, stream))
+                                        m.full, m.vs, m.as, nb, device, stream))
             return rc;
     }
     return GRBDA_OK;
@@ -1652,110 +1582,7 @@ int centroidal_matrix(const grbda_plan *p, const T *q, T *A, size_t B, int devic
 }
 
 // ---- frame Jacobians and their drift at a listed few body frames (include/grbda_hip_jacobians.h; frame_jacobian_kernels.hip) ------------
-// The walk of route 0 (devplan.h, JacWalkStep), built on the host per call like build_body_walk: the same depth-first order, except that a
-// body's in-cluster child comes first among its children, so that the cluster's axes go on accumulating in registers from the one step
-// to the next.  walk_len and max_saved are counted in full; `route` is 1 -- the expanded batch through the listed twists -- when a root
-// path holds anything but the floating base and explicit clusters of 1..kJacMaxDof coordinates, on the spanning-tree route, when a body of
-// the walk has two in-cluster children, and past the caps: kMaxWalk steps, kJacMaxSlots frames and saved values together, 128 velocities.
-// cols: per frame, the velocity columns on its root path (on either route).
-struct JacWalkHost {
-    int walk_len = 0, max_saved = 0, route = 0, n = 0;
-    JacWalkStep step[kMaxWalk] = {};
-    uint64_t cols[kMaxBodyList][kJacMaskWords] = {};
-    uint8_t canon[kMaxBodyList] = {};
-};
-// (n and every index checked by the caller)
-JacWalkHost build_jac_walk(const HostPlan &h, const Layout &L, int n, const int *bodies)
-{
-    JacWalkHost W;
-    W.n = n;
-    const int nbod = h.n_bodies;
-    std::vector<int> cluster_of(static_cast<size_t>(nbod), -1);
-    for (size_t ci = 0; ci < L.clusters.size(); ci++)
-        for (int i = 0; i < L.clusters[ci].k; i++) cluster_of[L.clusters[ci].first_body + i] = static_cast<int>(ci);
-    const auto parent_of = [&](int b) { return L.clusters[cluster_of[b]].kind == CK_FREE ? -1 : L.bodies[b].parent; };
-    bool ok = !h.big_clusters && h.nv <= 64 * kJacMaskWords && nbod <= 32767 && h.nq <= 32767;
-    const bool masks = h.nv <= 64 * kJacMaskWords;
-    std::vector<unsigned> below(static_cast<size_t>(nbod), 0);
-    for (int i = 0; i < n; i++) {
-        W.canon[i] = static_cast<uint8_t>(L.bodies[bodies[i]].canon_axis);
-        if (!masks) W.cols[i][0] = W.cols[i][1] = ~0ull;
-        for (int b = bodies[i]; b >= 0; b = parent_of(b)) {
-            below[b] |= 1u << i;
-            const ClusterRec &c = L.clusters[cluster_of[b]];
-            const int nc = c.kind == CK_FREE ? 6 : c.n;
-            if (masks)
-                for (int k = c.v_index; k < c.v_index + nc; k++) W.cols[i][k >> 6] |= 1ull << (k & 63);
-            if (c.kind == CK_FREE) ok = ok && L.bodies[b].canon_axis == 2;
-            else ok = ok && c.kind == CK_STATIC && c.n >= 1 && c.n <= kJacMaxDof && L.bodies[b].jtype == 0;
-        }
-    }
-    // children in the walk: the in-cluster child first, the others in index order
-    std::vector<std::vector<int>> kids(static_cast<size_t>(nbod));
-    std::vector<int> roots;
-    for (int b = 0; b < nbod; b++) {
-        if (!below[b]) continue;
-        const int par = parent_of(b);
-        if (par < 0) roots.push_back(b);
-        else if (L.bodies[b].lam == par && cluster_of[b] == cluster_of[par]) {
-            if (!kids[par].empty() && L.bodies[kids[par][0]].lam == par && cluster_of[kids[par][0]] == cluster_of[par]) ok = false;
-            kids[par].insert(kids[par].begin(), b);
-        } else kids[par].push_back(b);
-    }
-    std::vector<char> slot_used;
-    int in_use = 0;
-    struct Item {
-        int body, restore;
-        bool last;
-    };
-    std::vector<Item> stack;
-    for (auto it = roots.rbegin(); it != roots.rend(); ++it) stack.push_back({*it, -1, false});
-    while (!stack.empty()) {
-        const Item item = stack.back();
-        stack.pop_back();
-        const int b = item.body;
-        if (item.restore >= 0 && item.last) {  // (the step reads the slot before it writes one of its own)
-            slot_used[item.restore] = 0;
-            in_use--;
-        }
-        int save = -1;
-        if (kids[b].size() >= 2) {
-            size_t sl = 0;
-            while (sl < slot_used.size() && slot_used[sl]) sl++;
-            if (sl == slot_used.size()) slot_used.push_back(0);
-            slot_used[sl] = 1;
-            save = static_cast<int>(sl);
-            in_use++;
-            W.max_saved = std::max(W.max_saved, in_use);
-        }
-        const int s = W.walk_len++;
-        if (s < kMaxWalk && ok) {
-            const ClusterRec &c = L.clusters[cluster_of[b]];
-            const BodyRec &br = L.bodies[b];
-            JacWalkStep &st = W.step[s];
-            st.cofs = br.cofs;
-            st.free = c.kind == CK_FREE;
-            st.q_col = static_cast<int16_t>(c.q_index);
-            st.v_col = static_cast<int16_t>(c.v_index);
-            st.n = static_cast<uint8_t>(st.free ? 0 : c.n);
-            st.axis = static_cast<uint8_t>(br.axis);
-            st.root = parent_of(b) < 0;
-            st.save = static_cast<uint8_t>(save >= 0 && save < kJacMaxSlots ? save : kWalkNone);
-            st.restore = static_cast<uint8_t>(item.restore >= 0 && item.restore < kJacMaxSlots ? item.restore : kWalkNone);
-            const bool in_cluster = !st.root && br.lam == br.parent && cluster_of[b] == cluster_of[br.parent];
-            st.cont = in_cluster;
-            st.below = static_cast<uint16_t>(below[b]);
-            unsigned deeper = 0;  // frames that meet the cluster again further down
-            if (!kids[b].empty() && L.bodies[kids[b][0]].lam == b && cluster_of[kids[b][0]] == cluster_of[b]) deeper = below[kids[b][0]];
-            st.emit = static_cast<uint16_t>(below[b] & ~deeper);
-            for (int i = 0; i < n; i++)
-                if (bodies[i] == b) st.own |= static_cast<uint16_t>(1u << i);
-        }
-        for (size_t k = kids[b].size(); k-- > 0;) stack.push_back({kids[b][k], k == 0 ? -1 : save, k + 1 == kids[b].size()});
-    }
-    W.route = (!ok || W.walk_len > kMaxWalk || n + W.max_saved > kJacMaxSlots) ? 1 : 0;
-    return W;
-}
+// (the walk of route 0, JacWalkHost and build_jac_walk: walk.h)
 template <class T>
 JacWalk<T> device_jac_walk(const grbda_plan *p, const DeviceTables &t, const JacWalkHost &H, const double *offsets, int frame)
 {
@@ -1780,10 +1607,7 @@ template <class T>
 int frame_jacobians_args(const grbda_plan *p, const T *q, const T *qd, int n, const int *bodies, int frame, const T *J, const T *drift, size_t B)
 {
     if (!q) return set_err(GRBDA_EINVAL, "null argument");
-    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
-    if (n > 0 && !bodies) return set_err(GRBDA_EINVAL, "null argument");
-    for (int i = 0; i < n; i++)
-        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    if (int rc = body_list_check(p, n, bodies, bodies)) return rc;
     if (frame != GRBDA_WRENCH_BODY && frame != GRBDA_WRENCH_WORLD) return set_err(GRBDA_EINVAL, "frame must be GRBDA_WRENCH_BODY or GRBDA_WRENCH_WORLD");
     if (n > 0 && !J && !drift) return set_err(GRBDA_EINVAL, "no output asked for: J and drift are both null");
     if (n > 0 && drift && !qd) return set_err(GRBDA_EINVAL, "the drift needs qd");
@@ -1817,8 +1641,8 @@ int frame_jacobians_run(const grbda_plan *p, const T *q, const T *qd, int n, con
         for (int k = 0; k < 3; k++) F.off[i][k] = offsets ? static_cast<T>(offsets[3 * i + k]) : T(0);
     std::memcpy(F.cols, JH.cols, sizeof(F.cols));
     const bool walk = J && JH.route == 0, columns = J && JH.route == 1, poses = F.world && (columns || drift);
-    const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, ns = static_cast<size_t>(span_count(p)), n12 = static_cast<size_t>(n) * 12;
-    const size_t full = H.route == 1 ? nbod * 12 : 0, jn = static_cast<size_t>(n) * 6 * nv;
+    const size_t nq = p->host.nq, nv = p->host.nv, jn = static_cast<size_t>(n) * 6 * nv;
+    const ListWork lp = list_work(p, H, false, n), lt = list_work(p, H, true, n);  // the listed poses; the listed twists
     const auto launch_walk = [&](size_t b0, size_t nb) {
         const JacWalk<T> W = device_jac_walk<T>(p, *t, JH, offsets, frame);
         const size_t lds = static_cast<size_t>(JH.max_saved + n) * 12 * kWave * sizeof(T);
@@ -1826,7 +1650,7 @@ int frame_jacobians_run(const grbda_plan *p, const T *q, const T *qd, int n, con
         hipError_t e = launch_frame_jacobian_walk<T>(W, q + b0 * nq, J + b0 * jn, nb, grid, hs);
         return e == hipSuccess ? GRBDA_OK : hip_err(e, "frame Jacobian walk launch");
     };
-    const size_t per_state = (poses ? n12 + full : 0) + (columns ? nv * (nq + 2 * nv + n12 + full + 2 * ns) : 0) + (drift ? nv + n12 + full + 2 * ns : 0);
+    const size_t per_state = (poses ? lp.per_state() : 0) + (columns ? nv * (nq + 2 * nv + lt.per_state()) : 0) + (drift ? nv + lt.per_state() : 0);
     if (per_state == 0) return launch_walk(0, B);
     const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
@@ -1836,29 +1660,30 @@ int frame_jacobians_run(const grbda_plan *p, const T *q, const T *qd, int n, con
         const T *qc = q + b0 * nq;
         T *Xa = nullptr;
         if (poses) {
-            Xa = w.take(nb * n12);
-            T *fl = full ? w.take(nb * full) : nullptr;
-            if (int rc = body_list_stage<T>(p, *t, H, false, qc, nullptr, nullptr, Xa, fl, nullptr, nullptr, nb, device, stream)) return rc;
+            const auto m = lp.take(w, nb);
+            Xa = m.out;
+            if (int rc = body_list_stage<T>(p, *t, H, false, qc, nullptr, nullptr, Xa, m.full, m.vs, m.as, nb, device, stream)) return rc;
         }
         if (walk)
             if (int rc = launch_walk(b0, nb)) return rc;
         if (columns) {
             const size_t rows = nb * nv;
-            T *q_x = w.take(rows * nq), *qd_x = w.take(rows * nv), *z_x = w.take(rows * nv), *Vx = w.take(rows * n12);
-            T *fl = full ? w.take(rows * full) : nullptr, *vs = w.take(rows * ns), *as = w.take(rows * ns);
+            T *q_x = w.take(rows * nq), *qd_x = w.take(rows * nv), *z_x = w.take(rows * nv);
+            const auto m = lt.take(w, rows);
             hipLaunchKernelGGL((unit_velocity_rows_kernel<T>), dim3(blocks_for(rows * (nq + nv))), dim3(256), 0, hs, qc, static_cast<int>(nq),
                                static_cast<int>(nv), nb, q_x, qd_x);
             if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_err(e, "unit velocity rows launch");
             if (hipError_t e = hipMemsetAsync(z_x, 0, rows * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-            if (int rc = body_list_stage<T>(p, *t, H, true, q_x, qd_x, z_x, Vx, fl, vs, as, rows, device, stream)) return rc;
-            if (hipError_t e = launch_frame_jacobian_columns<T>(F, Vx, Xa, static_cast<int>(nv), nb, J + b0 * jn, hs); e != hipSuccess)
+            if (int rc = body_list_stage<T>(p, *t, H, true, q_x, qd_x, z_x, m.out, m.full, m.vs, m.as, rows, device, stream)) return rc;
+            if (hipError_t e = launch_frame_jacobian_columns<T>(F, m.out, Xa, static_cast<int>(nv), nb, J + b0 * jn, hs); e != hipSuccess)
                 return hip_err(e, "frame Jacobian columns launch");
         }
         if (drift) {
-            T *z = w.take(nb * nv), *V = w.take(nb * n12), *fl = full ? w.take(nb * full) : nullptr, *vs = w.take(nb * ns), *as = w.take(nb * ns);
+            T *z = w.take(nb * nv);
+            const auto m = lt.take(w, nb);
             if (hipError_t e = hipMemsetAsync(z, 0, nb * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-            if (int rc = body_list_stage<T>(p, *t, H, true, qc, qd + b0 * nv, z, V, fl, vs, as, nb, device, stream, false)) return rc;
-            if (hipError_t e = launch_frame_drift<T>(F, V, Xa, nb, drift + b0 * static_cast<size_t>(n) * 6, hs); e != hipSuccess)
+            if (int rc = body_list_stage<T>(p, *t, H, true, qc, qd + b0 * nv, z, m.out, m.full, m.vs, m.as, nb, device, stream, false)) return rc;
+            if (hipError_t e = launch_frame_drift<T>(F, m.out, Xa, nb, drift + b0 * static_cast<size_t>(n) * 6, hs); e != hipSuccess)
                 return hip_err(e, "frame drift launch");
         }
     }
@@ -2440,22 +2265,22 @@ int wrench_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T 
     if (chain && frame == GRBDA_WRENCH_BODY) return launch(W, 0, B);
     const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, n6 = static_cast<size_t>(n) * 6;
     const bool rotate = chain || frame == GRBDA_WRENCH_BODY;  // (the poses are computed only then)
-    const size_t n12 = static_cast<size_t>(n) * 12;
     // the poses of the listed bodies alone, in list order (body_list_stage); a list past the walk's caps takes the full rows as well
     const BodyWalkHost H = rotate ? build_body_walk(p->host, layout_of(p->host, sizeof(T) == 4 ? 0 : 1), n, bodies) : BodyWalkHost{};
-    const size_t per_state = (rotate ? n12 + body_list_per_state(p, H, false) : 0) + (chain ? n6 : nbod * 6);
+    const ListWork lw = rotate ? list_work(p, H, false, n) : ListWork{};
+    const size_t per_state = lw.per_state() + (chain ? n6 : nbod * 6);
     const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
     if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
         Carver<T> w(wptr, c.chunk * per_state);
-        T *Xa = rotate ? w.take(nb * n12) : nullptr;
-        T *full = rotate && H.route == 1 ? w.take(nb * nbod * 12) : nullptr;
+        const auto m = lw.take(w, nb);
+        T *Xa = m.out;
         WrenchList<T> Wc = W;
         Wc.w = wrench + b0 * n6;
         if (rotate)
-            if (int rc = body_list_stage<T>(p, *t, H, false, q + b0 * nq, nullptr, nullptr, Xa, full, nullptr, nullptr, nb, device, stream)) return rc;
+            if (int rc = body_list_stage<T>(p, *t, H, false, q + b0 * nq, nullptr, nullptr, Xa, m.full, m.vs, m.as, nb, device, stream)) return rc;
         if (chain) {
             T *wb = w.take(nb * n6);
             hipError_t e = launch_wrench_to_body<T>(Wc, Xa, nb, wb, hs);
@@ -4476,10 +4301,7 @@ int grbda_body_list_walk(const grbda_plan *p, int n, const int *bodies, int *wal
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
-    if (n > 0 && !bodies) return set_err(GRBDA_EINVAL, "null argument");
-    for (int i = 0; i < n; i++)
-        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    if (int rc = body_list_check(p, n, bodies, bodies)) return rc;
     const BodyWalkHost H = build_body_walk(p->host, p->host.lay64, n, bodies);
     if (walk_len) *walk_len = H.walk_len;
     if (max_saved) *max_saved = H.max_saved;
@@ -4505,10 +4327,7 @@ int grbda_frame_jacobians_route(const grbda_plan *p, int n, const int *bodies, i
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
-    if (n < 0 || n > kMaxBodyList) return set_err(GRBDA_EINVAL, "0..16 bodies per call");
-    if (n > 0 && !bodies) return set_err(GRBDA_EINVAL, "null argument");
-    for (int i = 0; i < n; i++)
-        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    if (int rc = body_list_check(p, n, bodies, bodies)) return rc;
     const JacWalkHost H = build_jac_walk(p->host, p->host.lay64, n, bodies);
     if (route) *route = H.route;
     if (walk_len) *walk_len = H.walk_len;

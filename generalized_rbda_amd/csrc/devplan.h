@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "plan.h"
+#include "walk.h"
 
 namespace grbda_hip {
 
@@ -188,34 +189,8 @@ hipError_t launch_wrench_to_body(const WrenchList<T> &W, const T *Xa, size_t nb,
 template <class T>
 hipError_t launch_wrench_scatter(const WrenchList<T> &W, const T *Xa, int from_body, int n_bodies, size_t nb, T *fext, hipStream_t stream);
 
-// Poses and twists of a listed few bodies (include/grbda_hip_bodies.h; body_list_kernels.hip).  capi.cpp builds the WALK per call from the
-// caller's host list and it travels by value in the kernel arguments, like WrenchList and ContactSet: the union of the listed bodies'
-// ancestors, each body once, depth first from the roots with the children in index order.  A step computes its body from the running value
-// of the root path, which the kernels hold in registers: the step before it is its tree parent, unless `restore` names the saved value of a
-// branch point to start from.  `save` names the slot that keeps the body's value for its later children (a body with two or more children
-// in the walk); a slot is free again once the last child has read it.  Saved values live in LDS, [slot][value 12][lane].  The n_out
-// output slots a step stores are the next n_out entries of BodyWalk::slot.
-constexpr int kMaxBodyList = 16;
-// steps of a walk: the MIT humanoid's two feet take 11, the sixteen last bodies of the humanoid, Tello and the Mini Cheetah 17 to 18.  The cap
-// is kept where a list can pass it on a model of the test set (all sixteen of the 20 bodies of parallel_chain_exp_d10_l16 walk 20), so that
-// the fallback is a route that runs; a step is 20 bytes of kernel arguments, and nothing but this constant stands against a longer walk
-constexpr int kMaxWalk = 19;
-constexpr int kMaxSaved = 4;   // values saved at once: 4 x 12 x 64 lanes x 8 bytes = 24 KiB of LDS in fp64
-constexpr int kWalkNone = 0xFF;
-struct BodyWalkStep {
-    int32_t cofs;      // BodyRec::cofs
-    int16_t body;      // plan body index
-    int16_t q_col;     // first position column the joint angle reads (an implicit cluster: the body's own spanning position)
-    int16_t span_col;  // the body's first spanning rate
-    uint8_t free;      // 1: the floating base (its own pose and twist, no parent)
-    uint8_t n;         // explicit clusters: the angle is the body's G row times the cluster's n positions; 0: q[q_col] itself
-    uint8_t axis;      // BodyRec::axis
-    uint8_t canon;     // BodyRec::canon_axis
-    uint8_t root;      // 1: no tree parent
-    uint8_t save;      // slot to keep the body's value in, or kWalkNone
-    uint8_t restore;   // slot to start from, or kWalkNone: the running value
-    uint8_t n_out;     // output slots stored after the step
-};
+// Poses and twists of a listed few bodies (include/grbda_hip_bodies.h; body_list_kernels.hip): the walk of walk.h (BodyWalkStep, the caps) with
+// what the kernels need beside the steps.
 template <class T>
 struct BodyWalk {
     int n_steps, n_list, n_saved;  // steps, outputs per state, peak number of saved values
@@ -231,37 +206,20 @@ template <class T>
 hipError_t launch_body_poses_list(const BodyWalk<T> &W, const T *q, T *out, size_t nb, int grid, hipStream_t stream);
 template <class T>
 hipError_t launch_body_twists_list(const BodyWalk<T> &W, const T *q, const T *qd_span, const T *qdd_span, T *out, size_t nb, int grid, hipStream_t stream);
-// the walk's fallback: out[nb][n][12] = full[nb][n_bodies][12] at the listed bodies
-struct BodyList {
-    int n;
-    int body[kMaxBodyList];
-};
+// the walk's fallback (walk.h, BodyList): out[nb][n][12] = full[nb][n_bodies][12] at the listed bodies
 template <class T>
 hipError_t launch_body_gather(const BodyList &L, const T *full, int n_bodies, size_t nb, T *out, hipStream_t stream);
 
 // Frame Jacobians and their drift at a listed few body frames (include/grbda_hip_jacobians.h; frame_jacobian_kernels.hip).  A frame is the
 // body-fixed point off[i] of body bodies[i]; FrameSet travels by value like ContactSet: the offsets in the REFERENCE's body axes, and per
 // frame the bit mask of the velocity columns on its root path (every other column of J is a structural zero; all ones when nv > 128).
-constexpr int kJacMaskWords = 2;
 template <class T>
 struct FrameSet {
     int n, world;  // world: 0 the body's axes, 1 world axes (origin at the point either way)
     T off[kMaxBodyList][3];
     uint64_t cols[kMaxBodyList][kJacMaskWords];
 };
-// The walk of route 0: the steps of a BodyWalk with, per step, the frames at or below the body (`below`), the frames that ARE the body
-// (`own`: the first pass leaves their [E | point] in LDS slot n_saved + i) and the frames whose columns of the body's cluster are complete
-// at this step (`emit`: the body is the deepest one of its cluster on their root paths).  cont: the step before is the body's in-cluster
-// parent and the cluster's world-frame axes A[n][6] go on accumulating; otherwise they start from zero.  Only the floating base and
-// explicit clusters of 1..kJacMaxDof coordinates walk; G rows at kBodyConstFixed.  off: the offsets in the PLAN's (canonical) body axes.
-constexpr int kJacMaxDof = 4;
-constexpr int kJacMaxSlots = 10;  // saved values + frames: 10 x 12 x 64 lanes x 8 bytes = 60 KiB of LDS in fp64, what a launch gets unasked
-struct JacWalkStep {
-    int32_t cofs;
-    int16_t q_col, v_col;
-    uint16_t below, own, emit;
-    uint8_t free, n, axis, root, save, restore, cont, pad[3];
-};
+// The walk of route 0 (walk.h, JacWalkStep).  off: the offsets in the PLAN's (canonical) body axes.
 template <class T>
 struct JacWalk {
     int n_steps, n_list, n_saved;

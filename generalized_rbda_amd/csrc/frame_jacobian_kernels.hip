@@ -2,11 +2,12 @@
 // frame_jacobians_run).
 //
 // Route 0, frame_jacobian_walk_kernel: the execution model of body_list_kernels.hip -- one state per lane, one-wavefront workgroups, a
-// grid-stride loop over tiles of 64 states, the walk (devplan.h, JacWalk) in the kernel arguments and read through the scalar unit, every
-// branch on it a scalar branch, no per-lane array indexed at run time, saved values in LDS as [slot][value][lane] (a lane reads what it
-// wrote: no barrier), global memory written once and never read back.  Two passes over the walk per tile:
-//   1. the poses of the root paths, as body_poses_list_kernel; a listed frame leaves [E | p], p = r + E^T offset its point in world
-//      coordinates, in LDS slot n_saved + i;
+// grid-stride loop over tiles of 64 states, the walk (walk.h, JacWalkStep; devplan.h, JacWalk) in the kernel arguments and read through the
+// scalar unit, every branch on it a scalar branch, no per-lane array indexed at run time, saved values in LDS as [slot][value][lane] (a lane
+// reads what it wrote: no barrier), global memory written once and never read back.  The LDS slots and the pose step are walk_dev.h's, the
+// ones body_poses_list_kernel runs.  Two passes over the walk per tile:
+//   1. the poses of the root paths (walk_pose_step); a listed frame leaves [E | p], p = r + E^T offset its point in world coordinates, in
+//      LDS slot n_saved + i;
 //   2. the poses again, and from each the joint's screw axis in WORLD coordinates about the world origin: a revolute joint [w ; r x w] with
 //      w = E^T e, the base its six body axes [E^T e_j ; r x E^T e_j], [0 ; E^T e_j].  World-frame axes of one cluster add, so a cluster's
 //      n columns A[a] = sum over its bodies on the root path of G[body][a] [w ; r x w] accumulate in registers while the walk stays inside
@@ -24,62 +25,10 @@
 namespace grbda_hip {
 
 #include "devmath.h"
+#include "walk_dev.h"
 
 namespace {
 
-template <class T>
-__device__ __forceinline__ void slot_put(int slot, int lane, const T (&x)[12])
-{
-    T *p = reinterpret_cast<T *>(grbda_smem) + slot * 12 * kWave + lane;
-#pragma unroll
-    for (int k = 0; k < 12; k++) p[k * kWave] = x[k];
-}
-template <class T>
-__device__ __forceinline__ void slot_get(int slot, int lane, T (&x)[12])
-{
-    const T *p = reinterpret_cast<const T *>(grbda_smem) + slot * 12 * kWave + lane;
-#pragma unroll
-    for (int k = 0; k < 12; k++) x[k] = p[k * kWave];
-}
-// X = [E 9 | r 3] of the step's body from the running value (body_poses_list_kernel, term by term)
-template <class T>
-__device__ __forceinline__ void step_pose(const JacWalkStep &st, cptr<T> consts, int ori_repr, const T *qr, int lane, T (&X)[12])
-{
-    if (st.restore != kWalkNone) slot_get(st.restore, lane, X);
-    T E[9], rr[3];
-    if (st.free) {
-        T o[4];
-        const int nori = ori_repr == 0 ? 4 : 3;
-        for (int j = 0; j < 4; j++) o[j] = j < nori ? qr[st.q_col + 3 + j] : T(0);
-        free_rotation(ori_repr, o, E);
-        for (int j = 0; j < 3; j++) rr[j] = qr[st.q_col + j];
-    } else {
-        cptr<T> C = consts + st.cofs;
-        T qi = 0;
-        for (int a = 0; a < st.n; a++) qi += C[kBodyConstFixed + a] * qr[st.q_col + a];
-        T sn, cs, El[9];
-        sincos_t(qi, &sn, &cs);
-        build_E((int)st.axis, sn, cs, C, El);
-        if (!st.root) {
-#pragma unroll
-            for (int u = 0; u < 3; u++)
-#pragma unroll
-                for (int w = 0; w < 3; w++) E[3 * u + w] = El[3 * u] * X[w] + El[3 * u + 1] * X[3 + w] + El[3 * u + 2] * X[6 + w];
-#pragma unroll
-            for (int u = 0; u < 3; u++) rr[u] = X[9 + u] + X[u] * C[9] + X[3 + u] * C[10] + X[6 + u] * C[11];
-        } else {
-#pragma unroll
-            for (int u = 0; u < 9; u++) E[u] = El[u];
-#pragma unroll
-            for (int u = 0; u < 3; u++) rr[u] = C[9 + u];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 9; u++) X[u] = E[u];
-#pragma unroll
-    for (int u = 0; u < 3; u++) X[9 + u] = rr[u];
-    if (st.save != kWalkNone) slot_put(st.save, lane, X);
-}
 // one column of one frame: the world-frame axis S = [w ; m] about the world origin, seen at the frame F = [E | p].  o: the column's first
 // row, rows nv apart; body axes are permuted to the reference's as store_row permutes a twist
 template <class T>
@@ -129,7 +78,7 @@ __global__ __launch_bounds__(kWave, 1) void frame_jacobian_walk_kernel(JacWalk<T
         // pass 1: the frames, [E | p]
         for (int s = 0; s < W.n_steps; s++) {
             const JacWalkStep st = W.step[s];
-            step_pose(st, consts, W.ori_repr, qr, lane, X);
+            walk_pose_step(st, consts, W.ori_repr, qr, lane, X);
             if (st.own == 0) continue;
             for (int i = 0; i < W.n_list; i++) {
                 if (!((st.own >> i) & 1)) continue;
@@ -150,7 +99,7 @@ __global__ __launch_bounds__(kWave, 1) void frame_jacobian_walk_kernel(JacWalk<T
             for (int u = 0; u < 6; u++) A[a][u] = 0;
         for (int s = 0; s < W.n_steps; s++) {
             const JacWalkStep st = W.step[s];
-            step_pose(st, consts, W.ori_repr, qr, lane, X);
+            walk_pose_step(st, consts, W.ori_repr, qr, lane, X);
             if (st.free) {
                 for (int i = 0; i < W.n_list; i++) {
                     if (!((st.below >> i) & 1)) continue;
