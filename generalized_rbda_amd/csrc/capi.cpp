@@ -1240,8 +1240,8 @@ int contact_set(const grbda_plan *p, int n_contacts, const int *bodies, const do
     return GRBDA_OK;
 }
 // no output array may share a byte with an input array or with another output (null entries are skipped)
-template <size_t NI, size_t NO>
-int no_overlap(const void *const (&in)[NI], const size_t (&in_bytes)[NI], const void *const (&out)[NO], const size_t (&out_bytes)[NO])
+template <class In, class Out, size_t NI, size_t NO>
+int no_overlap(In (&in)[NI], const size_t (&in_bytes)[NI], Out (&out)[NO], const size_t (&out_bytes)[NO])
 {
     for (size_t i = 0; i < NO; i++) {
         for (size_t j = 0; j < NI; j++)
@@ -3113,106 +3113,9 @@ int rnea_derivatives(const grbda_plan *p, const T *q, const T *qd, const T *ydd,
     return id_derivs<T>(p, q, qd, ydd, step, dq, dqd, B, device, stream);
 }
 
-// ---- vector-Jacobian products (include/grbda_hip_vjp.h): grbda_rnea_vjp_* / grbda_aba_vjp_* -------------------------------------------
-// the argument rules of both (device and host arrays alike); x: ydd / tau, g: the cotangent, grad_x: grad_ydd / grad_tau, ydd_out: the
-// forward dynamics' optional result.  Everything that can be refused is refused here, before a device is looked at.
-template <class T>
-int vjp_args(const grbda_plan *p, const T *q, const T *qd, const T *x, const T *g, double step, const T *grad_q, const T *grad_qd, const T *grad_x,
-             const T *ydd_out, size_t B)
-{
-    if (!q || !qd || !x || !g) return set_err(GRBDA_EINVAL, "null argument");
-    if (!grad_q && !grad_qd && !grad_x) return set_err(GRBDA_EINVAL, "no output asked for");
-    const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
-    const void *const in[4] = {q, qd, x, g}, *const out[4] = {grad_q, grad_qd, grad_x, ydd_out};
-    const size_t in_bytes[4] = {bq, bv, bv, bv}, out_bytes[4] = {bv, bv, bv, bv};
-    if (int rc = no_overlap(in, in_bytes, out, out_bytes)) return rc;
-    // (the one use of `step`: d tau / d q by central differences, id_derivs off the analytic route)
-    if (grad_q && !analytic_covers(p) && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
-    return GRBDA_OK;
-}
-// Chunk by chunk through the plan's work_vjp slab.  forward: ydd = ABA(q, qd, tau); mu = H^-1 g as ABA(q, 0, g) - ABA(q, 0, 0); d tau / d q and
-// d tau / d qd at (q, qd, ydd) by id_derivs into the slab, row-major; grad_q = -mu^T d tau / d q, grad_qd = -mu^T d tau / d qd, grad_tau = mu
-// (vjp_contract_kernel forms the difference and writes all three).  Inverse: the matrices at the caller's ydd contracted with g, and
-// grad_ydd = H g as RNEA(q, 0, g) - RNEA(q, 0, 0).  The runs of a zero-velocity pair carry no gravity (run(), gravity = false): on plans
-// without the spanning-tree route the second of them is then exactly zero and the first is not rounded against a bias it does not need.
-// Only the stages the asked-for outputs need are enqueued, and each output has the same bits in every subset.
-template <class T>
-int vjp_run(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *g, double step, T *grad_q, T *grad_qd, T *grad_x,
-            T *ydd_out, size_t B, int device, void *stream)
-{
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
-    const bool need_d = grad_q || grad_qd;
-    const bool need_pair = forward || grad_x;                        // the two launches at zero velocity
-    const bool need_ydd = forward && (need_d || ydd_out);
-    // per state: the matrices asked for; zeros, and the two results of the zero-velocity pair; ydd when the caller keeps none
-    const size_t per_state = (grad_q ? nn : 0) + (grad_qd ? nn : 0) + (need_pair ? 3 * nv : 0) + (need_ydd && !ydd_out ? nv : 0);
-    const Chunk c = budgeted_chunk(p, p->work_vjp, device, stream, 4096ull << 20, per_state * sizeof(T), B);
-    void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work_vjp, device, stream, c.bytes, &wptr)) return rc;
-    Carver<T> w(wptr, c.chunk * per_state);
-    auto take = [&](bool wanted, size_t per) { return wanted ? w.take(c.chunk * per) : nullptr; };
-    T *Mq = take(grad_q, nn), *Mqd = take(grad_qd, nn), *zeros = take(need_pair, nv), *r1 = take(need_pair, nv), *r0 = take(need_pair, nv);
-    T *ydd_slab = take(need_ydd && !ydd_out, nv);
-    assert(w.taken == w.cap);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const int nvi = static_cast<int>(nv);
-    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
-        const T *qc = q + b0 * nq, *qdc = qd + b0 * nv, *xc = x + b0 * nv, *gc = g + b0 * nv;
-        T *ydd = ydd_out ? ydd_out + b0 * nv : ydd_slab;
-        T *oq = grad_q ? grad_q + b0 * nv : nullptr, *oqd = grad_qd ? grad_qd + b0 * nv : nullptr, *ox = grad_x ? grad_x + b0 * nv : nullptr;
-        if (need_ydd)
-            if (int rc = run<T>(p, false, qc, qdc, xc, nullptr, ydd, nb, device, stream)) return rc;
-        if (need_pair) {
-            if (hipError_t e = hipMemsetAsync(zeros, 0, nb * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-            if (int rc = run<T>(p, !forward, qc, zeros, gc, nullptr, r1, nb, device, stream, false)) return rc;
-            if (int rc = run<T>(p, !forward, qc, zeros, zeros, nullptr, r0, nb, device, stream, false)) return rc;
-        }
-        if (need_d)
-            if (int rc = id_derivs<T>(p, qc, qdc, forward ? ydd : xc, step, Mq, Mqd, nb, device, stream)) return rc;
-        const VjpLaunch L = vjp_contract_launch(nvi, sizeof(T), t->n_cu, nb);
-        hipError_t e = hipSuccess;
-        if (forward) {
-            e = launch_vjp_contract<T>(L, Mq, Mqd, r1, r0, T(-1), nvi, nb, oq, oqd, ox, hs);
-        } else {
-            if (ox) e = launch_vjp_contract<T>(L, nullptr, nullptr, r1, r0, T(1), nvi, nb, nullptr, nullptr, ox, hs);
-            if (e == hipSuccess && need_d) e = launch_vjp_contract<T>(L, Mq, Mqd, gc, nullptr, T(1), nvi, nb, oq, oqd, nullptr, hs);
-        }
-        if (e != hipSuccess) return hip_err(e, "vjp contraction launch");
-    }
-    return GRBDA_OK;
-}
-template <class T>
-int vjp(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *g, double step, T *grad_q, T *grad_qd, T *grad_x, T *ydd_out,
-        size_t B, int device, void *stream)
-{
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    if (int rc = vjp_args<T>(p, q, qd, x, g, step, grad_q, grad_qd, grad_x, ydd_out, B)) return rc;
-    if (B == 0) return GRBDA_OK;
-    return vjp_run<T>(p, forward, q, qd, x, g, step, grad_q, grad_qd, grad_x, ydd_out, B, device, stream);
-}
-int vjp_host_f64(const grbda_plan *p, bool forward, const double *q, const double *qd, const double *x, const double *g, double step, double *grad_q,
-                 double *grad_qd, double *grad_x, double *ydd_out, size_t B, int device)
-{
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    if (int rc = vjp_args<double>(p, q, qd, x, g, step, grad_q, grad_qd, grad_x, ydd_out, B)) return rc;
-    if (B == 0) return GRBDA_OK;
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    DeviceTables *t = nullptr;
-    if (int rc0 = ensure_device(p, device, &t)) return rc0;  // `device` current before anything is allocated on it
-    HostStage st;
-    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bx = st.in(x, B * nv), *bg = st.in(g, B * nv);
-    double *b1 = grad_q ? st.out(grad_q, B * nv) : nullptr, *b2 = grad_qd ? st.out(grad_qd, B * nv) : nullptr,
-           *b3 = grad_x ? st.out(grad_x, B * nv) : nullptr, *b4 = ydd_out ? st.out(ydd_out, B * nv) : nullptr;
-    return st.run([&] { return vjp_run<double>(p, forward, bq, bqd, bx, bg, step, b1, b2, b3, b4, B, device, nullptr); });
-}
-
-// ---- vector-Jacobian products of integrate, step and rollout (include/grbda_hip_step_vjp.h; step_vjp_kernels.hip) ---------------------
-// The plans the three families refuse: what grbda_step_* refuses, and every implicit cluster (the Jacobian of the Newton re-projection is
-// not built).  *base: the index of the quaternion base's cluster record, -1 for a plan without one.
+// ---- vector-Jacobian and Jacobian-vector products (include/grbda_hip_vjp.h, grbda_hip_step_vjp.h, grbda_hip_jvp.h) --------------------
+// The plans the stepping entry points of the three headers refuse: what grbda_step_* refuses, and every implicit cluster (the Jacobian of
+// the Newton re-projection is not built).  *base: the index of the quaternion base's cluster record, -1 for a plan without one.
 int step_vjp_plan(const grbda_plan *p, int *base)
 {
     *base = -1;
@@ -3229,48 +3132,208 @@ int step_vjp_plan(const grbda_plan *p, int *base)
                                            "the Newton re-projection is not built");
     return GRBDA_OK;
 }
-// the rules the three share once their pointers are sorted into inputs and outputs: a cotangent, an output, a finite dt, no overlap, the
-// plan, and the step where grbda_aba_vjp_* will take differences in q (need_q)
-template <size_t NI, size_t NO>
-int step_vjp_rules(const grbda_plan *p, const void *g_q, const void *g_qd, double dt, bool differentiates, bool need_q, double step,
-                   const void *const (&in)[NI], const size_t (&in_bytes)[NI], const void *const (&out)[NO], const size_t (&out_bytes)[NO], int *base)
+// an array of a call and the bytes it spans (bytes, not a width: the rollout's arrays hold a block of the batch per step)
+struct Extent {
+    const void *ptr;
+    size_t bytes;
+};
+using Extents = std::initializer_list<Extent>;
+constexpr char kNoCotangent[] = "both cotangents are null", kNoTangent[] = "all tangents are null";
+// The argument rules of every entry point of the three headers (device and host arrays alike), in the one order all of them apply:
+//   1 every state input is given                      2 one of the optional (co)tangents is (`none`: the message; no list, no rule)
+//   3 one of the first `asked` outputs is (an output behind them, ydd of the forward side, is no product of its own)
+//   4 dt, where the entry point has one, is finite    5 no output shares a byte with an input or with another output
+//   6 stepping: the plan is one step_vjp_plan takes (it fills *base)
+//   7 diff_q: the step is positive off the analytic route (its one use: d tau / d q by central differences, id_derivs)
+// Everything that can be refused is refused here, before a device is looked at.
+int product_rules(const grbda_plan *p, Extents state, Extents tangents, const char *none, Extents out, size_t asked, const double *dt, bool stepping,
+                  bool diff_q, double step, int *base)
 {
-    if (!g_q && !g_qd) return set_err(GRBDA_EINVAL, "both cotangents are null");
-    bool any = false;
-    for (const void *o : out) any = any || o;
-    if (!any) return set_err(GRBDA_EINVAL, "no output asked for");
-    if (!std::isfinite(dt)) return set_err(GRBDA_EINVAL, "dt is not finite");
-    if (int rc = no_overlap(in, in_bytes, out, out_bytes)) return rc;
-    if (int rc = step_vjp_plan(p, base)) return rc;
-    if (differentiates && need_q && !analytic_covers(p) && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+    const void *in[8] = {}, *o[4] = {};  // (a null entry is skipped by no_overlap)
+    size_t in_bytes[8] = {}, o_bytes[4] = {}, ni = 0, no = 0;
+    assert(state.size() + tangents.size() <= 8 && out.size() <= 4);
+    bool any_tangent = tangents.size() == 0, any_out = false;
+    for (const Extent &e : state) {
+        if (!e.ptr) return set_err(GRBDA_EINVAL, "null argument");
+        in[ni] = e.ptr, in_bytes[ni++] = e.bytes;
+    }
+    for (const Extent &e : tangents) {
+        any_tangent = any_tangent || e.ptr;
+        in[ni] = e.ptr, in_bytes[ni++] = e.bytes;
+    }
+    if (!any_tangent) return set_err(GRBDA_EINVAL, none);
+    for (const Extent &e : out) {
+        any_out = any_out || (no < asked && e.ptr);
+        o[no] = e.ptr, o_bytes[no++] = e.bytes;
+    }
+    if (!any_out) return set_err(GRBDA_EINVAL, "no output asked for");
+    if (dt && !std::isfinite(*dt)) return set_err(GRBDA_EINVAL, "dt is not finite");
+    if (int rc = no_overlap(in, in_bytes, o, o_bytes)) return rc;
+    if (stepping)
+        if (int rc = step_vjp_plan(p, base)) return rc;
+    if (diff_q && !analytic_covers(p) && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
+    return GRBDA_OK;
+}
+// The arrays of an entry point as its body declares them, in the order of HostStage: the caller's device arrays as they are, or -- the
+// *_host_f64 variants -- a staged copy of every array that is given.  run(): the call, between the copies in and out where there are any.
+struct ProductArrays {
+    HostStage *stage;
+    template <class T>
+    const T *in(const T *a, size_t count) { return stage && a ? stage->in(a, count) : a; }
+    template <class T>
+    T *out(T *a, size_t count) { return stage && a ? stage->out(a, count) : a; }
+    template <class Call>
+    int run(Call call) { return stage ? stage->run(call) : call(); }
+};
+// The entry of the family, device and host arrays alike: a null plan, the call scope, the entry point's rules (rules(&base)), an empty
+// batch, the device -- current before a host variant allocates anything on it --, then body(arrays, tables, base).
+template <class Rules, class Body>
+int product_entry(const grbda_plan *p, size_t B, int device, bool host, Rules rules, Body body)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    int base = -1;
+    if (int rc = rules(&base)) return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    HostStage st;  // (holds nothing for device arrays)
+    ProductArrays a{host ? &st : nullptr};
+    return body(a, *t, base);
+}
+// `rows` arrays [B][nv] from a pool of the plan (work_step_vjp, work_step_jvp): not chunked -- they are the size of the inputs
+template <class T>
+int rows_slab(const grbda_plan *p, SlabPool &pool, size_t rows, size_t B, int device, void *stream, T **w)
+{
+    void *ptr = nullptr;
+    if (int rc = ensure_work(p, pool, device, stream, rows * B * p->host.nv * sizeof(T) + 256, &ptr)) return rc;
+    *w = static_cast<T *>(ptr);
+    return GRBDA_OK;
+}
+// the quaternion base's cluster record on the device, null for a plan without one: what the two integrate kernels read the base's v_index
+// from (the record of the fp64 layout: the cluster's v_index is the same in every layout)
+const ClusterRec *base_record(const DeviceTables &t, int base) { return base >= 0 ? t.clusters[1] + base : nullptr; }
+
+// The linearisation both products are built on, chunk by chunk through a slab of the plan (`pool`: work_vjp or work_jvp), and its stages
+// on the states [b0, b0 + nb) of a chunk:
+//   ydd_stage       forward: ydd = ABA(q, qd, tau), into the caller's ydd_out where it keeps one, into the slab otherwise
+//   matrices_stage  d tau / d q and d tau / d qd at (q, qd, ydd) by id_derivs into the slab, row-major (ydd: the forward side's own, or x)
+//   pair_stage      the zero-velocity pair r1 = F(q, 0, rhs), r0 = F(q, 0, 0), F the ABA (forward) or the RNEA: r1 - r0 is H^-1 rhs or
+//                   H rhs.  The runs of a pair carry no gravity (run(), gravity = false): on plans without the spanning-tree route the
+//                   second of them is then exactly zero and the first is not rounded against a bias it does not need.
+// A stage enqueues nothing where need_ydd / need_d / need_pair says that no asked-for result needs it, so every result has the same bits in
+// every subset.  carve(): wq, wqd: the matrix is wanted (its gradient is asked for, its tangent is given); wx: so is the pair of the inverse
+// side (grad_ydd, dydd); with_mid: one more vector between r0 and ydd where matrices and pair meet (jvp_run).  Per state of the chunk: the
+// matrices wanted; zeros and the two results of the pair; mid; ydd when the caller keeps none.
+template <class T>
+struct ProductWork {
+    const grbda_plan *p;
+    bool forward;
+    const T *q, *qd, *x;  // the batch; x: tau (forward) or ydd
+    T *ydd_out;           // forward: the caller's ydd, where it keeps one
+    double step;
+    int device;
+    void *stream;
+    bool need_d = false, need_pair = false, need_ydd = false;
+    size_t chunk = 0;  // states per pass
+    T *Mq = nullptr, *Mqd = nullptr, *zeros = nullptr, *r1 = nullptr, *r0 = nullptr, *mid = nullptr, *ydd_slab = nullptr;
+
+    int carve(SlabPool &pool, bool wq, bool wqd, bool wx, bool with_mid, size_t B)
+    {
+        const size_t nv = p->host.nv, nn = nv * nv;
+        need_d = wq || wqd;
+        need_pair = forward || wx;
+        need_ydd = forward && (need_d || ydd_out);
+        const bool need_mid = with_mid && need_d && need_pair, own_ydd = need_ydd && !ydd_out;
+        const size_t per_state = (wq ? nn : 0) + (wqd ? nn : 0) + (need_pair ? 3 * nv : 0) + (need_mid ? nv : 0) + (own_ydd ? nv : 0);
+        const Chunk c = budgeted_chunk(p, pool, device, stream, 4096ull << 20, per_state * sizeof(T), B);
+        void *wptr = nullptr;
+        if (int rc = ensure_work(p, pool, device, stream, c.bytes, &wptr)) return rc;
+        Carver<T> w(wptr, c.chunk * per_state);
+        auto take = [&](bool wanted, size_t per) { return wanted ? w.take(c.chunk * per) : nullptr; };
+        Mq = take(wq, nn), Mqd = take(wqd, nn), zeros = take(need_pair, nv), r1 = take(need_pair, nv), r0 = take(need_pair, nv);
+        mid = take(need_mid, nv), ydd_slab = take(own_ydd, nv);
+        assert(w.taken == w.cap);
+        chunk = c.chunk;
+        return GRBDA_OK;
+    }
+    T *ydd(size_t b0) const { return ydd_out ? ydd_out + b0 * p->host.nv : ydd_slab; }
+    int ydd_stage(size_t b0, size_t nb) const
+    {
+        const size_t nv = p->host.nv;
+        return need_ydd ? run<T>(p, false, q + b0 * p->host.nq, qd + b0 * nv, x + b0 * nv, nullptr, ydd(b0), nb, device, stream) : GRBDA_OK;
+    }
+    int matrices_stage(size_t b0, size_t nb) const
+    {
+        const size_t nv = p->host.nv;
+        return need_d ? id_derivs<T>(p, q + b0 * p->host.nq, qd + b0 * nv, forward ? ydd(b0) : x + b0 * nv, step, Mq, Mqd, nb, device, stream) : GRBDA_OK;
+    }
+    int pair_stage(size_t b0, size_t nb, const T *rhs) const
+    {
+        if (!need_pair) return GRBDA_OK;
+        const T *qc = q + b0 * p->host.nq;
+        if (hipError_t e = hipMemsetAsync(zeros, 0, nb * p->host.nv * sizeof(T), static_cast<hipStream_t>(stream)); e != hipSuccess)
+            return hip_err(e, "hipMemsetAsync");
+        if (int rc = run<T>(p, !forward, qc, zeros, rhs, nullptr, r1, nb, device, stream, false)) return rc;
+        return run<T>(p, !forward, qc, zeros, zeros, nullptr, r0, nb, device, stream, false);
+    }
+};
+
+// ---- grbda_rnea_vjp_* / grbda_aba_vjp_* (include/grbda_hip_vjp.h; vjp_kernels.hip) ---------------------------------------------------------
+// x: ydd / tau, g: the cotangent, grad_x: grad_ydd / grad_tau, ydd_out: the forward dynamics' optional result.
+// Forward: mu = H^-1 g by the ABA pair, the matrices at ydd = ABA(q, qd, tau); grad_q = -mu^T d tau / d q, grad_qd = -mu^T d tau / d qd,
+// grad_tau = mu (vjp_contract_kernel forms the difference of the pair and writes all three).  Inverse: the matrices at the caller's ydd
+// contracted with g, and grad_ydd = H g by the RNEA pair.
+template <class T>
+int vjp_run(const grbda_plan *p, const DeviceTables &t, bool forward, const T *q, const T *qd, const T *x, const T *g, double step, T *grad_q, T *grad_qd,
+            T *grad_x, T *ydd_out, size_t B, int device, void *stream)
+{
+    ProductWork<T> w{p, forward, q, qd, x, ydd_out, step, device, stream};
+    if (int rc = w.carve(p->work_vjp, grad_q, grad_qd, grad_x, false, B)) return rc;
+    const size_t nv = p->host.nv;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int nvi = static_cast<int>(nv);
+    for (const auto [b0, nb] : ChunkWalk{B, w.chunk}) {
+        const T *gc = g + b0 * nv;
+        T *oq = grad_q ? grad_q + b0 * nv : nullptr, *oqd = grad_qd ? grad_qd + b0 * nv : nullptr, *ox = grad_x ? grad_x + b0 * nv : nullptr;
+        if (int rc = w.ydd_stage(b0, nb)) return rc;
+        if (int rc = w.pair_stage(b0, nb, gc)) return rc;
+        if (int rc = w.matrices_stage(b0, nb)) return rc;
+        const VjpLaunch L = vjp_contract_launch(nvi, sizeof(T), t.n_cu, nb);
+        hipError_t e = hipSuccess;
+        if (forward) {
+            e = launch_vjp_contract<T>(L, w.Mq, w.Mqd, w.r1, w.r0, T(-1), nvi, nb, oq, oqd, ox, hs);
+        } else {
+            if (ox) e = launch_vjp_contract<T>(L, nullptr, nullptr, w.r1, w.r0, T(1), nvi, nb, nullptr, nullptr, ox, hs);
+            if (e == hipSuccess && w.need_d) e = launch_vjp_contract<T>(L, w.Mq, w.Mqd, gc, nullptr, T(1), nvi, nb, oq, oqd, nullptr, hs);
+        }
+        if (e != hipSuccess) return hip_err(e, "vjp contraction launch");
+    }
     return GRBDA_OK;
 }
 template <class T>
-int integrate_vjp_args(const grbda_plan *p, const T *qd_next, double dt, const T *g_q, const T *g_qd, const T *grad_q, const T *grad_qd,
-                       const T *grad_ydd, size_t B, int *base)
+int vjp(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *g, double step, T *grad_q, T *grad_qd, T *grad_x, T *ydd_out,
+        size_t B, int device, void *stream, bool host = false)
 {
-    if (!qd_next) return set_err(GRBDA_EINVAL, "null argument");
-    const size_t bv = B * p->host.nv * sizeof(T);
-    const void *const in[3] = {qd_next, g_q, g_qd}, *const out[3] = {grad_q, grad_qd, grad_ydd};
-    const size_t in_bytes[3] = {bv, bv, bv}, out_bytes[3] = {bv, bv, bv};
-    return step_vjp_rules(p, g_q, g_qd, dt, false, false, 0.0, in, in_bytes, out, out_bytes, base);
+    const auto rules = [&](int *) {
+        const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
+        return product_rules(p, {{q, bq}, {qd, bv}, {x, bv}, {g, bv}}, {}, nullptr, {{grad_q, bv}, {grad_qd, bv}, {grad_x, bv}, {ydd_out, bv}}, 3, nullptr,
+                             false, grad_q, step, nullptr);
+    };
+    return product_entry(p, B, device, host, rules, [&](ProductArrays &a, const DeviceTables &t, int) {
+        const size_t nq = p->host.nq, nv = p->host.nv;
+        const T *bq = a.in(q, B * nq), *bqd = a.in(qd, B * nv), *bx = a.in(x, B * nv), *bg = a.in(g, B * nv);
+        T *b1 = a.out(grad_q, B * nv), *b2 = a.out(grad_qd, B * nv), *b3 = a.out(grad_x, B * nv), *b4 = a.out(ydd_out, B * nv);
+        return a.run([&] { return vjp_run<T>(p, t, forward, bq, bqd, bx, bg, step, b1, b2, b3, b4, B, device, stream); });
+    });
 }
-template <class T>
-int step_vjp_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *g_q, const T *g_qd, double step,
-                  const T *grad_q, const T *grad_qd, const T *grad_tau, size_t B, int *base)
-{
-    if (!q || !qd || !tau || !qd_next) return set_err(GRBDA_EINVAL, "null argument");
-    const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
-    const void *const in[6] = {q, qd, tau, qd_next, g_q, g_qd}, *const out[3] = {grad_q, grad_qd, grad_tau};
-    const size_t in_bytes[6] = {bq, bv, bv, bv, bv, bv}, out_bytes[3] = {bv, bv, bv};
-    return step_vjp_rules(p, g_q, g_qd, dt, true, grad_q != nullptr, step, in, in_bytes, out, out_bytes, base);
-}
+
+// ---- vector-Jacobian products of integrate, step and rollout (include/grbda_hip_step_vjp.h; step_vjp_kernels.hip) ---------------------
 template <class T>
 hipError_t integrate_vjp_launch(const DeviceTables &t, int base, const T *qd_next, double dt, const T *g_q, const T *g_qd, T *grad_q, T *grad_qd,
                                 T *grad_ydd, int nv, size_t B, void *stream)
 {
-    // (the record of the fp64 layout: the cluster's v_index is the same in every layout)
-    return launch_integrate_vjp<T>(base >= 0 ? t.clusters[1] + base : nullptr, qd_next, static_cast<T>(dt), g_q, g_qd, grad_q, grad_qd, grad_ydd, nv, B,
+    return launch_integrate_vjp<T>(base_record(t, base), qd_next, static_cast<T>(dt), g_q, g_qd, grad_q, grad_qd, grad_ydd, nv, B,
                                    static_cast<hipStream_t>(stream));
 }
 constexpr size_t kStepVjpRows = 5, kRolloutVjpRows = 10;  // [B][nv] arrays of the slab: one step's; with the loop's adjoints behind them
@@ -3287,69 +3350,45 @@ int step_vjp_run(const grbda_plan *p, const DeviceTables &t, int base, const T *
       *a_qd = grad_qd ? w + 4 * n : nullptr;
     if (hipError_t e = integrate_vjp_launch<T>(t, base, qd_next, dt, g_q, g_qd, i_q, i_qd, g_ydd, nvi, B, stream); e != hipSuccess)
         return hip_err(e, "integrate vjp launch");
-    if (int rc = vjp_run<T>(p, true, q, qd, tau, g_ydd, step, a_q, a_qd, grad_tau, nullptr, B, device, stream)) return rc;
+    if (int rc = vjp_run<T>(p, t, true, q, qd, tau, g_ydd, step, a_q, a_qd, grad_tau, nullptr, B, device, stream)) return rc;
     hipError_t e = hipSuccess;
     if (grad_q) e = launch_vjp_add<T>(i_q, a_q, grad_q, n, hs);
     if (e == hipSuccess && grad_qd) e = launch_vjp_add<T>(i_qd, a_qd, grad_qd, n, hs);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "vjp add launch");
 }
 template <class T>
-int step_vjp_slab(const grbda_plan *p, size_t rows, size_t B, int device, void *stream, T **w)
-{
-    void *ptr = nullptr;
-    if (int rc = ensure_work(p, p->work_step_vjp, device, stream, rows * B * p->host.nv * sizeof(T) + 256, &ptr)) return rc;
-    *w = static_cast<T *>(ptr);
-    return GRBDA_OK;
-}
-template <class T>
 int integrate_vjp(const grbda_plan *p, const T *qd_next, double dt, const T *g_q, const T *g_qd, T *grad_q, T *grad_qd, T *grad_ydd, size_t B, int device,
                   void *stream)
 {
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    int base = -1;
-    if (int rc = integrate_vjp_args<T>(p, qd_next, dt, g_q, g_qd, grad_q, grad_qd, grad_ydd, B, &base)) return rc;
-    if (B == 0) return GRBDA_OK;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    hipError_t e = integrate_vjp_launch<T>(*t, base, qd_next, dt, g_q, g_qd, grad_q, grad_qd, grad_ydd, static_cast<int>(p->host.nv), B, stream);
-    return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate vjp launch");
+    const auto rules = [&](int *base) {
+        const size_t bv = B * p->host.nv * sizeof(T);
+        return product_rules(p, {{qd_next, bv}}, {{g_q, bv}, {g_qd, bv}}, kNoCotangent, {{grad_q, bv}, {grad_qd, bv}, {grad_ydd, bv}}, 3, &dt, true, false,
+                             0.0, base);
+    };
+    return product_entry(p, B, device, false, rules, [&](ProductArrays &, const DeviceTables &t, int base) {
+        hipError_t e = integrate_vjp_launch<T>(t, base, qd_next, dt, g_q, g_qd, grad_q, grad_qd, grad_ydd, static_cast<int>(p->host.nv), B, stream);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate vjp launch");
+    });
 }
 template <class T>
 int step_vjp(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *g_q, const T *g_qd, double step, T *grad_q,
-             T *grad_qd, T *grad_tau, size_t B, int device, void *stream)
+             T *grad_qd, T *grad_tau, size_t B, int device, void *stream, bool host = false)
 {
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    int base = -1;
-    if (int rc = step_vjp_args<T>(p, q, qd, tau, qd_next, dt, g_q, g_qd, step, grad_q, grad_qd, grad_tau, B, &base)) return rc;
-    if (B == 0) return GRBDA_OK;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    T *w = nullptr;
-    if (int rc = step_vjp_slab<T>(p, kStepVjpRows, B, device, stream, &w)) return rc;
-    return step_vjp_run<T>(p, *t, base, q, qd, tau, qd_next, dt, g_q, g_qd, step, grad_q, grad_qd, grad_tau, B, device, stream, w);
-}
-int step_vjp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt, const double *g_q,
-                      const double *g_qd, double step, double *grad_q, double *grad_qd, double *grad_tau, size_t B, int device)
-{
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    int base = -1;
-    if (int rc = step_vjp_args<double>(p, q, qd, tau, qd_next, dt, g_q, g_qd, step, grad_q, grad_qd, grad_tau, B, &base)) return rc;
-    if (B == 0) return GRBDA_OK;
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;  // `device` current before anything is allocated on it
-    HostStage st;
-    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bt = st.in(tau, B * nv), *bn = st.in(qd_next, B * nv);
-    const double *bgq = g_q ? st.in(g_q, B * nv) : nullptr, *bgqd = g_qd ? st.in(g_qd, B * nv) : nullptr;
-    double *o1 = grad_q ? st.out(grad_q, B * nv) : nullptr, *o2 = grad_qd ? st.out(grad_qd, B * nv) : nullptr,
-           *o3 = grad_tau ? st.out(grad_tau, B * nv) : nullptr;
-    return st.run([&] {
-        double *w = nullptr;
-        if (int rc = step_vjp_slab<double>(p, kStepVjpRows, B, device, nullptr, &w)) return rc;
-        return step_vjp_run<double>(p, *t, base, bq, bqd, bt, bn, dt, bgq, bgqd, step, o1, o2, o3, B, device, nullptr, w);
+    const auto rules = [&](int *base) {  // (the step: where grbda_aba_vjp_* will take differences in q)
+        const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
+        return product_rules(p, {{q, bq}, {qd, bv}, {tau, bv}, {qd_next, bv}}, {{g_q, bv}, {g_qd, bv}}, kNoCotangent,
+                             {{grad_q, bv}, {grad_qd, bv}, {grad_tau, bv}}, 3, &dt, true, grad_q, step, base);
+    };
+    return product_entry(p, B, device, host, rules, [&](ProductArrays &a, const DeviceTables &t, int base) {
+        const size_t nq = p->host.nq, nv = p->host.nv;
+        const T *bq = a.in(q, B * nq), *bqd = a.in(qd, B * nv), *bt = a.in(tau, B * nv), *bn = a.in(qd_next, B * nv);
+        const T *bgq = a.in(g_q, B * nv), *bgqd = a.in(g_qd, B * nv);
+        T *o1 = a.out(grad_q, B * nv), *o2 = a.out(grad_qd, B * nv), *o3 = a.out(grad_tau, B * nv);
+        return a.run([&] {
+            T *w = nullptr;
+            if (int rc = rows_slab<T>(p, p->work_step_vjp, kStepVjpRows, B, device, stream, &w)) return rc;
+            return step_vjp_run<T>(p, t, base, bq, bqd, bt, bn, dt, bgq, bgqd, step, o1, o2, o3, B, device, stream, w);
+        });
     });
 }
 // The loop of grbda_step_vjp_* from state T back to state 0.  The adjoint lambda_k is the step's output gamma itself, or gamma + g[k] in a
@@ -3361,22 +3400,23 @@ int rollout_vjp(const grbda_plan *p, const T *q0, const T *qd0, const T *q_traj,
 {
     if (!p) return set_err(GRBDA_EINVAL, "null plan");
     GRBDA_CALL_SCOPE(p);
+    // (a missing state input and the three counts in front of the family's rules: the counts size the arrays)
     if (!q0 || !qd0 || !q_traj || !qd_traj || !tau) return set_err(GRBDA_EINVAL, "null argument");
     if (n_steps < 0) return set_err(GRBDA_EINVAL, "T is negative");
     if (tau_steps != 1 && tau_steps != n_steps) return set_err(GRBDA_EINVAL, "tau_steps must be 1 or T");
     if (g_steps != 1 && g_steps != n_steps) return set_err(GRBDA_EINVAL, "g_steps must be 1 or T");
     const size_t nq = p->host.nq, nv = p->host.nv, bq = B * nq * sizeof(T), bv = B * nv * sizeof(T), steps = static_cast<size_t>(n_steps);
     const size_t ts = static_cast<size_t>(tau_steps), gs = static_cast<size_t>(g_steps);
-    const void *const in[7] = {q0, qd0, q_traj, qd_traj, tau, g_q, g_qd}, *const out[3] = {grad_q0, grad_qd0, grad_tau};
-    const size_t in_bytes[7] = {bq, bv, steps * bq, steps * bv, ts * bv, gs * bv, gs * bv}, out_bytes[3] = {bv, bv, ts * bv};
     int base = -1;
     // (the steps k >= 1 hand their position gradient on, whatever the caller asks of state 0)
-    if (int rc = step_vjp_rules(p, g_q, g_qd, dt, true, grad_q0 || n_steps > 1, step, in, in_bytes, out, out_bytes, &base)) return rc;
+    if (int rc = product_rules(p, {{q0, bq}, {qd0, bv}, {q_traj, steps * bq}, {qd_traj, steps * bv}, {tau, ts * bv}}, {{g_q, gs * bv}, {g_qd, gs * bv}},
+                               kNoCotangent, {{grad_q0, bv}, {grad_qd0, bv}, {grad_tau, ts * bv}}, 3, &dt, true, grad_q0 || n_steps > 1, step, &base))
+        return rc;
     if (B == 0 || n_steps == 0) return GRBDA_OK;
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
     T *w = nullptr;
-    if (int rc = step_vjp_slab<T>(p, kRolloutVjpRows, B, device, stream, &w)) return rc;
+    if (int rc = rows_slab<T>(p, p->work_step_vjp, kRolloutVjpRows, B, device, stream, &w)) return rc;
     const size_t n = B * nv;
     T *gam_q = w + kStepVjpRows * n, *gam_qd = gam_q + n, *sum_q = gam_qd + n, *sum_qd = sum_q + n, *gam_tau = sum_qd + n;
     hipStream_t hs = static_cast<hipStream_t>(stream);
@@ -3406,170 +3446,83 @@ int rollout_vjp(const grbda_plan *p, const T *q0, const T *qd0, const T *q_traj,
 }
 
 // ---- Jacobian-vector products (include/grbda_hip_jvp.h; jvp_kernels.hip, integrate_jvp_kernel of step_vjp_kernels.hip) ----------------
-// The rules every entry point of the header shares once its pointers are sorted into state inputs, tangents and outputs, in this order:
-// a state input, a tangent, an output, a finite dt, no overlap, the plan (stepping entry points), the step where differences in q are taken.
-// Everything that can be refused is refused here, before a device is looked at.  *base: as step_vjp_plan gives it.
-template <size_t NS, size_t NO>
-int jvp_rules(const grbda_plan *p, size_t elem, size_t B, const void *const (&state)[NS], const size_t (&state_width)[NS], const void *dq,
-              const void *dqd, const void *dx, const void *const (&out)[NO], bool need_out0, const double *dt, bool stepping, bool differentiates,
-              double step, int *base)
-{
-    for (const void *s : state)
-        if (!s) return set_err(GRBDA_EINVAL, "null argument");
-    if (!dq && !dqd && !dx) return set_err(GRBDA_EINVAL, "all tangents are null");
-    bool any = false;
-    for (const void *o : out) any = any || o;
-    if (need_out0 ? !out[0] : !any) return set_err(GRBDA_EINVAL, "no output asked for");
-    if (dt && !std::isfinite(*dt)) return set_err(GRBDA_EINVAL, "dt is not finite");
-    const size_t bv = B * p->host.nv * elem;
-    const void *in[NS + 3];
-    size_t in_bytes[NS + 3], out_bytes[NO];
-    for (size_t i = 0; i < NS; i++) {
-        in[i] = state[i];
-        in_bytes[i] = B * state_width[i] * elem;
-    }
-    in[NS] = dq, in[NS + 1] = dqd, in[NS + 2] = dx;
-    in_bytes[NS] = in_bytes[NS + 1] = in_bytes[NS + 2] = bv;
-    for (size_t i = 0; i < NO; i++) out_bytes[i] = bv;
-    if (int rc = no_overlap(reinterpret_cast<const void *const(&)[NS + 3]>(in), in_bytes, out, out_bytes)) return rc;
-    if (stepping)
-        if (int rc = step_vjp_plan(p, base)) return rc;
-    // (the one use of `step`: d tau / d q by central differences, id_derivs off the analytic route)
-    if (differentiates && dq && !analytic_covers(p) && !(step > 0)) return set_err(GRBDA_EINVAL, "step must be positive");
-    return GRBDA_OK;
-}
-// x: ydd / tau, dx: dydd / dtau, out: dtau_out / dydd_out, ydd_out: the forward dynamics' optional result
+// x: ydd / tau, dx: dydd / dtau, out: dtau_out / dydd_out, ydd_out: the forward dynamics' optional result.
+// Inverse: the matrices of the given tangents at the caller's ydd, H dydd by the RNEA pair (vjp_contract_kernel without matrices forms the
+// difference, into mid), and jvp_contract_kernel sums the rows against the tangents on top of it.  Forward: the matrices at
+// ydd = ABA(q, qd, tau); r = dtau - d tau / d q dq - d tau / d qd dqd (the same kernel, sign -1, dtau added in, into mid); dydd = H^-1 r by
+// the ABA pair.
 template <class T>
-int jvp_args(const grbda_plan *p, const T *q, const T *qd, const T *x, const T *dq, const T *dqd, const T *dx, double step, const T *out, const T *ydd_out,
-             size_t B)
+int jvp_run(const grbda_plan *p, const DeviceTables &t, bool forward, const T *q, const T *qd, const T *x, const T *dq, const T *dqd, const T *dx,
+            double step, T *out, T *ydd_out, size_t B, int device, void *stream)
 {
-    const void *const state[3] = {q, qd, x}, *const outs[2] = {out, ydd_out};
-    const size_t nq = p->host.nq, nv = p->host.nv, width[3] = {nq, nv, nv};
-    return jvp_rules(p, sizeof(T), B, state, width, dq, dqd, dx, outs, true, nullptr, false, true, step, nullptr);
-}
-// Chunk by chunk through the plan's work_jvp slab.  Inverse: d tau / d q, d tau / d qd at (q, qd, ydd) by id_derivs into the slab (each only
-// when its tangent is given), H dydd = RNEA(q, 0, dydd) - RNEA(q, 0, 0) (vjp_contract_kernel without matrices forms the difference), and
-// jvp_contract_kernel sums the rows against the tangents on top of it.  Forward: ydd = ABA(q, qd, tau); r = dtau - d tau / d q dq -
-// d tau / d qd dqd at ydd (the same kernel, sign -1, dtau added in); dydd = ABA(q, 0, r) - ABA(q, 0, 0).  The runs of a zero-velocity pair
-// carry no gravity, as in vjp_run.  Only the stages the given tangents need are enqueued.
-template <class T>
-int jvp_run(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *dq, const T *dqd, const T *dx, double step, T *out,
-            T *ydd_out, size_t B, int device, void *stream)
-{
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    const size_t nq = p->host.nq, nv = p->host.nv, nn = nv * nv;
-    const bool need_d = dq || dqd;
-    const bool need_pair = forward || dx;  // the two launches at zero velocity
-    const bool need_ydd = forward && (need_d || ydd_out);
-    const bool need_mid = need_d && need_pair;  // forward: r; inverse: H dydd, before the rows are summed on top of it
-    // per state: the matrices of the given tangents; zeros, and the two results of the zero-velocity pair; the vector in between; ydd when
-    // the caller keeps none
-    const size_t per_state = (dq ? nn : 0) + (dqd ? nn : 0) + (need_pair ? 3 * nv : 0) + (need_mid ? nv : 0) + (need_ydd && !ydd_out ? nv : 0);
-    const Chunk c = budgeted_chunk(p, p->work_jvp, device, stream, 4096ull << 20, per_state * sizeof(T), B);
-    void *wptr = nullptr;
-    if (int rc = ensure_work(p, p->work_jvp, device, stream, c.bytes, &wptr)) return rc;
-    Carver<T> w(wptr, c.chunk * per_state);
-    auto take = [&](bool wanted, size_t per) { return wanted ? w.take(c.chunk * per) : nullptr; };
-    T *Mq = take(dq, nn), *Mqd = take(dqd, nn), *zeros = take(need_pair, nv), *r1 = take(need_pair, nv), *r0 = take(need_pair, nv);
-    T *mid = take(need_mid, nv), *ydd_slab = take(need_ydd && !ydd_out, nv);
-    assert(w.taken == w.cap);
+    ProductWork<T> w{p, forward, q, qd, x, ydd_out, step, device, stream};
+    if (int rc = w.carve(p->work_jvp, dq, dqd, dx, true, B)) return rc;
+    const size_t nv = p->host.nv;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     const int nvi = static_cast<int>(nv);
-    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
-        const T *qc = q + b0 * nq, *qdc = qd + b0 * nv, *xc = x + b0 * nv;
+    for (const auto [b0, nb] : ChunkWalk{B, w.chunk}) {
         const T *dqc = dq ? dq + b0 * nv : nullptr, *dqdc = dqd ? dqd + b0 * nv : nullptr, *dxc = dx ? dx + b0 * nv : nullptr;
-        T *ydd = ydd_out ? ydd_out + b0 * nv : ydd_slab, *oc = out + b0 * nv;
-        const JvpLaunch J = jvp_contract_launch(nvi, sizeof(T), t->n_cu, nb);
-        const VjpLaunch V = vjp_contract_launch(nvi, sizeof(T), t->n_cu, nb);
-        if (need_ydd)
-            if (int rc = run<T>(p, false, qc, qdc, xc, nullptr, ydd, nb, device, stream)) return rc;
-        if (need_d)
-            if (int rc = id_derivs<T>(p, qc, qdc, forward ? ydd : xc, step, Mq, Mqd, nb, device, stream)) return rc;
+        T *oc = out + b0 * nv;
+        const JvpLaunch J = jvp_contract_launch(nvi, sizeof(T), t.n_cu, nb);
+        const VjpLaunch V = vjp_contract_launch(nvi, sizeof(T), t.n_cu, nb);
+        if (int rc = w.ydd_stage(b0, nb)) return rc;
+        if (int rc = w.matrices_stage(b0, nb)) return rc;
         const T *rhs = dxc;  // what the pair runs on: dydd; forward: dtau, or r once the rows are taken off it
-        if (forward && need_d) {
-            if (hipError_t e = launch_jvp_contract<T>(J, Mq, Mqd, dqc, dqdc, dxc, T(-1), nvi, nb, mid, hs); e != hipSuccess)
+        if (forward && w.need_d) {
+            if (hipError_t e = launch_jvp_contract<T>(J, w.Mq, w.Mqd, dqc, dqdc, dxc, T(-1), nvi, nb, w.mid, hs); e != hipSuccess)
                 return hip_err(e, "jvp contraction launch");
-            rhs = mid;
+            rhs = w.mid;
         }
-        if (need_pair) {
-            if (hipError_t e = hipMemsetAsync(zeros, 0, nb * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-            if (int rc = run<T>(p, !forward, qc, zeros, rhs, nullptr, r1, nb, device, stream, false)) return rc;
-            if (int rc = run<T>(p, !forward, qc, zeros, zeros, nullptr, r0, nb, device, stream, false)) return rc;
+        if (int rc = w.pair_stage(b0, nb, rhs)) return rc;
+        if (w.need_pair) {
             // (out_w = r1 - r0 and nothing else: the difference of the pair as vjp_run forms it)
-            T *diff = !forward && need_d ? mid : oc;
-            if (hipError_t e = launch_vjp_contract<T>(V, nullptr, nullptr, r1, r0, T(1), nvi, nb, nullptr, nullptr, diff, hs); e != hipSuccess)
+            T *diff = !forward && w.need_d ? w.mid : oc;
+            if (hipError_t e = launch_vjp_contract<T>(V, nullptr, nullptr, w.r1, w.r0, T(1), nvi, nb, nullptr, nullptr, diff, hs); e != hipSuccess)
                 return hip_err(e, "pair difference launch");
         }
-        if (!forward && need_d)
-            if (hipError_t e = launch_jvp_contract<T>(J, Mq, Mqd, dqc, dqdc, need_pair ? mid : nullptr, T(1), nvi, nb, oc, hs); e != hipSuccess)
+        if (!forward && w.need_d)  // (mid: null without a pair)
+            if (hipError_t e = launch_jvp_contract<T>(J, w.Mq, w.Mqd, dqc, dqdc, w.mid, T(1), nvi, nb, oc, hs); e != hipSuccess)
                 return hip_err(e, "jvp contraction launch");
     }
     return GRBDA_OK;
 }
 template <class T>
 int jvp(const grbda_plan *p, bool forward, const T *q, const T *qd, const T *x, const T *dq, const T *dqd, const T *dx, double step, T *out, T *ydd_out,
-        size_t B, int device, void *stream)
+        size_t B, int device, void *stream, bool host = false)
 {
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    if (int rc = jvp_args<T>(p, q, qd, x, dq, dqd, dx, step, out, ydd_out, B)) return rc;
-    if (B == 0) return GRBDA_OK;
-    return jvp_run<T>(p, forward, q, qd, x, dq, dqd, dx, step, out, ydd_out, B, device, stream);
-}
-int jvp_host_f64(const grbda_plan *p, bool forward, const double *q, const double *qd, const double *x, const double *dq, const double *dqd,
-                 const double *dx, double step, double *out, double *ydd_out, size_t B, int device)
-{
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    if (int rc = jvp_args<double>(p, q, qd, x, dq, dqd, dx, step, out, ydd_out, B)) return rc;
-    if (B == 0) return GRBDA_OK;
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    DeviceTables *t = nullptr;
-    if (int rc0 = ensure_device(p, device, &t)) return rc0;  // `device` current before anything is allocated on it
-    HostStage st;
-    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bx = st.in(x, B * nv);
-    const double *bdq = dq ? st.in(dq, B * nv) : nullptr, *bdqd = dqd ? st.in(dqd, B * nv) : nullptr, *bdx = dx ? st.in(dx, B * nv) : nullptr;
-    double *b1 = st.out(out, B * nv), *b2 = ydd_out ? st.out(ydd_out, B * nv) : nullptr;
-    return st.run([&] { return jvp_run<double>(p, forward, bq, bqd, bx, bdq, bdqd, bdx, step, b1, b2, B, device, nullptr); });
-}
-template <class T>
-int integrate_jvp_args(const grbda_plan *p, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dydd, const T *dq_next, const T *dqd_next,
-                       size_t B, int *base)
-{
-    const void *const state[1] = {qd_next}, *const outs[2] = {dq_next, dqd_next};
-    const size_t nv = p->host.nv, width[1] = {nv};
-    return jvp_rules(p, sizeof(T), B, state, width, dq, dqd, dydd, outs, false, &dt, true, false, 0.0, base);
-}
-template <class T>
-int step_jvp_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dtau,
-                  double step, const T *dq_next, const T *dqd_next, size_t B, int *base)
-{
-    const void *const state[4] = {q, qd, tau, qd_next}, *const outs[2] = {dq_next, dqd_next};
-    const size_t nq = p->host.nq, nv = p->host.nv, width[4] = {nq, nv, nv, nv};
-    return jvp_rules(p, sizeof(T), B, state, width, dq, dqd, dtau, outs, false, &dt, true, true, step, base);
+    const auto rules = [&](int *) {
+        const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
+        return product_rules(p, {{q, bq}, {qd, bv}, {x, bv}}, {{dq, bv}, {dqd, bv}, {dx, bv}}, kNoTangent, {{out, bv}, {ydd_out, bv}}, 1, nullptr, false, dq,
+                             step, nullptr);
+    };
+    return product_entry(p, B, device, host, rules, [&](ProductArrays &a, const DeviceTables &t, int) {
+        const size_t nq = p->host.nq, nv = p->host.nv;
+        const T *bq = a.in(q, B * nq), *bqd = a.in(qd, B * nv), *bx = a.in(x, B * nv);
+        const T *bdq = a.in(dq, B * nv), *bdqd = a.in(dqd, B * nv), *bdx = a.in(dx, B * nv);
+        T *b1 = a.out(out, B * nv), *b2 = a.out(ydd_out, B * nv);
+        return a.run([&] { return jvp_run<T>(p, t, forward, bq, bqd, bx, bdq, bdqd, bdx, step, b1, b2, B, device, stream); });
+    });
 }
 template <class T>
 hipError_t integrate_jvp_launch(const DeviceTables &t, int base, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dydd, T *dq_next,
                                 T *dqd_next, int nv, size_t B, void *stream)
 {
-    // (the record of the fp64 layout, as integrate_vjp_launch takes it)
-    return launch_integrate_jvp<T>(base >= 0 ? t.clusters[1] + base : nullptr, qd_next, static_cast<T>(dt), dq, dqd, dydd, dq_next, dqd_next, nv, B,
+    return launch_integrate_jvp<T>(base_record(t, base), qd_next, static_cast<T>(dt), dq, dqd, dydd, dq_next, dqd_next, nv, B,
                                    static_cast<hipStream_t>(stream));
 }
 template <class T>
 int integrate_jvp(const grbda_plan *p, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dydd, T *dq_next, T *dqd_next, size_t B, int device,
                   void *stream)
 {
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    int base = -1;
-    if (int rc = integrate_jvp_args<T>(p, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, B, &base)) return rc;
-    if (B == 0) return GRBDA_OK;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    hipError_t e = integrate_jvp_launch<T>(*t, base, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, static_cast<int>(p->host.nv), B, stream);
-    return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate jvp launch");
+    const auto rules = [&](int *base) {
+        const size_t bv = B * p->host.nv * sizeof(T);
+        return product_rules(p, {{qd_next, bv}}, {{dq, bv}, {dqd, bv}, {dydd, bv}}, kNoTangent, {{dq_next, bv}, {dqd_next, bv}}, 2, &dt, true, false, 0.0,
+                             base);
+    };
+    return product_entry(p, B, device, false, rules, [&](ProductArrays &, const DeviceTables &t, int base) {
+        hipError_t e = integrate_jvp_launch<T>(t, base, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, static_cast<int>(p->host.nv), B, stream);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate jvp launch");
+    });
 }
 // The two stages of grbda_step_jvp_* (arguments checked, B > 0, device found): grbda_aba_jvp_* into the [B][nv] work array, then the
 // integrate kernel on it.
@@ -3577,42 +3530,28 @@ template <class T>
 int step_jvp_run(const grbda_plan *p, const DeviceTables &t, int base, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *dq,
                  const T *dqd, const T *dtau, double step, T *dq_next, T *dqd_next, size_t B, int device, void *stream)
 {
-    void *ptr = nullptr;
-    if (int rc = ensure_work(p, p->work_step_jvp, device, stream, B * p->host.nv * sizeof(T) + 256, &ptr)) return rc;
-    T *dydd = static_cast<T *>(ptr);
-    if (int rc = jvp_run<T>(p, true, q, qd, tau, dq, dqd, dtau, step, dydd, nullptr, B, device, stream)) return rc;
+    T *dydd = nullptr;
+    if (int rc = rows_slab<T>(p, p->work_step_jvp, 1, B, device, stream, &dydd)) return rc;
+    if (int rc = jvp_run<T>(p, t, true, q, qd, tau, dq, dqd, dtau, step, dydd, nullptr, B, device, stream)) return rc;
     hipError_t e = integrate_jvp_launch<T>(t, base, qd_next, dt, dq, dqd, dydd, dq_next, dqd_next, static_cast<int>(p->host.nv), B, stream);
     return e == hipSuccess ? GRBDA_OK : hip_err(e, "integrate jvp launch");
 }
 template <class T>
 int step_jvp(const grbda_plan *p, const T *q, const T *qd, const T *tau, const T *qd_next, double dt, const T *dq, const T *dqd, const T *dtau, double step,
-             T *dq_next, T *dqd_next, size_t B, int device, void *stream)
+             T *dq_next, T *dqd_next, size_t B, int device, void *stream, bool host = false)
 {
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    int base = -1;
-    if (int rc = step_jvp_args<T>(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, &base)) return rc;
-    if (B == 0) return GRBDA_OK;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;
-    return step_jvp_run<T>(p, *t, base, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, device, stream);
-}
-int step_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt, const double *dq,
-                      const double *dqd, const double *dtau, double step, double *dq_next, double *dqd_next, size_t B, int device)
-{
-    if (!p) return set_err(GRBDA_EINVAL, "null plan");
-    GRBDA_CALL_SCOPE(p);
-    int base = -1;
-    if (int rc = step_jvp_args<double>(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, &base)) return rc;
-    if (B == 0) return GRBDA_OK;
-    const size_t nq = p->host.nq, nv = p->host.nv;
-    DeviceTables *t = nullptr;
-    if (int rc = ensure_device(p, device, &t)) return rc;  // `device` current before anything is allocated on it
-    HostStage st;
-    const double *bq = st.in(q, B * nq), *bqd = st.in(qd, B * nv), *bt = st.in(tau, B * nv), *bn = st.in(qd_next, B * nv);
-    const double *bdq = dq ? st.in(dq, B * nv) : nullptr, *bdqd = dqd ? st.in(dqd, B * nv) : nullptr, *bdt = dtau ? st.in(dtau, B * nv) : nullptr;
-    double *o1 = dq_next ? st.out(dq_next, B * nv) : nullptr, *o2 = dqd_next ? st.out(dqd_next, B * nv) : nullptr;
-    return st.run([&] { return step_jvp_run<double>(p, *t, base, bq, bqd, bt, bn, dt, bdq, bdqd, bdt, step, o1, o2, B, device, nullptr); });
+    const auto rules = [&](int *base) {
+        const size_t bq = B * p->host.nq * sizeof(T), bv = B * p->host.nv * sizeof(T);
+        return product_rules(p, {{q, bq}, {qd, bv}, {tau, bv}, {qd_next, bv}}, {{dq, bv}, {dqd, bv}, {dtau, bv}}, kNoTangent,
+                             {{dq_next, bv}, {dqd_next, bv}}, 2, &dt, true, dq, step, base);
+    };
+    return product_entry(p, B, device, host, rules, [&](ProductArrays &a, const DeviceTables &t, int base) {
+        const size_t nq = p->host.nq, nv = p->host.nv;
+        const T *bq = a.in(q, B * nq), *bqd = a.in(qd, B * nv), *bt = a.in(tau, B * nv), *bn = a.in(qd_next, B * nv);
+        const T *bdq = a.in(dq, B * nv), *bdqd = a.in(dqd, B * nv), *bdt = a.in(dtau, B * nv);
+        T *o1 = a.out(dq_next, B * nv), *o2 = a.out(dqd_next, B * nv);
+        return a.run([&] { return step_jvp_run<T>(p, t, base, bq, bqd, bt, bn, dt, bdq, bdqd, bdt, step, o1, o2, B, device, stream); });
+    });
 }
 
 // the kernel of a route (choose_aba / choose_rnea) by name; the template arguments mirror the launchers' own dispatch in chain_kernels.hip
@@ -4621,7 +4560,7 @@ int grbda_rnea_vjp_f32(const grbda_plan *p, const float *q, const float *qd, con
 int grbda_rnea_vjp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, const double *g_tau, double step,
                             double *grad_q, double *grad_qd, double *grad_ydd, size_t B, int device)
 {
-    return vjp_host_f64(p, false, q, qd, ydd, g_tau, step, grad_q, grad_qd, grad_ydd, nullptr, B, device);
+    return vjp<double>(p, false, q, qd, ydd, g_tau, step, grad_q, grad_qd, grad_ydd, nullptr, B, device, nullptr, true);
 }
 int grbda_aba_vjp_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *g_ydd, double step, double *grad_q,
                       double *grad_qd, double *grad_tau, double *ydd, size_t B, int device, void *stream)
@@ -4636,7 +4575,7 @@ int grbda_aba_vjp_f32(const grbda_plan *p, const float *q, const float *qd, cons
 int grbda_aba_vjp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *g_ydd, double step,
                            double *grad_q, double *grad_qd, double *grad_tau, double *ydd, size_t B, int device)
 {
-    return vjp_host_f64(p, true, q, qd, tau, g_ydd, step, grad_q, grad_qd, grad_tau, ydd, B, device);
+    return vjp<double>(p, true, q, qd, tau, g_ydd, step, grad_q, grad_qd, grad_tau, ydd, B, device, nullptr, true);
 }
 int grbda_vjp_contract_launch(int nv, size_t nb, int n_cu, size_t *units, size_t *grid)
 {
@@ -4671,7 +4610,7 @@ int grbda_step_vjp_host_f64(const grbda_plan *p, const double *q, const double *
                             const double *g_q_next, const double *g_qd_next, double step, double *grad_q, double *grad_qd, double *grad_tau,
                             size_t B, int device)
 {
-    return step_vjp_host_f64(p, q, qd, tau, qd_next, dt, g_q_next, g_qd_next, step, grad_q, grad_qd, grad_tau, B, device);
+    return step_vjp<double>(p, q, qd, tau, qd_next, dt, g_q_next, g_qd_next, step, grad_q, grad_qd, grad_tau, B, device, nullptr, true);
 }
 int grbda_rollout_vjp_f64(const grbda_plan *p, const double *q0, const double *qd0, const double *q_traj, const double *qd_traj, const double *tau,
                           int tau_steps, double dt, int T, const double *g_q, const double *g_qd, int g_steps, double step, double *grad_q0,
@@ -4700,7 +4639,7 @@ int grbda_rnea_jvp_f32(const grbda_plan *p, const float *q, const float *qd, con
 int grbda_rnea_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *ydd, const double *dq, const double *dqd,
                             const double *dydd, double step, double *dtau_out, size_t B, int device)
 {
-    return jvp_host_f64(p, false, q, qd, ydd, dq, dqd, dydd, step, dtau_out, nullptr, B, device);
+    return jvp<double>(p, false, q, qd, ydd, dq, dqd, dydd, step, dtau_out, nullptr, B, device, nullptr, true);
 }
 int grbda_aba_jvp_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *dq, const double *dqd, const double *dtau,
                       double step, double *dydd_out, double *ydd, size_t B, int device, void *stream)
@@ -4715,7 +4654,7 @@ int grbda_aba_jvp_f32(const grbda_plan *p, const float *q, const float *qd, cons
 int grbda_aba_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *dq, const double *dqd,
                            const double *dtau, double step, double *dydd_out, double *ydd, size_t B, int device)
 {
-    return jvp_host_f64(p, true, q, qd, tau, dq, dqd, dtau, step, dydd_out, ydd, B, device);
+    return jvp<double>(p, true, q, qd, tau, dq, dqd, dtau, step, dydd_out, ydd, B, device, nullptr, true);
 }
 int grbda_integrate_jvp_f64(const grbda_plan *p, const double *qd_next, double dt, const double *dq, const double *dqd, const double *dydd,
                             double *dq_next, double *dqd_next, size_t B, int device, void *stream)
@@ -4740,7 +4679,7 @@ int grbda_step_jvp_f32(const grbda_plan *p, const float *q, const float *qd, con
 int grbda_step_jvp_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, const double *qd_next, double dt, const double *dq,
                             const double *dqd, const double *dtau, double step, double *dq_next, double *dqd_next, size_t B, int device)
 {
-    return step_jvp_host_f64(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, device);
+    return step_jvp<double>(p, q, qd, tau, qd_next, dt, dq, dqd, dtau, step, dq_next, dqd_next, B, device, nullptr, true);
 }
 int grbda_jvp_contract_launch(int nv, size_t nb, int n_cu, size_t *units, size_t *grid)
 {

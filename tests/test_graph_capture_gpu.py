@@ -103,6 +103,9 @@ def test_capture_of_a_larger_batch_is_refused(what, model, env, entry, B_warm, B
     assert node_counts(g)["kernel"] == 0  # (host-side, before any launch; the graph is never replayed)
     stream.synchronize()
     g.reset()
+    # (the refused graph goes HERE: `err` holds a traceback that holds this frame, and a graph left to the garbage collector may be
+    # destroyed inside a later capture, where its destructor's device synchronisation is an error thrown out of a destructor)
+    del g, err
     # the stream is usable again, and the small batch still captures
     cap = capture(lambda: call(plan, small), stream=stream)
     cap.drop()
@@ -127,6 +130,7 @@ def test_release_work_during_capture_is_refused(gpu):
     assert err.value.code == -1
     stream.synchronize()
     g.reset()
+    del g, err  # (as above: not left to a garbage collection inside a later capture)
     assert plan.release_work() > 0  # (the slab was kept, and goes now)
 
 
