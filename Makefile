@@ -123,3 +123,13 @@ lds-check:
 	g++ -std=c++17 -O1 -g -Wall -I include -I generalized_rbda_amd/include tests/cpp/lds_schedule_check.cpp $(CSRC)/plan.cpp \
 	    $(CSRC)/urdf.cpp -o build/lds_check/lds_schedule_check
 .PHONY: lds-check
+
+# host-side check of the chain forward dynamics' slab rule (devplan.h, chain_slab_rows) over the plans of real robots, under
+# AddressSanitizer + UBSan (host code only; tests/test_chain_slab_rule_cpu.py)
+#   make slab-check && build/slab_check/chain_slab_check tests/golden/robot-models/*.urdf
+slab-check:
+	@mkdir -p build/slab_check
+	$(HIPCC) -x hip --cuda-host-only -std=c++17 -O1 -g -Wall -Wno-unused-function -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
+	    -I include -I generalized_rbda_amd/include tests/cpp/chain_slab_check.cpp $(CSRC)/plan.cpp $(CSRC)/urdf.cpp \
+	    -fsanitize=address,undefined -o build/slab_check/chain_slab_check
+.PHONY: slab-check

@@ -1743,13 +1743,17 @@ template hipError_t launch_aba_gen1<double>(const ChainDev<double> &, int, int, 
 // MODE 1: the program has differential clusters (ChainDiff).  A kernel variant of its own, so that the models without them
 // (every URDF robot of the reference) keep the register allocation of the plain run / pair / free code.  MODE 2: the program
 // has generic clusters (ChainGen; gen_segments.h) and possibly differentials: translation unit 2.  MODE kModeInReg: the program of MODE 0
-// with the tile's inputs held in registers (ChainMemR above; launch_aba_chain decides).
-template <class T, int WPS, int MODE>
+// with the tile's inputs held in registers (ChainMemR above; launch_aba_chain decides).  DIRECT (MODE kModeInReg only; kDirectQ / kDirectQd /
+// kDirectX, devplan.h): the inputs whose rows the lanes fetch from global memory themselves instead of through LDS -- a template argument,
+// not a run-time test: the kernel sits at 243 of 256 registers, and a prologue with both paths for every array spilled two of the three
+// input vectors (132 bytes of scratch per lane).
+template <class T, int WPS, int MODE, int DIRECT = 0>
 __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, const T *__restrict__ q, const T *__restrict__ qd,
                                                              const T *__restrict__ tau, T *__restrict__ ydd, size_t B,
                                                              T *__restrict__ scratch)
 {
     constexpr bool DIFF = MODE == 1 || MODE == 2, GEN = MODE == 2, INREG = MODE == kModeInReg;
+    static_assert(INREG || DIRECT == 0, "direct row loads fill the register vectors of kModeInReg");
     ChainTables<T> P;
     P.segs = (cptr<ChainSeg>)DP.segs;
     P.links = (cptr<ChainLink>)DP.links;
@@ -1767,18 +1771,20 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
 #pragma unroll
     for (int i = 0; i < 6; i++) P.a_root[i] = DP.a_root[i];
     const int lane = threadIdx.x;
-    // wave slab: [nq + 2 nv input rows][n_glb_slots rows], 64 scalars per row
-    T *slab = scratch + (size_t)blockIdx.x * (size_t)(DP.n_glb_slots + P.nq + 2 * P.nv) * kWave;
+    // wave slab, 64 scalars per row: [nq + 2 nv input rows][n_glb_slots rows], or without the input rows when they live in registers
+    // (devplan.h, chain_slab_rows: the host sizes the slab by the same rule)
+    const ChainSlabRows rows = chain_slab_rows(INREG, P.nq, P.nv, DP.n_glb_slots, DP.out_lds);
+    T *slab = scratch + (size_t)blockIdx.x * (size_t)rows.total * kWave;
     std::conditional_t<INREG, ChainMemR<T>, ChainMem<T>> M;
     M.lane = lane;
     M.lane_b = (unsigned)lane * (unsigned)sizeof(T);
     M.gmul = 1;
     M.amask = ~0;
-    M.glb_u = slab + (size_t)(P.nq + 2 * P.nv) * kWave;
-    M.in_q_u = slab;
+    M.glb_u = slab + (size_t)rows.glb * kWave;
+    M.in_q_u = slab;  // (the input rows: read by ChainMem only)
     M.in_qd_u = slab + (size_t)P.nq * kWave;
     M.in_x_u = slab + (size_t)(P.nq + P.nv) * kWave;
-    M.out_u = slab + (size_t)(P.nq + P.nv) * kWave;
+    M.out_u = slab + (size_t)rows.out * kWave;
     M.set_out(DP.out_lds);
     M.bad = 0;
 
@@ -1786,14 +1792,21 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t left = B - tile * kWave;
         const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
-        if constexpr (INREG) stage_inputs_reg<kInRegCols>(q, qd, tau, tile, rows_valid, P.nq, P.nv, M.rq, M.rqd, M.rx, lane, DP.lds_bytes);
+        if constexpr (INREG)
+            stage_inputs_reg<kInRegCols, (DIRECT & kDirectQ) != 0, (DIRECT & kDirectQd) != 0, (DIRECT & kDirectX) != 0>(
+                q, qd, tau, tile, rows_valid, P.nq, P.nv, M.rq, M.rqd, M.rx, lane, DP.lds_bytes);
         else stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
-        if (DP.fuse & 1) {  // the floating base's velocity: from the lane's row of the staged block (still there) to its LDS slot
-            const T *mine = reinterpret_cast<const T *>(grbda_smem) + (kWave * P.nq + lane * P.nv + DP.stage_v_index);
+        if (DP.fuse & 1) {  // the floating base's velocity to its LDS slot: from the lane's row of the staged block (still there) ...
             T v[6];
+            if constexpr ((DIRECT & kDirectQd) != 0) {  // ... or, when qd was never staged, from the lane's registers (a wave-uniform index)
 #pragma unroll
-            for (int j = 0; j < 6; j++) v[j] = mine[j];
-            wave_lds_fence();
+                for (int j = 0; j < 6; j++) v[j] = M.rqd[DP.stage_v_index + j];
+            } else {
+                const T *mine = reinterpret_cast<const T *>(grbda_smem) + (kWave * P.nq + lane * P.nv + DP.stage_v_index);
+#pragma unroll
+                for (int j = 0; j < 6; j++) v[j] = mine[j];
+                wave_lds_fence();
+            }
             M.lds_st(DP.stage_lds_v, v);
         }
         for (int s = 0; s < P.n_segs; s++) {
@@ -1841,7 +1854,7 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
             }
         }
         if (M.out_row >= 0) write_outputs_lds<T>(M.out_row, ydd, tile, rows_valid, P.nv, lane);
-        else write_outputs(slab + (size_t)(P.nq + P.nv) * kWave, ydd, tile, rows_valid, P.nv, lane);
+        else write_outputs(slab + (size_t)rows.out * kWave, ydd, tile, rows_valid, P.nv, lane);
         M.flush_bad(DP.bad_count, rows_valid);
     }
 }
@@ -2459,7 +2472,15 @@ hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const
     }
     if constexpr (sizeof(T) == 4) {
         if (chain_inputs_in_registers(sizeof(T), P.n_gens, P.n_diffs, P.sv_global, P.nq, P.nv)) {
-            hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
+            // (P.direct_in: one of the sets chain_direct_inputs hands out, each an instantiation of its own)
+            if (P.direct_in == (kDirectQ | kDirectQd | kDirectX))
+                hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg, kDirectQ | kDirectQd | kDirectX>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd,
+                                   tau, ydd, B, scratch);
+            else if (P.direct_in == (kDirectQd | kDirectX))
+                hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg, kDirectQd | kDirectX>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau,
+                                   ydd, B, scratch);
+            else
+                hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
             return hipGetLastError();
         }
     }
@@ -3428,6 +3449,8 @@ hipError_t set_max_dynamic_lds_chain()
     const void *const kernels[] = {
         reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 0>), reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 1>),
         reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, kModeInReg>),
+        reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, kModeInReg, kDirectQd | kDirectX>),
+        reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, kModeInReg, kDirectQ | kDirectQd | kDirectX>),
         reinterpret_cast<const void *>(&aba_chain_kernel<double, 2, 0>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<float, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<float, 1, false>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<double, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<double, 1, false>),

@@ -498,38 +498,89 @@ __device__ __forceinline__ void stage_row_regs(int ncols, unsigned lds_byte_off,
     for (int c = 0; c < N; c++)
         if (c < ncols) r[c] = stage[lane * ncols + c];
 }
-template <int N, class T, class ROW>
+// The same row WITHOUT the LDS round trip: lane l fetches row tile * kWave + l of the row-major array from global memory with 16-byte
+// loads, straight into the register vector (rows of whole 16-byte units on a 16-byte aligned base: devplan.h, chain_direct_inputs).  The
+// tile's rows are one contiguous block, so the wave's ncols / V loads touch exactly the cache lines the staged copy touches.  A lane
+// past the batch's last row reads that last row again (no address beyond the array; its results are never written).  All N / V
+// loads are issued whatever ncols is -- those past the row's end read the row's last unit again (a hit in the line just fetched; entries
+// from ncols on are never used) -- so that nothing is masked or branched over, no entry is carried from tile to tile, and the number of
+// loads is the constant N / V: the caller's counted wait relies on it.
+template <class T, int N, class ROW>
+__device__ __forceinline__ void load_row_regs(const T *__restrict__ src, size_t tile, int rows_valid, int ncols, ROW &r, int lane)
+{
+    constexpr int V = 16 / (int)sizeof(T);
+    static_assert(N % V == 0, "whole 16-byte loads");
+    struct alignas(16) Vec { T v[V]; };
+    const int row = lane < rows_valid ? lane : rows_valid - 1;
+    const Vec *mine = reinterpret_cast<const Vec *>(src + (tile * (size_t)kWave + (size_t)row) * (size_t)ncols);
+    const int last = ncols / V - 1;
+#pragma unroll
+    for (int c = 0; c < N; c += V) {
+        const Vec x = mine[c / V < last ? c / V : last];
+#pragma unroll
+        for (int k = 0; k < V; k++) r[c + k] = x.v[k];
+    }
+}
+// s_waitcnt vmcnt(K): all but the K youngest vector-memory operations of the wave have completed
+template <int K>
+__device__ __forceinline__ void wait_all_but_youngest()
+{
+    static_assert(K >= 0 && K < 64, "six bits of vmcnt");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory");
+}
+// DQ / DQD / DX (compile-time: the kernel is instantiated per set, chain_kernels.hip): that array goes through load_row_regs instead of
+// LDS.  The staged copies are issued FIRST and the direct loads behind them: the memory counter retires in order, so "all but the direct
+// loads" is a counted wait, the staged rows are read back while the direct loads are still in flight, and the first USE of a directly
+// loaded vector waits for it (the compiler's own wait).  The staged blocks keep their LDS offsets whichever arrays go direct.  With
+// nothing direct this is the all-staged prologue, instruction for instruction.
+template <int N, bool DQ, bool DQD, bool DX, class T, class ROW>
 __device__ __forceinline__ void stage_inputs_reg(const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ x, size_t tile,
                                                  int rows_valid, int nq, int nv, ROW &rq, ROW &rqd, ROW &rx, int lane, int lds_bytes)
 {
+    constexpr int V = 16 / (int)sizeof(T), kDirectLoads = ((DQ ? 1 : 0) + (DQD ? 1 : 0) + (DX ? 1 : 0)) * (N / V);
     const unsigned bq = (unsigned)(kWave * nq) * (unsigned)sizeof(T), bv = (unsigned)(kWave * nv) * (unsigned)sizeof(T);
     if ((int)(bq + 2 * bv) <= lds_bytes) {
-        stage_issue(q, tile, rows_valid, nq, 0u, lane);
-        stage_issue(qd, tile, rows_valid, nv, bq, lane);
-        stage_issue(x, tile, rows_valid, nv, bq + bv, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (!DQ) stage_issue(q, tile, rows_valid, nq, 0u, lane);
+        if constexpr (!DQD) stage_issue(qd, tile, rows_valid, nv, bq, lane);
+        if constexpr (!DX) stage_issue(x, tile, rows_valid, nv, bq + bv, lane);
+        if constexpr (kDirectLoads > 0) asm volatile("" ::: "memory");  // (the direct loads stay behind the copies)
+        if constexpr (DQ) load_row_regs<T, N>(q, tile, rows_valid, nq, rq, lane);
+        if constexpr (DQD) load_row_regs<T, N>(qd, tile, rows_valid, nv, rqd, lane);
+        if constexpr (DQD && DX) asm volatile("" ::: "memory");  // (program order qd, then x: qd is used first)
+        if constexpr (DX) load_row_regs<T, N>(x, tile, rows_valid, nv, rx, lane);
+        if constexpr (DQ && DQD && DX) return;  // (nothing staged, LDS untouched)
+        wait_all_but_youngest<kDirectLoads>();
         wave_lds_fence();
-        stage_row_regs<T, N>(nq, 0u, rq, lane);
-        stage_row_regs<T, N>(nv, bq, rqd, lane);
-        stage_row_regs<T, N>(nv, bq + bv, rx, lane);
+        if constexpr (!DQ) stage_row_regs<T, N>(nq, 0u, rq, lane);
+        if constexpr (!DQD) stage_row_regs<T, N>(nv, bq, rqd, lane);
+        if constexpr (!DX) stage_row_regs<T, N>(nv, bq + bv, rx, lane);
         wave_lds_fence();
     } else {
-        // LDS too small for the whole tile: one array at a time (see stage_inputs)
-        stage_issue(q, tile, rows_valid, nq, 0u, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_lds_fence();
-        stage_row_regs<T, N>(nq, 0u, rq, lane);
-        wave_lds_fence();
-        stage_issue(qd, tile, rows_valid, nv, 0u, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_lds_fence();
-        stage_row_regs<T, N>(nv, 0u, rqd, lane);
-        wave_lds_fence();
-        stage_issue(x, tile, rows_valid, nv, 0u, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_lds_fence();
-        stage_row_regs<T, N>(nv, 0u, rx, lane);
-        wave_lds_fence();
+        // LDS too small for the whole tile: one array at a time (see stage_inputs); these waits drain the direct loads as well
+        if constexpr (DQ) load_row_regs<T, N>(q, tile, rows_valid, nq, rq, lane);
+        if constexpr (DQD) load_row_regs<T, N>(qd, tile, rows_valid, nv, rqd, lane);
+        if constexpr (DX) load_row_regs<T, N>(x, tile, rows_valid, nv, rx, lane);
+        if constexpr (!DQ) {
+            stage_issue(q, tile, rows_valid, nq, 0u, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wave_lds_fence();
+            stage_row_regs<T, N>(nq, 0u, rq, lane);
+            wave_lds_fence();
+        }
+        if constexpr (!DQD) {
+            stage_issue(qd, tile, rows_valid, nv, 0u, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wave_lds_fence();
+            stage_row_regs<T, N>(nv, 0u, rqd, lane);
+            wave_lds_fence();
+        }
+        if constexpr (!DX) {
+            stage_issue(x, tile, rows_valid, nv, 0u, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wave_lds_fence();
+            stage_row_regs<T, N>(nv, 0u, rx, lane);
+            wave_lds_fence();
+        }
     }
 }
 

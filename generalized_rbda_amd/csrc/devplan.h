@@ -94,7 +94,9 @@ struct ChainDev {
     int n_glb_slots;
     int lds_bytes;
     int ori_repr;
-    int debug;   // unused (kept so that the argument layout does not move); the host writes 0
+    // aba_chain_kernel<float, 2, kModeInReg> only: kDirectQ / kDirectQd / kDirectX -- the lanes fetch their own rows of that input from
+    // global memory with 16-byte loads instead of the LDS staging (chain_direct_inputs below; every other launch: 0)
+    int direct_in;
     int sv_global;  // ChainProgram::sv_global
     int out_lds;    // ChainProgram::out_lds
     // aba_chain_kernel only (capi.cpp, run_chain): bit 0 -- the program starts with the floating base's forward segment, whose whole work is
@@ -114,6 +116,32 @@ constexpr int kModeInReg = 3;
 inline bool chain_inputs_in_registers(size_t elem, int n_gens, int n_diffs, int sv_global, int nq, int nv)
 {
     return elem == 4 && n_gens == 0 && n_diffs == 0 && !sv_global && nq <= kInRegCols && nv <= kInRegCols;
+}
+// Which inputs of that kernel skip the LDS staging (ChainDev::direct_in; devmath.h, stage_inputs_reg): every lane fetches its own row with
+// 16-byte loads, which takes rows of whole 16-byte units on a 16-byte aligned base.  Decided once per launch, on the host.  The kernel is
+// instantiated per set, so only three sets are handed out: all three inputs, qd and tau (they share nv; q is read first and stays staged),
+// or none.
+constexpr int kDirectQ = 1, kDirectQd = 2, kDirectX = 4;
+inline int chain_direct_inputs(size_t elem, int nq, int nv, const void *q, const void *qd, const void *x)
+{
+    const auto direct = [elem](int ncols, const void *base) {
+        return (static_cast<size_t>(ncols) * elem) % 16 == 0 && reinterpret_cast<uintptr_t>(base) % 16 == 0;
+    };
+    if (!direct(nv, qd) || !direct(nv, x)) return 0;
+    return kDirectQd | kDirectX | (direct(nq, q) ? kDirectQ : 0);
+}
+// The rows (of kWave scalars) of a wavefront's slab in a launch of aba_chain_kernel -- ONE rule, read by the kernel for its pointers and by
+// the host for the allocation (capi.cpp, run_chain).  Staged inputs: [q: nq][qd: nv][tau: nv, the result rows once tau is dead][global
+// slots].  Inputs in registers: no input rows -- [global slots][result rows: nv, only when the plan keeps no result rows in LDS].
+struct ChainSlabRows {
+    int glb;    // first row of the global slots
+    int out;    // first of the result rows (out_lds < 0)
+    int total;  // rows per wavefront
+};
+__host__ __device__ inline ChainSlabRows chain_slab_rows(bool in_registers, int nq, int nv, int n_glb_slots, int out_lds)
+{
+    if (!in_registers) return {nq + 2 * nv, nq + nv, nq + 2 * nv + n_glb_slots};
+    return {0, out_lds < 0 ? n_glb_slots : 0, n_glb_slots + (out_lds < 0 ? nv : 0)};
 }
 template <class T>
 hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const T *tau, T *ydd, size_t B, T *scratch, int grid,
