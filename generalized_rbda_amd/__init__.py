@@ -11,7 +11,8 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import BODIES_SIGNATURES, JACOBIAN_SIGNATURES, JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES, VJP_SIGNATURES, WRENCH_SIGNATURES
+from ._abi import (BODIES_SIGNATURES, JACOBIAN_PRODUCT_SIGNATURES, JACOBIAN_SIGNATURES, JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES,
+                   VJP_SIGNATURES, WRENCH_SIGNATURES)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GRBDA_HIP_LIB: another build of the same library (for example the parent commit's); development A/B runs only
@@ -63,9 +64,9 @@ def lib() -> ctypes.CDLL:
         fn.restype, fn.argtypes = restype, list(argtypes)
     # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
     # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule; then grbda_hip_wrench.h, grbda_hip_jvp.h and
-    # grbda_hip_bodies.h, and last grbda_hip_jacobians.h
+    # grbda_hip_bodies.h, grbda_hip_jacobians.h, and last grbda_hip_jacobian_products.h
     for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES, **JVP_SIGNATURES, **BODIES_SIGNATURES,
-                                      **JACOBIAN_SIGNATURES}.items():
+                                      **JACOBIAN_SIGNATURES, **JACOBIAN_PRODUCT_SIGNATURES}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
@@ -414,6 +415,52 @@ class _JacobianMethods:
         return (J, d) if drift else J
 
 
+class _JacobianProductMethods:
+    """J v and J^T f with the frame Jacobians of a listed few body frames, J never formed (include/grbda_hip_jacobian_products.h), kept
+    apart like _JacobianMethods, whose frames (bodies, offsets, frame) these are: J is the J of frame_jacobians for the same arguments."""
+
+    def frame_jacobian_products(self, q, bodies, v=None, f=None, offsets=None, frame="body", stream=None):
+        """(Jv, JTf) (grbda_frame_jacobian_products_*): Jv[B, n, 6] = J v for v[B, nv], each frame [angular 3; linear 3], and JTf[B, nv] =
+        sum over the frames of J_i^T f[:, i] for f[B, n, 6], per frame [moment 3; force 3] in the frame of J.  v or f may be None, not both;
+        the product of the one left out is None and its work is skipped."""
+        n, arr, off, fr = self._frames(bodies, offsets, frame)
+        if v is None and f is None:
+            raise ValueError("v and f cannot both be None")
+        ins = dict(self._state(q), v=(v, self.nv), f=(f, (n, 6)))
+        outs = dict(Jv=None if v is None else (n, 6), JTf=None if f is None else self.nv)
+        return self._call("frame_jacobian_products", stream, ins, outs, ("q", "v", "f", n, arr, off, fr, "Jv", "JTf"))
+
+    def frame_jv(self, q, v, bodies, offsets=None, frame="body", stream=None):
+        """Jv[B, n, 6] alone: the frames' velocities for the joint-space direction v."""
+        if v is None:
+            raise ValueError("v cannot be None")
+        return self.frame_jacobian_products(q, bodies, v=v, offsets=offsets, frame=frame, stream=stream)[0]
+
+    def frame_jtf(self, q, f, bodies, offsets=None, frame="body", stream=None):
+        """JTf[B, nv] alone: the joint torques of the frames' wrenches f."""
+        if f is None:
+            raise ValueError("f cannot be None")
+        return self.frame_jacobian_products(q, bodies, f=f, offsets=offsets, frame=frame, stream=stream)[1]
+
+    def frame_jacobian_products_host(self, q, bodies, v=None, f=None, offsets=None, frame="body", device: int = 0):
+        import numpy as np
+
+        n, arr, off, fr = self._frames(bodies, offsets, frame)
+        if v is None and f is None:
+            raise ValueError("v and f cannot both be None")
+        q = np.ascontiguousarray(q, dtype="float64")
+        B = q.shape[0]
+        v = None if v is None else np.ascontiguousarray(v, dtype="float64")
+        f = None if f is None else np.ascontiguousarray(f, dtype="float64")
+        if (v is not None and v.shape != (B, self.nv)) or (f is not None and f.shape != (B, n, 6)):
+            raise ValueError(f"expected v[{B},{self.nv}], f[{B},{n},6]")
+        Jv = None if v is None else np.empty((B, n, 6))
+        JTf = None if f is None else np.empty((B, self.nv))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(lib().grbda_frame_jacobian_products_host_f64(self._h, q.ctypes.data, ptr(v), ptr(f), n, arr, off, fr, ptr(Jv), ptr(JTf), B, device))
+        return Jv, JTf
+
+
 class _JvpMethods:
     """The Jacobian-vector products of Plan (include/grbda_hip_jvp.h), kept apart like _VjpMethods.  Every tangent is [B, nv]; a position
     tangent lies along the tangent step of fd_dq, the coordinates of the "q" gradients of id_vjp / fd_vjp / step_vjp, so that
@@ -461,7 +508,7 @@ class _JvpMethods:
                           ("q", "qd", "tau", "qd_next", float(dt), "dq", "dqd", "dtau", float(step), "dq_next", "dqd_next"), skip_empty=True)
 
 
-class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _BodyListMethods, _JacobianMethods, _JvpMethods):
+class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _BodyListMethods, _JacobianMethods, _JacobianProductMethods, _JvpMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):

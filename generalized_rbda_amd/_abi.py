@@ -154,3 +154,13 @@ JACOBIAN_SIGNATURES = {
     "grbda_frame_jacobians_route": (P, I, BODIES, POINTER(c_int), POINTER(c_int), POINTER(c_int)),  # n bodies route walk_len max_saved
 }
 JACOBIAN_SIGNATURES = {name: (c_int, args) for name, args in JACOBIAN_SIGNATURES.items()}
+
+# include/grbda_hip_jacobian_products.h, J v and J^T f at a listed few body frames: a table of its own, applied by `lib()` after the others;
+# tests/test_jacobian_products_args_cpu.py holds it to that header
+_JACOBIAN_PRODUCT_PAIR = (P, P, P, P, I, BODIES, OFFSETS, I, P, P, *TAIL)  # q v f n bodies offsets frame Jv JTf
+JACOBIAN_PRODUCT_SIGNATURES = {
+    "grbda_frame_jacobian_products_f64": _JACOBIAN_PRODUCT_PAIR,
+    "grbda_frame_jacobian_products_f32": _JACOBIAN_PRODUCT_PAIR,
+    "grbda_frame_jacobian_products_host_f64": _JACOBIAN_PRODUCT_PAIR[:-1],
+}
+JACOBIAN_PRODUCT_SIGNATURES = {name: (c_int, args) for name, args in JACOBIAN_PRODUCT_SIGNATURES.items()}

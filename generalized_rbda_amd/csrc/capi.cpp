@@ -20,6 +20,7 @@
 #include "../../include/grbda_hip_wrench.h"
 #include "../../include/grbda_hip_bodies.h"
 #include "../../include/grbda_hip_jacobians.h"
+#include "../../include/grbda_hip_jacobian_products.h"
 #include "../../include/grbda_model_desc.h"
 #include "devplan.h"
 
@@ -1622,6 +1623,44 @@ int frame_jacobians_args(const grbda_plan *p, const T *q, const T *qd, int n, co
     const size_t out_bytes[2] = {B * static_cast<size_t>(n) * 6 * nv * sizeof(T), B * static_cast<size_t>(n) * 6 * sizeof(T)};
     return no_overlap(in, in_bytes, outs, out_bytes);
 }
+// Route 1 of J over nb states, the stage grbda_frame_jacobians_* and the route-1 J^T f share: the expanded batch (nv rows per state: q, the
+// unit velocities, zero accelerations) through body_list_stage and the finishing kernel.  lt: list_work of the listed twists; the stage
+// takes jacobian_columns_work() elements per state from w.  Xa: the listed poses, read for world frames only.
+size_t jacobian_columns_work(size_t nq, size_t nv, const ListWork &lt) { return nv * (nq + 2 * nv + lt.per_state()); }
+template <class T>
+int jacobian_columns_stage(const grbda_plan *p, const DeviceTables &t, const BodyWalkHost &H, const FrameSet<T> &F, const ListWork &lt, Carver<T> &w,
+                           const T *qc, const T *Xa, size_t nb, T *J, int device, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const size_t nq = p->host.nq, nv = p->host.nv, rows = nb * nv;
+    T *q_x = w.take(rows * nq), *qd_x = w.take(rows * nv), *z_x = w.take(rows * nv);
+    const auto m = lt.take(w, rows);
+    hipLaunchKernelGGL((unit_velocity_rows_kernel<T>), dim3(blocks_for(rows * (nq + nv))), dim3(256), 0, hs, qc, static_cast<int>(nq),
+                       static_cast<int>(nv), nb, q_x, qd_x);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_err(e, "unit velocity rows launch");
+    if (hipError_t e = hipMemsetAsync(z_x, 0, rows * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    if (int rc = body_list_stage<T>(p, t, H, true, q_x, qd_x, z_x, m.out, m.full, m.vs, m.as, rows, device, stream)) return rc;
+    if (hipError_t e = launch_frame_jacobian_columns<T>(F, m.out, Xa, static_cast<int>(nv), nb, J, hs); e != hipSuccess)
+        return hip_err(e, "frame Jacobian columns launch");
+    return GRBDA_OK;
+}
+// the frames as the finishing kernels of route 1 take them: the offsets in the reference's body axes, the column masks of the walk builder
+template <class T>
+FrameSet<T> frame_set(const JacWalkHost &JH, int n, const double *offsets, int frame)
+{
+    FrameSet<T> F{};
+    F.n = n;
+    F.world = frame == GRBDA_WRENCH_WORLD;
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) F.off[i][k] = offsets ? static_cast<T>(offsets[3 * i + k]) : T(0);
+    std::memcpy(F.cols, JH.cols, sizeof(F.cols));
+    return F;
+}
+// the launch shape of the walk kernels of this family: one-wavefront workgroups, as many per CU as `lds` bytes each allow, at most eight
+int jac_walk_grid(const DeviceTables &t, size_t lds, size_t nb)
+{
+    return static_cast<int>(tile_grid(t.n_cu, std::min<size_t>(8, lds_workgroups_per_cu(lds)), nb));
+}
 // Route 0: the walk kernel writes J.  Route 1: per chunk the expanded batch (nv rows per state: q, the unit velocities, zero accelerations)
 // through body_list_stage and the finishing kernel.  The drift, on both routes: the listed twists at (q, qd, 0) with a zero root
 // acceleration, and the finishing kernel.  World frames read the listed poses (body_list_stage) in both finishing kernels.
@@ -1639,23 +1678,18 @@ int frame_jacobians_run(const grbda_plan *p, const T *q, const T *qd, int n, con
     const Layout &L = layout_of(p->host, sizeof(T) == 4 ? 0 : 1);
     const JacWalkHost JH = build_jac_walk(p->host, L, n, bodies);
     const BodyWalkHost H = build_body_walk(p->host, L, n, bodies);
-    FrameSet<T> F{};
-    F.n = n;
-    F.world = frame == GRBDA_WRENCH_WORLD;
-    for (int i = 0; i < n; i++)
-        for (int k = 0; k < 3; k++) F.off[i][k] = offsets ? static_cast<T>(offsets[3 * i + k]) : T(0);
-    std::memcpy(F.cols, JH.cols, sizeof(F.cols));
+    const FrameSet<T> F = frame_set<T>(JH, n, offsets, frame);
     const bool walk = J && JH.route == 0, columns = J && JH.route == 1, poses = F.world && (columns || drift);
     const size_t nq = p->host.nq, nv = p->host.nv, jn = static_cast<size_t>(n) * 6 * nv;
     const ListWork lp = list_work(p, H, false, n), lt = list_work(p, H, true, n);  // the listed poses; the listed twists
     const auto launch_walk = [&](size_t b0, size_t nb) {
         const JacWalk<T> W = device_jac_walk<T>(p, *t, JH, offsets, frame);
         const size_t lds = static_cast<size_t>(JH.max_saved + n) * 12 * kWave * sizeof(T);
-        const int grid = static_cast<int>(tile_grid(t->n_cu, std::min<size_t>(8, lds_workgroups_per_cu(lds)), nb));
+        const int grid = jac_walk_grid(*t, lds, nb);
         hipError_t e = launch_frame_jacobian_walk<T>(W, q + b0 * nq, J + b0 * jn, nb, grid, hs);
         return e == hipSuccess ? GRBDA_OK : hip_err(e, "frame Jacobian walk launch");
     };
-    const size_t per_state = (poses ? lp.per_state() : 0) + (columns ? nv * (nq + 2 * nv + lt.per_state()) : 0) + (drift ? nv + lt.per_state() : 0);
+    const size_t per_state = (poses ? lp.per_state() : 0) + (columns ? jacobian_columns_work(nq, nv, lt) : 0) + (drift ? nv + lt.per_state() : 0);
     if (per_state == 0) return launch_walk(0, B);
     const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
     void *wptr = nullptr;
@@ -1671,18 +1705,8 @@ int frame_jacobians_run(const grbda_plan *p, const T *q, const T *qd, int n, con
         }
         if (walk)
             if (int rc = launch_walk(b0, nb)) return rc;
-        if (columns) {
-            const size_t rows = nb * nv;
-            T *q_x = w.take(rows * nq), *qd_x = w.take(rows * nv), *z_x = w.take(rows * nv);
-            const auto m = lt.take(w, rows);
-            hipLaunchKernelGGL((unit_velocity_rows_kernel<T>), dim3(blocks_for(rows * (nq + nv))), dim3(256), 0, hs, qc, static_cast<int>(nq),
-                               static_cast<int>(nv), nb, q_x, qd_x);
-            if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_err(e, "unit velocity rows launch");
-            if (hipError_t e = hipMemsetAsync(z_x, 0, rows * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
-            if (int rc = body_list_stage<T>(p, *t, H, true, q_x, qd_x, z_x, m.out, m.full, m.vs, m.as, rows, device, stream)) return rc;
-            if (hipError_t e = launch_frame_jacobian_columns<T>(F, m.out, Xa, static_cast<int>(nv), nb, J + b0 * jn, hs); e != hipSuccess)
-                return hip_err(e, "frame Jacobian columns launch");
-        }
+        if (columns)
+            if (int rc = jacobian_columns_stage<T>(p, *t, H, F, lt, w, qc, Xa, nb, J + b0 * jn, device, stream)) return rc;
         if (drift) {
             T *z = w.take(nb * nv);
             const auto m = lt.take(w, nb);
@@ -1708,6 +1732,95 @@ int frame_jacobians_host_f64(const grbda_plan *p, const double *q, const double 
     const double *dq = st.in(q, B * nq), *dqd = drift ? st.in(qd, B * nv) : nullptr;
     double *dJ = J ? st.out(J, B * static_cast<size_t>(n) * 6 * nv) : nullptr, *dd = drift ? st.out(drift, B * static_cast<size_t>(n) * 6) : nullptr;
     return st.run([&] { return frame_jacobians_run<double>(p, dq, dqd, n, bodies, offsets, frame, dJ, dd, B, device, nullptr); });
+}
+
+// ---- J v and J^T f at a listed few body frames (include/grbda_hip_jacobian_products.h; frame_product_kernels.hip) -------------------
+// Everything the entry points refuse, on the host and before any device call
+template <class T>
+int frame_products_args(const grbda_plan *p, const T *q, const T *v, const T *f, int n, const int *bodies, int frame, const T *Jv, const T *JTf,
+                        size_t B)
+{
+    if (!q) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = body_list_check(p, n, bodies, bodies)) return rc;
+    if (frame != GRBDA_WRENCH_BODY && frame != GRBDA_WRENCH_WORLD) return set_err(GRBDA_EINVAL, "frame must be GRBDA_WRENCH_BODY or GRBDA_WRENCH_WORLD");
+    if (n > 0 && !Jv && !JTf) return set_err(GRBDA_EINVAL, "no output asked for: Jv and JTf are both null");
+    if (n > 0 && !Jv != !v) return set_err(GRBDA_EINVAL, Jv ? "Jv needs v" : "v is given without Jv");
+    if (n > 0 && !JTf != !f) return set_err(GRBDA_EINVAL, JTf ? "JTf needs f" : "f is given without JTf");
+    const size_t nv = p->host.nv, n6 = static_cast<size_t>(n) * 6;
+    const void *const in[3] = {q, n > 0 ? v : nullptr, n > 0 ? f : nullptr}, *const outs[2] = {n > 0 ? Jv : nullptr, n > 0 ? JTf : nullptr};
+    const size_t in_bytes[3] = {B * static_cast<size_t>(p->host.nq) * sizeof(T), B * nv * sizeof(T), B * n6 * sizeof(T)};
+    const size_t out_bytes[2] = {B * n6 * sizeof(T), B * nv * sizeof(T)};
+    return no_overlap(in, in_bytes, outs, out_bytes);
+}
+// The route is the one of frame_jacobians_run for the list (build_jac_walk).  Route 0: one walk kernel, no work memory.  Route 1, per
+// chunk of the work slab: the listed poses for world frames; J v from the listed twists at (q, v, 0) with a zero root acceleration -- one
+// row per state -- and the finishing kernel; J^T f from the chunk's J by jacobian_columns_stage and the contraction kernel.
+template <class T>
+int frame_products_run(const grbda_plan *p, const T *q, const T *v, const T *f, int n, const int *bodies, const double *offsets, int frame, T *Jv,
+                       T *JTf, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = frame_products_args<T>(p, q, v, f, n, bodies, frame, Jv, JTf, B)) return rc;
+    if (n == 0 || B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const Layout &L = layout_of(p->host, sizeof(T) == 4 ? 0 : 1);
+    const JacWalkHost JH = build_jac_walk(p->host, L, n, bodies);
+    const size_t nq = p->host.nq, nv = p->host.nv, n6 = static_cast<size_t>(n) * 6, jn = n6 * nv;
+    if (JH.route == 0) {
+        const JacWalk<T> W = device_jac_walk<T>(p, *t, JH, offsets, frame);
+        const size_t lds = static_cast<size_t>(18 * JH.max_saved + 6 * n) * kWave * sizeof(T);
+        hipError_t e = launch_frame_product_walk<T>(W, q, v, f, Jv, JTf, B, jac_walk_grid(*t, lds, B), hs);
+        return e == hipSuccess ? GRBDA_OK : hip_err(e, "frame product walk launch");
+    }
+    const BodyWalkHost H = build_body_walk(p->host, L, n, bodies);
+    const FrameSet<T> F = frame_set<T>(JH, n, offsets, frame);
+    const ListWork lp = list_work(p, H, false, n), lt = list_work(p, H, true, n);  // the listed poses; the listed twists
+    const size_t per_state = (F.world ? lp.per_state() : 0) + (Jv ? nv + lt.per_state() : 0) + (JTf ? jn + jacobian_columns_work(nq, nv, lt) : 0);
+    const Chunk c = budgeted_chunk(p, p->work, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    void *wptr = nullptr;
+    if (int rc = ensure_work(p, p->work, device, stream, c.bytes, &wptr)) return rc;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        const T *qc = q + b0 * nq;
+        T *Xa = nullptr;
+        if (F.world) {
+            const auto m = lp.take(w, nb);
+            Xa = m.out;
+            if (int rc = body_list_stage<T>(p, *t, H, false, qc, nullptr, nullptr, Xa, m.full, m.vs, m.as, nb, device, stream)) return rc;
+        }
+        if (Jv) {
+            T *z = w.take(nb * nv);
+            const auto m = lt.take(w, nb);
+            if (hipError_t e = hipMemsetAsync(z, 0, nb * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+            if (int rc = body_list_stage<T>(p, *t, H, true, qc, v + b0 * nv, z, m.out, m.full, m.vs, m.as, nb, device, stream, false)) return rc;
+            if (hipError_t e = launch_frame_jv<T>(F, m.out, Xa, nb, Jv + b0 * n6, hs); e != hipSuccess) return hip_err(e, "frame Jv launch");
+        }
+        if (JTf) {
+            T *J = w.take(nb * jn);
+            if (int rc = jacobian_columns_stage<T>(p, *t, H, F, lt, w, qc, Xa, nb, J, device, stream)) return rc;
+            if (hipError_t e = launch_frame_jtf<T>(J, f + b0 * n6, n, static_cast<int>(nv), nb, JTf + b0 * nv, hs); e != hipSuccess)
+                return hip_err(e, "frame JTf launch");
+        }
+    }
+    return GRBDA_OK;
+}
+int frame_products_host_f64(const grbda_plan *p, const double *q, const double *v, const double *f, int n, const int *bodies, const double *offsets,
+                            int frame, double *Jv, double *JTf, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (int rc = frame_products_args<double>(p, q, v, f, n, bodies, frame, Jv, JTf, B)) return rc;
+    if (n == 0 || B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, n6 = static_cast<size_t>(n) * 6;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dv = Jv ? st.in(v, B * nv) : nullptr, *df = JTf ? st.in(f, B * n6) : nullptr;
+    double *dJv = Jv ? st.out(Jv, B * n6) : nullptr, *dJTf = JTf ? st.out(JTf, B * nv) : nullptr;
+    return st.run([&] { return frame_products_run<double>(p, dq, dv, df, n, bodies, offsets, frame, dJv, dJTf, B, device, nullptr); });
 }
 
 // ---- inverse operational-space inertia of a set of contact frames (include/grbda_hip.h) -----------------------
@@ -4277,6 +4390,21 @@ int grbda_frame_jacobians_route(const grbda_plan *p, int n, const int *bodies, i
     if (walk_len) *walk_len = H.walk_len;
     if (max_saved) *max_saved = H.max_saved;
     return GRBDA_OK;
+}
+int grbda_frame_jacobian_products_f64(const grbda_plan *p, const double *q, const double *v, const double *f, int n, const int *bodies,
+                                      const double *offsets, int frame, double *Jv, double *JTf, size_t B, int device, void *stream)
+{
+    return frame_products_run<double>(p, q, v, f, n, bodies, offsets, frame, Jv, JTf, B, device, stream);
+}
+int grbda_frame_jacobian_products_f32(const grbda_plan *p, const float *q, const float *v, const float *f, int n, const int *bodies,
+                                      const double *offsets, int frame, float *Jv, float *JTf, size_t B, int device, void *stream)
+{
+    return frame_products_run<float>(p, q, v, f, n, bodies, offsets, frame, Jv, JTf, B, device, stream);
+}
+int grbda_frame_jacobian_products_host_f64(const grbda_plan *p, const double *q, const double *v, const double *f, int n, const int *bodies,
+                                           const double *offsets, int frame, double *Jv, double *JTf, size_t B, int device)
+{
+    return frame_products_host_f64(p, q, v, f, n, bodies, offsets, frame, Jv, JTf, B, device);
 }
 int grbda_body_poses_f64(const grbda_plan *p, const double *q, double *Xa, size_t B, int device, void *stream)
 {

@@ -270,6 +270,18 @@ hipError_t launch_frame_jacobian_columns(const FrameSet<T> &F, const T *Vx, cons
 template <class T>
 hipError_t launch_frame_drift(const FrameSet<T> &F, const T *V, const T *Xa, size_t nb, T *drift, hipStream_t stream);
 
+// The products with those Jacobians, J never formed (include/grbda_hip_jacobian_products.h; frame_product_kernels.hip).  Route 0: the
+// walk of JacWalk again; v[nb][nv] -> Jv[nb][n][6], f[nb][n][6] -> JTf[nb][nv], every entry written; either pair may be null.  Its LDS is
+// (18 n_saved + 6 n_list) rows of kWave lanes, never more than the (n_saved + n_list) x 12 of the Jacobian walk: n_saved < n_list.
+template <class T>
+hipError_t launch_frame_product_walk(const JacWalk<T> &W, const T *q, const T *v, const T *f, T *Jv, T *JTf, size_t nb, int grid, hipStream_t stream);
+// route 1: V[nb][n][12], the listed twists at (q, v, 0); Xa as above -> Jv[nb][n][6]
+template <class T>
+hipError_t launch_frame_jv(const FrameSet<T> &F, const T *V, const T *Xa, size_t nb, T *Jv, hipStream_t stream);
+// route 1: J[nb][n][6][nv], f[nb][n][6] -> JTf[nb][nv]
+template <class T>
+hipError_t launch_frame_jtf(const T *J, const T *f, int n, int nv, size_t nb, T *JTf, hipStream_t stream);
+
 // single-cluster programs (RneaChainProgram::single_gen; chain_kernels.hip, rnea_gen1_kernel): P.lds_bytes = the work area, lds_bytes =
 // work area + nq + 2 nv rows of staged inputs
 template <class T>

@@ -1,5 +1,5 @@
 // walk.h -- the ancestor walk of a listed few bodies: the step records the walk kernels read (body_list_kernels.hip,
-// frame_jacobian_kernels.hip, through walk_dev.h) and the host builders of walk.cpp.  Plain C++: built with g++ like plan.cpp, so that the
+// frame_jacobian_kernels.hip, frame_product_kernels.hip, through walk_dev.h) and the host builders of walk.cpp.  Plain C++: built with g++ like plan.cpp, so that the
 // sanitizer driver (tools/asan_driver.cpp) reaches the builders; devplan.h includes this header for the kernels and capi.cpp.
 //
 // A WALK is the union of the listed bodies' ancestors, each body once, depth first from the roots.  capi.cpp builds it per call from the

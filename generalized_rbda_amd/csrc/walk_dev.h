@@ -1,4 +1,4 @@
-// walk_dev.h -- the device side of an ancestor walk (walk.h), shared by the walk kernels (body_list_kernels.hip, frame_jacobian_kernels.hip):
+// walk_dev.h -- the device side of an ancestor walk (walk.h), shared by the walk kernels (body_list_kernels.hip, frame_jacobian_kernels.hip, frame_product_kernels.hip):
 // the saved values' LDS slots, the joint angle of a step and the pose step.  A step record is wave-uniform -- it sits in the kernel
 // arguments and is read through the scalar unit -- so every branch on it is a scalar branch, and nothing here indexes a per-lane array at
 // run time.  Included inside namespace grbda_hip, after devmath.h.
@@ -18,6 +18,22 @@ __device__ __forceinline__ void slot_get(int slot, int lane, T (&x)[12])
     const T *p = reinterpret_cast<const T *>(grbda_smem) + slot * 12 * kWave + lane;
 #pragma unroll
     for (int k = 0; k < 12; k++) x[k] = p[k * kWave];
+}
+// six values in the LDS rows [row, row + 6) of kWave lanes each (a slot of 12 is rows [12 slot, 12 slot + 12)): what the product walk
+// (frame_product_kernels.hip) keeps next to the saved poses -- a branch point's running twist, a frame's world wrench
+template <class T>
+__device__ __forceinline__ void rows6_put(int row, int lane, const T (&x)[6])
+{
+    T *p = reinterpret_cast<T *>(grbda_smem) + row * kWave + lane;
+#pragma unroll
+    for (int k = 0; k < 6; k++) p[k * kWave] = x[k];
+}
+template <class T>
+__device__ __forceinline__ void rows6_get(int row, int lane, T (&x)[6])
+{
+    const T *p = reinterpret_cast<const T *>(grbda_smem) + row * kWave + lane;
+#pragma unroll
+    for (int k = 0; k < 6; k++) x[k] = p[k * kWave];
 }
 // the spanning joint angle of the step's body: its G row times the cluster's n positions; n == 0: q[q_col] itself (BodyWalkStep::n)
 template <class T, class Step>
