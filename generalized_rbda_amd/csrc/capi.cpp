@@ -460,7 +460,7 @@ template <class T>
 ChainDev<T> chain_dev(const grbda_plan *p, const DeviceTables &t, ChainSlot slot)
 {
     const ChainProgram &cp = p->host.chain[slot];
-    ChainDev<T> d{};  // (direct_in, fuse, stage_*: 0)
+    ChainDev<T> d{};  // (fuse, stage_*: 0)
     fill_chain_tables(d, cp, t.chain[slot]);
     fill_chain_model<T>(d, p->host, t);
     d.sv_global = cp.sv_global ? 1 : 0;
@@ -725,9 +725,8 @@ int run_chain(const grbda_plan *p, const DeviceTables &t, const Route &r, const 
             d.fuse |= 2;
     }
     d.lds_bytes = static_cast<int>(s.lds_bytes);
-    // (the launch that keeps the inputs in registers -- launch_aba_chain reads the same rule: which of them the lanes fetch themselves)
+    // (the launch that keeps the inputs in registers -- launch_aba_chain reads the same rule)
     const bool inreg = !wrenches && chain_inputs_in_registers(sizeof(T), d.n_gens, d.n_diffs, d.sv_global, d.nq, d.nv);
-    if (inreg) d.direct_in = chain_direct_inputs(sizeof(T), d.nq, d.nv, q, qd, tau);
     // (the slab: the rows the kernel's own rule gives a wavefront -- no input rows when they live in registers)
     const size_t slab_rows = static_cast<size_t>(chain_slab_rows(inreg, d.nq, d.nv, d.n_glb_slots, d.out_lds).total);
     if (int rc = ensure_scratch(p, device, stream, scratch_bytes(s.grid, slab_rows, sizeof(T)), &scratch)) return rc;

@@ -187,17 +187,24 @@ struct ChainMem {
 // The tile's inputs in REGISTERS instead of slab rows (aba_chain_kernel<float, 2, kModeInReg>): every lane keeps its own state's q, qd and
 // tau in three arrays of kInRegCols (devplan.h) entries.  The column numbers come from the plan records, which are wave-uniform, so an
 // access is an indexed register move (s_set_gpr_idx_on / v_mov_b32 / s_set_gpr_idx_off) -- no address arithmetic, no vmcnt wait and no
-// slab traffic; the prologue writes no input row (stage_inputs_reg, devmath.h).  The arrays are VECTOR values, not C arrays: the
+// slab traffic; the prologue writes no input row (load_inputs_reg, devmath.h).  The arrays are VECTOR values, not C arrays: the
 // compiler turns a dynamically indexed C array into registers only within a budget of a quarter of the register file for the whole
-// kernel (two of these three would go to scratch), a vector is a register tuple to begin with.  Everything else (slots, [K | y0]
-// blocks, result rows) is ChainMem's.
+// kernel (two of these three would go to scratch), a vector is a register tuple to begin with.
+// The RESULTS live there too: tau[j] is last read by the backward segment of coordinate j's cluster, which precedes the segment that
+// produces ydd[j], so ydd[j] takes tau[j]'s register (an indexed write; the segments hold the memory object by const reference, hence
+// mutable) and the tile epilogue stores the lane's own row from rx (store_row_regs, devmath.h): no result row in LDS or in the slab, and
+// ChainMem's result stores and read-back do not exist here.  Everything else (slots, [K | y0] blocks) is ChainMem's.
 template <class T>
 struct ChainMemR : ChainMem<T> {
     typedef T Row __attribute__((ext_vector_type(kInRegCols)));
-    Row rq, rqd, rx;
+    Row rq, rqd;
+    mutable Row rx;  // tau, then ydd
     __device__ __forceinline__ T q(int j) const { return rq[j]; }
     __device__ __forceinline__ T qd(int j) const { return rqd[j]; }
     __device__ __forceinline__ T x(int j) const { return rx[j]; }
+    __device__ __forceinline__ void put_f(int j, T v) const { rx[j] = v; }
+    void put(int, T) const = delete;
+    T got(int) const = delete;
 };
 
 // Sparse body wrenches (devplan.h, WrenchList; aba_chain_wrench_kernel / rnea_chain_wrench_kernel): the call's body list in scalar
@@ -656,8 +663,8 @@ __device__ __forceinline__ void pair_bwd(const ChainTables<T> &P, const MM &M, c
     else pair_bwd_k<T, OSIM, -1, -1>(P, M, pr, IA, psi);
 }
 
-template <class T>
-__device__ __forceinline__ void pair_acc(const ChainTables<T> &P, const ChainMem<T> &M, const ChainPair &pr)
+template <class T, class MM>
+__device__ __forceinline__ void pair_acc(const ChainTables<T> &P, const MM &M, const ChainPair &pr)
 {
     T blk[14], va[12];
     M.glb_ld(pr.glb_k, blk);
@@ -1288,8 +1295,8 @@ __device__ __forceinline__ void run_bwd(const ChainTables<T> &P, const MM &M, co
 // ---------------------------------------------------------------------------------------------------------------
 // acceleration run (ClusterTreeDynamics.cpp:131-152), root side first: ydd = y0 - K a_p; a = X a_p + c + z g0 ydd
 // ---------------------------------------------------------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ void run_acc(const ChainTables<T> &P, const ChainMem<T> &M, const ChainSeg &sg)
+template <class T, class MM>
+__device__ __forceinline__ void run_acc(const ChainTables<T> &P, const MM &M, const ChainSeg &sg)
 {
     T vp[6], ap[6];
     if (sg.lds_pva >= 0) {
@@ -1472,8 +1479,8 @@ __device__ __forceinline__ void free_fwd(const ChainTables<T> &P, const MM &M, c
 
 template <class T, class MM>
 __device__ __forceinline__ void free_acc_inputs(const ChainTables<T> &P, const MM &M, const ChainFree &f, T (&o)[4], T (&r)[3]);
-template <class T>
-__device__ __forceinline__ void free_acc_core(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f, const T (&y0)[6],
+template <class T, class MM>
+__device__ __forceinline__ void free_acc_core(const ChainTables<T> &P, const MM &M, const ChainFree &f, const T (&y0)[6],
                                               const T (&o)[4], const T (&r)[3], const T (&vb)[6]);
 template <class T, bool OSIM, class MM>
 __device__ __forceinline__ void free_bwd(const ChainTables<T> &P, const MM &M, const ChainFree &f, bool fuse_acc = false)
@@ -1556,8 +1563,8 @@ __device__ __forceinline__ void free_acc_inputs(const ChainTables<T> &P, const M
 #pragma unroll
     for (int j = 0; j < 3; j++) r[j] = M.q(f.q_index + j);
 }
-template <class T>
-__device__ __forceinline__ void free_acc_core(const ChainTables<T> &P, const ChainMem<T> &M, const ChainFree &f, const T (&y0)[6],
+template <class T, class MM>
+__device__ __forceinline__ void free_acc_core(const ChainTables<T> &P, const MM &M, const ChainFree &f, const T (&y0)[6],
                                               const T (&o)[4], const T (&r)[3], const T (&vb)[6])
 {
     T E[9], g[6], ag[6];
@@ -1743,17 +1750,14 @@ template hipError_t launch_aba_gen1<double>(const ChainDev<double> &, int, int, 
 // MODE 1: the program has differential clusters (ChainDiff).  A kernel variant of its own, so that the models without them
 // (every URDF robot of the reference) keep the register allocation of the plain run / pair / free code.  MODE 2: the program
 // has generic clusters (ChainGen; gen_segments.h) and possibly differentials: translation unit 2.  MODE kModeInReg: the program of MODE 0
-// with the tile's inputs held in registers (ChainMemR above; launch_aba_chain decides).  DIRECT (MODE kModeInReg only; kDirectQ / kDirectQd /
-// kDirectX, devplan.h): the inputs whose rows the lanes fetch from global memory themselves instead of through LDS -- a template argument,
-// not a run-time test: the kernel sits at 243 of 256 registers, and a prologue with both paths for every array spilled two of the three
-// input vectors (132 bytes of scratch per lane).
-template <class T, int WPS, int MODE, int DIRECT = 0>
+// with the tile's inputs held in registers (ChainMemR above; launch_aba_chain decides): the lanes fetch their own rows from global memory
+// (devmath.h, load_inputs_reg), nothing of a tile's input passes through LDS.
+template <class T, int WPS, int MODE>
 __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, const T *__restrict__ q, const T *__restrict__ qd,
                                                              const T *__restrict__ tau, T *__restrict__ ydd, size_t B,
                                                              T *__restrict__ scratch)
 {
     constexpr bool DIFF = MODE == 1 || MODE == 2, GEN = MODE == 2, INREG = MODE == kModeInReg;
-    static_assert(INREG || DIRECT == 0, "direct row loads fill the register vectors of kModeInReg");
     ChainTables<T> P;
     P.segs = (cptr<ChainSeg>)DP.segs;
     P.links = (cptr<ChainLink>)DP.links;
@@ -1792,13 +1796,11 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t left = B - tile * kWave;
         const int rows_valid = left < (size_t)kWave ? (int)left : kWave;
-        if constexpr (INREG)
-            stage_inputs_reg<kInRegCols, (DIRECT & kDirectQ) != 0, (DIRECT & kDirectQd) != 0, (DIRECT & kDirectX) != 0>(
-                q, qd, tau, tile, rows_valid, P.nq, P.nv, M.rq, M.rqd, M.rx, lane, DP.lds_bytes);
+        if constexpr (INREG) load_inputs_reg<kInRegCols>(q, qd, tau, tile, rows_valid, P.nq, P.nv, M.rq, M.rqd, M.rx, lane);
         else stage_inputs(q, qd, tau, tile, rows_valid, P.nq, P.nv, slab, lane, DP.lds_bytes);
         if (DP.fuse & 1) {  // the floating base's velocity to its LDS slot: from the lane's row of the staged block (still there) ...
             T v[6];
-            if constexpr ((DIRECT & kDirectQd) != 0) {  // ... or, when qd was never staged, from the lane's registers (a wave-uniform index)
+            if constexpr (INREG) {  // ... or, when nothing was staged, from the lane's registers (a wave-uniform index)
 #pragma unroll
                 for (int j = 0; j < 6; j++) v[j] = M.rqd[DP.stage_v_index + j];
             } else {
@@ -1853,7 +1855,8 @@ __global__ __launch_bounds__(kWave, WPS) void aba_chain_kernel(ChainDev<T> DP, c
                     break;
             }
         }
-        if (M.out_row >= 0) write_outputs_lds<T>(M.out_row, ydd, tile, rows_valid, P.nv, lane);
+        if constexpr (INREG) store_row_regs<T, kInRegCols>(ydd, tile, rows_valid, P.nv, M.rx, lane);  // (the results are in the lane's registers)
+        else if (M.out_row >= 0) write_outputs_lds<T>(M.out_row, ydd, tile, rows_valid, P.nv, lane);
         else write_outputs(slab + (size_t)rows.out * kWave, ydd, tile, rows_valid, P.nv, lane);
         M.flush_bad(DP.bad_count, rows_valid);
     }
@@ -2472,15 +2475,7 @@ hipError_t launch_aba_chain(const ChainDev<T> &P, const T *q, const T *qd, const
     }
     if constexpr (sizeof(T) == 4) {
         if (chain_inputs_in_registers(sizeof(T), P.n_gens, P.n_diffs, P.sv_global, P.nq, P.nv)) {
-            // (P.direct_in: one of the sets chain_direct_inputs hands out, each an instantiation of its own)
-            if (P.direct_in == (kDirectQ | kDirectQd | kDirectX))
-                hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg, kDirectQ | kDirectQd | kDirectX>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd,
-                                   tau, ydd, B, scratch);
-            else if (P.direct_in == (kDirectQd | kDirectX))
-                hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg, kDirectQd | kDirectX>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau,
-                                   ydd, B, scratch);
-            else
-                hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
+            hipLaunchKernelGGL((aba_chain_kernel<T, 2, kModeInReg>), dim3(grid), dim3(kWave), lds_bytes, stream, P, q, qd, tau, ydd, B, scratch);
             return hipGetLastError();
         }
     }
@@ -3449,8 +3444,6 @@ hipError_t set_max_dynamic_lds_chain()
     const void *const kernels[] = {
         reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 0>), reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, 1>),
         reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, kModeInReg>),
-        reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, kModeInReg, kDirectQd | kDirectX>),
-        reinterpret_cast<const void *>(&aba_chain_kernel<float, 2, kModeInReg, kDirectQ | kDirectQd | kDirectX>),
         reinterpret_cast<const void *>(&aba_chain_kernel<double, 2, 0>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<float, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<float, 1, false>),
         reinterpret_cast<const void *>(&rnea_chain_kernel<double, 0, false>), reinterpret_cast<const void *>(&rnea_chain_kernel<double, 1, false>),

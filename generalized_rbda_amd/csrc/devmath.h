@@ -469,119 +469,100 @@ __device__ __forceinline__ void stage_inputs(const T *__restrict__ q, const T *_
     }
 }
 
-// The prologue of the kernel that keeps a tile's inputs in registers (chain_kernels.hip, ChainMemR): the same asynchronous copies, then
-// every lane reads ITS OWN row of each staged block into a per-lane register vector of N entries -- 16-byte reads where
-// stage_transpose uses them, 4-byte reads otherwise (an odd row stride: conflict-free).  No slab row is written.  The loops are
-// unrolled over all N entries with a wave-uniform test per read, so that every index is a constant; entries from ncols on keep what
-// they held.  When LDS holds all three blocks at once they are still there when this returns (the caller may read the base's
-// velocity from them).  Needs nq, nv <= N (devplan.h, chain_inputs_in_registers).
-template <class T, int N, class ROW>
-__device__ __forceinline__ void stage_row_regs(int ncols, unsigned lds_byte_off, ROW &r, int lane)
+// The prologue of the kernel that keeps a tile's inputs in registers (chain_kernels.hip, ChainMemR): lane l fetches row tile * kWave + l of
+// the row-major array from global memory straight into a per-lane register vector of N entries -- no LDS, no slab row.  The row may start
+// on any element boundary and hold any ncols <= N: ncols / V 16-byte loads through a type that claims no more than the element's own
+// alignment (the target fetches a dword-aligned global_load_dwordx4), then element loads for the ncols % V columns left, so that no byte
+// outside [src, src + B * ncols) is touched -- the batch's last row is not read past.  The tile's rows are one contiguous block: the wave
+// fetches every byte of the lines it touches, once.  A lane past the batch's last row reads that last row again (no address beyond the
+// array; its results are never written).  The loops are unrolled over all N entries with a wave-uniform test per load, so that every
+// register index is a constant; entries from ncols on keep what they held and are never used.  The wide loads and the tail are two
+// passes (one loop with both has the compiler share their registers and addresses: loads and stores of three dwords and one).  Needs
+// nq, nv <= N (devplan.h, chain_inputs_in_registers).
+template <class T, int V>
+struct alignas(sizeof(T)) RowUnit {
+    T v[V];
+};
+// the column count as a value of THIS tile: the tests on it stay scalar compares where they stand -- as loop invariants of the
+// persistent loop each would be computed up front and live in a pair of spilled scalar registers
+__device__ __forceinline__ int tile_local(int ncols)
 {
-    const T *stage = reinterpret_cast<const T *>(grbda_smem + lds_byte_off);
-    constexpr int V = 16 / (int)sizeof(T);
-    static_assert(N % V == 0, "whole 16-byte reads");
-    if ((ncols % V) == 0 && (lds_byte_off % 16u) == 0) {
-        struct alignas(16) Vec { T v[V]; };
-        const Vec *rows = reinterpret_cast<const Vec *>(stage + lane * ncols);
-#pragma unroll
-        for (int c = 0; c < N; c += V) {
-            if (c < ncols) {
-                const Vec x = rows[c / V];
-#pragma unroll
-                for (int k = 0; k < V; k++) r[c + k] = x.v[k];
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < N; c++)
-        if (c < ncols) r[c] = stage[lane * ncols + c];
+    asm volatile("" : "+s"(ncols));
+    return ncols;
 }
-// The same row WITHOUT the LDS round trip: lane l fetches row tile * kWave + l of the row-major array from global memory with 16-byte
-// loads, straight into the register vector (rows of whole 16-byte units on a 16-byte aligned base: devplan.h, chain_direct_inputs).  The
-// tile's rows are one contiguous block, so the wave's ncols / V loads touch exactly the cache lines the staged copy touches.  A lane
-// past the batch's last row reads that last row again (no address beyond the array; its results are never written).  All N / V
-// loads are issued whatever ncols is -- those past the row's end read the row's last unit again (a hit in the line just fetched; entries
-// from ncols on are never used) -- so that nothing is masked or branched over, no entry is carried from tile to tile, and the number of
-// loads is the constant N / V: the caller's counted wait relies on it.
 template <class T, int N, class ROW>
 __device__ __forceinline__ void load_row_regs(const T *__restrict__ src, size_t tile, int rows_valid, int ncols, ROW &r, int lane)
 {
     constexpr int V = 16 / (int)sizeof(T);
-    static_assert(N % V == 0, "whole 16-byte loads");
-    struct alignas(16) Vec { T v[V]; };
+    static_assert(N % V == 0, "whole 16-byte units");
     const int row = lane < rows_valid ? lane : rows_valid - 1;
-    const Vec *mine = reinterpret_cast<const Vec *>(src + (tile * (size_t)kWave + (size_t)row) * (size_t)ncols);
-    const int last = ncols / V - 1;
+    const T *mine = src + (tile * (size_t)kWave + (size_t)row) * (size_t)ncols;
+    const int n = tile_local(ncols), wide = n - n % V;
 #pragma unroll
     for (int c = 0; c < N; c += V) {
-        const Vec x = mine[c / V < last ? c / V : last];
+        if (c < wide) {
+            const RowUnit<T, V> x = *reinterpret_cast<const RowUnit<T, V> *>(mine + c);
 #pragma unroll
-        for (int k = 0; k < V; k++) r[c + k] = x.v[k];
-    }
-}
-// s_waitcnt vmcnt(K): all but the K youngest vector-memory operations of the wave have completed
-template <int K>
-__device__ __forceinline__ void wait_all_but_youngest()
-{
-    static_assert(K >= 0 && K < 64, "six bits of vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory");
-}
-// DQ / DQD / DX (compile-time: the kernel is instantiated per set, chain_kernels.hip): that array goes through load_row_regs instead of
-// LDS.  The staged copies are issued FIRST and the direct loads behind them: the memory counter retires in order, so "all but the direct
-// loads" is a counted wait, the staged rows are read back while the direct loads are still in flight, and the first USE of a directly
-// loaded vector waits for it (the compiler's own wait).  The staged blocks keep their LDS offsets whichever arrays go direct.  With
-// nothing direct this is the all-staged prologue, instruction for instruction.
-template <int N, bool DQ, bool DQD, bool DX, class T, class ROW>
-__device__ __forceinline__ void stage_inputs_reg(const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ x, size_t tile,
-                                                 int rows_valid, int nq, int nv, ROW &rq, ROW &rqd, ROW &rx, int lane, int lds_bytes)
-{
-    constexpr int V = 16 / (int)sizeof(T), kDirectLoads = ((DQ ? 1 : 0) + (DQD ? 1 : 0) + (DX ? 1 : 0)) * (N / V);
-    const unsigned bq = (unsigned)(kWave * nq) * (unsigned)sizeof(T), bv = (unsigned)(kWave * nv) * (unsigned)sizeof(T);
-    if ((int)(bq + 2 * bv) <= lds_bytes) {
-        if constexpr (!DQ) stage_issue(q, tile, rows_valid, nq, 0u, lane);
-        if constexpr (!DQD) stage_issue(qd, tile, rows_valid, nv, bq, lane);
-        if constexpr (!DX) stage_issue(x, tile, rows_valid, nv, bq + bv, lane);
-        if constexpr (kDirectLoads > 0) asm volatile("" ::: "memory");  // (the direct loads stay behind the copies)
-        if constexpr (DQ) load_row_regs<T, N>(q, tile, rows_valid, nq, rq, lane);
-        if constexpr (DQD) load_row_regs<T, N>(qd, tile, rows_valid, nv, rqd, lane);
-        if constexpr (DQD && DX) asm volatile("" ::: "memory");  // (program order qd, then x: qd is used first)
-        if constexpr (DX) load_row_regs<T, N>(x, tile, rows_valid, nv, rx, lane);
-        if constexpr (DQ && DQD && DX) return;  // (nothing staged, LDS untouched)
-        wait_all_but_youngest<kDirectLoads>();
-        wave_lds_fence();
-        if constexpr (!DQ) stage_row_regs<T, N>(nq, 0u, rq, lane);
-        if constexpr (!DQD) stage_row_regs<T, N>(nv, bq, rqd, lane);
-        if constexpr (!DX) stage_row_regs<T, N>(nv, bq + bv, rx, lane);
-        wave_lds_fence();
-    } else {
-        // LDS too small for the whole tile: one array at a time (see stage_inputs); these waits drain the direct loads as well
-        if constexpr (DQ) load_row_regs<T, N>(q, tile, rows_valid, nq, rq, lane);
-        if constexpr (DQD) load_row_regs<T, N>(qd, tile, rows_valid, nv, rqd, lane);
-        if constexpr (DX) load_row_regs<T, N>(x, tile, rows_valid, nv, rx, lane);
-        if constexpr (!DQ) {
-            stage_issue(q, tile, rows_valid, nq, 0u, lane);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            wave_lds_fence();
-            stage_row_regs<T, N>(nq, 0u, rq, lane);
-            wave_lds_fence();
-        }
-        if constexpr (!DQD) {
-            stage_issue(qd, tile, rows_valid, nv, 0u, lane);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            wave_lds_fence();
-            stage_row_regs<T, N>(nv, 0u, rqd, lane);
-            wave_lds_fence();
-        }
-        if constexpr (!DX) {
-            stage_issue(x, tile, rows_valid, nv, 0u, lane);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            wave_lds_fence();
-            stage_row_regs<T, N>(nv, 0u, rx, lane);
-            wave_lds_fence();
+            for (int k = 0; k < V; k++) r[c + k] = x.v[k];
         }
     }
+    if (wide == n) return;
+#pragma unroll
+    for (int c = 0; c < N; c += V) {
+        if (c == wide) {
+#pragma unroll
+            for (int k = 0; k < V - 1; k++)
+                if (c + k < n) r[c + k] = mine[c + k];
+        }
+    }
+}
+// s_waitcnt's immediate on gfx9: vmcnt in bits [15:14] and [3:0], expcnt in [6:4], lgkmcnt in [11:8].  vmcnt(0), the other two counters at
+// their largest value (no wait on them):
+constexpr int kWaitVmcnt0 = (0x7 << 4) | (0xf << 8);
+static_assert(kWaitVmcnt0 == 0x0f70, "vmcnt(0) expcnt(7) lgkmcnt(15)");
+// The epilogue of that kernel, the same shape the other way: lane l < rows_valid stores the first ncols entries of its register vector to
+// row tile * kWave + l of the row-major result -- nothing before the row, nothing behind it.
+template <class T, int N, class ROW>
+__device__ __forceinline__ void store_row_regs(T *__restrict__ dst, size_t tile, int rows_valid, int ncols, const ROW &r, int lane)
+{
+    constexpr int V = 16 / (int)sizeof(T);
+    static_assert(N % V == 0, "whole 16-byte units");
+    // (ONE wait for the loads behind the results, stated where the compiler's wait-count pass reads it: left to itself it merges the
+    // branches below and waits in front of every store for the store before it)
+    __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
+    if (lane >= rows_valid) return;
+    T *mine = dst + (tile * (size_t)kWave + (size_t)lane) * (size_t)ncols;
+    const int n = tile_local(ncols), wide = n - n % V;
+#pragma unroll
+    for (int c = 0; c < N; c += V) {
+        if (c < wide) {
+            RowUnit<T, V> x;
+#pragma unroll
+            for (int k = 0; k < V; k++) x.v[k] = r[c + k];
+            *reinterpret_cast<RowUnit<T, V> *>(mine + c) = x;
+        }
+    }
+    if (wide == n) return;
+#pragma unroll
+    for (int c = 0; c < N; c += V) {
+        if (c == wide) {
+#pragma unroll
+            for (int k = 0; k < V - 1; k++)
+                if (c + k < n) mine[c + k] = r[c + k];
+        }
+    }
+}
+// q, qd and x in program order -- q and qd are used first, x not before the backward sweep -- and no wait here: the first USE of a vector
+// waits for it (the compiler's own wait).
+template <int N, class T, class ROW>
+__device__ __forceinline__ void load_inputs_reg(const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ x, size_t tile,
+                                                int rows_valid, int nq, int nv, ROW &rq, ROW &rqd, ROW &rx, int lane)
+{
+    load_row_regs<T, N>(q, tile, rows_valid, nq, rq, lane);
+    asm volatile("" ::: "memory");
+    load_row_regs<T, N>(qd, tile, rows_valid, nv, rqd, lane);
+    asm volatile("" ::: "memory");
+    load_row_regs<T, N>(x, tile, rows_valid, nv, rx, lane);
 }
 
 // Tile epilogue: the nv result rows of the slab ([coordinate][state]) become the tile's [state][coordinate]

@@ -94,9 +94,6 @@ struct ChainDev {
     int n_glb_slots;
     int lds_bytes;
     int ori_repr;
-    // aba_chain_kernel<float, 2, kModeInReg> only: kDirectQ / kDirectQd / kDirectX -- the lanes fetch their own rows of that input from
-    // global memory with 16-byte loads instead of the LDS staging (chain_direct_inputs below; every other launch: 0)
-    int direct_in;
     int sv_global;  // ChainProgram::sv_global
     int out_lds;    // ChainProgram::out_lds
     // aba_chain_kernel only (capi.cpp, run_chain): bit 0 -- the program starts with the floating base's forward segment, whose whole work is
@@ -117,22 +114,12 @@ inline bool chain_inputs_in_registers(size_t elem, int n_gens, int n_diffs, int 
 {
     return elem == 4 && n_gens == 0 && n_diffs == 0 && !sv_global && nq <= kInRegCols && nv <= kInRegCols;
 }
-// Which inputs of that kernel skip the LDS staging (ChainDev::direct_in; devmath.h, stage_inputs_reg): every lane fetches its own row with
-// 16-byte loads, which takes rows of whole 16-byte units on a 16-byte aligned base.  Decided once per launch, on the host.  The kernel is
-// instantiated per set, so only three sets are handed out: all three inputs, qd and tau (they share nv; q is read first and stays staged),
-// or none.
-constexpr int kDirectQ = 1, kDirectQd = 2, kDirectX = 4;
-inline int chain_direct_inputs(size_t elem, int nq, int nv, const void *q, const void *qd, const void *x)
-{
-    const auto direct = [elem](int ncols, const void *base) {
-        return (static_cast<size_t>(ncols) * elem) % 16 == 0 && reinterpret_cast<uintptr_t>(base) % 16 == 0;
-    };
-    if (!direct(nv, qd) || !direct(nv, x)) return 0;
-    return kDirectQd | kDirectX | (direct(nq, q) ? kDirectQ : 0);
-}
+// Its lanes fetch their own rows of q, qd and tau from global memory (devmath.h, load_row_regs): 16-byte loads at the element's own
+// alignment plus a narrow tail, so any row size and any base offset a tensor of that element type can have will do.
 // The rows (of kWave scalars) of a wavefront's slab in a launch of aba_chain_kernel -- ONE rule, read by the kernel for its pointers and by
 // the host for the allocation (capi.cpp, run_chain).  Staged inputs: [q: nq][qd: nv][tau: nv, the result rows once tau is dead][global
-// slots].  Inputs in registers: no input rows -- [global slots][result rows: nv, only when the plan keeps no result rows in LDS].
+// slots].  Inputs in registers: no input rows -- [global slots][result rows: nv, only when the plan keeps no result rows in LDS; that kernel
+// keeps its results in registers and leaves them unwritten -- the rule and its host-side check, tests/cpp/chain_slab_check.cpp, stand as they were].
 struct ChainSlabRows {
     int glb;    // first row of the global slots
     int out;    // first of the result rows (out_lds < 0)
