@@ -70,6 +70,10 @@ $(OBJ)/manifold_kernels.o: $(CSRC)/manifold_kernels.hip $(CSRC)/plan.h $(CSRC)/d
 $(OBJ)/contact_kernels.o: $(CSRC)/contact_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
+# the solve of the scheduled contacts (include/grbda_hip_contact_step.h)
+$(OBJ)/contact_step_kernels.o: $(CSRC)/contact_step_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
 $(OBJ)/centroidal_kernels.o: $(CSRC)/centroidal_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/devmath.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
@@ -82,7 +86,7 @@ $(OBJ)/jvp_kernels.o: $(CSRC)/jvp_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h
 $(OBJ)/step_vjp_kernels.o: $(CSRC)/step_vjp_kernels.hip $(CSRC)/plan.h $(CSRC)/devplan.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
-$(OBJ)/capi.o: $(CSRC)/capi.cpp $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/walk.h include/grbda_hip.h include/grbda_hip_vjp.h include/grbda_hip_step_vjp.h include/grbda_hip_jvp.h include/grbda_hip_wrench.h include/grbda_hip_bodies.h include/grbda_hip_jacobians.h include/grbda_hip_jacobian_products.h include/grbda_model_desc.h
+$(OBJ)/capi.o: $(CSRC)/capi.cpp $(CSRC)/plan.h $(CSRC)/devplan.h $(CSRC)/walk.h include/grbda_hip.h include/grbda_hip_vjp.h include/grbda_hip_step_vjp.h include/grbda_hip_jvp.h include/grbda_hip_wrench.h include/grbda_hip_contact_step.h include/grbda_hip_bodies.h include/grbda_hip_jacobians.h include/grbda_hip_jacobian_products.h include/grbda_model_desc.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(OBJ)/plan.o: $(CSRC)/plan.cpp $(CSRC)/plan.h include/grbda_hip.h include/grbda_model_desc.h
@@ -96,7 +100,7 @@ $(OBJ)/urdf.o: $(CSRC)/urdf.cpp include/grbda_hip.h include/grbda_model_desc.h g
 	@mkdir -p $(OBJ)
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 
-$(LIB): $(OBJ)/kernels.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/chain_kernels_u4.o $(OBJ)/wrench_kernels.o $(OBJ)/body_list_kernels.o $(OBJ)/frame_jacobian_kernels.o $(OBJ)/frame_product_kernels.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/contact_kernels.o $(OBJ)/centroidal_kernels.o $(OBJ)/vjp_kernels.o $(OBJ)/jvp_kernels.o $(OBJ)/step_vjp_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/walk.o $(OBJ)/urdf.o
+$(LIB): $(OBJ)/kernels.o $(OBJ)/chain_kernels.o $(OBJ)/chain_kernels_u1.o $(OBJ)/chain_kernels_u2.o $(OBJ)/chain_kernels_u3.o $(OBJ)/chain_kernels_u4.o $(OBJ)/wrench_kernels.o $(OBJ)/body_list_kernels.o $(OBJ)/frame_jacobian_kernels.o $(OBJ)/frame_product_kernels.o $(OBJ)/crba_kernels.o $(OBJ)/deriv_kernels.o $(OBJ)/minv_kernels.o $(OBJ)/manifold_kernels.o $(OBJ)/contact_kernels.o $(OBJ)/contact_step_kernels.o $(OBJ)/centroidal_kernels.o $(OBJ)/vjp_kernels.o $(OBJ)/jvp_kernels.o $(OBJ)/step_vjp_kernels.o $(OBJ)/capi.o $(OBJ)/plan.o $(OBJ)/walk.o $(OBJ)/urdf.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle:

@@ -11,7 +11,7 @@ import os
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 from . import modeldesc  # noqa: F401  (model-description builder)
-from ._abi import (BODIES_SIGNATURES, JACOBIAN_PRODUCT_SIGNATURES, JACOBIAN_SIGNATURES, JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES,
+from ._abi import (BODIES_SIGNATURES, CONTACT_STEP_SIGNATURES, JACOBIAN_PRODUCT_SIGNATURES, JACOBIAN_SIGNATURES, JVP_SIGNATURES, SIGNATURES, STEP_VJP_SIGNATURES,
                    VJP_SIGNATURES, WRENCH_SIGNATURES)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,9 +64,9 @@ def lib() -> ctypes.CDLL:
         fn.restype, fn.argtypes = restype, list(argtypes)
     # include/grbda_hip_vjp.h (an older build named by GRBDA_HIP_LIB has none of it: a call then raises AttributeError)
     # ... and include/grbda_hip_step_vjp.h, the third table, under the same rule; then grbda_hip_wrench.h, grbda_hip_jvp.h and
-    # grbda_hip_bodies.h, grbda_hip_jacobians.h, and last grbda_hip_jacobian_products.h
+    # grbda_hip_bodies.h, grbda_hip_jacobians.h, grbda_hip_jacobian_products.h, and last grbda_hip_contact_step.h
     for name, (restype, argtypes) in {**VJP_SIGNATURES, **STEP_VJP_SIGNATURES, **WRENCH_SIGNATURES, **JVP_SIGNATURES, **BODIES_SIGNATURES,
-                                      **JACOBIAN_SIGNATURES, **JACOBIAN_PRODUCT_SIGNATURES}.items():
+                                      **JACOBIAN_SIGNATURES, **JACOBIAN_PRODUCT_SIGNATURES, **CONTACT_STEP_SIGNATURES}.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
@@ -312,6 +312,115 @@ class _WrenchMethods:
         return self._wrench_host("rnea_wrench_host_f64", q, qd, ydd, bodies, wrench, frame, device)
 
 
+class _ContactStepMethods:
+    """Scheduled contacts (include/grbda_hip_contact_step.h), kept apart like _WrenchMethods: the contacts of contact_dynamics /
+    contact_impulse -- bodies[n], offsets[n][3], n in 1..8 -- with a mask per state, active[B] (any integer tensor on the device; bit c
+    set: contact c is closed in that state).  They go through Plan._call like every other method; the masks are made int32 and
+    contiguous on the call's stream."""
+
+    @staticmethod
+    def _mask(stream, device, mask, shape):
+        """the mask as the entry points take it (int32, contiguous, on the call's stream), or None"""
+        import torch
+
+        if mask is None:
+            return None
+        if not getattr(mask, "is_cuda", False) or mask.dtype.is_floating_point or mask.device != device or tuple(mask.shape) != tuple(shape):
+            raise ValueError(f"expected an integer device tensor active[{','.join(str(d) for d in shape)}] on the device of q")
+        with torch.cuda.stream(torch.cuda.current_stream(device) if stream is None else stream):
+            m = mask.to(torch.int32).contiguous()
+        if stream is not None:
+            mask.record_stream(stream)
+            m.record_stream(stream)
+        return m
+
+    def contact_dynamics_active(self, q, qd, tau, bodies, offsets, active, a_des=None, kd: float = 0.0, damping: float = 0.0, stream=None):
+        """contact_dynamics on the contacts whose bit is set in active[B], state by state (grbda_contact_dynamics_active_*), with the
+        right-hand side a_des - kd p_dot - p_ddot(ydd_free).  Returns (ydd[B, nv], lambda[B, n, 3] -- exactly 0 for the open contacts --,
+        ydd_free[B, nv]); a state with no closed contact has ydd == ydd_free."""
+        c = self._contacts(bodies, offsets)
+        m = self._mask(stream, q.device, active, (q.shape[0],))
+        return self._call("contact_dynamics_active", stream, dict(self._state(q, qd=qd, tau=tau), a_des=(a_des, (c[0], 3))),
+                          dict(ydd=self.nv, lam=(c[0], 3), ydd_free=self.nv),
+                          ("q", "qd", "tau", *c, m.data_ptr(), "a_des", float(kd), float(damping), "ydd", "lam", "ydd_free"))
+
+    def contact_impulse_active(self, q, qd, bodies, offsets, active, v_des=None, restitution: float = 0.0, damping: float = 0.0, out=None,
+                               stream=None):
+        """contact_impulse on the contacts whose bit is set in active[B], state by state (grbda_contact_impulse_active_*).  Returns
+        (qd_next[B, nv], impulse[B, n, 3] -- exactly 0 for the open contacts); a state with no closed contact keeps the bits of qd.
+        out: the tensor qd_next is written to; it may be qd."""
+        c = self._contacts(bodies, offsets)
+        m = self._mask(stream, q.device, active, (q.shape[0],))
+        return self._call("contact_impulse_active", stream, dict(self._state(q, qd=qd), v_des=(v_des, (c[0], 3))),
+                          dict(qd_next=self.nv, impulse=(c[0], 3)),
+                          ("q", "qd", *c, m.data_ptr(), "v_des", float(restitution), float(damping), "qd_next", "impulse"),
+                          fixed=dict(qd_next=(out, self.nv)))
+
+    def contact_step(self, q, qd, tau, bodies, offsets, active, dt: float, prev_active=None, kd: float = 0.0, restitution: float = 0.0,
+                     damping: float = 0.0, out=None, stream=None):
+        """One contact-aware step (grbda_contact_step_*): where a contact closes against prev_active[B], the impact with every closed
+        contact as a constraint (contact_impulse_active, v_des = 0); contact_dynamics_active at the velocities after it; integrate.
+        prev_active=None: no impulse stage at all.  Returns (q_next, qd_next, ydd, lambda[B, n, 3], impulse[B, n, 3] or None,
+        ok[B] bool).  out: (q_next, qd_next) to write to; they may be q and qd themselves."""
+        c = self._contacts(bodies, offsets)
+        m = self._mask(stream, q.device, active, (q.shape[0],))
+        mp = self._mask(stream, q.device, prev_active, (q.shape[0],))
+        qn, vn = (None, None) if out is None else out
+        return self._call("contact_step", stream, self._state(q, qd=qd, tau=tau),
+                          dict(q_next=self.nq, qd_next=self.nv, ydd=self.nv, lam=(c[0], 3), impulse=None if mp is None else (c[0], 3), ok=bool),
+                          ("q", "qd", "tau", *c, m.data_ptr(), None if mp is None else mp.data_ptr(), float(kd), float(restitution), float(damping),
+                           float(dt), "ydd", "lam", "impulse", "q_next", "qd_next", "ok"),
+                          fixed=dict(q_next=(qn, self.nq), qd_next=(vn, self.nv)))
+
+    def contact_rollout(self, q, qd, tau, bodies, offsets, active, dt: float, T: int, active_prev=None, with_impulses: bool = True,
+                        kd: float = 0.0, restitution: float = 0.0, damping: float = 0.0, record: bool = False, stream=None):
+        """T contact-aware steps from (q, qd), which are left untouched (grbda_contact_rollout_* on copies).  tau: [B, nv] held, or
+        [T, B, nv]; active: [B] held, or [T, B].  Step t closes contacts against active[t - 1], step 0 against active_prev (None:
+        nothing closes); with_impulses=False: no impulse stage in any step.  Returns (q_T, qd_T, ok[B] bool -- the AND over the steps),
+        and with record=True also (q_traj[T,B,nq], qd_traj[T,B,nv], lambda_traj[T,B,n,3])."""
+        import torch
+
+        T = int(T)
+        c = self._contacts(bodies, offsets)
+        per_step = tau.dim() == 3
+        B, dtype, device, _ = self._checked(dict(self._state(q, qd=qd), tau=(tau, (T, "B", self.nv) if per_step else self.nv)))
+        s, t = self._contiguous(stream, device, dict(tau=tau))
+        masks = active.dim() == 2
+        m = self._mask(stream, device, active, (T, B) if masks else (B,))
+        mp = self._mask(stream, device, active_prev, (B,))
+        self._hold(stream, q, qd, tau, t["tau"])
+        with torch.cuda.stream(s):  # (the copies are enqueued, and everything the steps write is allocated, on the call's stream)
+            qT, vT = q.clone(memory_format=torch.contiguous_format), qd.clone(memory_format=torch.contiguous_format)
+            work = torch.empty_like(vT)
+            ok = torch.ones((B,), dtype=torch.int32, device=device)
+            qt = torch.empty((T, B, self.nq), dtype=dtype, device=device) if record else None
+            vt = torch.empty((T, B, self.nv), dtype=dtype, device=device) if record else None
+            lt = torch.empty((T, B, c[0], 3), dtype=dtype, device=device) if record else None
+            ptr = lambda a: None if a is None else a.data_ptr()
+            self._dispatch("contact_rollout", dtype, qT.data_ptr(), vT.data_ptr(), t["tau"].data_ptr(), T if per_step else 1, *c, m.data_ptr(),
+                           T if masks else 1, ptr(mp), 1 if with_impulses else 0, float(kd), float(restitution), float(damping), float(dt), T,
+                           work.data_ptr(), ptr(qt), ptr(vt), ptr(lt), ok.data_ptr(), B, device.index or 0, s.cuda_stream)
+            return (qT, vT, ok.bool(), qt, vt, lt) if record else (qT, vT, ok.bool())
+
+    def contact_step_host(self, q, qd, tau, bodies, offsets, active, dt: float, prev_active=None, kd: float = 0.0, restitution: float = 0.0,
+                          damping: float = 0.0, device: int = 0):
+        """contact_step on host arrays (grbda_contact_step_host_f64): returns (q_next, qd_next, ydd, lambda, impulse or None, ok)."""
+        import numpy as np
+
+        c = self._contacts(bodies, offsets)
+        q, qd, tau = (np.ascontiguousarray(a, dtype="float64") for a in (q, qd, tau))
+        B = q.shape[0]
+        m = np.ascontiguousarray(active, dtype="int32")
+        mp = None if prev_active is None else np.ascontiguousarray(prev_active, dtype="int32")
+        qn, vn, ydd = np.empty_like(q), np.empty_like(qd), np.empty_like(qd)
+        lam, ok = np.empty((B, c[0], 3)), np.empty((B,), dtype="int32")
+        imp = None if mp is None else np.empty((B, c[0], 3))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(lib().grbda_contact_step_host_f64(self._h, ptr(q), ptr(qd), ptr(tau), *c, ptr(m), ptr(mp), float(kd), float(restitution), float(damping),
+                                                 float(dt), ptr(ydd), ptr(lam), ptr(imp), ptr(qn), ptr(vn), ptr(ok), B, device))
+        return qn, vn, ydd, lam, imp, ok.astype(bool)
+
+
 class _BodyListMethods:
     """Poses and twists of a listed few bodies (include/grbda_hip_bodies.h), kept apart like _WrenchMethods.  bodies: up to 16 plan body
     indices in any order; a body may repeat and may stand next to its ancestors.  Slot i of a result is row bodies[i] of body_poses /
@@ -508,7 +617,7 @@ class _JvpMethods:
                           ("q", "qd", "tau", "qd_next", float(dt), "dq", "dqd", "dtau", float(step), "dq_next", "dqd_next"), skip_empty=True)
 
 
-class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _BodyListMethods, _JacobianMethods, _JacobianProductMethods, _JvpMethods):
+class Plan(_VjpMethods, _StepVjpMethods, _WrenchMethods, _ContactStepMethods, _BodyListMethods, _JacobianMethods, _JacobianProductMethods, _JvpMethods):
     """An immutable compiled model (``grbda_plan``)."""
 
     def __init__(self, blob: bytes):

@@ -164,3 +164,19 @@ JACOBIAN_PRODUCT_SIGNATURES = {
     "grbda_frame_jacobian_products_host_f64": _JACOBIAN_PRODUCT_PAIR[:-1],
 }
 JACOBIAN_PRODUCT_SIGNATURES = {name: (c_int, args) for name, args in JACOBIAN_PRODUCT_SIGNATURES.items()}
+
+# include/grbda_hip_contact_step.h, scheduled contacts -- per-state active sets, the contact-aware step, the rollout: a table of its own,
+# applied by `lib()` after the others; tests/test_contact_step_args_cpu.py holds it to that header
+_CONTACT_STEP_PAIRS = {
+    "contact_dynamics_active": (P, P, P, P, I, BODIES, OFFSETS, P, P, D, D, P, P, P, *TAIL),  # q qd tau n bodies offsets active a_des kd damping ydd lambda ydd_free
+    "contact_impulse_active": (P, P, P, I, BODIES, OFFSETS, P, P, D, D, P, P, *TAIL),         # q qd n bodies offsets active v_des restitution damping qd_next impulse
+    # q qd tau n bodies offsets active prev_active kd restitution damping dt ydd lambda impulse q_next qd_next ok
+    "contact_step": (P, P, P, P, I, BODIES, OFFSETS, P, P, D, D, D, D, P, P, P, P, P, P, *TAIL),
+    # q qd tau tau_steps n bodies offsets active active_steps active_prev with_impulses kd restitution damping dt T ydd_work q_traj qd_traj lambda_traj ok
+    "contact_rollout": (P, P, P, P, I, I, BODIES, OFFSETS, P, I, P, I, D, D, D, D, I, P, P, P, P, P, *TAIL),
+}
+CONTACT_STEP_SIGNATURES = {}
+for _stem, _args in _CONTACT_STEP_PAIRS.items():
+    CONTACT_STEP_SIGNATURES[f"grbda_{_stem}_f64"] = CONTACT_STEP_SIGNATURES[f"grbda_{_stem}_f32"] = _args
+CONTACT_STEP_SIGNATURES["grbda_contact_step_host_f64"] = _CONTACT_STEP_PAIRS["contact_step"][:-1]
+CONTACT_STEP_SIGNATURES = {name: (c_int, args) for name, args in CONTACT_STEP_SIGNATURES.items()}

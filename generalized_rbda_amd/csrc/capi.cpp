@@ -18,6 +18,7 @@
 #include "../../include/grbda_hip_step_vjp.h"
 #include "../../include/grbda_hip_jvp.h"
 #include "../../include/grbda_hip_wrench.h"
+#include "../../include/grbda_hip_contact_step.h"
 #include "../../include/grbda_hip_bodies.h"
 #include "../../include/grbda_hip_jacobians.h"
 #include "../../include/grbda_hip_jacobian_products.h"
@@ -140,6 +141,7 @@ struct grbda_plan {
     mutable SlabPool work_step_vjp;  // step_vjp_run / rollout_vjp (they call vjp_run, which carves work_vjp)
     mutable SlabPool work_jvp;       // jvp_run (its id_derivs stage carves `work` on the difference routes)
     mutable SlabPool work_step_jvp;  // step_jvp_run: dydd between jvp_run and the integrate kernel
+    mutable SlabPool work_contact;   // the scheduled contacts (their sparse-wrench stage carves `work` on its fallback routes)
     // the chunk decision of the last eager analytic_derivs call per (device, stream): a capture of the same call replays it
     struct DerivChunk {
         size_t B = 0, per_state_bytes = 0, chunk = 0;
@@ -313,6 +315,7 @@ int ensure_device(const grbda_plan *p, int device, DeviceTables **out)
     if ((e = set_max_dynamic_lds_deriv()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     if ((e = set_max_dynamic_lds_minv()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     if ((e = set_max_dynamic_lds_contact()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
+    if ((e = set_max_dynamic_lds_contact_step()) != hipSuccess) return hip_err(e, "hipFuncSetAttribute");
     t.bad_count = spd_bad_count_address();
     auto ins = p->dev.emplace(device, t);
     *out = &ins.first->second;
@@ -2308,6 +2311,21 @@ int contact_dynamics(const grbda_plan *p, const T *q, const T *qd, const T *tau,
 }
 
 // ---- sparse body wrenches (include/grbda_hip_wrench.h) --------------------------------------------------------------------------------
+// The list as the wrench-carrying kernels take it, for n <= kMaxWrenches checked body indices: ONE filler for wrench_args and for the
+// scheduled contacts (active_contacts), so that the canon bits cannot differ between them.
+template <class T>
+WrenchList<T> wrench_list(const grbda_plan *p, int n, const int *bodies, const T *wrench)
+{
+    WrenchList<T> W;
+    W.n = n;
+    W.w = wrench;
+    W.canon = 0;
+    for (int i = 0; i < kMaxWrenches; i++) {
+        W.body[i] = i < n ? bodies[i] : -1;
+        if (i < n) W.canon |= static_cast<unsigned>(p->host.lay64.bodies[bodies[i]].canon_axis & 3) << (2 * i);
+    }
+    return W;
+}
 // Everything grbda_aba_wrench_* / grbda_rnea_wrench_* refuse, on the host and before any device call; fills the kernels' list.
 template <class T>
 int wrench_args(const grbda_plan *p, const T *q, const T *qd, const T *x, int n, const int *bodies, const T *wrench, int frame, const T *out, size_t B,
@@ -2317,14 +2335,9 @@ int wrench_args(const grbda_plan *p, const T *q, const T *qd, const T *x, int n,
     if (n < 0 || n > kMaxWrenches) return set_err(GRBDA_EINVAL, "0..16 body wrenches per call");
     if (frame != GRBDA_WRENCH_BODY && frame != GRBDA_WRENCH_WORLD) return set_err(GRBDA_EINVAL, "frame must be GRBDA_WRENCH_BODY or GRBDA_WRENCH_WORLD");
     if (n > 0 && (!bodies || !wrench)) return set_err(GRBDA_EINVAL, "null argument");
-    W.n = n;
-    W.w = wrench;
-    W.canon = 0;
-    for (int i = 0; i < kMaxWrenches; i++) {
-        if (i < n && (bodies[i] < 0 || bodies[i] >= p->host.n_bodies)) return set_err(GRBDA_EINVAL, "body index out of range");
-        W.body[i] = i < n ? bodies[i] : -1;
-        if (i < n) W.canon |= static_cast<unsigned>(p->host.lay64.bodies[bodies[i]].canon_axis & 3) << (2 * i);
-    }
+    for (int i = 0; i < n; i++)
+        if (bodies[i] < 0 || bodies[i] >= p->host.n_bodies) return set_err(GRBDA_EINVAL, "body index out of range");
+    W = wrench_list<T>(p, n, bodies, wrench);
     const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
     const void *const in[4] = {q, qd, x, n > 0 ? wrench : nullptr}, *const outs[1] = {out};
     const size_t in_bytes[4] = {bq, bv, bv, B * static_cast<size_t>(n) * 6 * sizeof(T)}, out_bytes[1] = {bv};
@@ -2360,6 +2373,11 @@ Route wrench_route(const grbda_plan *p, bool rnea, int n_cu, size_t B, const Wre
 // Forward / inverse dynamics with the listed wrenches.  Chain route, body frame: one launch on the caller's arrays, no work memory.  Chain
 // route, world frame: per chunk the poses of the listed bodies (body_list_stage), wrench_to_body_kernel, the launch.  Fallback: per chunk a
 // zeroed dense chunk, (body frame: the listed poses,) wrench_scatter_kernel, run().  The chunks come off p->work (run() itself uses the scratch slab and work_proj only).
+// wrench_stage: the call with its arguments checked, a list of n > 0, B > 0 and the device found -- what grbda_aba_wrench_* / grbda_rnea_wrench_*
+// run, and the wrench-carrying forward dynamics of the scheduled contacts (gravity = false there: run()'s rule).
+template <class T>
+int wrench_stage(const grbda_plan *p, const DeviceTables *t, const WrenchList<T> &W, bool rnea, const T *q, const T *qd, const T *x, int n,
+                 const int *bodies, const T *wrench, int frame, T *out, size_t B, int device, void *stream, bool gravity = true);
 template <class T>
 int wrench_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T *x, int n, const int *bodies, const T *wrench, int frame, T *out,
                size_t B, int device, void *stream)
@@ -2372,12 +2390,18 @@ int wrench_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T 
     if (B == 0) return GRBDA_OK;
     DeviceTables *t = nullptr;
     if (int rc = ensure_device(p, device, &t)) return rc;
+    return wrench_stage<T>(p, t, W, rnea, q, qd, x, n, bodies, wrench, frame, out, B, device, stream);
+}
+template <class T>
+int wrench_stage(const grbda_plan *p, const DeviceTables *t, const WrenchList<T> &W, bool rnea, const T *q, const T *qd, const T *x, int n,
+                 const int *bodies, const T *wrench, int frame, T *out, size_t B, int device, void *stream, bool gravity)
+{
     const Route r = wrench_route<T>(p, rnea, t->n_cu, B, W);
     const bool chain = r.path == ROUTE_CHAIN;
     const auto launch = [&](const WrenchList<T> &Wc, size_t b0, size_t nb) {
         const size_t nq = p->host.nq, nv = p->host.nv;
-        return rnea ? run_rnea_chain<T>(p, *t, r, q + b0 * nq, qd + b0 * nv, x + b0 * nv, out + b0 * nv, nb, device, stream, true, &Wc)
-                    : run_chain<T>(p, *t, r, q + b0 * nq, qd + b0 * nv, x + b0 * nv, out + b0 * nv, nb, device, stream, true, &Wc);
+        return rnea ? run_rnea_chain<T>(p, *t, r, q + b0 * nq, qd + b0 * nv, x + b0 * nv, out + b0 * nv, nb, device, stream, gravity, &Wc)
+                    : run_chain<T>(p, *t, r, q + b0 * nq, qd + b0 * nv, x + b0 * nv, out + b0 * nv, nb, device, stream, gravity, &Wc);
     };
     if (chain && frame == GRBDA_WRENCH_BODY) return launch(W, 0, B);
     const size_t nq = p->host.nq, nv = p->host.nv, nbod = p->host.n_bodies, n6 = static_cast<size_t>(n) * 6;
@@ -2409,7 +2433,7 @@ int wrench_run(const grbda_plan *p, bool rnea, const T *q, const T *qd, const T 
             hipError_t e = hipMemsetAsync(fext, 0, nb * nbod * 6 * sizeof(T), hs);
             if (e == hipSuccess) e = launch_wrench_scatter<T>(Wc, Xa, frame == GRBDA_WRENCH_BODY, static_cast<int>(nbod), nb, fext, hs);
             if (e != hipSuccess) return hip_err(e, "wrench scatter launch");
-            if (int rc = run<T>(p, rnea, q + b0 * nq, qd + b0 * nv, x + b0 * nv, fext, out + b0 * nv, nb, device, stream)) return rc;
+            if (int rc = run<T>(p, rnea, q + b0 * nq, qd + b0 * nv, x + b0 * nv, fext, out + b0 * nv, nb, device, stream, gravity)) return rc;
         }
     }
     return GRBDA_OK;
@@ -2493,6 +2517,350 @@ int contact_impulse(const grbda_plan *p, const T *q, const T *qd, int n_contacts
         if ((rc = run<T>(p, false, qc, zero, zero, wrench, y1, nb, device, stream)) || (rc = run<T>(p, false, qc, zero, zero, nullptr, y0, nb, device, stream)))
             return rc;
         if ((e = launch_impulse_finish<T>(qdc, y1, y0, nb * nv, qd_next + b0 * nv, hs)) != hipSuccess) return hip_err(e, "impulse finish launch");
+    }
+    return GRBDA_OK;
+}
+
+// ---- scheduled contacts: per-state active sets, the contact-aware step, the rollout (include/grbda_hip_contact_step.h) -----------------
+// What every entry point of the header derives from its contact description once the arguments are checked: the set and the body-frame
+// wrench list of the same bodies (both travel by value), the inverse-OSIM route contact_dynamics would take, and the walk of the listed
+// poses and twists -- the list is `bodies` itself, slot c belongs to contact c.
+template <class T>
+struct ActiveContacts {
+    ContactSet<T> cs;
+    WrenchList<T> W;  // (w: set per chunk)
+    const int *bodies;
+    OsimRoute<T> r;
+    BodyWalkHost H;
+    ListWork lwp, lwt;  // the listed poses, the listed twists
+    size_t n, m6;
+    // scalars of work space per state of the stages every pipeline shares: poses, twists, Linv and the inverse OSIM's own, the wrench list
+    size_t shared_per_state() const { return lwp.per_state() + lwt.per_state() + m6 * m6 + r.ws_per_state + n * 6; }
+};
+template <class T>
+ActiveContacts<T> active_contacts(const grbda_plan *p, const ContactSet<T> &cs, const int *bodies, const double *offsets)
+{
+    ActiveContacts<T> A{};
+    A.cs = cs;
+    A.bodies = bodies;
+    A.n = static_cast<size_t>(cs.n);
+    A.m6 = 6 * A.n;
+    A.W = wrench_list<T>(p, cs.n, bodies, static_cast<const T *>(nullptr));
+    A.r = choose_osim<T>(p, cs.n, bodies, offsets, false, nullptr, nullptr, nullptr);
+    A.H = build_body_walk(p->host, layout_of(p->host, sizeof(T) == 4 ? 0 : 1), cs.n, bodies);
+    A.lwp = list_work(p, A.H, false, cs.n);
+    A.lwt = list_work(p, A.H, true, cs.n);
+    return A;
+}
+// the shared arrays of one chunk, carved in the order shared_per_state() counts them (the inverse OSIM takes its own from the carver)
+template <class T>
+struct ActiveWork {
+    ListWork::Arrays<T> mp, mt;
+    T *Linv, *wrench;
+    ActiveWork(const ActiveContacts<T> &A, Carver<T> &w, size_t nb)
+        : mp(A.lwp.take(w, nb)), mt(A.lwt.take(w, nb)), Linv(w.take(nb * A.m6 * A.m6)), wrench(w.take(nb * A.n * 6))
+    {
+    }
+};
+// The stages below run nb states of one chunk: arguments checked, device found, every pointer at the chunk's first state.
+// What depends on q alone: the listed poses and the inverse OSIM of all n contact frames (contact_step uses one pair for both solves).
+template <class T>
+int active_frames_stage(const grbda_plan *p, const DeviceTables &t, const ActiveContacts<T> &A, const ActiveWork<T> &k, const T *q, size_t nb,
+                        int device, void *stream, Carver<T> &w)
+{
+    if (int rc = body_list_stage<T>(p, t, A.H, false, q, nullptr, nullptr, k.mp.out, k.mp.full, k.mp.vs, k.mp.as, nb, device, stream)) return rc;
+    return osim_stage<T>(p, t, A.r, A.cs, q, k.Linv, nullptr, nb, device, stream, w);
+}
+//   1 ydd_free = FD(q, qd, tau)          2 listed twists at ydd_free          3 contact_active_solve_kernel: lambda and the body-frame wrench list
+//   4 ydd = FD(q, qd, tau, wrench list), the sparse-wrench call on its own routes          5 the states with an empty set keep ydd_free
+template <class T>
+int active_dynamics_stage(const grbda_plan *p, const DeviceTables &t, const ActiveContacts<T> &A, const ActiveWork<T> &k, const T *q, const T *qd,
+                          const T *tau, const int32_t *active, const T *a_des, double kd, double damping, T *ydd, T *lambda, T *yf, size_t nb,
+                          int device, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const std::array<T, 3> g = gravity3<T>(p);
+    int rc;
+    if ((rc = run<T>(p, false, q, qd, tau, nullptr, yf, nb, device, stream)) ||
+        (rc = body_list_stage<T>(p, t, A.H, true, q, qd, yf, k.mt.out, k.mt.full, k.mt.vs, k.mt.as, nb, device, stream)))
+        return rc;
+    hipError_t e = launch_contact_active_solve<T>(false, A.cs, k.Linv, k.mp.out, k.mt.out, a_des, active, static_cast<T>(damping), static_cast<T>(kd),
+                                                  g.data(), nb, lambda, k.wrench, t.bad_count, t.n_cu, hs);
+    if (e != hipSuccess) return hip_err(e, "contact solve launch");
+    WrenchList<T> W = A.W;
+    W.w = k.wrench;
+    if ((rc = wrench_stage<T>(p, &t, W, false, q, qd, tau, W.n, A.bodies, k.wrench, GRBDA_WRENCH_BODY, ydd, nb, device, stream))) return rc;
+    e = launch_free_states_copy<T>(active, W.n, yf, p->host.nv, nb, ydd, hs);
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "free states launch");
+}
+//   1 listed twists at (q, qd, 0)          2 contact_active_solve_kernel, velocity level: the impulses and the body-frame wrench list
+//   3 y1 = FD(q, 0, 0, wrench list), y0 = FD(q, 0, 0), both without gravity: at rest each term of y0, and of y1 in a state with an empty
+//     set, is exactly zero          4 qd_next = qd + (y1 - y0) (impulse_finish_kernel; qd_next may be qd)
+template <class T>
+int active_impulse_stage(const grbda_plan *p, const DeviceTables &t, const ActiveContacts<T> &A, const ActiveWork<T> &k, const T *q, const T *qd,
+                         const int32_t *active, const T *v_des, double restitution, double damping, T *qd_next, T *impulse, const T *zero, T *y1,
+                         T *y0, size_t nb, int device, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const T g0[3] = {0, 0, 0};
+    if (int rc = body_list_stage<T>(p, t, A.H, true, q, qd, zero, k.mt.out, k.mt.full, k.mt.vs, k.mt.as, nb, device, stream)) return rc;
+    hipError_t e = launch_contact_active_solve<T>(true, A.cs, k.Linv, k.mp.out, k.mt.out, v_des, active, static_cast<T>(damping),
+                                                  T(1) + static_cast<T>(restitution), g0, nb, impulse, k.wrench, t.bad_count, t.n_cu, hs);
+    if (e != hipSuccess) return hip_err(e, "impulse solve launch");
+    WrenchList<T> W = A.W;
+    W.w = k.wrench;
+    int rc;
+    if ((rc = wrench_stage<T>(p, &t, W, false, q, zero, zero, W.n, A.bodies, k.wrench, GRBDA_WRENCH_BODY, y1, nb, device, stream, false)) ||
+        (rc = run<T>(p, false, q, zero, zero, nullptr, y0, nb, device, stream, false)))
+        return rc;
+    e = launch_impulse_finish<T>(qd, y1, y0, nb * static_cast<size_t>(p->host.nv), qd_next, hs);
+    return e == hipSuccess ? GRBDA_OK : hip_err(e, "impulse finish launch");
+}
+// the rules the entry points share: the contact description, then the gains
+template <class T>
+int active_set_args(const grbda_plan *p, int n_contacts, const int *bodies, const double *offsets, const double *kd, const double *restitution,
+                    double damping, ContactSet<T> &cs)
+{
+    if (int rc = contact_set<T>(p, n_contacts, bodies, offsets, "points", cs)) return rc;
+    if (kd && (!std::isfinite(*kd) || *kd < 0)) return set_err(GRBDA_EINVAL, "kd must be finite and not negative");
+    if (!std::isfinite(damping) || damping < 0) return set_err(GRBDA_EINVAL, "damping must be finite and not negative");
+    if (restitution && (!std::isfinite(*restitution) || *restitution < 0 || *restitution > 1))
+        return set_err(GRBDA_EINVAL, "restitution must lie in [0, 1]");
+    return GRBDA_OK;
+}
+// the work pool of the scheduled contacts: chunk and slab for `per_state` scalars per state
+template <class T>
+int active_pool(const grbda_plan *p, size_t per_state, size_t B, int device, void *stream, Chunk &c, void **wptr)
+{
+    c = budgeted_chunk(p, p->work_contact, device, stream, 1024ull << 20, per_state * sizeof(T), B);
+    return ensure_work(p, p->work_contact, device, stream, c.bytes, wptr);
+}
+
+template <class T>
+int contact_dynamics_active_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, int n_contacts, const int *bodies, const double *offsets,
+                                 const int32_t *active, const T *a_des, double kd, double damping, const T *ydd, const T *lambda, const T *ydd_free,
+                                 size_t B, ContactSet<T> &cs)
+{
+    if (!q || !qd || !tau || !active || !ydd || !lambda) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = active_set_args<T>(p, n_contacts, bodies, offsets, &kd, nullptr, damping, cs)) return rc;
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const size_t bc = B * static_cast<size_t>(n_contacts) * 3 * sizeof(T);
+    const void *const in[5] = {q, qd, tau, active, a_des}, *const out[3] = {ydd, lambda, ydd_free};
+    const size_t in_bytes[5] = {bq, bv, bv, B * sizeof(int32_t), bc}, out_bytes[3] = {bv, bc, bv};
+    return no_overlap(in, in_bytes, out, out_bytes);
+}
+template <class T>
+int contact_dynamics_active(const grbda_plan *p, const T *q, const T *qd, const T *tau, int n_contacts, const int *bodies, const double *offsets,
+                            const int32_t *active, const T *a_des, double kd, double damping, T *ydd, T *lambda, T *ydd_free, size_t B, int device,
+                            void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<T> cs;
+    if (int rc = contact_dynamics_active_args<T>(p, q, qd, tau, n_contacts, bodies, offsets, active, a_des, kd, damping, ydd, lambda, ydd_free, B, cs))
+        return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const ActiveContacts<T> A = active_contacts<T>(p, cs, bodies, offsets);
+    const size_t nq = p->host.nq, nv = p->host.nv, n = A.n;
+    const size_t per_state = (ydd_free ? 0 : nv) + A.shared_per_state();
+    Chunk c;
+    void *wptr = nullptr;
+    if (int rc = active_pool<T>(p, per_state, B, device, stream, c, &wptr)) return rc;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        T *yf = ydd_free ? ydd_free + b0 * nv : w.take(nb * nv);
+        const ActiveWork<T> k(A, w, nb);
+        int rc;
+        if ((rc = active_frames_stage<T>(p, *t, A, k, q + b0 * nq, nb, device, stream, w)) ||
+            (rc = active_dynamics_stage<T>(p, *t, A, k, q + b0 * nq, qd + b0 * nv, tau + b0 * nv, active + b0, a_des ? a_des + b0 * n * 3 : nullptr, kd,
+                                           damping, ydd + b0 * nv, lambda + b0 * n * 3, yf, nb, device, stream)))
+            return rc;
+    }
+    return GRBDA_OK;
+}
+
+template <class T>
+int contact_impulse_active_args(const grbda_plan *p, const T *q, const T *qd, int n_contacts, const int *bodies, const double *offsets,
+                                const int32_t *active, const T *v_des, double restitution, double damping, const T *qd_next, const T *impulse,
+                                size_t B, ContactSet<T> &cs)
+{
+    if (!q || !qd || !active || !qd_next || !impulse) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = active_set_args<T>(p, n_contacts, bodies, offsets, nullptr, &restitution, damping, cs)) return rc;
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const size_t bc = B * static_cast<size_t>(n_contacts) * 3 * sizeof(T);
+    const void *const in[4] = {q, qd_next == qd ? nullptr : qd, active, v_des}, *const out[2] = {qd_next, impulse};  // (null entries are skipped)
+    const size_t in_bytes[4] = {bq, bv, B * sizeof(int32_t), bc}, out_bytes[2] = {bv, bc};
+    return no_overlap(in, in_bytes, out, out_bytes);
+}
+// (a chunk reads its rows of qd -- the twists -- before its last stage writes them, so qd_next == qd is safe, as for contact_impulse)
+template <class T>
+int contact_impulse_active(const grbda_plan *p, const T *q, const T *qd, int n_contacts, const int *bodies, const double *offsets,
+                           const int32_t *active, const T *v_des, double restitution, double damping, T *qd_next, T *impulse, size_t B, int device,
+                           void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<T> cs;
+    if (int rc = contact_impulse_active_args<T>(p, q, qd, n_contacts, bodies, offsets, active, v_des, restitution, damping, qd_next, impulse, B, cs))
+        return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const ActiveContacts<T> A = active_contacts<T>(p, cs, bodies, offsets);
+    const size_t nq = p->host.nq, nv = p->host.nv, n = A.n;
+    const size_t per_state = 3 * nv + A.shared_per_state();  // zeros, y1, y0
+    Chunk c;
+    void *wptr = nullptr;
+    if (int rc = active_pool<T>(p, per_state, B, device, stream, c, &wptr)) return rc;
+    // (the zeros lead the slab at the chunk's full size: every pass finds them where this call cleared them)
+    if (hipError_t e = hipMemsetAsync(wptr, 0, c.chunk * nv * sizeof(T), static_cast<hipStream_t>(stream)); e != hipSuccess)
+        return hip_err(e, "hipMemsetAsync");
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        const T *zero = w.take(c.chunk * nv);
+        T *y1 = w.take(nb * nv), *y0 = w.take(nb * nv);
+        const ActiveWork<T> k(A, w, nb);
+        int rc;
+        if ((rc = active_frames_stage<T>(p, *t, A, k, q + b0 * nq, nb, device, stream, w)) ||
+            (rc = active_impulse_stage<T>(p, *t, A, k, q + b0 * nq, qd + b0 * nv, active + b0, v_des ? v_des + b0 * n * 3 : nullptr, restitution, damping,
+                                          qd_next + b0 * nv, impulse + b0 * n * 3, zero, y1, y0, nb, device, stream)))
+            return rc;
+    }
+    return GRBDA_OK;
+}
+
+// Everything grbda_contact_step_* refuses: its own rules, then the integrator's (the aliasing of q_next / qd_next and what grbda_step_*
+// does not cover), then the overlaps of the arrays the integrator does not know.
+template <class T>
+int contact_step_args(const grbda_plan *p, const T *q, const T *qd, const T *tau, int n_contacts, const int *bodies, const double *offsets,
+                      const int32_t *active, const int32_t *prev_active, double kd, double restitution, double damping, double dt, const T *ydd,
+                      const T *lambda, const T *impulse, const T *q_next, const T *qd_next, const int32_t *ok, size_t B, ContactSet<T> &cs)
+{
+    if (!q || !qd || !tau || !active || !ydd || !lambda || !q_next || !qd_next) return set_err(GRBDA_EINVAL, "null argument");
+    if (int rc = active_set_args<T>(p, n_contacts, bodies, offsets, &kd, &restitution, damping, cs)) return rc;
+    if (impulse && !prev_active) return set_err(GRBDA_EINVAL, "impulse needs prev_active: without it no impulse stage runs");
+    if (int rc = integrate_args<T>(p, q, qd, ydd, dt, q_next, qd_next, kStepMaxIter, kStepTol, B)) return rc;
+    const size_t bq = B * static_cast<size_t>(p->host.nq) * sizeof(T), bv = B * static_cast<size_t>(p->host.nv) * sizeof(T);
+    const size_t bc = B * static_cast<size_t>(n_contacts) * 3 * sizeof(T), bi = B * sizeof(int32_t);
+    // (q_next == q and qd_next == qd passed the integrator's rule: the pair then counts once, as an output)
+    const void *const in[5] = {q_next == q ? nullptr : q, qd_next == qd ? nullptr : qd, tau, active, prev_active};
+    const void *const out[6] = {ydd, lambda, impulse, q_next, qd_next, ok};
+    const size_t in_bytes[5] = {bq, bv, bv, bi, bi}, out_bytes[6] = {bv, bc, bc, bq, bv, bi};
+    return no_overlap(in, in_bytes, out, out_bytes);
+}
+// scalars of the work pool per state of a step: the shared stages, and for the impulse stage the zeros, y1, y0, the impact masks (one cell
+// each) and the impulses nobody keeps.  grbda_contact_rollout_* counts the same, so that its steps chunk as single steps do.
+template <class T>
+size_t contact_step_per_state(const grbda_plan *p, const ActiveContacts<T> &A)
+{
+    return A.shared_per_state() + 3 * static_cast<size_t>(p->host.nv) + 1 + 2 * A.n * 3;
+}
+// One step on a checked call (B > 0, device found, the pool's slab and chunk in hand): per chunk the poses and Linv once, the impulse stage
+// when prev_active is given (it leaves qd+ in qd_next), the dynamics at qd+; then the integrator over the batch.  lambda == nullptr: the
+// pool keeps the forces (the rollout without lambda_traj).
+template <class T>
+int contact_step_run(const grbda_plan *p, const DeviceTables &t, const ActiveContacts<T> &A, const Chunk &c, void *wptr, const T *q, const T *qd,
+                     const T *tau, const int32_t *active, const int32_t *prev_active, double kd, double restitution, double damping, double dt, T *ydd,
+                     T *lambda, T *impulse, T *q_next, T *qd_next, int32_t *ok, bool ok_and, size_t B, int device, void *stream)
+{
+    const size_t nq = p->host.nq, nv = p->host.nv, n = A.n, per_state = contact_step_per_state<T>(p, A);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    static_assert(sizeof(T) >= sizeof(int32_t), "an impact mask takes one cell of the pool");
+    if (prev_active)
+        if (hipError_t e = hipMemsetAsync(wptr, 0, c.chunk * nv * sizeof(T), hs); e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    const T *qd_plus = prev_active ? qd_next : qd;
+    for (const auto [b0, nb] : ChunkWalk{B, c.chunk}) {
+        Carver<T> w(wptr, c.chunk * per_state);
+        const T *zero = w.take(c.chunk * nv);
+        T *y1 = w.take(nb * nv), *y0 = w.take(nb * nv);
+        int32_t *impact = reinterpret_cast<int32_t *>(w.take(nb));
+        T *imp = w.take(nb * n * 3), *lam = w.take(nb * n * 3);
+        const ActiveWork<T> k(A, w, nb);
+        const T *qc = q + b0 * nq;
+        int rc;
+        if ((rc = active_frames_stage<T>(p, t, A, k, qc, nb, device, stream, w))) return rc;
+        if (prev_active) {
+            if (hipError_t e = launch_impact_mask(active + b0, prev_active + b0, static_cast<int>(n), nb, impact, hs); e != hipSuccess)
+                return hip_err(e, "impact mask launch");
+            if ((rc = active_impulse_stage<T>(p, t, A, k, qc, qd + b0 * nv, impact, static_cast<const T *>(nullptr), restitution, damping,
+                                              qd_next + b0 * nv, impulse ? impulse + b0 * n * 3 : imp, zero, y1, y0, nb, device, stream)))
+                return rc;
+        }
+        // (ydd_free goes where y1 was: the impulse stage is done with it)
+        if ((rc = active_dynamics_stage<T>(p, t, A, k, qc, qd_plus + b0 * nv, tau + b0 * nv, active + b0, static_cast<const T *>(nullptr), kd, damping,
+                                           ydd + b0 * nv, lambda ? lambda + b0 * n * 3 : lam, y1, nb, device, stream)))
+            return rc;
+    }
+    return integrate_launch<T>(p, q, qd_plus, ydd, dt, q_next, qd_next, ok, kStepMaxIter, kStepTol, B, device, stream, ok_and);
+}
+template <class T>
+int contact_step(const grbda_plan *p, const T *q, const T *qd, const T *tau, int n_contacts, const int *bodies, const double *offsets,
+                 const int32_t *active, const int32_t *prev_active, double kd, double restitution, double damping, double dt, T *ydd, T *lambda,
+                 T *impulse, T *q_next, T *qd_next, int32_t *ok, size_t B, int device, void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<T> cs;
+    if (int rc = contact_step_args<T>(p, q, qd, tau, n_contacts, bodies, offsets, active, prev_active, kd, restitution, damping, dt, ydd, lambda, impulse,
+                                      q_next, qd_next, ok, B, cs))
+        return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const ActiveContacts<T> A = active_contacts<T>(p, cs, bodies, offsets);
+    Chunk c;
+    void *wptr = nullptr;
+    if (int rc = active_pool<T>(p, contact_step_per_state<T>(p, A), B, device, stream, c, &wptr)) return rc;
+    return contact_step_run<T>(p, *t, A, c, wptr, q, qd, tau, active, prev_active, kd, restitution, damping, dt, ydd, lambda, impulse, q_next, qd_next, ok,
+                               false, B, device, stream);
+}
+// T steps in place; every state (and every step's forces) copied to the trajectory arrays on the same stream
+template <class T>
+int contact_rollout(const grbda_plan *p, T *q, T *qd, const T *tau, int tau_steps, int n_contacts, const int *bodies, const double *offsets,
+                    const int32_t *active, int active_steps, const int32_t *active_prev, int with_impulses, double kd, double restitution,
+                    double damping, double dt, int n_steps, T *ydd_work, T *q_traj, T *qd_traj, T *lambda_traj, int32_t *ok, size_t B, int device,
+                    void *stream)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    if (!q || !qd || !tau || !active || !ydd_work) return set_err(GRBDA_EINVAL, "null argument");
+    ContactSet<T> cs;
+    if (int rc = active_set_args<T>(p, n_contacts, bodies, offsets, &kd, &restitution, damping, cs)) return rc;
+    if (n_steps < 0) return set_err(GRBDA_EINVAL, "T is negative");
+    if (tau_steps != 1 && tau_steps != n_steps) return set_err(GRBDA_EINVAL, "tau_steps must be 1 or T");
+    if (active_steps != 1 && active_steps != n_steps) return set_err(GRBDA_EINVAL, "active_steps must be 1 or T");
+    if (int rc = integrate_args<T>(p, q, qd, ydd_work, dt, q, qd, kStepMaxIter, kStepTol, B)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, n = static_cast<size_t>(n_contacts), steps = static_cast<size_t>(n_steps);
+    const size_t bq = B * nq * sizeof(T), bv = B * nv * sizeof(T), bc = B * n * 3 * sizeof(T), bi = B * sizeof(int32_t);
+    // (tau[T][B][nv], active[T][B]: every step's block stays clear of what the steps write)
+    const void *const in[3] = {tau, active, with_impulses ? active_prev : nullptr};
+    const void *const out[7] = {q, qd, ydd_work, q_traj, qd_traj, lambda_traj, ok};
+    const size_t in_bytes[3] = {static_cast<size_t>(tau_steps) * bv, static_cast<size_t>(active_steps) * bi, bi};
+    const size_t out_bytes[7] = {bq, bv, bv, steps * bq, steps * bv, steps * bc, bi};
+    if (int rc = no_overlap(in, in_bytes, out, out_bytes)) return rc;
+    if (B == 0 || n_steps == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const ActiveContacts<T> A = active_contacts<T>(p, cs, bodies, offsets);
+    Chunk c;
+    void *wptr = nullptr;
+    if (int rc = active_pool<T>(p, contact_step_per_state<T>(p, A), B, device, stream, c, &wptr)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    for (int s = 0; s < n_steps; s++) {
+        const size_t at = static_cast<size_t>(s);
+        const int32_t *as = active + (active_steps > 1 ? at * B : 0);
+        // (a NULL active_prev stands for active[0]; a held mask is its own predecessor)
+        const int32_t *prev = !with_impulses ? nullptr : s == 0 ? (active_prev ? active_prev : active) : active + (active_steps > 1 ? (at - 1) * B : 0);
+        // (ok: the first step writes the flags, the later ones AND theirs into them)
+        if (int rc = contact_step_run<T>(p, *t, A, c, wptr, q, qd, tau + (tau_steps > 1 ? at * B * nv : 0), as, prev, kd, restitution, damping, dt, ydd_work,
+                                         lambda_traj ? lambda_traj + at * B * n * 3 : nullptr, static_cast<T *>(nullptr), q, qd, ok, s > 0, B, device,
+                                         stream))
+            return rc;
+        hipError_t e;
+        if (q_traj && (e = hipMemcpyAsync(q_traj + at * B * nq, q, bq, hipMemcpyDeviceToDevice, hs)) != hipSuccess) return hip_err(e, "hipMemcpyAsync");
+        if (qd_traj && (e = hipMemcpyAsync(qd_traj + at * B * nv, qd, bv, hipMemcpyDeviceToDevice, hs)) != hipSuccess) return hip_err(e, "hipMemcpyAsync");
     }
     return GRBDA_OK;
 }
@@ -4061,7 +4429,7 @@ void grbda_plan_free(grbda_plan *p)
         }
         for (int w = 0; w < kLayouts; w++) { (void)hipFree(t.acc_k[w]); (void)hipFree(t.clusters[w]); (void)hipFree(t.rnea_clusters[w]); (void)hipFree(t.bodies[w]); (void)hipFree(t.rnea_bodies[w]); }
     }
-    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp})
+    for (auto *m : {&p->scratch, &p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp, &p->work_contact})
         for (auto &kv : *m) {
             if (hipSetDevice(kv.first.first) != hipSuccess) continue;
             if (kv.second.ptr) (void)hipFree(kv.second.ptr);
@@ -4073,7 +4441,7 @@ void grbda_plan_free(grbda_plan *p)
 // (and of its spanning-tree plan) is checked first, so that a refused release frees nothing.
 static bool holds_capturing_slab(const grbda_plan *p)
 {
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp, &p->work_contact})
         for (auto &kv : *m)
             if (kv.second.ptr && is_capturing(kv.first.second)) return true;
     return p->span && holds_capturing_slab(p->span);
@@ -4086,7 +4454,7 @@ int grbda_plan_release_work(grbda_plan *p, unsigned long long *bytes_released)
     if (holds_capturing_slab(p))
         return set_err(GRBDA_EINVAL, "a stream of this plan is capturing: its work buffers cannot be released now");
     unsigned long long total = 0;
-    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp})
+    for (auto *m : {&p->work, &p->work_cvt, &p->work_proj, &p->work_vjp, &p->work_step_vjp, &p->work_jvp, &p->work_step_jvp, &p->work_contact})
         for (auto &kv : *m) {
             if (!kv.second.ptr) continue;
             hipError_t e = hipSetDevice(kv.first.first);
@@ -4971,6 +5339,91 @@ int grbda_step_host_f64(const grbda_plan *p, const double *q, const double *qd, 
     double *dy = st.out(ydd, B * nv), *dqn = st.out(q_next, B * nq), *dvn = st.out(qd_next, B * nv);
     int32_t *dok = st.out(ok, B);
     return st.run([&] { return step<double>(p, dq, dqd, dt_, dfe, dt, dy, dqn, dvn, dok, B, device, nullptr); });
+}
+
+// ---- include/grbda_hip_contact_step.h ---------------------------------------------------------------------------------------------------
+int grbda_contact_dynamics_active_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, int n_contacts, const int *bodies,
+                                      const double *offsets, const int32_t *active, const double *a_des, double kd, double damping, double *ydd,
+                                      double *lambda, double *ydd_free, size_t B, int device, void *stream)
+{
+    return contact_dynamics_active<double>(p, q, qd, tau, n_contacts, bodies, offsets, active, a_des, kd, damping, ydd, lambda, ydd_free, B, device, stream);
+}
+int grbda_contact_dynamics_active_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, int n_contacts, const int *bodies,
+                                      const double *offsets, const int32_t *active, const float *a_des, double kd, double damping, float *ydd,
+                                      float *lambda, float *ydd_free, size_t B, int device, void *stream)
+{
+    return contact_dynamics_active<float>(p, q, qd, tau, n_contacts, bodies, offsets, active, a_des, kd, damping, ydd, lambda, ydd_free, B, device, stream);
+}
+int grbda_contact_impulse_active_f64(const grbda_plan *p, const double *q, const double *qd, int n_contacts, const int *bodies, const double *offsets,
+                                     const int32_t *active, const double *v_des, double restitution, double damping, double *qd_next,
+                                     double *impulse, size_t B, int device, void *stream)
+{
+    return contact_impulse_active<double>(p, q, qd, n_contacts, bodies, offsets, active, v_des, restitution, damping, qd_next, impulse, B, device, stream);
+}
+int grbda_contact_impulse_active_f32(const grbda_plan *p, const float *q, const float *qd, int n_contacts, const int *bodies, const double *offsets,
+                                     const int32_t *active, const float *v_des, double restitution, double damping, float *qd_next, float *impulse,
+                                     size_t B, int device, void *stream)
+{
+    return contact_impulse_active<float>(p, q, qd, n_contacts, bodies, offsets, active, v_des, restitution, damping, qd_next, impulse, B, device, stream);
+}
+int grbda_contact_step_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, int n_contacts, const int *bodies,
+                           const double *offsets, const int32_t *active, const int32_t *prev_active, double kd, double restitution, double damping,
+                           double dt, double *ydd, double *lambda, double *impulse, double *q_next, double *qd_next, int32_t *ok, size_t B,
+                           int device, void *stream)
+{
+    return contact_step<double>(p, q, qd, tau, n_contacts, bodies, offsets, active, prev_active, kd, restitution, damping, dt, ydd, lambda, impulse, q_next,
+                                qd_next, ok, B, device, stream);
+}
+int grbda_contact_step_f32(const grbda_plan *p, const float *q, const float *qd, const float *tau, int n_contacts, const int *bodies,
+                           const double *offsets, const int32_t *active, const int32_t *prev_active, double kd, double restitution, double damping,
+                           double dt, float *ydd, float *lambda, float *impulse, float *q_next, float *qd_next, int32_t *ok, size_t B, int device,
+                           void *stream)
+{
+    return contact_step<float>(p, q, qd, tau, n_contacts, bodies, offsets, active, prev_active, kd, restitution, damping, dt, ydd, lambda, impulse, q_next,
+                               qd_next, ok, B, device, stream);
+}
+int grbda_contact_step_host_f64(const grbda_plan *p, const double *q, const double *qd, const double *tau, int n_contacts, const int *bodies,
+                                const double *offsets, const int32_t *active, const int32_t *prev_active, double kd, double restitution,
+                                double damping, double dt, double *ydd, double *lambda, double *impulse, double *q_next, double *qd_next,
+                                int32_t *ok, size_t B, int device)
+{
+    if (!p) return set_err(GRBDA_EINVAL, "null plan");
+    GRBDA_CALL_SCOPE(p);
+    ContactSet<double> cs;
+    if (int rc = contact_step_args<double>(p, q, qd, tau, n_contacts, bodies, offsets, active, prev_active, kd, restitution, damping, dt, ydd, lambda,
+                                           impulse, q_next, qd_next, ok, B, cs))
+        return rc;
+    if (B == 0) return GRBDA_OK;
+    DeviceTables *t = nullptr;
+    if (int rc = ensure_device(p, device, &t)) return rc;
+    const size_t nq = p->host.nq, nv = p->host.nv, no = B * static_cast<size_t>(n_contacts) * 3;
+    HostStage st;
+    const double *dq = st.in(q, B * nq), *dqd = st.in(qd, B * nv), *dt_ = st.in(tau, B * nv);
+    const int32_t *da = st.in(active, B), *dp = prev_active ? st.in(prev_active, B) : nullptr;
+    double *dy = st.out(ydd, B * nv), *dl = st.out(lambda, no), *di = impulse ? st.out(impulse, no) : nullptr;
+    // (q_next == q, qd_next == qd on the host: two device arrays each, the inputs copied first)
+    double *dqn = st.out(q_next, B * nq), *dvn = st.out(qd_next, B * nv);
+    int32_t *dok = st.out(ok, B);
+    return st.run([&] {
+        return contact_step<double>(p, dq, dqd, dt_, n_contacts, bodies, offsets, da, dp, kd, restitution, damping, dt, dy, dl, di, dqn, dvn, dok, B, device,
+                                    nullptr);
+    });
+}
+int grbda_contact_rollout_f64(const grbda_plan *p, double *q, double *qd, const double *tau, int tau_steps, int n_contacts, const int *bodies,
+                              const double *offsets, const int32_t *active, int active_steps, const int32_t *active_prev, int with_impulses,
+                              double kd, double restitution, double damping, double dt, int T, double *ydd_work, double *q_traj, double *qd_traj,
+                              double *lambda_traj, int32_t *ok, size_t B, int device, void *stream)
+{
+    return contact_rollout<double>(p, q, qd, tau, tau_steps, n_contacts, bodies, offsets, active, active_steps, active_prev, with_impulses, kd, restitution,
+                                   damping, dt, T, ydd_work, q_traj, qd_traj, lambda_traj, ok, B, device, stream);
+}
+int grbda_contact_rollout_f32(const grbda_plan *p, float *q, float *qd, const float *tau, int tau_steps, int n_contacts, const int *bodies,
+                              const double *offsets, const int32_t *active, int active_steps, const int32_t *active_prev, int with_impulses,
+                              double kd, double restitution, double damping, double dt, int T, float *ydd_work, float *q_traj, float *qd_traj,
+                              float *lambda_traj, int32_t *ok, size_t B, int device, void *stream)
+{
+    return contact_rollout<float>(p, q, qd, tau, tau_steps, n_contacts, bodies, offsets, active, active_steps, active_prev, with_impulses, kd, restitution,
+                                  damping, dt, T, ydd_work, q_traj, qd_traj, lambda_traj, ok, B, device, stream);
 }
 
 int grbda_plan_total_mass(const grbda_plan *p, double *mass)

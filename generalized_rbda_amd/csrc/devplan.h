@@ -349,6 +349,19 @@ hipError_t launch_impulse_solve(const ContactSet<T> &cs, const T *Linv, const T 
 template <class T>
 hipError_t launch_impulse_finish(const T *qd, const T *y1, const T *y0, size_t total, T *qd_next, hipStream_t stream);
 hipError_t set_max_dynamic_lds_contact();
+// Scheduled contacts (contact_step_kernels.hip; include/grbda_hip_contact_step.h).  launch_contact_active_solve: the solve of the contacts
+// whose bit is set in active[nb], on the launch record above -- Xl, Vl the LISTED poses and twists [nb][n][12] (slot c: the body of contact
+// c), des = a_des / v_des [nb][n][3] or null, c_vel = kd (vel = false) or 1 + e (vel = true); writes out = lambda / impulse [nb][n][3],
+// exactly 0 off the set, and the body-frame wrench list [nb][n][6].  launch_impact_mask: out[b] = active[b] where a contact closes against
+// prev[b], else 0.  launch_free_states_copy: ydd[b] = ydd_free[b] for the states whose set is empty.
+template <class T>
+hipError_t launch_contact_active_solve(bool vel, const ContactSet<T> &cs, const T *Linv, const T *Xl, const T *Vl, const T *des, const int *active,
+                                       T mu, T c_vel, const T g[3], size_t nb, T *out, T *wrench, unsigned long long *bad_count, int n_cu,
+                                       hipStream_t stream);
+hipError_t launch_impact_mask(const int *active, const int *prev, int n, size_t nb, int *out, hipStream_t stream);
+template <class T>
+hipError_t launch_free_states_copy(const int *active, int n, const T *ydd_free, int nv, size_t nb, T *ydd, hipStream_t stream);
+hipError_t set_max_dynamic_lds_contact_step();
 
 // energy, centre of mass and centroidal momentum (centroidal_kernels.hip).  A body with children keeps its pose (12), velocity (6) and
 // acceleration (6) in kCentroidalBodyRows rows [value][kWave] of the wavefront's scratch; `rows` holds per body (its first row or -1 for
